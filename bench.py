@@ -25,6 +25,8 @@ Prints ONE JSON line on rank 0 (contract in the task statement), with:
                 per-signal results (events, stats, energies) copied back every step
   cpu_baseline  the NumPy port of the reference's CPU path (oracle/numpy_port.py) timed AFTER the GPU section in a fresh
                 child process (one worker per host core) on a bounded sample (rank 0, N=1 only)
+  dump_outputs  with --dump-outputs DIR: where the arrays of the last timed step went (dump_cmp, bench_hsc.dump_outputs).  The
+                inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -40,6 +42,61 @@ if ROOT not in sys.path:
 PEAK_FP32_MFMA_TFLOPS = 157.3     # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense, = fp32 vector peak
 PEAK_FP64_MFMA_TFLOPS = 78.6      # AMD MI355X datasheet (v_mfma_f64_16x16x4_f64); used with --dtype f64 only
 PEAK_HBM_BYTES = 8.0e12           # MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
+DUMP_BYTES = 64 * 10 ** 6         # --dump-outputs writes at most this much in all (64 MB)
+
+
+def dump_sample(sizes, budget):
+    """--dump-outputs: the signals (ascending indices) whose outputs are written when not all of them fit -- taken in a fixed,
+    seeded order while their sizes in bytes fit in `budget`."""
+    import numpy as np
+    taken, used = [], 0
+    for b in np.random.RandomState(0).permutation(len(sizes)):
+        if used + sizes[b] > budget:
+            break
+        taken.append(b)
+        used += sizes[b]
+    return np.sort(np.asarray(taken, dtype=np.int64))
+
+
+def write_dump(out_dir, arrays):
+    """--dump-outputs: DIR/<name>.npy for every array, in float32 or float64 (integers as float64, exact). Returns the line's record."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        total += a.nbytes
+    assert total <= DUMP_BYTES, total
+    return {'dir': out_dir, 'bytes': total, 'arrays': sorted(arrays)}
+
+
+def dump_cmp(out_dir, eng, stats, energies, residual):
+    """--dump-outputs of config 2: what an encode leaves its caller, after the last timed step.
+      events         [n, 4] (signal, t, k, c): every signal's selections in selection order
+      coefficients   [n, 4] (signal, t, k, value): every signal's non-zero coefficients (distinct (t, k), first-selection order)
+      stats [B, 8], energies [B, 2]
+      residual       [S, T, F] of the signals in residual_signals [S]: a fixed, seeded sample (the budget left by the lists when
+                     every list is full, so the sample depends on the arguments alone)"""
+    import numpy as np
+    from hsc_amd import _native
+    ev_t, ev_k, ev_c = eng.fetch_events()
+    sl_t, sl_k, sl_a = eng.fetch_slots()
+    B = stats.shape[0]
+    row_bytes = 4 * 8 * (ev_t.shape[1] + sl_t.shape[1])                 # both lists full
+    budget = DUMP_BYTES - 8 * (stats.size + energies.size)
+    lists = dump_sample(np.full(B, row_bytes), budget)
+
+    def rows(b, n, t, k, v):
+        return np.stack([np.full(n, b, dtype=np.float64), t[b, :n], k[b, :n], v[b, :n]], axis=1).astype(np.float64)
+
+    events = [rows(b, stats[b, _native.STAT_EVENTS], ev_t, ev_k, ev_c) for b in lists]
+    coefficients = [rows(b, stats[b, _native.STAT_SLOTS], sl_t, sl_k, sl_a) for b in lists]
+    sample = dump_sample(np.full(B, residual[0].nbytes), budget - len(lists) * row_bytes)
+    return write_dump(out_dir, {'events': np.concatenate(events + [np.zeros((0, 4))]),
+                                'coefficients': np.concatenate(coefficients + [np.zeros((0, 4))]),
+                                'stats': stats, 'energies': energies,
+                                'residual': residual[sample], 'residual_signals': sample})
 
 
 def host_cores():
@@ -148,6 +205,8 @@ def main():
     ap.add_argument('--cpu-procs', type=int, default=0, help='processes of the CPU baseline (0 = one per usable core, at most 16: the CPU share of one GPU; the port is memory-bound and slows down beyond that)')
     ap.add_argument('--cpu-signals-per-proc', type=int, default=2, help='signals each CPU process encodes (~3-6 s each)')
     ap.add_argument('--profile-steps', type=int, default=5, help='extra untimed steps used for per-kernel HIP-event timing')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write what the last one computed (rank 0\'s '
+                    'signals) as DIR/<name>.npy, at most 64 MB in all (larger outputs: a fixed, seeded sample of the signals)')
     ap.add_argument('--cpu-baseline-only', default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_baseline_only:
@@ -258,6 +317,7 @@ def bench_cmp(args, ctx):
     r = eng.fetch_residual()
     e_rec = np.sum(np.square(r.astype(np.float64)), axis=(1, 2))
     check['tracked_energy_matches_residual'] = bool(np.all(np.abs(e_rec - energies[:, 1]) <= 1e-5 * energies[:, 0]))
+    dumped = dump_cmp(args.dump_outputs, eng, stats, energies, r) if args.dump_outputs and rank == 0 else None
     del r
 
     # ---- per-kernel durations (HIP events on the engine's stream), untimed extra steps
@@ -396,6 +456,8 @@ def bench_cmp(args, ctx):
     }
     if check and not all(check.values()):
         out['config']['output_check']['FAILED'] = True
+    if dumped:
+        out['dump_outputs'] = dumped
     # ---- the hierarchical configurations of BASELINE.json at their own sizes, a few steps each (bounded: it must never
     #      cost the headline line): configs[3] with 17 and with the literal 16 level-1 taps, configs[4] at its per-GPU share
     if world == 1:
@@ -420,6 +482,7 @@ def run_secondary(args, ctx):
     try:
         a = copy.copy(args)
         a.dtype, a.steps, a.warmup, a.no_cpu_baseline, a.no_secondary, a.no_transfers, a.profile_steps = 'f64', 3, 1, True, True, True, 2
+        a.dump_outputs = None
         t0 = time.perf_counter()
         o = bench_cmp(a, ctx)
         sec['config2_f64'] = {'value': o['value'], 'unit': o['unit'], 'ms_per_step': o['ms_per_step'], 'steps': o['steps'], 'dtype': 'f64',
@@ -438,7 +501,7 @@ def run_secondary(args, ctx):
             continue
         a = copy.copy(args)
         a.config, a.level1_taps, a.batch, a.T, a.method = config, taps, 0, 65536, method
-        a.steps, a.warmup, a.no_cpu_baseline = (3 if method == 'cmp' else 2), 1, True
+        a.steps, a.warmup, a.no_cpu_baseline, a.dump_outputs = (3 if method == 'cmp' else 2), 1, True, None
         t0 = time.perf_counter()
         try:
             sec[name] = bench_hsc.compact(bench_hsc.run(a, ctx))

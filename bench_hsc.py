@@ -159,6 +159,27 @@ def cpu_baseline_main(payload):
                       'per_core': nsel / wall / cfg['nproc']}))
 
 
+def dump_outputs(out_dir, coefs, energies):
+    """bench.py --dump-outputs of configs 4 / 5: what the encode returns its caller, after the last timed step.
+      energies               [B] residual energy of every signal
+      coefficients_level<l>  [n, 4] (signal, t, k, value): level l's non-zeros in (t, k) order, for every signal if all fit in the
+                             budget, else for a fixed, seeded sample of them"""
+    import scipy.sparse
+    import bench as _b
+    nlev = len(coefs[0])
+    mats = [[scipy.sparse.coo_matrix(c[l]) for l in range(nlev)] for c in coefs]
+    sample = _b.dump_sample([4 * 8 * sum(m.nnz for m in ms) for ms in mats], _b.DUMP_BYTES - 8 * energies.size)
+    arrays = {'energies': energies}
+    for l in range(nlev):
+        rows = [np.zeros((0, 4))]
+        for b in sample:
+            m = mats[b][l]
+            o = np.lexsort((m.col, m.row))
+            rows.append(np.stack([np.full(m.nnz, b, dtype=np.float64), m.row[o], m.col[o], m.data[o]], axis=1).astype(np.float64))
+        arrays['coefficients_level%d' % l] = np.concatenate(rows)
+    return _b.write_dump(out_dir, arrays)
+
+
 def run(args, ctx):
     import hsc_amd.synth as synth  # noqa: F401
     from hsc_amd import _native
@@ -197,6 +218,7 @@ def run(args, ctx):
     if world > 1:
         dist.barrier()
     nsel_local = int(sum(tm['selections'] for tm in timings))
+    dumped = dump_outputs(args.dump_outputs, coefs, energies) if getattr(args, 'dump_outputs', None) and rank == 0 else None
     # the same step with the residual samples fetched (never `value`)
     nres = max(1, min(3, steps))
     t1 = time.perf_counter()
@@ -302,6 +324,8 @@ def run(args, ctx):
                               'note': 'the same step with the float64 residual samples of every signal fetched to the host (this rank)'},
         'cpu_baseline': None,
     }
+    if dumped:
+        out['dump_outputs'] = dumped
     if world == 1 and not args.no_cpu_baseline:
         nproc = args.cpu_procs or min(16, _b.host_cores())
         payload = json.dumps(dict(config=config, nproc=nproc, T=T, level1_taps=args.level1_taps))

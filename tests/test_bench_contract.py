@@ -90,3 +90,48 @@ def test_no_tools_script_shadows_a_root_module():
     assert callable(bench_hsc.compact) and callable(bench_hsc.run)
     import tools_csrc_digest
     assert len(tools_csrc_digest.csrc_digest()) == 64
+
+
+def test_dump_outputs_fit_the_budget_and_keep_their_sample(tmp_path):
+    """bench.py --dump-outputs on stand-in results of the config-2 path at its default shape: float32 / float64 arrays only, at most
+    64 MB in all, the lists of every signal, and a residual sample that depends on the arguments alone."""
+    import numpy as np
+    import bench
+    from hsc_amd import _native
+    B, T, cap = 1024, 65536, 576
+    rs = np.random.RandomState(3)
+    ev = rs.randint(0, T, (B, cap)).astype(np.int32), rs.randint(0, 256, (B, cap)).astype(np.int32), rs.rand(B, cap).astype(np.float32)
+    sl = rs.randint(0, T, (B, cap)).astype(np.int32), rs.randint(0, 256, (B, cap)).astype(np.int32), rs.rand(B, cap)
+
+    class Engine(object):
+        def fetch_events(self):
+            return ev
+
+        def fetch_slots(self):
+            return sl
+
+    stats = np.zeros((B, _native.STAT_COUNT), dtype=np.int32)
+    energies = rs.rand(B, 2)
+    residual = np.zeros((B, T, 1), dtype=np.float32)
+    residual[:, 0, 0] = np.arange(B)
+    samples = []
+    for run, n_events in enumerate((256, cap)):
+        stats[:, _native.STAT_EVENTS] = n_events
+        stats[:, _native.STAT_SLOTS] = 200
+        d = str(tmp_path / str(run))
+        rec = bench.dump_cmp(d, Engine(), stats, energies, residual)
+        got = {n: np.load(os.path.join(d, n + '.npy')) for n in rec['arrays']}
+        assert sorted(os.listdir(d)) == sorted(n + '.npy' for n in rec['arrays'])
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert rec['bytes'] == sum(a.nbytes for a in got.values()) <= 64 * 10 ** 6
+        assert got['events'].shape == (B * n_events, 4) and got['coefficients'].shape == (B * 200, 4)
+        b = 17
+        e = got['events'][got['events'][:, 0] == b]
+        assert np.array_equal(e[:, 1], ev[0][b, :n_events]) and np.array_equal(e[:, 3], ev[2][b, :n_events])
+        c = got['coefficients'][got['coefficients'][:, 0] == b]
+        assert np.array_equal(c[:, 2], sl[1][b, :200]) and np.array_equal(c[:, 3], sl[2][b, :200])
+        assert np.array_equal(got['stats'], stats) and np.array_equal(got['energies'], energies)
+        sample = got['residual_signals']
+        assert 0 < len(sample) < B and np.array_equal(got['residual'][:, 0, 0], sample)
+        samples.append(sample)
+    assert np.array_equal(samples[0], samples[1])

@@ -19,6 +19,7 @@ Files written:
   tests/golden/synth_small.npz  -- dataset synthesis (hsc/dataset.py:412-796) under fixed numpy seeds: generated
                                    multilevel dictionaries (raw, representations, decompositions), Poisson
                                    events with / without rate scaling, rendered signals
+  tests/golden/synth_seeds.npz  -- the same generators of the reference on other seeds: dictionaries and one event stream
   tests/golden/learn_small.npz  -- convolutional k-means dictionary learner (modeling.py:420-524) under fixed seeds and
                                    its window-assignment step (convolve1d_batch + arg-max) on fixed windows
   tests/golden/hsc_medium.npz   -- 2-level hierarchical encoder on generated data (8192 samples, level-1 dictionary
@@ -686,7 +687,7 @@ def gen_locomp_hier():
 
 
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
-from golden_util import SYNTH_CASES, LEARN_CASES, learn_signal  # noqa: E402  (case tables shared with the tests)
+from golden_util import SYNTH_CASES, SYNTH_SEEDS_CASE, LEARN_CASES, learn_signal  # noqa: E402  (case tables shared with the tests)
 
 
 def gen_synth():
@@ -720,6 +721,27 @@ def gen_synth():
             out['%s__%s_autolen' % (name, tag)] = np.int64(len(gen.generateSignalFromEvents(events)))
         print('synth', name, [d.shape for d in mld.dictionaries], len(events), 'events')
     path = os.path.join(OUT, 'synth_small.npz')
+    np.savez_compressed(path, **out)
+    print('wrote', path, os.path.getsize(path), 'bytes')
+
+
+def gen_synth_seeds():
+    """Dataset synthesis of the REAL reference on other seeds than synth_small.npz: the generated dictionaries and one
+    event stream without rate scaling."""
+    ref = load_reference()
+    kw, dseed, rates, eseed, n = SYNTH_SEEDS_CASE
+    np.random.seed(dseed)
+    mld = ref.dataset.MultilevelDictionaryGenerator().generate(**kw)
+    out = {'nlevels': np.int64(mld.getNbLevels())}
+    for l in range(mld.getNbLevels()):
+        out['raw%d' % l] = mld.dictionaries[l]
+        out['rep%d' % l] = mld.representations[l]
+    np.random.seed(eseed)
+    events = ref.dataset.SignalGenerator(mld, rates).generateEvents(n)
+    for f in events.dtype.names:
+        out['ev_' + f] = events[f]
+    print('synthseeds', [d.shape for d in mld.dictionaries], len(events), 'events')
+    path = os.path.join(OUT, 'synth_seeds.npz')
     np.savez_compressed(path, **out)
     print('wrote', path, os.path.getsize(path), 'bytes')
 
@@ -764,7 +786,7 @@ def scipy_sparse(c):
 if __name__ == '__main__':
     assert load_reference() is not None, 'the reference is not available in this environment'
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ['small', 'functions', 'config', 'hsc', 'hscmed', 'hsc4', 'mldpkl', 'locomp', 'locomphier', 'synth', 'learn']
+    which = sys.argv[1:] or ['small', 'functions', 'config', 'hsc', 'hscmed', 'hsc4', 'mldpkl', 'locomp', 'locomphier', 'synth', 'synthseeds', 'learn']
     if 'small' in which:
         gen_small()
     if 'functions' in which:
@@ -785,5 +807,7 @@ if __name__ == '__main__':
         gen_locomp_hier()
     if 'synth' in which:
         gen_synth()
+    if 'synthseeds' in which:
+        gen_synth_seeds()
     if 'learn' in which:
         gen_learn()
