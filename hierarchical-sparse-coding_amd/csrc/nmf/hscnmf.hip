@@ -1,0 +1,463 @@
+// hscnmf.hip -- libhscnmf.so: convolutional NMF coefficients (hsc/modeling.py:662-747) on gfx950, C ABI in
+// include/hscnmf.h.  DESIGN.md section 10.
+//
+// Per signal, A [L = T-W+1 rows][K] (rows past T-W never reach a reconstruction and are not kept).  One
+// multiplicative step t is one launch of nmf_step_kernel; a workgroup owns kRows rows s of A and
+//   1. forms P[r][j*F+f] = sum_k A[r][k] D[k][j][f] on the matrix cores for the rows r it needs (its own rows
+//      shifted by t, plus a halo of W-1 rows before them: recomputed, never exchanged),
+//   2. sums the diagonals recon[n][f] = sum_j P[n-j][j*F+f] (j ascending),
+//   3. R = x / |recon|, U[s][k] = (sum_f D[k][t][f] R[s+t][f]) / (sum_f D[k][t][f]), A'[s][k] = A[s][k] * U[s][k],
+// reading A from one buffer of a ping-pong pair and writing the other.  After the W steps of an iteration
+// nmf_residual_kernel reconstructs once more (residual, per-tile max|r| and sum r^2) and nmf_decide_kernel takes
+// the reference's stop decision per signal on the device; a finished signal's workgroups return at once.
+#include "../../../include/hscnmf.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace {
+
+constexpr int kThreads = 256;                 // four waves
+constexpr int kRows = 128;                    // A rows (and reconstructed samples) per workgroup
+constexpr int kLdsBytes = 64 * 1024;          // P slab + reconstruction tile
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+template <typename T> struct Tile;
+// v_mfma_f32_32x32x2_f32: A lane l = row l&31, k l>>5; B k l>>5, col l&31; C col l&31, row (r&3)+8(r>>2)+4(l>>5)
+template <> struct Tile<float> { static constexpr int RB = 32, CB = 32; };
+// v_mfma_f64_16x16x4_f64: A lane l = row l&15, k l>>4; B k l>>4, col l&15; C col l&15, row (l>>4)+4r
+template <> struct Tile<double> { static constexpr int RB = 16, CB = 16; };
+
+// One RB x CB block of P = A . D (rows r0.., columns c0..), written to LDS out[row][col] (row stride ldo).
+// A rows outside [0, L) are the reference's zero padding.  The k order inside the MFMA chain is fixed
+// (eight k per load group), so a block's value does not depend on anything but its inputs.
+__device__ __forceinline__ void p_block(const float* __restrict__ A, int L, int K, const float* __restrict__ D, int NW,
+                                        int r0, int c0, float* out, int ldo)
+{
+    const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
+    const int r = r0 + i, c = c0 + i;
+    const bool vr = r >= 0 && r < L, vc = c < NW;
+    const float* ar = A + (size_t)(vr ? r : 0) * K;
+    f32x16 acc = {};
+    if ((K & 7) == 0) {
+        for (int k0 = 0; k0 < K; k0 += 8) {
+            const int kb = k0 + 4 * h;
+            const f32x4 a = vr ? *reinterpret_cast<const f32x4*>(ar + kb) : f32x4{0.f, 0.f, 0.f, 0.f};
+            float b[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) b[q] = vc ? D[(size_t)(kb + q) * NW + c] : 0.f;
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], b[0], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[1], b[1], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], b[2], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[3], b[3], acc, 0, 0, 0);
+        }
+    } else {
+        for (int k0 = 0; k0 < K; k0 += 8) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int k = k0 + 4 * h + q;
+                const float a = (vr && k < K) ? ar[k] : 0.f;
+                const float b = (vc && k < K) ? D[(size_t)k * NW + c] : 0.f;
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 16; ++e) out[((e & 3) + 8 * (e >> 2) + 4 * h) * ldo + i] = acc[e];
+}
+
+__device__ __forceinline__ void p_block(const double* __restrict__ A, int L, int K, const double* __restrict__ D, int NW,
+                                        int r0, int c0, double* out, int ldo)
+{
+    const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
+    const int r = r0 + i, c = c0 + i;
+    const bool vr = r >= 0 && r < L, vc = c < NW;
+    const double* ar = A + (size_t)(vr ? r : 0) * K;
+    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+    if ((K & 7) == 0) {
+        for (int k0 = 0; k0 < K; k0 += 8) {
+            const int kb = k0 + 2 * g;
+            const f64x2 a = vr ? *reinterpret_cast<const f64x2*>(ar + kb) : f64x2{0.0, 0.0};
+            const double b0 = vc ? D[(size_t)kb * NW + c] : 0.0;
+            const double b1 = vc ? D[(size_t)(kb + 1) * NW + c] : 0.0;
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[0], b0, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[1], b1, acc, 0, 0, 0);
+        }
+    } else {
+        for (int k0 = 0; k0 < K; k0 += 8) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int k = k0 + 2 * g + q;
+                const double a = (vr && k < K) ? ar[k] : 0.0;
+                const double b = (vc && k < K) ? D[(size_t)k * NW + c] : 0.0;
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) out[(g + 4 * e) * ldo + i] = acc[e];
+}
+
+// rec[nl][f] = sum_j sum_k A[nbase+nl-j][k] D[k][j][f] for nl in [0, kRows): P rows nbase-(W-1) .. nbase+kRows-1
+// (PR of them, a multiple of RB), column blocks `slab` at a time through the LDS slab Pl.
+template <typename T>
+__device__ void tile_recon(const T* __restrict__ A, int L, int K, const T* __restrict__ D, int W, int F, int nbase,
+                           int PR, int slab, T* rec, T* Pl)
+{
+    constexpr int RB = Tile<T>::RB, CB = Tile<T>::CB;
+    const int NW = W * F, ncb = (NW + CB - 1) / CB, nrb = PR / RB, ldo = slab * CB;
+    const int wave = threadIdx.x >> 6, rbase = nbase - (W - 1);
+    for (int e = threadIdx.x; e < kRows * F; e += kThreads) rec[e] = T(0);
+    for (int cb0 = 0; cb0 < ncb; cb0 += slab) {
+        const int nb = min(slab, ncb - cb0);
+        for (int it = wave; it < nrb * nb; it += kThreads / 64) {
+            const int rb = it % nrb, cbi = it / nrb;
+            p_block(A, L, K, D, NW, rbase + rb * RB, (cb0 + cbi) * CB, Pl + (size_t)rb * RB * ldo + cbi * CB, ldo);
+        }
+        __syncthreads();
+        const int c_lo = cb0 * CB, c_hi = min((cb0 + nb) * CB, NW);
+        for (int e = threadIdx.x; e < kRows * F; e += kThreads) {
+            const int nl = e / F, f = e - nl * F;
+            T acc = rec[e];
+            for (int c = c_lo + ((f - c_lo % F) + F) % F; c < c_hi; c += F) {
+                const int j = c / F;
+                acc = acc + Pl[(size_t)(nl + W - 1 - j) * ldo + (c - c_lo)];
+            }
+            rec[e] = acc;
+        }
+        __syncthreads();
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void nmf_step_kernel(const T* __restrict__ Ain, T* __restrict__ Aout,
+                                                            const T* __restrict__ X, const T* __restrict__ D,
+                                                            const int* __restrict__ done, int L, int Tn, int K, int W,
+                                                            int F, int t, int PR, int slab)
+{
+    const int b = blockIdx.y;
+    if (done[b]) return;
+    extern __shared__ __align__(16) unsigned char smem[];
+    T* rec = reinterpret_cast<T*>(smem);
+    T* Pl = rec + kRows * F;
+    const int s0 = blockIdx.x * kRows;
+    const T* A = Ain + (size_t)b * L * K;
+    const int nbase = s0 + t;                                        // R[s+t] for the own rows s
+    tile_recon(A, L, K, D, W, F, nbase, PR, slab, rec, Pl);
+    for (int e = threadIdx.x; e < kRows * F; e += kThreads) {
+        const int nl = e / F, f = e - nl * F, n = nbase + nl;
+        rec[e] = n < Tn ? X[((size_t)b * Tn + n) * F + f] / fabs(rec[e]) : T(0);
+    }
+    __syncthreads();
+    const int rows = min(kRows, L - s0);
+    T* Ao = Aout + (size_t)b * L * K;
+    for (int e = threadIdx.x; e < rows * K; e += kThreads) {
+        const int sl = e / K, k = e - sl * K;
+        const T* d = D + ((size_t)k * W + t) * F;
+        T num = T(0), den = T(0);
+        for (int f = 0; f < F; ++f) {
+            num = num + d[f] * rec[sl * F + f];
+            den = den + d[f];
+        }
+        const T u = num / den;
+        const size_t o = (size_t)(s0 + sl) * K + k;
+        Ao[o] = A[o] * u;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void nmf_residual_kernel(const T* __restrict__ Abuf, const T* __restrict__ X,
+                                                                const T* __restrict__ D, const int* __restrict__ done,
+                                                                T* __restrict__ resid, double* __restrict__ part, int L,
+                                                                int Tn, int K, int W, int F, int PR, int slab)
+{
+    const int b = blockIdx.y;
+    if (done[b]) return;
+    extern __shared__ __align__(16) unsigned char smem[];
+    T* rec = reinterpret_cast<T*>(smem);
+    T* Pl = rec + kRows * F;
+    const int n0 = blockIdx.x * kRows;
+    tile_recon(Abuf + (size_t)b * L * K, L, K, D, W, F, n0, PR, slab, rec, Pl);
+    double mx = 0.0, ss = 0.0;
+    for (int e = threadIdx.x; e < kRows * F; e += kThreads) {
+        const int n = n0 + e / F;
+        if (n >= Tn) break;
+        const size_t o = ((size_t)b * Tn + n0) * F + e;
+        const T r = X[o] - rec[e];
+        resid[o] = r;
+        const double rd = (double)r;
+        mx = fmax(mx, fabs(rd));
+        ss = ss + rd * rd;
+    }
+    double* red = reinterpret_cast<double*>(Pl);                     // (the slab is free again)
+    red[threadIdx.x] = mx;
+    red[kThreads + threadIdx.x] = ss;
+    __syncthreads();
+    for (int w = kThreads / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + w]);
+            red[kThreads + threadIdx.x] = red[kThreads + threadIdx.x] + red[kThreads + threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        part[((size_t)b * gridDim.x + blockIdx.x) * 2] = red[0];
+        part[((size_t)b * gridDim.x + blockIdx.x) * 2 + 1] = red[kThreads];
+    }
+}
+
+// one workgroup (64 threads) per signal: the stop rules of hsc/modeling.py:729-740, in that order
+__global__ __launch_bounds__(64) void nmf_decide_kernel(const double* __restrict__ part, int ntiles,
+                                                        const double* __restrict__ energy, int* __restrict__ done,
+                                                        int* __restrict__ iters, int* __restrict__ stop,
+                                                        double* __restrict__ snr, double* __restrict__ rscale,
+                                                        int it1, hscnmf_params p)
+{
+    const int b = blockIdx.x;
+    if (done[b]) return;
+    __shared__ double smx[64], sss[64];
+    double mx = 0.0, ss = 0.0;
+    for (int i = threadIdx.x; i < ntiles; i += 64) {
+        mx = fmax(mx, part[((size_t)b * ntiles + i) * 2]);
+        ss = ss + part[((size_t)b * ntiles + i) * 2 + 1];
+    }
+    smx[threadIdx.x] = mx;
+    sss[threadIdx.x] = ss;
+    __syncthreads();
+    for (int w = 32; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            smx[threadIdx.x] = fmax(smx[threadIdx.x], smx[threadIdx.x + w]);
+            sss[threadIdx.x] = sss[threadIdx.x] + sss[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double rs = smx[0], s = 10.0 * log10(energy[b] / sss[0]);
+        int code = HSCNMF_STOP_RUNNING;
+        if (it1 >= p.max_iterations) code = HSCNMF_STOP_MAX_ITERATIONS;
+        else if (p.has_residual_scale && rs <= p.tolerance_residual_scale) code = HSCNMF_STOP_RESIDUAL_SCALE;
+        else if (p.has_snr && s >= p.tolerance_snr) code = HSCNMF_STOP_SNR;
+        iters[b] = it1;
+        snr[b] = s;
+        rscale[b] = rs;
+        stop[b] = code;
+        if (code != HSCNMF_STOP_RUNNING) done[b] = 1;
+    }
+}
+
+thread_local std::string g_err;
+
+}  // namespace
+
+struct hscnmf_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    std::string err;
+};
+
+static int fail(hscnmf_ctx* ctx, int code, const char* fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    (ctx ? ctx->err : g_err) = buf;
+    return code;
+}
+
+#define NMF_TRY(expr)                                                                                        \
+    do {                                                                                                     \
+        hipError_t e_ = (expr);                                                                              \
+        if (e_ != hipSuccess) { rc = fail(ctx, HSCNMF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); goto done; } \
+    } while (0)
+
+extern "C" int hscnmf_version(void) { return 1; }
+
+extern "C" const char* hscnmf_last_error(hscnmf_ctx* ctx) { return ctx ? ctx->err.c_str() : g_err.c_str(); }
+
+extern "C" int hscnmf_create(hscnmf_ctx** out, int device_id)
+{
+    if (!out) return fail(nullptr, HSCNMF_ERR_INVALID, "hscnmf_create: out is NULL");
+    *out = nullptr;
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n <= 0)
+        return fail(nullptr, HSCNMF_ERR_NO_DEVICE, "hscnmf_create: no HIP device visible (%s)", hipGetErrorString(e));
+    if (device_id < 0 || device_id >= n)
+        return fail(nullptr, HSCNMF_ERR_INVALID, "hscnmf_create: device %d out of range (%d devices)", device_id, n);
+    hscnmf_ctx* ctx = new hscnmf_ctx();
+    ctx->device = device_id;
+    e = hipSetDevice(device_id);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
+    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&ctx->ev[i]);
+    if (e != hipSuccess) {
+        int rc = fail(nullptr, HSCNMF_ERR_HIP, "hscnmf_create: %s", hipGetErrorString(e));
+        hscnmf_destroy(ctx);
+        return rc;
+    }
+    *out = ctx;
+    return HSCNMF_OK;
+}
+
+extern "C" void hscnmf_destroy(hscnmf_ctx* ctx)
+{
+    if (!ctx) return;
+    (void)hipSetDevice(ctx->device);
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    for (hipEvent_t ev : ctx->ev) if (ev) (void)hipEventDestroy(ev);
+    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    delete ctx;
+}
+
+// LDS layout of one workgroup: reconstruction tile [kRows][F], then the P slab [PR][slab * CB] (also the
+// residual kernel's reduction scratch, 2 * kThreads doubles)
+template <typename T>
+static bool lds_plan(int W, int F, int& PR, int& slab, size_t& bytes)
+{
+    constexpr int RB = Tile<T>::RB, CB = Tile<T>::CB;
+    PR = (kRows + W - 1 + RB - 1) / RB * RB;
+    const size_t rec = (size_t)kRows * F * sizeof(T), col = (size_t)PR * CB * sizeof(T);
+    if (rec + col > (size_t)kLdsBytes) return false;
+    const int ncb = (W * F + CB - 1) / CB;
+    slab = std::max(1, std::min(ncb, (int)(((size_t)kLdsBytes - rec) / col)));
+    bytes = rec + std::max(col * slab, (size_t)2 * kThreads * sizeof(double));
+    return bytes <= (size_t)kLdsBytes;
+}
+
+template <typename T>
+static int compute_t(hscnmf_ctx* ctx, const T* x, int B, int Tn, int F, const T* D, int K, int W, const T* a_init,
+                     const double* energy, const hscnmf_params& p, T* coef, T* resid, int32_t* iters, int32_t* stop,
+                     double* snr, double* rscale, double* timing)
+{
+    int rc = HSCNMF_OK;
+    const int L = Tn - W + 1, ntl = (L + kRows - 1) / kRows, ntt = (Tn + kRows - 1) / kRows, off = (W - 1) / 2;
+    const bool need_flags = p.has_residual_scale || p.has_snr;
+    int PR = 0, slab = 0;
+    size_t lds = 0;
+    T *dA[2] = {nullptr, nullptr}, *dX = nullptr, *dR = nullptr, *dD = nullptr;
+    double *dPart = nullptr, *dEn = nullptr, *dSnr = nullptr, *dRs = nullptr;
+    int *dDone = nullptr, *dIt = nullptr, *dStop = nullptr;
+    size_t freeb = 0, totalb = 0, per = 0, budget = 0;
+    int Bc = 0;
+    std::vector<int> hdone;
+    double tm[5] = {0, 0, 0, 0, 0};
+    if (!lds_plan<T>(W, F, PR, slab, lds))
+        return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_compute: W = %d, F = %d needs more than %d bytes of LDS per workgroup",
+                    W, F, kLdsBytes);
+    NMF_TRY(hipSetDevice(ctx->device));
+    NMF_TRY(hipMemGetInfo(&freeb, &totalb));
+    per = (2 * (size_t)L * K + 2 * (size_t)Tn * F) * sizeof(T) + (size_t)ntt * 2 * sizeof(double) + 3 * sizeof(double) + 3 * sizeof(int);
+    budget = p.memory_budget ? (size_t)p.memory_budget : freeb / 10 * 6;
+    Bc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)B, budget / per, (size_t)65535}));
+    NMF_TRY(hipMalloc(&dA[0], (size_t)Bc * L * K * sizeof(T)));
+    NMF_TRY(hipMalloc(&dA[1], (size_t)Bc * L * K * sizeof(T)));
+    NMF_TRY(hipMalloc(&dX, (size_t)Bc * Tn * F * sizeof(T)));
+    NMF_TRY(hipMalloc(&dR, (size_t)Bc * Tn * F * sizeof(T)));
+    NMF_TRY(hipMalloc(&dD, (size_t)K * W * F * sizeof(T)));
+    NMF_TRY(hipMalloc(&dPart, (size_t)Bc * ntt * 2 * sizeof(double)));
+    NMF_TRY(hipMalloc(&dEn, (size_t)Bc * sizeof(double)));
+    NMF_TRY(hipMalloc(&dSnr, (size_t)Bc * sizeof(double)));
+    NMF_TRY(hipMalloc(&dRs, (size_t)Bc * sizeof(double)));
+    NMF_TRY(hipMalloc(&dDone, (size_t)Bc * sizeof(int)));
+    NMF_TRY(hipMalloc(&dIt, (size_t)Bc * sizeof(int)));
+    NMF_TRY(hipMalloc(&dStop, (size_t)Bc * sizeof(int)));
+    NMF_TRY(hipMemcpyAsync(dD, D, (size_t)K * W * F * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    hdone.resize(Bc);
+    for (int c0 = 0; c0 < B; c0 += Bc) {
+        const int nb = std::min(Bc, B - c0);
+        NMF_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+        NMF_TRY(hipMemcpyAsync(dX, x + (size_t)c0 * Tn * F, (size_t)nb * Tn * F * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+        NMF_TRY(hipMemcpy2DAsync(dA[0], (size_t)L * K * sizeof(T), a_init + (size_t)c0 * Tn * K, (size_t)Tn * K * sizeof(T),
+                                 (size_t)L * K * sizeof(T), nb, hipMemcpyHostToDevice, ctx->stream));
+        NMF_TRY(hipMemcpyAsync(dEn, energy + c0, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        NMF_TRY(hipMemsetAsync(dDone, 0, (size_t)nb * sizeof(int), ctx->stream));
+        NMF_TRY(hipMemsetAsync(dIt, 0, (size_t)nb * sizeof(int), ctx->stream));
+        NMF_TRY(hipMemsetAsync(dStop, 0, (size_t)nb * sizeof(int), ctx->stream));
+        NMF_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+        int it = 0;
+        for (; it < p.max_iterations; ++it) {
+            for (int t = 0; t < W; ++t) {
+                const int g = it * W + t;
+                hipLaunchKernelGGL(nmf_step_kernel<T>, dim3(ntl, nb), dim3(kThreads), lds, ctx->stream, dA[g & 1],
+                                   dA[(g + 1) & 1], dX, dD, dDone, L, Tn, K, W, F, t, PR, slab);
+            }
+            hipLaunchKernelGGL(nmf_residual_kernel<T>, dim3(ntt, nb), dim3(kThreads), lds, ctx->stream,
+                               dA[((it + 1) * W) & 1], dX, dD, dDone, dR, dPart, L, Tn, K, W, F, PR, slab);
+            hipLaunchKernelGGL(nmf_decide_kernel, dim3(nb), dim3(64), 0, ctx->stream, dPart, ntt, dEn, dDone, dIt, dStop, dSnr,
+                               dRs, it + 1, p);
+            NMF_TRY(hipGetLastError());
+            if (need_flags && it + 1 < p.max_iterations) {       // one read of the flags per iteration, only with tolerances
+                NMF_TRY(hipMemcpyAsync(hdone.data(), dDone, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+                NMF_TRY(hipStreamSynchronize(ctx->stream));
+                if (std::all_of(hdone.begin(), hdone.begin() + nb, [](int v) { return v != 0; })) { ++it; break; }
+            }
+        }
+        NMF_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+        NMF_TRY(hipMemcpyAsync(iters + c0, dIt, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        NMF_TRY(hipMemcpyAsync(stop + c0, dStop, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        NMF_TRY(hipMemcpyAsync(snr + c0, dSnr, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        NMF_TRY(hipMemcpyAsync(rscale + c0, dRs, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        NMF_TRY(hipMemcpyAsync(resid + (size_t)c0 * Tn * F, dR, (size_t)nb * Tn * F * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+        NMF_TRY(hipStreamSynchronize(ctx->stream));
+        for (int b = 0; b < nb; ++b) {
+            // a signal that stopped after n iterations holds its coefficients in buffer (n * W) mod 2
+            const int n = iters[c0 + b];
+            if (n < 1 || n > it) { rc = fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_compute: signal %d has no result", c0 + b); goto done; }
+            T* dst = coef + (size_t)(c0 + b) * Tn * K;
+            std::memset(dst, 0, (size_t)off * K * sizeof(T));
+            std::memset(dst + (size_t)(off + L) * K, 0, (size_t)(Tn - off - L) * K * sizeof(T));
+            NMF_TRY(hipMemcpyAsync(dst + (size_t)off * K, dA[((size_t)n * W) & 1] + (size_t)b * L * K, (size_t)L * K * sizeof(T),
+                                   hipMemcpyDeviceToHost, ctx->stream));
+        }
+        NMF_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
+        NMF_TRY(hipStreamSynchronize(ctx->stream));
+        float ms[3] = {0, 0, 0};
+        for (int i = 0; i < 3; ++i) NMF_TRY(hipEventElapsedTime(&ms[i], ctx->ev[i], ctx->ev[i + 1]));
+        tm[0] += ms[0];
+        tm[1] += ms[1];
+        tm[2] += ms[2];
+        tm[3] += 1;
+        tm[4] += it;
+    }
+    if (timing) std::memcpy(timing, tm, sizeof(tm));
+done:
+    (void)hipStreamSynchronize(ctx->stream);
+    void* ptrs[] = {dA[0], dA[1], dX, dR, dD, dPart, dEn, dSnr, dRs, dDone, dIt, dStop};
+    for (void* q : ptrs) if (q) (void)hipFree(q);
+    return rc;
+}
+
+extern "C" int hscnmf_compute(hscnmf_ctx* ctx, int dtype, const void* x, int B, int T, int F, const void* D, int K, int W,
+                              const void* a_init, const double* energy, const hscnmf_params* params, void* coefficients,
+                              void* residual, int32_t* iterations, int32_t* stop, double* snr, double* residual_scale,
+                              double* timing_ms)
+{
+    if (!ctx) return fail(nullptr, HSCNMF_ERR_INVALID, "hscnmf_compute: ctx is NULL");
+    if (!x || !D || !a_init || !energy || !params || !coefficients || !residual || !iterations || !stop || !snr || !residual_scale)
+        return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_compute: NULL argument");
+    if (dtype != HSCNMF_F32 && dtype != HSCNMF_F64) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_compute: unknown dtype %d", dtype);
+    if (B < 1 || K < 1 || F < 1) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_compute: B = %d, K = %d, F = %d", B, K, F);
+    if (W < 2) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_compute: filter width %d (the reference needs W >= 2)", W);
+    if (T < W) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_compute: signal length %d is shorter than the filter width %d", T, W);
+    if (params->max_iterations < 1) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_compute: max_iterations = %d", params->max_iterations);
+    if ((int64_t)W * F > (1 << 24) || (int64_t)(T - W + 1) * K > ((int64_t)1 << 31) / 8)
+        return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_compute: shape out of range");
+    if (dtype == HSCNMF_F32)
+        return compute_t<float>(ctx, (const float*)x, B, T, F, (const float*)D, K, W, (const float*)a_init, energy, *params,
+                                (float*)coefficients, (float*)residual, iterations, stop, snr, residual_scale, timing_ms);
+    return compute_t<double>(ctx, (const double*)x, B, T, F, (const double*)D, K, W, (const double*)a_init, energy, *params,
+                             (double*)coefficients, (double*)residual, iterations, stop, snr, residual_scale, timing_ms);
+}

@@ -6,7 +6,8 @@ Reference surface reproduced here (hsc/modeling.py):
   convolve1d (:149-188), reconstructSignal (:226-263), Atom (:840-864),
   ConvolutionalMatchingPursuit.computeCoefficients (:1053-1186),
   ConvolutionalSparseCoder (:1656-1669).
-The hierarchical encoder lives in hsc_amd.hierarchical and is re-exported below.
+The hierarchical encoder lives in hsc_amd.hierarchical and ConvolutionalNMF (:662-747) in hsc_amd.nmf;
+both are re-exported below.
 
 Added (the reference has no batch dimension): ConvolutionalMatchingPursuit.computeCoefficientsBatch.
 
@@ -409,6 +410,9 @@ def __getattr__(name):
     if name == 'LoCOMP':
         from . import locomp
         return locomp.LoCOMP
+    if name == 'ConvolutionalNMF':
+        from . import nmf
+        return nmf.ConvolutionalNMF
     if name in ('ConvolutionalDictionaryLearner', 'extractRandomWindows', 'extractWindows', 'extractWindowsBatch'):
         from . import learning
         return getattr(learning, name)

@@ -1,0 +1,193 @@
+"""Convolutional NMF coefficients on MI355X: the reference's ConvolutionalNMF (hsc/modeling.py:662-747)
+through libhscnmf.so (include/hscnmf.h).  DESIGN.md section 10.
+
+Reference behaviour kept:
+  * the initial coefficients are np.random.random((T, K)).astype(sequence.dtype) + 2.0 from numpy's global
+    generator, one draw per signal, in batch order;
+  * one iteration is W multiplicative steps, then the additive residual; the stop rules are checked in the
+    order nbMaxIterations, toleranceResidualScale, toleranceSnr, and nbMaxIterations=None stops after the
+    first iteration (Python 2: `int >= None` is true);
+  * the coefficients returned are the centred [T,K] array (rows (W-1)//2 .. (W-1)//2+T-W, zero elsewhere),
+    the residual is squeezed to [T] for a [K,W] dictionary or a [T] signal.
+
+Added: computeCoefficientsBatch (signals [B,T(,F)] sharing D).  There is no CPU path: without libhscnmf.so or a
+visible GPU the calls raise hsc_amd._native.HscmpError.
+"""
+import ctypes
+import logging
+import os
+
+import numpy as np
+
+from . import _native
+from .modeling import SparseApproximator, _compute_dtype
+
+logger = logging.getLogger(__name__)
+
+LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'nmf', 'libhscnmf.so')
+EXPORTS = ['hscnmf_version', 'hscnmf_create', 'hscnmf_destroy', 'hscnmf_last_error', 'hscnmf_compute']
+STOP_NAMES = {0: 'running', 1: 'max_iterations', 2: 'residual_scale', 3: 'snr'}
+
+
+class HscnmfParams(ctypes.Structure):
+    _fields_ = [('max_iterations', ctypes.c_int32), ('has_residual_scale', ctypes.c_int32), ('has_snr', ctypes.c_int32),
+                ('reserved', ctypes.c_int32), ('tolerance_residual_scale', ctypes.c_double),
+                ('tolerance_snr', ctypes.c_double), ('memory_budget', ctypes.c_uint64)]
+
+
+_lib = None
+
+
+def load_library():
+    """Load libhscnmf.so; raises (never falls back) when it is missing."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.isfile(LIB_PATH):
+        raise _native.HscmpError('libhscnmf.so is not built (%s). Run `python __graft_entry__.py build` '
+                                 '(hipcc --offload-arch=gfx950). There is no CPU fallback.' % LIB_PATH)
+    lib = ctypes.CDLL(LIB_PATH)
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib.hscnmf_version.restype = ci
+    lib.hscnmf_create.argtypes = [ctypes.POINTER(vp), ci]
+    lib.hscnmf_create.restype = ci
+    lib.hscnmf_destroy.argtypes = [vp]
+    lib.hscnmf_destroy.restype = None
+    lib.hscnmf_last_error.argtypes = [vp]
+    lib.hscnmf_last_error.restype = ctypes.c_char_p
+    lib.hscnmf_compute.argtypes = [vp, ci, vp, ci, ci, ci, vp, ci, ci, vp, vp, ctypes.POINTER(HscnmfParams),
+                                   vp, vp, vp, vp, vp, vp, vp]
+    lib.hscnmf_compute.restype = ci
+    _lib = lib
+    return lib
+
+
+class _Context(object):
+    def __init__(self, device):
+        self._lib = load_library()
+        h = ctypes.c_void_p()
+        rc = self._lib.hscnmf_create(ctypes.byref(h), int(device))
+        if rc != 0:
+            ex = _native.HscmpError('hscnmf_create failed (%d): %s' % (rc, self._lib.hscnmf_last_error(None).decode()))
+            ex.code = int(rc)
+            raise ex
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, '_h', None):
+            self._lib.hscnmf_destroy(self._h)
+            self._h = None
+
+
+_contexts = {}
+
+
+def _context(device):
+    if device not in _contexts:
+        _contexts[device] = _Context(device)
+    return _contexts[device]
+
+
+def check_shapes(T, W):
+    """The reference fails for these shapes (an empty slice, a zero-width pad); raise a clear error instead."""
+    if W < 2:
+        raise Exception('ConvolutionalNMF: the filter width must be at least 2 (got W = %d)' % W)
+    if T < W:
+        raise Exception('ConvolutionalNMF: the signal (length %d) is shorter than the filter width %d' % (T, W))
+
+
+def draw_initial_coefficients(T, K, dtype):
+    """hsc/modeling.py:684, from numpy's global generator."""
+    return np.random.random((T, K)).astype(dtype) + 2.0
+
+
+class NMFStats(object):
+    """Per-signal outcome of computeCoefficientsBatch."""
+
+    def __init__(self, iterations, stop, snr, residual_scale, timing_ms):
+        self.iterations = iterations              # int32 [B]
+        self.stop = stop                          # int32 [B], include/hscnmf.h HSCNMF_STOP_*
+        self.snr = snr                            # float64 [B], dB, of the returned residual
+        self.residual_scale = residual_scale      # float64 [B], max |residual|
+        self.timing_ms = timing_ms                # upload, iterations, download (HIP events), chunks, iterations run
+
+    def stop_reasons(self):
+        return [STOP_NAMES.get(int(s), int(s)) for s in self.stop]
+
+
+class ConvolutionalNMF(SparseApproximator):
+    """hsc/modeling.py:662-747, on the GPU."""
+
+    def __init__(self, device=0, memoryBudget=None):
+        self.device = device
+        self.memoryBudget = memoryBudget          # device bytes per chunk of signals (None: 60% of the free memory)
+        self.lastStats = None
+
+    def computeCoefficientsBatch(self, sequences, D, nbMaxIterations=None, toleranceResidualScale=None, toleranceSnr=None,
+                                 initialCoefficients=None):
+        """`sequences` [B,T] or [B,T,F], D [K,W] or [K,W,F].  Returns (coefficients [B,T,K], residuals [B,T(,F)], NMFStats).
+        initialCoefficients [B,T,K]: used instead of the reference's draw from the global generator."""
+        sequences = np.asarray(sequences)
+        assert sequences.ndim == 2 or sequences.ndim == 3
+        assert D.ndim == 2 or D.ndim == 3
+        B, T = sequences.shape[0], sequences.shape[1]
+        K, W = D.shape[0], D.shape[1]
+        check_shapes(T, W)
+        dt = _compute_dtype(sequences.dtype, D.dtype)
+        x = np.ascontiguousarray(sequences.reshape((B, T, -1)), dtype=dt)
+        D3 = np.ascontiguousarray(D.reshape((K, W, -1)), dtype=dt)
+        F = D3.shape[2]
+        assert x.shape[2] == F
+        if initialCoefficients is None:
+            a0 = np.empty((B, T, K), dtype=dt)
+            for b in range(B):
+                a0[b] = draw_initial_coefficients(T, K, sequences.dtype)
+        else:
+            a0 = np.ascontiguousarray(initialCoefficients, dtype=dt)
+            assert a0.shape == (B, T, K)
+        energy = np.array([np.sum(np.square(x[b])) for b in range(B)], dtype=np.float64)       # modeling.py:681
+
+        params = HscnmfParams()
+        params.max_iterations = 1 if nbMaxIterations is None else int(nbMaxIterations)
+        if params.max_iterations < 1:
+            params.max_iterations = 1         # (the reference checks the count after the first iteration)
+        params.has_residual_scale = toleranceResidualScale is not None
+        params.tolerance_residual_scale = 0.0 if toleranceResidualScale is None else float(toleranceResidualScale)
+        params.has_snr = toleranceSnr is not None
+        params.tolerance_snr = 0.0 if toleranceSnr is None else float(toleranceSnr)
+        params.memory_budget = 0 if self.memoryBudget is None else int(self.memoryBudget)
+
+        ctx = _context(self.device)
+        coef = np.empty((B, T, K), dtype=dt)
+        resid = np.empty((B, T, F), dtype=dt)
+        iters = np.zeros((B,), dtype=np.int32)
+        stop = np.zeros((B,), dtype=np.int32)
+        snr = np.zeros((B,), dtype=np.float64)
+        rscale = np.zeros((B,), dtype=np.float64)
+        timing = np.zeros((5,), dtype=np.float64)
+        p = _native._ptr
+        rc = ctx._lib.hscnmf_compute(ctx._h, _native.dtype_code(dt), p(x), B, T, F, p(D3), K, W, p(a0), p(energy),
+                                     ctypes.byref(params), p(coef), p(resid), p(iters), p(stop), p(snr), p(rscale), p(timing))
+        if rc != 0:
+            ex = _native.HscmpError('hscnmf_compute failed (%d): %s' % (rc, ctx._lib.hscnmf_last_error(ctx._h).decode()))
+            ex.code = int(rc)
+            raise ex
+        if sequences.ndim == 2 or D.ndim == 2:
+            resid = np.squeeze(resid, axis=2)                                                  # modeling.py:744-745
+        if np.issubdtype(sequences.dtype, np.floating) and resid.dtype != sequences.dtype:
+            coef, resid = coef.astype(sequences.dtype), resid.astype(sequences.dtype)
+        stats = NMFStats(iters, stop, snr, rscale, timing)
+        self.lastStats = stats
+        for b in range(B):
+            logger.debug('signal %d: SNR of %f dB after %d iterations, stop: %s' % (
+                b, snr[b], iters[b], STOP_NAMES.get(int(stop[b]))))
+        return coef, resid, stats
+
+    def computeCoefficients(self, sequence, D, nbMaxIterations=None, toleranceResidualScale=None, toleranceSnr=None):
+        """hsc/modeling.py:667-747.  Returns (coefficients [T,K] dense, residual [T] or [T,F])."""
+        sequence = np.asarray(sequence)
+        assert sequence.ndim == 1 or sequence.ndim == 2
+        assert D.ndim == 2 or D.ndim == 3
+        coef, resid, _ = self.computeCoefficientsBatch(sequence[np.newaxis], D, nbMaxIterations, toleranceResidualScale,
+                                                       toleranceSnr)
+        return coef[0], resid[0]
