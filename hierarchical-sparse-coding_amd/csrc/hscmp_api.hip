@@ -8,6 +8,7 @@
 
 #include "hscmp_kernels.h"
 #include "hscmp_mfma.h"
+#include "hscmp_bound.h"
 #include "hscmp_sparse.h"
 #include "hscmp_rp.h"
 #include "hscmp_rp_sparse.h"
@@ -35,6 +36,8 @@ struct hscmp_ctx {
     void* d_D = nullptr;
     void* d_w = nullptr;      // nullptr when no weights
     void* d_Dfrag = nullptr;  // MFMA fragment-ordered copy (f32, F == 1)
+    unsigned short* d_Bimg = nullptr;   // bf16 hi / lo images of the bound pass (f32, F == 1, dictionary inside its model: hscmp_bound.h)
+    float bound_cmax = 0.0f;            // >= max_k ||d_k|| |w_k|
     void* d_Dt = nullptr;     // [W][F][K] transposed copy for the sparsity-aware kernels (F > 1)
     void* d_Dc = nullptr;     // [K][F][W] chain-ordered copy for the dense chains (F > 1)
     void* d_scratch = nullptr;
@@ -77,6 +80,7 @@ struct hscmp_ctx {
     bool timed = false;
     bool timed_loop_only = false;   // the last timed launch was a hscmp_continue (no prepare / initial correlation)
     bool mfma_state = false;        // the batch's table-free state is the score-only form of the MFMA kernels
+    bool bound_state = false;       // ... and positions with best_k == -1 hold upper bounds (hscmp_bound.h)
     bool rp_last = false;           // the last loop launch was the round-parallel form (hscmp_rp.h)
     int method = 0;                 // hscmp_set_method: 0 = greedy pursuit (modeling.py:1053), 1 = LoCOMP (:1267)
     bool locomp_state = false;      // the batch was encoded by the LoCOMP loop (hscmp_continue resumes it)
@@ -169,7 +173,7 @@ extern "C" int hscmp_create(hscmp_ctx** out, int device_id)
 static void free_all(hscmp_ctx* c)
 {
     for (void* p : c->d_epi) if (p) (void)hipFree(p);
-    void* ptrs[] = {c->d_D, c->d_w, c->d_Dfrag, c->d_Dt, c->d_Dc, c->d_nzptr, c->d_nzwf, c->d_nzval, c->d_fptr, c->d_fkw, c->d_fval, c->d_rl_cnt, c->d_rl_f, c->d_scratch, c->d_rowflag, c->d_x, c->d_resid, c->d_best_c, c->d_best_k, c->d_ev_t, c->d_ev_k, c->d_ev_c,
+    void* ptrs[] = {c->d_D, c->d_w, c->d_Dfrag, c->d_Bimg, c->d_Dt, c->d_Dc, c->d_nzptr, c->d_nzwf, c->d_nzval, c->d_fptr, c->d_fkw, c->d_fval, c->d_rl_cnt, c->d_rl_f, c->d_scratch, c->d_rowflag, c->d_x, c->d_resid, c->d_best_c, c->d_best_k, c->d_ev_t, c->d_ev_k, c->d_ev_c,
                     c->d_slot_t, c->d_slot_k, c->d_slot_a, c->d_hkey, c->d_hval, c->d_head, c->d_lgram, c->d_sel_t, c->d_sel_k, c->d_sel_c, c->d_stats, c->d_energy, c->d_edge};
     for (void* p : ptrs) if (p) (void)hipFree(p);
 }
@@ -223,6 +227,7 @@ extern "C" int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W,
     if (ctx->d_D) { (void)hipFree(ctx->d_D); ctx->d_D = nullptr; }
     if (ctx->d_w) { (void)hipFree(ctx->d_w); ctx->d_w = nullptr; }
     if (ctx->d_Dfrag) { (void)hipFree(ctx->d_Dfrag); ctx->d_Dfrag = nullptr; ctx->Dfrag_bytes = 0; }
+    if (ctx->d_Bimg) { (void)hipFree(ctx->d_Bimg); ctx->d_Bimg = nullptr; }
     if (ctx->d_Dt) { (void)hipFree(ctx->d_Dt); ctx->d_Dt = nullptr; }
     if (ctx->d_Dc) { (void)hipFree(ctx->d_Dc); ctx->d_Dc = nullptr; }
     if (ctx->d_nzptr) { (void)hipFree(ctx->d_nzptr); ctx->d_nzptr = nullptr; }
@@ -321,6 +326,16 @@ extern "C" int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W,
         ctx->Dfrag_bytes = frag.size() * sizeof(float);
         HIP_TRY(ctx, hipMalloc(&ctx->d_Dfrag, ctx->Dfrag_bytes));
         HIP_TRY(ctx, hipMemcpy(ctx->d_Dfrag, frag.data(), ctx->Dfrag_bytes, hipMemcpyHostToDevice));
+        // the bound pass of the initial correlation (hscmp_bound.h): bf16 images no larger than the float32 one, and a
+        // dictionary and weights inside the error model; otherwise every encode runs the exact initial correlation
+        std::vector<unsigned short> bimg;
+        float cmax = 0.0f;
+        if ((size_t)2 * mfma_groups(K) * bound_steps(W) * 1024 <= TileF32::kMaxImageBytes &&
+            bound_build_dict_image((const float*)D, (const float*)weights, K, W, bimg, cmax)) {
+            HIP_TRY(ctx, hipMalloc((void**)&ctx->d_Bimg, bimg.size() * sizeof(unsigned short)));
+            HIP_TRY(ctx, hipMemcpy(ctx->d_Bimg, bimg.data(), bimg.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
+            ctx->bound_cmax = cmax;
+        }
     } else if (dtype == HSCMP_F64 && mfma_supported<double>(K, W, F)) {
         std::vector<double> frag;
         mfma_build_dict_image_f64((const double*)D, K, W, frag);
@@ -708,11 +723,28 @@ template <typename R> static int run_encode(hscmp_ctx* ctx, const DevParams& P, 
     const bool loc = ctx->method == HSCMP_METHOD_LOCOMP;       // (its loop keeps coefficient + atom per position: no score-only state)
     if (!loc && use_mfma(ctx, P.T) && mfma_launch_corr_init<R>(ctx->stream, P, S, (const R*)ctx->d_Dfrag, true) == 0 &&
         mfma_launch_iterate<R>(ctx->stream, P, S, (const R*)ctx->d_Dfrag, true) == 0) {
-        if (mfma_launch_corr_init<R>(ctx->stream, P, S, (const R*)ctx->d_Dfrag) != 0)
-            return fail(ctx, HSCMP_ERR_HIP, "the MFMA initial correlation could not be launched");
         mf = true;
     }
+    // float32 single-arg-max encodes: the initial correlation as upper bounds on the bf16 matrix cores, refined by the loop
+    // where a selection needs it (hscmp_bound.h).  HSCMP_EXACT_INIT=1: the exact pass everywhere.
+    bool bnd = false;
+    if constexpr (sizeof(R) == 4) {
+        if (mf && !P.blocked && !P.select_only && ctx->d_Bimg && !getenv("HSCMP_EXACT_INIT") &&
+            bound_launch_corr_init(ctx->stream, P, S, (const float*)ctx->d_Dfrag, ctx->d_Bimg, ctx->bound_cmax, true) == 0)
+            bnd = true;
+    }
+    if (mf) {
+        int rc;
+        if constexpr (sizeof(R) == 4) rc = bnd ? bound_launch_corr_init(ctx->stream, P, S, (const float*)ctx->d_Dfrag, ctx->d_Bimg, ctx->bound_cmax)
+                                               : mfma_launch_corr_init<R>(ctx->stream, P, S, (const R*)ctx->d_Dfrag);
+        else rc = mfma_launch_corr_init<R>(ctx->stream, P, S, (const R*)ctx->d_Dfrag);
+        if (rc != 0) return fail(ctx, HSCMP_ERR_HIP, "the MFMA initial correlation could not be launched");
+    }
+    ctx->P.bound_init = bnd ? 1 : 0;                  // (hscmp_continue resumes on the same state)
+    DevParams PL = P;
+    PL.bound_init = ctx->P.bound_init;
     ctx->mfma_state = mf;
+    ctx->bound_state = bnd;
     if (!mf && use_sparse_loop(ctx) && use_row_lists(ctx) && !ctx->rl_filled) {
         // per-row lists of the input's non-zero cells (the level chaining writes them while it scatters)
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_rl_cnt, 0, (size_t)P.B * P.T * sizeof(int), ctx->stream));
@@ -732,8 +764,15 @@ template <typename R> static int run_encode(hscmp_ctx* ctx, const DevParams& P, 
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
     bool mfi = false;
+    if (mf && getenv("HSCMP_INIT_ONLY")) {
+        // diagnostic / test knob: stop behind the initial correlation (its best_c / best_k through hscmp_get_device_view)
+        HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+        ctx->timed = true; ctx->timed_loop_only = false;
+        ctx->variant = bnd ? "bound_init" : "mfma_init";
+        return HSCMP_OK;
+    }
     if (mf) {
-        if (launch_mfma_loop<R>(ctx, P, S) != 0)
+        if (launch_mfma_loop<R>(ctx, PL, S) != 0)
             return fail(ctx, HSCMP_ERR_HIP, "the MFMA loop could not be launched on the state of the MFMA initial correlation");
         mfi = true;
     }
@@ -756,7 +795,8 @@ template <typename R> static int run_encode(hscmp_ctx* ctx, const DevParams& P, 
     HIP_TRY(ctx, hipGetLastError());
     ctx->timed = true; ctx->timed_loop_only = false;
     ctx->variant = std::string(mf ? "mfma" : own_init ? "own" : spi ? (ctx->d_nzptr ? "dictlist" : "sparse") : "generic") + "_init+" + (loc ? (locs ? "locomp_dictlist" : locm ? "locomp_mfma" : "locomp") : mfi ? "mfma" : spl ? (ctx->d_nzptr ? "dictlist" : "gathered") : "generic") +
-                   "_loop_" + (sizeof(R) == 4 ? "f32" : "f64") + ((mfi || spl) && ctx->rp_last ? std::string("_rp") : mfi && mfma_last_group() > 1 ? "_x" + std::to_string(mfma_last_group()) : std::string());
+                   "_loop_" + (sizeof(R) == 4 ? "f32" : "f64") + (bnd ? "_bound" : "") +
+                   ((mfi || spl) && ctx->rp_last ? std::string("_rp") : mfi && mfma_last_group() > 1 ? "_x" + std::to_string(mfma_last_group()) : std::string());
     return HSCMP_OK;
 }
 

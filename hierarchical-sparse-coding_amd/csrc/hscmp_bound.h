@@ -1,0 +1,328 @@
+// hscmp_bound.h -- the initial correlation as certified UPPER BOUNDS on the bf16 matrix cores (float32, F == 1).
+//
+// What the greedy loop needs from the initial correlation is the per-position score max_k |c[t,k] * w_k| of
+// DESIGN.md section 2, but only for positions that can win a selection.  This pass writes an upper bound
+// ub[t] >= score[t] into best_c and best_k[t] = -1 ("bound, not a score"); the loop computes the exact score
+// of such a position the first time it wins a selection (MfmaRecorr::refine).  Outputs
+// stay bit-identical: the arg-max over bounds and exact scores, refined until the winner is exact, is the
+// arg-max over exact scores with the same tie rule.
+//
+// The products: every float32 operand v splits into bf16 hi = rn(v), lo = rn(v - hi) (v - hi is exact in
+// float32), and the tile sums hi.hi + hi.lo + lo.hi on v_mfma_f32_32x32x16_bf16 (3/16 of the cycles of the
+// float32 form: 12 instead of 32 MFMAs per 32 x 32 tile and atom group at W = 64, each 32 cycles instead of 64;
+// measured in DESIGN.md section 11).
+//
+// ---- derivation of the error constant ------------------------------------------------------------------------
+// u = 2^-8 (bf16 round to nearest), u' = 2^-23 (one accumulation step of the matrix core, ANY order and ANY
+// rounding direction), u'' = 2^-24 (float32 round to nearest), n = 3 * 16 * SB <= 192 products per output,
+// W <= 16 * SB <= 64 taps.  For x (signal) and d (atom) write x = xh + xl + xr (xr the split remainder):
+//   |x - xh| <= u|x|,  |xl| <= (1+u) u |x|,  |xr| <= u |x - xh| <= u^2 |x|, and the same for d.
+// (1) dropped terms: x d - (xh dh + xh dl + xl dh) = xh dr + xl dl + xl dr + xr d, so per tap
+//       |dropped| <= u^2 ((1+u) + (1+u)^2 + (1+u) u + 1) |x||d| = u^2 (3 + 4u + 2u^2) |x||d| = 4.6020e-5 |x||d|.
+// (2) the matrix core: each bf16 product is exact in float32 (8 x 8 significant bits; the input ranges below keep
+//       every product normal), the sum of n products with relative error <= u' per step in any order is off by at
+//       most gamma_n(u') sum|products| (gamma_n = n u' / (1 - n u') = 2.2889e-5), and
+//       sum|products| <= (1+u)^2 (1 + 2u) |x||d| = 1.015686 |x||d|  ->  2.3248e-5 |x||d|.
+//     A partial sum that cancels below 2^-126 may be flushed to zero: at most n 2^-126 |w_k| < 2^-88 absolute,
+//     covered by kBoundAbs.
+// (3) the score is NOT the exact real sum but the pinned float32 fmaf chain over the W taps:
+//       |chain - sum| <= gamma_W(u'') sum|x||d| <= 64 2^-24 / (1 - 64 2^-24) = 3.8147e-6 per |x||d|.
+//   Together, per atom:  |chain_k - acc_k| <= eps_0 sum_w |x_w||d_kw| <= eps_0 ||x_win||_2 ||d_k||_2   (Cauchy-Schwarz)
+//       eps_0 = 4.6020e-5 + 2.3248e-5 + 3.8147e-6 = 7.3083e-5  (= 2^-13.74).
+// (4) the bound's own arithmetic.  score_k = rn(|chain_k w_k|) <= (1+u'')|chain_k||w_k|, and the tile's
+//     v_k = rn(acc_k w_k) >= (1-u'')|acc_k w_k|, so
+//       score <= (1+u'')/(1-u'') max_k v_k + (1+u'') eps_0 ||x_win|| max_k ||d_k|| |w_k|.
+//     The tile forms ub = fmaf(M, 1 + 2^-20, rn(rn(kBoundEps * rn(sqrt(ss))) * cmax) + 2^-80), with M = max_k v_k,
+//     ss the float32 sum of (xh+xl)^2 over the 16 SB taps of the window (xh + xl is exact; ||x|| <= ||xh+xl|| / (1-u^2)),
+//     cmax >= max_k ||d_k|| |w_k| rounded up on the host.  Every rounding of that expression (at most 40 float32
+//     roundings and a sqrt good to 2 ulp) loses less than a factor 1 - 2^-17, and kBoundEps = 2^-13 = 1.2207e-4 is
+//     1.67 eps_0: ub >= score with room to spare.  M's factor 1 + 2^-20 after the final rounding still exceeds
+//     (1+u'')/(1-u'') = 1 + 2^-23.
+//
+// Inputs outside the model run the exact float32 tile (same kernel, same result as corr_init_mfma_kernel):
+//   a chunk (with its halo) that holds a sample that is not finite, or a non-zero |x| outside [2^-60, 2^60];
+//   a dictionary (or weights) with a non-zero magnitude outside [2^-30, 2^30] does not get a bf16 image at all
+//   (hscmp_set_dictionary), and the encode runs corr_init_mfma_kernel.
+// tools/bf16_bound_probe.hip checks assumption (2) on the hardware (profiles/r05_bf16_probe.txt).
+#pragma once
+
+#include "hscmp_mfma.h"
+
+#include <cmath>
+#include <cstring>
+
+namespace hscmp {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr float kBoundEps = 0x1p-13f;        // >= 1.67 eps_0 (see above)
+constexpr float kBoundRel = 1.0f + 0x1p-20f;
+constexpr float kBoundAbs = 0x1p-80f;
+constexpr float kBoundXMin = 0x1p-60f, kBoundXMax = 0x1p60f;     // signal samples (per chunk, on the device)
+constexpr double kBoundDMin = 0x1p-30, kBoundDMax = 0x1p30;     // dictionary entries and weights (host)
+
+// bf16 round-to-nearest-even of a finite float32 whose magnitude is far from FLT_MAX: the bits of the bf16 value as a float32
+__host__ __device__ inline unsigned bf16_rn_bits(unsigned b) { return (b + 0x7fffu + ((b >> 16) & 1u)) & 0xffff0000u; }
+__host__ __device__ inline void bf16_split(float v, unsigned short& hi, unsigned short& lo)
+{
+    unsigned b;
+    memcpy(&b, &v, 4);
+    const unsigned hb = bf16_rn_bits(b);
+    float hf;
+    memcpy(&hf, &hb, 4);
+    const float r = v - hf;                                     // exact
+    unsigned rb;
+    memcpy(&rb, &r, 4);
+    hi = (unsigned short)(hb >> 16);
+    lo = (unsigned short)(bf16_rn_bits(rb) >> 16);
+}
+
+// k-steps of 16 taps for the filter width (the bound pass is built for SB = 1, 2, 4: the float32 chunk counts 2, 4, 8)
+inline int bound_steps(int W) { return (W + 15) / 16; }
+
+// host: the two bf16 images Bimg[img][g][s][lane][8] (img 0 = hi, 1 = lo): element j of lane l in (group g, k-step s) is
+// D[32g + (l&31)][16s + 8(l>>5) + j] -- the A-operand map of v_mfma_f32_32x32x16_bf16; zero padded.  Also
+// cmax >= max_k ||d_k|| |w_k| (rounded up).  Returns false when the dictionary or the weights lie outside the model.
+inline bool bound_build_dict_image(const float* D, const float* wts, int K, int W, std::vector<unsigned short>& out, float& cmax)
+{
+    const int G = mfma_groups(K), SB = bound_steps(W);
+    const size_t per = (size_t)G * SB * 64 * 8;
+    out.assign(2 * per, 0);
+    double cm = 0.0;
+    auto in_model = [](double a) { return std::isfinite(a) && (a == 0.0 || (std::fabs(a) >= kBoundDMin && std::fabs(a) <= kBoundDMax)); };
+    for (int k = 0; k < K; ++k) {
+        double n2 = 0.0;
+        for (int w = 0; w < W; ++w) {
+            const double v = D[(size_t)k * W + w];
+            if (!in_model(v)) return false;
+            n2 += v * v;
+        }
+        const double wk = wts ? (double)wts[k] : 1.0;
+        if (!in_model(wk)) return false;
+        cm = std::max(cm, std::sqrt(n2) * std::fabs(wk));
+    }
+    for (int g = 0; g < G; ++g)
+        for (int s = 0; s < SB; ++s)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int j = 0; j < 8; ++j) {
+                    const int k = 32 * g + (lane & 31), w = 16 * s + 8 * (lane >> 5) + j;
+                    if (k >= K || w >= W) continue;
+                    unsigned short hi, lo;
+                    bf16_split(D[(size_t)k * W + w], hi, lo);
+                    const size_t i = (((size_t)g * SB + s) * 64 + lane) * 8 + j;
+                    out[i] = hi;
+                    out[per + i] = lo;
+                }
+    cm *= 1.0 + 0x1p-30;                                        // (the double sum and sqrt: relative error < 2^-45)
+    float f = (float)cm;
+    if ((double)f < cm) f = std::nextafter(f, INFINITY);
+    cmax = f;
+    return true;
+}
+
+__device__ __forceinline__ float bf16_lo_f(unsigned w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf16_hi_f(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
+
+// One 32-position tile against all atom groups: the bound of every position (lanes 0..31: position = lane).
+//   bimg: LDS [hi image][lo image];  xh, xl: the chunk's bf16 halves in LDS, 4-byte aligned, index 0 = the first tap
+//   of the tile's first position.  B operand of k-step s, lane (r, h): samples r + 16s + 8h + j, j = 0..7 -- 8
+//   consecutive bf16 at an odd or even start: five aligned dwords and v_alignbit.
+template <int SB, bool HAS_W>
+__device__ __forceinline__ float bound_tile(const bf16x8* __restrict__ bimg_h, const bf16x8* __restrict__ bimg_l,
+                                            const unsigned short* __restrict__ xh, const unsigned short* __restrict__ xl,
+                                            const float* __restrict__ wts, int G, int lane, float cmax)
+{
+    const int r = lane & 31, h = lane >> 5;
+    const unsigned* xh32 = reinterpret_cast<const unsigned*>(xh);
+    const unsigned* xl32 = reinterpret_cast<const unsigned*>(xl);
+    const unsigned sh = 16u * (unsigned)(r & 1);
+    u32x4 bh[SB], bl[SB];
+    float ss = 0.0f;
+#pragma unroll
+    for (int s = 0; s < SB; ++s) {
+        const int w0 = (r >> 1) + 8 * s + 4 * h;
+        unsigned a[5], b[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) { a[i] = xh32[w0 + i]; b[i] = xl32[w0 + i]; }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            bh[s][i] = __builtin_amdgcn_alignbit(a[i + 1], a[i], sh);
+            bl[s][i] = __builtin_amdgcn_alignbit(b[i + 1], b[i], sh);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {                           // ||xh + xl||^2 over this half-wave's taps (xh + xl exact)
+            const float y0 = bf16_lo_f(bh[s][i]) + bf16_lo_f(bl[s][i]);
+            const float y1 = bf16_hi_f(bh[s][i]) + bf16_hi_f(bl[s][i]);
+            ss = fmaf(y0, y0, ss);
+            ss = fmaf(y1, y1, ss);
+        }
+    }
+    ss = ss + swap_halves_f(ss, h);                             // both halves of the window (taps 16s + 0..15)
+    float bs = 0.0f;
+    auto katom = [&](int kbase, int e) { return kbase + (e & 3) + 8 * (e >> 2); };
+    auto chain = [&](int g, f32x16& acc) {
+        f32x16 z;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) z[e] = 0.0f;
+        acc = z;
+#pragma unroll
+        for (int s = 0; s < SB; ++s) {
+            const bf16x8 ah = bimg_h[(g * SB + s) * 64 + lane], al = bimg_l[(g * SB + s) * 64 + lane];
+            const bf16x8 xbh = __builtin_bit_cast(bf16x8, bh[s]), xbl = __builtin_bit_cast(bf16x8, bl[s]);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xbh, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xbl, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xbh, acc, 0, 0, 0);
+        }
+    };
+    auto reduce = [&](const f32x16& acc, int g) {
+        const int kbase = 32 * g + 4 * h;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) mfma_reduce_pair<HAS_W>(acc[2 * e], acc[2 * e + 1], katom(kbase, 2 * e), katom(kbase, 2 * e + 1), wts, bs);
+    };
+    // two accumulators: the reduction of group g-1 runs beside the MFMAs of group g
+    f32x16 acc0, acc1;
+    chain(0, acc0);
+    int g = 1;
+    for (; g + 1 < G; g += 2) {
+        chain(g, acc1);
+        reduce(acc0, g - 1);
+        chain(g + 1, acc0);
+        reduce(acc1, g);
+    }
+    if (g < G) {
+        chain(g, acc1);
+        reduce(acc0, g - 1);
+        reduce(acc1, g);
+    } else {
+        reduce(acc0, G - 1);
+    }
+    bs = fmaxf(bs, swap_halves_f(bs, h));
+    if (ss == 0.0f) return bs;                                  // all-zero window: every product and sum is an exact 0
+    const float e = __fmul_rn(__fmul_rn(kBoundEps, __fsqrt_rn(ss)), cmax) + kBoundAbs;
+    return fmaf(bs, kBoundRel, e);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The bound pass: the persistent grid of corr_init_mfma_kernel over (signal, 2048-position chunk) items.
+// LDS: [bf16 hi image][bf16 lo image][weights 32*G][chunk: bf16 hi + bf16 lo halves, or the float32 chunk of a chunk
+// outside the model].  A chunk outside the model (see the header) runs mfma_tile_score on the float32 image in global
+// memory (L2-resident): the exact score and group hint, bit for bit what corr_init_mfma_kernel writes.
+// A position whose bound came out as an exact 0 (all-zero window) gets the hint 0 like the exact tile: it is exact.
+// ------------------------------------------------------------------------------------------------
+template <int SB> __host__ __device__ constexpr int bound_chunk_samples() { return kMfmaChunk + 16 * SB + 32; }
+
+template <int SB, bool HAS_W>
+__global__ __launch_bounds__(kThreads) void corr_bound_kernel(DevParams P, State<float> S, MfmaArgs A,
+                                                              const unsigned short* __restrict__ bimg, float cmax)
+{
+    constexpr int S4C = 2 * SB;
+    constexpr int nx = bound_chunk_samples<SB>();       // chunk + 16 SB taps + the last tile's lane offset (even)
+    static_assert(nx <= kMfmaChunkLoads * kThreads, "staging registers");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int G = A.G;
+    const int nimg = G * SB * 64;                       // 16-byte fragments per image
+    bf16x8* bh = reinterpret_cast<bf16x8*>(smem);
+    bf16x8* bl = bh + nimg;
+    float* wts = reinterpret_cast<float*>(bl + nimg);
+    char* xbuf = reinterpret_cast<char*>(wts + 32 * G);
+    unsigned short* xh = reinterpret_cast<unsigned short*>(xbuf);
+    unsigned short* xl = xh + nx;
+    float* xs = reinterpret_cast<float*>(xbuf);         // (same bytes: a chunk is staged in one form or the other)
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int T = P.T;
+    const int cps = (T + kMfmaChunk - 1) / kMfmaChunk;
+    const int nitems = cps * P.B;
+
+    lds_copy16(bh, bimg, 2 * nimg * 16);
+    if (HAS_W) for (int i = tid; i < 32 * G; i += kThreads) wts[i] = i < P.K ? S.weights[i] : 0.0f;
+
+    float xr[kMfmaChunkLoads];
+    auto fetch = [&](int item) {                        // zero padding of 'same' (:159-164), as corr_init_mfma_kernel
+        const int b = item / cps, c0 = (item % cps) * kMfmaChunk;
+        const float* x = S.residual + (int64_t)b * T;
+#pragma unroll
+        for (int u = 0; u < kMfmaChunkLoads; ++u) {
+            const int i = u * kThreads + tid;
+            const int g = c0 - P.off + i;
+            xr[u] = (i < nx && g >= 0 && g < T) ? x[g] : 0.0f;
+        }
+    };
+
+    int item = blockIdx.x;
+    if (item < nitems) fetch(item);
+    for (; item < nitems; item += gridDim.x) {
+        bool out = false;
+#pragma unroll
+        for (int u = 0; u < kMfmaChunkLoads; ++u) {
+            const float a = fabsf(xr[u]);
+            out |= !(a <= kBoundXMax) || (a != 0.0f && a < kBoundXMin);      // (NaN fails the first test)
+        }
+        const bool exact = __syncthreads_or(out) != 0;  // (also: every tile of the previous chunk has read the buffer)
+#pragma unroll
+        for (int u = 0; u < kMfmaChunkLoads; ++u) {
+            const int i = u * kThreads + tid;
+            if (i < nx) {
+                if (exact) xs[i] = xr[u];
+                else { unsigned short hi, lo; bf16_split(xr[u], hi, lo); xh[i] = hi; xl[i] = lo; }
+            }
+        }
+        __syncthreads();
+        const int next = item + gridDim.x;
+        if (next < nitems) fetch(next);                 // in flight while this chunk is computed
+        const int b = item / cps, c0 = (item % cps) * kMfmaChunk;
+        const int npos = min(kMfmaChunk, T - c0);
+        const int ntiles = (npos + 31) / 32;
+        for (int q = wv; q < ntiles; q += kWaves) {
+            float sc;
+            int grp;
+            if (exact) sc = mfma_tile_score<S4C, HAS_W>(A.dimg, xs + 32 * q, wts, G, S4C, lane, grp);
+            else {
+                sc = bound_tile<SB, HAS_W>(bh, bl, xh + 32 * q, xl + 32 * q, wts, G, lane, cmax);
+                grp = sc == 0.0f ? 0 : -1;              // an exact 0 is a score (hint 0, as the exact tile); else a bound
+            }
+            const int t = c0 + 32 * q + lane;
+            if (lane < 32 && t < T) {
+                S.best_c[(int64_t)b * T + t] = sc;
+                S.best_k[(int64_t)b * T + t] = grp;
+            }
+        }
+    }
+}
+
+// LDS bytes of the bound pass
+inline size_t bound_lds_bytes(int G, int SB) { return (size_t)2 * G * SB * 1024 + (size_t)32 * G * 4 + (size_t)(kMfmaChunk + 16 * SB + 32) * 4; }
+
+template <int SB, bool HAS_W>
+static int bound_launch_t(hipStream_t stream, const DevParams& P, const State<float>& S, const MfmaArgs& A,
+                          const unsigned short* bimg, float cmax, bool dry)
+{
+    const size_t lds = bound_lds_bytes(A.G, SB);
+    auto kern = corr_bound_kernel<SB, HAS_W>;
+    if (set_dyn_lds((const void*)kern, lds) != hipSuccess) return -1;
+    if (dry) return 0;
+    const int cus = mfma_device_cus();
+    const int per_cu = cached_blocks_per_cu((const void*)kern, kThreads, lds);
+    const int64_t nitems = (int64_t)((P.T + kMfmaChunk - 1) / kMfmaChunk) * P.B;
+    int64_t grid = (int64_t)cus * per_cu;
+    if (grid > nitems) grid = nitems;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), lds, stream, P, S, A, bimg, cmax);
+    return 0;
+}
+
+// The bound pass for this shape, or -1 when it does not cover it (the caller then runs the exact corr_init):
+// the float32 chunk counts 2, 4, 8 of the compile-time MFMA kernels (W in 9..16, 25..32, 57..64).
+inline int bound_launch_corr_init(hipStream_t stream, const DevParams& P, const State<float>& S, const float* dimg,
+                                  const unsigned short* bimg, float cmax, bool dry = false)
+{
+    const MfmaArgs A = mfma_args<float>(P, S, dimg);
+    const bool hw = A.has_w != 0;
+    switch (A.S4) {
+    case 8: return hw ? bound_launch_t<4, true>(stream, P, S, A, bimg, cmax, dry) : bound_launch_t<4, false>(stream, P, S, A, bimg, cmax, dry);
+    case 4: return hw ? bound_launch_t<2, true>(stream, P, S, A, bimg, cmax, dry) : bound_launch_t<2, false>(stream, P, S, A, bimg, cmax, dry);
+    case 2: return hw ? bound_launch_t<1, true>(stream, P, S, A, bimg, cmax, dry) : bound_launch_t<1, false>(stream, P, S, A, bimg, cmax, dry);
+    default: return -1;
+    }
+}
+
+}  // namespace hscmp

@@ -199,6 +199,7 @@ struct DevParams {
     int lg_cap;         // LoCOMP: atoms of the largest group the signal's global scratch holds (lgram_doubles; larger: STOP_GROUP)
     int lc_ahead;       // LoCOMP: bit 2 = the rows of a batch of selections re-correlated behind its last one; bit 0 = the selections of a round that lie far enough apart are computed side by side, bit 1 = a group's rows
                         // re-correlated one wave per quarter on sparse dictionaries (hscmp_locomp.h; HSCMP_LOCOMP_AHEAD)
+    int bound_init;     // 1: the initial correlation left upper bounds (best_k == -1) that the MFMA loop refines on demand (hscmp_bound.h)
 };
 
 // LoCOMP: doubles of global scratch per signal for a group of up to `cap` atoms (hscmp_locomp.h, GroupGlobal): two packed triangles

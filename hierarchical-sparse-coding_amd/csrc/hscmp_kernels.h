@@ -599,6 +599,27 @@ template <typename SH> __device__ __forceinline__ FusedCtl fused_ctl_fetch(const
     return c;
 }
 
+// Positions whose bound (hscmp_bound.h) the select step of the current selection replaced by the exact score
+// (MfmaRecorr::refine), and the segment maxima that changed with them.  Every wave of the signal builds the same list
+// (wave-uniform, computed redundantly: no barrier).  It reaches memory only behind the atom's first barrier
+// (MfmaRecorr::apply_atom): until every wave has finished its selection, no wave may see another wave's refines, or
+// their views of the state -- and with them their selections -- could part.
+constexpr int kRefineCap = 4;
+template <typename R> struct RefineList {
+    int n;
+    int t[kRefineCap]; R s[kRefineCap]; int g[kRefineCap];       // refined position, exact score, group hint
+    int sg[kRefineCap]; R ms[kRefineCap]; int mt[kRefineCap];    // its segment and that segment's maximum after the refine
+    // exact score / hint of t if the list holds it (a later entry never repeats a position)
+    __device__ __forceinline__ bool find(int tq, R& so, int& go) const
+    {
+        bool f = false;
+#pragma unroll
+        for (int i = 0; i < kRefineCap; ++i)
+            if (i < n && t[i] == tq) { so = s[i]; go = g[i]; f = true; }
+        return f;
+    }
+};
+
 template <typename R> struct Sig {   // per-signal views
     R* r; R* bc; int* bk;
     int* ev_t; int* ev_k; R* ev_c;
@@ -1081,6 +1102,8 @@ __global__ __launch_bounds__(kThreads * Recorr::kGroup, Recorr::kMinWavesPerSimd
     if constexpr (GS > 1) __builtin_amdgcn_s_setprio(3);
 
     FusedCtl fc = fused_ctl_fetch(sh);                   // (behind the barrier above; only the fused bodies keep it current)
+    RefineList<R> rl;                                    // (fused bodies: refines of the current selection, see RefineList)
+    rl.n = 0;
     HSCMP_STAMP_BEGIN();
     for (int round = 0; P.max_rounds <= 0 || round < P.max_rounds; ++round) {
         if constexpr (Recorr::kMinWavesPerSimd >= 4) asm volatile("" : "+v"(tid));     // (register-constrained builds only)
@@ -1099,24 +1122,55 @@ __global__ __launch_bounds__(kThreads * Recorr::kGroup, Recorr::kMinWavesPerSimd
                 // signals every LDS round trip of a wave takes ~1000 cycles -- tools/serial_stretch_probe.hip; the scan is
                 // one batch of reads and an arg-max.)  Lane l looks at the `per` consecutive segments from l * per on -- lanes
                 // in index order, see wave_argmax_first -- and carries the position of its best.
-                Cand<R> c; c.s = (R)-1; c.i = INT_MAX;
-                const int per = (P.nseg + 63) >> 6;
-                for (int j0 = 0; j0 < per; j0 += 4) {                 // ascending i per lane: '>' keeps the first of equals
-                    // four maxima and their positions in ONE batch of LDS reads (clamped index, unconditional: a guarded
-                    // read per element compiles to a chain of dependent round trips)
-                    R sv[4]; int tv[4];
+                // A bound (hscmp_bound.h) that wins is refined -- replaced by the exact score -- and the selection runs again
+                // on the changed segment maximum, until the winner holds an exact score.  Bounds are >= the exact scores, so
+                // that winner, lowest t among equals, is the winner of the exact scores.
+                rl.n = 0;
+                for (;;) {
+                    Cand<R> c; c.s = (R)-1; c.i = INT_MAX;
+                    const int per = (P.nseg + 63) >> 6;
+                    for (int j0 = 0; j0 < per; j0 += 4) {                 // ascending i per lane: '>' keeps the first of equals
+                        // four maxima and their positions in ONE batch of LDS reads (clamped index, unconditional: a guarded
+                        // read per element compiles to a chain of dependent round trips)
+                        R sv[4]; int tv[4];
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int i = min(lane * per + j0 + u, P.nseg - 1);
-                        sv[u] = sh.seg_score[i]; tv[u] = sh.seg_t[i];
+                        for (int u = 0; u < 4; ++u) {
+                            const int i = min(lane * per + j0 + u, P.nseg - 1);
+                            sv[u] = sh.seg_score[i]; tv[u] = sh.seg_t[i];
+                        }
+                        asm volatile("" : "+v"(sv[0]), "+v"(sv[1]), "+v"(sv[2]), "+v"(sv[3]), "+v"(tv[0]), "+v"(tv[1]), "+v"(tv[2]), "+v"(tv[3]));
+                        if constexpr (Recorr::kRefine) {
+#pragma unroll
+                            for (int o = 0; o < kRefineCap; ++o)      // this selection's refined segment maxima (later entries win)
+                                if (o < rl.n) {
+#pragma unroll
+                                    for (int u = 0; u < 4; ++u)
+                                        if (min(lane * per + j0 + u, P.nseg - 1) == rl.sg[o]) { sv[u] = rl.ms[o]; tv[u] = rl.mt[o]; }
+                                }
+                        }
+#pragma unroll
+                        for (int u = 0; u < 4; ++u)
+                            if (j0 + u < per && lane * per + j0 + u < P.nseg && sv[u] > c.s) { c.s = sv[u]; c.i = tv[u]; }
                     }
-                    asm volatile("" : "+v"(sv[0]), "+v"(sv[1]), "+v"(sv[2]), "+v"(sv[3]), "+v"(tv[0]), "+v"(tv[1]), "+v"(tv[2]), "+v"(tv[3]));
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (j0 + u < per && lane * per + j0 + u < P.nseg && sv[u] > c.s) { c.s = sv[u]; c.i = tv[u]; }
+                    c = wave_argmax_first(c);
+                    p_sel = c.i;
+                    if constexpr (Recorr::kRefine) {
+                        if (!P.bound_init || p_sel == INT_MAX) break;
+                        p_sel = __builtin_amdgcn_readfirstlane(p_sel);
+                        R s_ex; int g_ex;
+                        if (rl.find(p_sel, s_ex, g_ex)) break;                 // refined by this selection: exact
+                        if (__builtin_amdgcn_readfirstlane(G.bk[p_sel]) != -1) break;   // an exact score
+                        if (rl.n == kRefineCap) {                              // (rare) the list is full: commit it, behind
+                            sy.full();                                         // every wave's reads of the state ...
+                            if (tid == 0) Recorr::refine_commit(G, sh, rl, INT_MAX, INT_MIN, INT_MAX, INT_MIN);
+                            sy.full();                                         // ... and before anybody's next read
+                            rl.n = 0;
+                        }
+                        Recorr::refine_position(P, G, A, plds, rl, p_sel, lane);
+                    } else {
+                        break;
+                    }
                 }
-                c = wave_argmax_first(c);
-                p_sel = c.i;
                 static_assert(Recorr::kScoreOnly, "the fused atom body resolves (k, c) itself");
                 // (k, c) and the null test (:974) are resolved inside apply_atom.  No position at all: every score is NaN
                 // (a pursuit that diverged until the residual overflowed) -- nothing is selected and the loop ends
@@ -1347,7 +1401,7 @@ __global__ __launch_bounds__(kThreads * Recorr::kGroup, Recorr::kMinWavesPerSimd
                 // policy-owned atom body: one batch of global loads, LDS-only barriers (hscmp_mfma.h);
                 // in blocked mode (k, c) were resolved at selection time
                 HSCMP_STAMP(11);                                   // selection + the round's checks
-                const bool stop_now = Recorr::apply_atom(P, S, G, sh, A, plds, p, k, c, P.blocked != 0, sy, fc);
+                const bool stop_now = Recorr::apply_atom(P, S, G, sh, A, plds, p, k, c, P.blocked != 0, sy, fc, rl);
                 HSCMP_STAMP(12);                                   // the atom body, entry checks included
                 if (stop_now) { fused_stop = true; break; }
                 continue;

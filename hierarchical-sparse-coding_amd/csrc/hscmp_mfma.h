@@ -701,6 +701,8 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
     using Sync = typename std::conditional<GS == 1, HwSync, SoftSync>::type;
     static constexpr int kEnergyWaves = kWaves;
     static constexpr bool kScoreOnly = true;    // best_c[t] holds max_k |c[t,k]*w_k|; (k, c) resolved on selection
+    // float32: best_c[t] may hold an upper bound instead (best_k[t] == -1, hscmp_bound.h), refined when it wins a selection
+    static constexpr bool kRefine = std::is_same<Tile, TileF32>::value;
     static constexpr int kBook = 192;           // bookkeeping thread: lane 0 of wave 3, idle while waves 0.. rescan segments
     using R = typename Tile::R;
     static constexpr int TP = Tile::TP;
@@ -872,13 +874,97 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
         c_out = wave_bcast(bc, best.i & (Tile::GA - 1));
     }
 
+    // ---- refining a bound --------------------------------------------------------------
+    // Position t holds an upper bound (best_k[t] == -1): its exact score and group hint, by every wave for itself.
+    // Exactness: a position still holding a bound has never been re-correlated, so no applied atom overlaps its window
+    // (an atom at p changes samples p - off .. p - off + W - 1 and re-correlates every row whose window holds one of
+    // them, p - (W-1) .. p + (W-1), clipped), and its window outside the signal is still the ZERO padding of the initial
+    // table (the edge bits of DESIGN.md section 2 are set only by a re-correlation; the stale row T-1 is a re-correlated
+    // row).  So the residual, zero padded, IS the window the initial correlation saw, and the pinned chain of every atom
+    // over it (resolve_chain: bit for bit the MFMA chain) reproduces the score and the hint of corr_init_mfma_kernel.
+    // The residual is the engine's own buffer: a caller's input that changes between resumed rounds does not matter.
+    static __device__ __forceinline__ void refine(const DevParams& P, const Sig<R>& Gs, const Args& A, char* lds, int t, int lane,
+                                                  R& s_out, int& g_out)
+    {
+        const Layout L = layout(P, A, lds);
+        const int S4 = S4C > 0 ? S4C : A.S4;
+        R* rw = L.rwin_w + (ltid() >> 6) * L.wp;            // this wave's strip (taps past W stay zero)
+        __builtin_amdgcn_wave_barrier();
+        for (int w = lane; w < P.W; w += 64) {
+            const int g = t - P.off + w;
+            rw[w] = (g >= 0 && g < P.T) ? Gs.r[g] : (R)0;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+        // lane l: atoms l, l + 64, ...; the score of the tile (|c * w_k|, max over atoms) and the lowest atom attaining it,
+        // whose group is the tile's hint (mfma_tile_score: the lowest group that holds an atom attaining the maximum)
+        R best = (R)-1;
+        int bk = INT_MAX;
+        for (int k = lane; k < P.K; k += 64) {
+            const R c = Tile::template resolve<S4C>(L.dimg, rw, k, S4);
+            const R v = HAS_W ? rabs(c * L.wts[k]) : rabs(c);
+            if (v > best) { best = v; bk = k; }
+        }
+        const int mb = wave_max_i32(__float_as_int(best));   // scores are >= 0 and finite here: bit order is value order
+        const int kmin = wave_min_i32(__float_as_int(best) == mb ? bk : INT_MAX);
+        s_out = __int_as_float(mb);
+        g_out = kmin >> 5;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+    }
+
+    // refine t and append it to the list, with the new maximum of its segment (the stored scores of the segment, this
+    // selection's refined ones in place of their bounds)
+    static __device__ __forceinline__ void refine_position(const DevParams& P, const Sig<R>& Gs, const Args& A, char* lds,
+                                                           RefineList<R>& rl, int t, int lane)
+    {
+        R s_ex;
+        int g_ex;
+        refine(P, Gs, A, lds, t, lane, s_ex, g_ex);
+        const int i = rl.n;
+        const int sg = t >> P.seg_shift;
+        // (constant indices only: the list stays in registers)
+#pragma unroll
+        for (int j = 0; j < kRefineCap; ++j) if (j == i) { rl.t[j] = t; rl.s[j] = s_ex; rl.g[j] = g_ex; }
+        rl.n = i + 1;
+        const int t0 = sg << P.seg_shift, t1 = min(P.T, t0 + P.seg);
+        const int per = P.seg >> 6;                         // consecutive positions per lane (wave_argmax_first)
+        Cand<R> best; best.s = (R)-1; best.i = INT_MAX;
+        for (int j = 0; j < per; ++j) {
+            const int tq = t0 + lane * per + j;
+            if (tq < t1) {
+                R v = Gs.bc[tq];
+                R so; int go;
+                if (rl.find(tq, so, go)) v = so;
+                if (v > best.s) { best.s = v; best.i = tq; }
+            }
+        }
+        best = wave_argmax_first(best);
+        const int bt = __builtin_amdgcn_readfirstlane(best.i);
+#pragma unroll
+        for (int j = 0; j < kRefineCap; ++j) if (j == i) { rl.sg[j] = sg; rl.ms[j] = best.s; rl.mt[j] = bt; }
+    }
+
+    // the list to memory (one thread): scores outside the rows [rlo, rhi] (those the atom re-correlates and stores itself),
+    // segment maxima outside the segments [slo, shi] (those the atom rescans)
+    template <typename SH>
+    static __device__ __forceinline__ void refine_commit(const Sig<R>& Gs, SH& sh, const RefineList<R>& rl, int rlo, int rhi, int slo, int shi)
+    {
+#pragma unroll
+        for (int i = 0; i < kRefineCap; ++i) {
+            if (i >= rl.n) break;
+            if (rl.t[i] < rlo || rl.t[i] > rhi) { Gs.bc[rl.t[i]] = rl.s[i]; Gs.bk[rl.t[i]] = rl.g[i]; }
+            if (rl.sg[i] < slo || rl.sg[i] > shi) { sh.seg_score[rl.sg[i]] = rl.ms[i]; sh.seg_t[rl.sg[i]] = rl.mt[i]; }
+        }
+    }
+
     // One applied atom at position p: modeling.py:1106-1142.  resolved: (k, c) already known (blocked
     // selection); otherwise they are resolved here and the null test of :974 is applied.
     // Returns true when the atom loop must stop.
     template <typename SH>
     static __device__ __forceinline__ bool apply_atom(const DevParams& P, const State<R>& S, const Sig<R>& Gs,
                                                       SH& sh, const Args& A, char* lds, int p, int k, R c, bool resolved, Sync& sy,
-                                                      FusedCtl& fc)
+                                                      FusedCtl& fc, const RefineList<R>& rl)
     {
         // single arg-max rounds without a residual-scale rule: the round's own bookkeeping (:1160-1163) is done here
         const bool round_is_atom = !P.blocked && !P.has_scale;
@@ -961,13 +1047,26 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
             os[u] = (R)0;
             if (i < nsb) os[u] = Gs.bc[segbase + i];            // old scores of the touched segments
         }
+        if constexpr (kRefine) {
+            // this selection's refines are not in memory yet (RefineList): their exact scores and hints in place of the bounds
+            if (rl.n > 0) {
+                R so; int go;
+#pragma unroll
+                for (int u = 0; u < 2; ++u) if (rl.find(segbase + tid + u * kThreads, so, go)) os[u] = so;
+                if (!resolved && rl.find(p, so, go)) gh = go;
+            }
+        }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int i = tid + u * kThreads;
             if (i < nsb) L.sbs[i] = os[u];
         }
         // signals longer than 131072 samples have segments of 512+ positions: the rest of the touched segments
-        for (int i = tid + 2 * kThreads; i < nsb; i += kThreads) L.sbs[i] = Gs.bc[segbase + i];
+        for (int i = tid + 2 * kThreads; i < nsb; i += kThreads) {
+            R v = Gs.bc[segbase + i];
+            if constexpr (kRefine) { R so; int go; if (rl.n > 0 && rl.find(segbase + i, so, go)) v = so; }
+            L.sbs[i] = v;
+        }
 
         HSCMP_STAMP(8);                                         // phase A issued
         HSCMP_MARK("resolve");
@@ -1081,6 +1180,9 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
         // thread has consumed what it loaded before it arrives here (its window entry depends on it).
 #pragma unroll
         for (int u = 0; u < kUS; ++u) if (own[u]) Gs.r[rm[u]] = rv[u];
+        // this selection's refines to memory: every wave has made its selection and loaded what it reads of the state.
+        // The rows this atom re-correlates and the segments it rescans are written below anyway (visible behind B5).
+        if constexpr (kRefine) if (rl.n > 0 && tid == 0) refine_commit(Gs, sh, rl, p - (W - 1), p + (W - 1), sg0, sg1);
         if (P.has_scale) {                                      // toleranceResidualScale: max|r| of touched segments
             sy.full();                                          // (the stores above are visible to the scan)
             for (int sg = (s >> P.seg_shift) + wv; sg <= ((e - 1) >> P.seg_shift); sg += kWaves) rscan_segment(P, Gs, sh, sg, lane);

@@ -258,6 +258,11 @@ typedef struct hscmp_device_view {
     void* ev_t; void* ev_k; void* ev_c; void* stats; void* residual; void* energies;
     void* best_c; void* best_k;   /* per-position best coefficient / atom (table-free state) */
 } hscmp_device_view;
+/* best_c / best_k after a float32 encode on the matrix-core kernels hold per-position SCORES max_k |c[t,k] w_k| and
+ * the 32-atom group of the first atom attaining them, not coefficients and atoms.  A position with best_k == -1 holds
+ * an UPPER BOUND of its score instead (the bound pass of the initial correlation): its exact
+ * score is only computed if the position competes for a selection.  HSCMP_EXACT_INIT=1 (read at encode time) makes
+ * every position exact. */
 int hscmp_get_device_view(hscmp_ctx* ctx, hscmp_device_view* view);
 
 /* Durations (ms, HIP events on the context's stream) of the kernels of the last encode:
