@@ -10,6 +10,7 @@
 // reading A from one buffer of a ping-pong pair and writing the other.  After the W steps of an iteration
 // nmf_residual_kernel reconstructs once more (residual, per-tile max|r| and sum r^2) and nmf_decide_kernel takes
 // the reference's stop decision per signal on the device; a finished signal's workgroups return at once.
+// hscnmf_learn (the dictionary learner) adds, per iteration, the ratio, partial and update kernels of section 12.
 #include "../../../include/hscnmf.h"
 
 #include <hip/hip_runtime.h>
@@ -143,11 +144,12 @@ __device__ void tile_recon(const T* __restrict__ A, int L, int K, const T* __res
 template <typename T>
 __global__ __launch_bounds__(kThreads) void nmf_step_kernel(const T* __restrict__ Ain, T* __restrict__ Aout,
                                                             const T* __restrict__ X, const T* __restrict__ D,
-                                                            const int* __restrict__ done, int L, int Tn, int K, int W,
-                                                            int F, int t, int PR, int slab)
+                                                            size_t dstride, const int* __restrict__ done, int L, int Tn,
+                                                            int K, int W, int F, int t, int PR, int slab)
 {
     const int b = blockIdx.y;
     if (done[b]) return;
+    D += (size_t)b * dstride;                                        // 0: one dictionary for the batch (the coder)
     extern __shared__ __align__(16) unsigned char smem[];
     T* rec = reinterpret_cast<T*>(smem);
     T* Pl = rec + kRows * F;
@@ -178,12 +180,14 @@ __global__ __launch_bounds__(kThreads) void nmf_step_kernel(const T* __restrict_
 
 template <typename T>
 __global__ __launch_bounds__(kThreads) void nmf_residual_kernel(const T* __restrict__ Abuf, const T* __restrict__ X,
-                                                                const T* __restrict__ D, const int* __restrict__ done,
-                                                                T* __restrict__ resid, double* __restrict__ part, int L,
-                                                                int Tn, int K, int W, int F, int PR, int slab)
+                                                                const T* __restrict__ D, size_t dstride,
+                                                                const int* __restrict__ done, T* __restrict__ resid,
+                                                                double* __restrict__ part, int L, int Tn, int K, int W, int F,
+                                                                int PR, int slab)
 {
     const int b = blockIdx.y;
     if (done[b]) return;
+    D += (size_t)b * dstride;
     extern __shared__ __align__(16) unsigned char smem[];
     T* rec = reinterpret_cast<T*>(smem);
     T* Pl = rec + kRows * F;
@@ -256,6 +260,144 @@ __global__ __launch_bounds__(64) void nmf_decide_kernel(const double* __restrict
     }
 }
 
+// ---- the dictionary update of the learner (hsc/modeling.py:383-395), DESIGN.md section 12 ----------------------------
+
+// R[n][f] = X[n][f] / |recon[n][f]| for the samples n0 .. n0+kRows-1 of the tile (the updated A, the old D)
+template <typename T>
+__global__ __launch_bounds__(kThreads) void nmf_ratio_kernel(const T* __restrict__ Abuf, const T* __restrict__ X,
+                                                             const T* __restrict__ D, size_t dstride,
+                                                             const int* __restrict__ done, T* __restrict__ R, int L, int Tn,
+                                                             int K, int W, int F, int PR, int slab)
+{
+    const int b = blockIdx.y;
+    if (done[b]) return;
+    extern __shared__ __align__(16) unsigned char smem[];
+    T* rec = reinterpret_cast<T*>(smem);
+    T* Pl = rec + kRows * F;
+    const int n0 = blockIdx.x * kRows;
+    tile_recon(Abuf + (size_t)b * L * K, L, K, D + (size_t)b * dstride, W, F, n0, PR, slab, rec, Pl);
+    for (int e = threadIdx.x; e < kRows * F; e += kThreads) {
+        const int n = n0 + e / F;
+        if (n >= Tn) break;
+        const size_t o = ((size_t)b * Tn + n0) * F + e;
+        R[o] = X[o] / fabs(rec[e]);
+    }
+}
+
+// One RB x CB block of C[k][c] = sum_{sl < rows} A[s0+sl][k] Rl[sl*F + c] (c = t*F+f: the Hankel matrix of the R tile,
+// Rl[(sl+t)*F+f] = Rl[sl*F+c]).  MFMA A operand: k across lanes (A is [L][K], so a half-wave loads 32 consecutive
+// values); B operand from LDS.  The reduction runs over sl in ascending pairs (f32) / quads (f64): fixed order.
+__device__ __forceinline__ void dpart_block(const float* __restrict__ A, int rows, int K, const float* Rl, int F, int NW,
+                                            int k0, int c0, float* __restrict__ out, int ld)
+{
+    const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
+    const int k = k0 + i, c = c0 + i;
+    const bool vk = k < K, vc = c < NW;
+    f32x16 acc = {};
+    for (int s2 = 0; s2 < rows; s2 += 2) {
+        const int sl = s2 + h;
+        const bool vs = sl < rows;
+        const float a = (vk && vs) ? A[(size_t)sl * K + k] : 0.f;
+        const float r = (vc && vs) ? Rl[sl * F + c] : 0.f;
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, r, acc, 0, 0, 0);
+    }
+    if (!vc) return;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int kr = k0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        if (kr < K) out[(size_t)kr * ld + c] = acc[e];
+    }
+}
+
+__device__ __forceinline__ void dpart_block(const double* __restrict__ A, int rows, int K, const double* Rl, int F, int NW,
+                                            int k0, int c0, double* __restrict__ out, int ld)
+{
+    const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
+    const int k = k0 + i, c = c0 + i;
+    const bool vk = k < K, vc = c < NW;
+    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+    for (int s4 = 0; s4 < rows; s4 += 4) {
+        const int sl = s4 + g;
+        const bool vs = sl < rows;
+        const double a = (vk && vs) ? A[(size_t)sl * K + k] : 0.0;
+        const double r = (vc && vs) ? Rl[sl * F + c] : 0.0;
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, r, acc, 0, 0, 0);
+    }
+    if (!vc) return;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int kr = k0 + g + 4 * e;
+        if (kr < K) out[(size_t)kr * ld + c] = acc[e];
+    }
+}
+
+// Partials of one row tile (s0 .. s0+kRows-1, rows < L only): part[b][tile][k][c] = sum_s A[s][k] R[s+t][f]
+// (c = t*F+f < NW) and part[b][tile][k][NW] = sum_s A[s][k] (ascending s), for the update kernel to sum.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void nmf_dpart_kernel(const T* __restrict__ Abuf, const T* __restrict__ R,
+                                                             const int* __restrict__ done, T* __restrict__ part, int L,
+                                                             int Tn, int K, int W, int F)
+{
+    constexpr int RB = Tile<T>::RB, CB = Tile<T>::CB;
+    const int b = blockIdx.y;
+    if (done[b]) return;
+    extern __shared__ __align__(16) unsigned char smem[];
+    T* Rl = reinterpret_cast<T*>(smem);                              // R samples s0 .. s0+kRows+W-2 (0 past T)
+    const int s0 = blockIdx.x * kRows, NW = W * F, ld = NW + 1, nr = (kRows + W - 1) * F;
+    const T* Rb = R + ((size_t)b * Tn + s0) * F;
+    for (int e = threadIdx.x; e < nr; e += kThreads) Rl[e] = s0 + e / F < Tn ? Rb[e] : T(0);
+    __syncthreads();
+    const int rows = min(kRows, L - s0);
+    const T* A = Abuf + ((size_t)b * L + s0) * K;
+    T* out = part + ((size_t)b * gridDim.x + blockIdx.x) * K * ld;
+    for (int k = threadIdx.x; k < K; k += kThreads) {
+        T acc = T(0);
+        for (int sl = 0; sl < rows; ++sl) acc = acc + A[(size_t)sl * K + k];
+        out[(size_t)k * ld + NW] = acc;
+    }
+    const int nkb = (K + RB - 1) / RB, ncb = (NW + CB - 1) / CB;
+    for (int it = threadIdx.x >> 6; it < nkb * ncb; it += kThreads / 64)
+        dpart_block(A, rows, K, Rl, F, NW, (it % nkb) * RB, (it / nkb) * CB, out, ld);
+}
+
+// One workgroup per (atom k, learner b): N and den summed over the tiles in ascending order, D[k] *= N / den, then
+// D[k] /= ||D[k]|| when the norm is > 0 (hsc/utils.py:67-74).  IEEE division and sqrt; no atomics.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void nmf_dupdate_kernel(const T* __restrict__ part, int ntiles,
+                                                               const int* __restrict__ done, T* __restrict__ D, int K, int NW)
+{
+    const int k = blockIdx.x, b = blockIdx.y;
+    if (done[b]) return;
+    extern __shared__ __align__(16) unsigned char smem[];
+    T* red = reinterpret_cast<T*>(smem);                             // [kThreads] sums of squares, then [NW + 1] sums
+    T* sum = red + kThreads;
+    const int ld = NW + 1;
+    const size_t tstride = (size_t)K * ld;
+    const T* p = part + (size_t)b * ntiles * tstride + (size_t)k * ld;
+    for (int c = threadIdx.x; c < ld; c += kThreads) {
+        T acc = T(0);
+        for (int i = 0; i < ntiles; ++i) acc = acc + p[(size_t)i * tstride + c];
+        sum[c] = acc;
+    }
+    __syncthreads();
+    T* d = D + ((size_t)b * K + k) * NW;
+    const T den = sum[NW];
+    T ss = T(0);
+    for (int c = threadIdx.x; c < NW; c += kThreads) {
+        const T v = d[c] * (sum[c] / den);
+        sum[c] = v;
+        ss = ss + v * v;
+    }
+    red[threadIdx.x] = ss;
+    __syncthreads();
+    for (int w = kThreads / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + w];
+        __syncthreads();
+    }
+    const T nrm = sqrt(red[0]);
+    for (int c = threadIdx.x; c < NW; c += kThreads) d[c] = nrm > T(0) ? sum[c] / nrm : sum[c];
+}
+
 thread_local std::string g_err;
 
 }  // namespace
@@ -284,7 +426,7 @@ static int fail(hscnmf_ctx* ctx, int code, const char* fmt, ...)
         if (e_ != hipSuccess) { rc = fail(ctx, HSCNMF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); goto done; } \
     } while (0)
 
-extern "C" int hscnmf_version(void) { return 1; }
+extern "C" int hscnmf_version(void) { return 2; }
 
 extern "C" const char* hscnmf_last_error(hscnmf_ctx* ctx) { return ctx ? ctx->err.c_str() : g_err.c_str(); }
 
@@ -392,10 +534,10 @@ static int compute_t(hscnmf_ctx* ctx, const T* x, int B, int Tn, int F, const T*
             for (int t = 0; t < W; ++t) {
                 const int g = it * W + t;
                 hipLaunchKernelGGL(nmf_step_kernel<T>, dim3(ntl, nb), dim3(kThreads), lds, ctx->stream, dA[g & 1],
-                                   dA[(g + 1) & 1], dX, dD, dDone, L, Tn, K, W, F, t, PR, slab);
+                                   dA[(g + 1) & 1], dX, dD, (size_t)0, dDone, L, Tn, K, W, F, t, PR, slab);
             }
             hipLaunchKernelGGL(nmf_residual_kernel<T>, dim3(ntt, nb), dim3(kThreads), lds, ctx->stream,
-                               dA[((it + 1) * W) & 1], dX, dD, dDone, dR, dPart, L, Tn, K, W, F, PR, slab);
+                               dA[((it + 1) * W) & 1], dX, dD, (size_t)0, dDone, dR, dPart, L, Tn, K, W, F, PR, slab);
             hipLaunchKernelGGL(nmf_decide_kernel, dim3(nb), dim3(64), 0, ctx->stream, dPart, ntt, dEn, dDone, dIt, dStop, dSnr,
                                dRs, it + 1, p);
             NMF_TRY(hipGetLastError());
@@ -460,4 +602,136 @@ extern "C" int hscnmf_compute(hscnmf_ctx* ctx, int dtype, const void* x, int B, 
                                 (float*)coefficients, (float*)residual, iterations, stop, snr, residual_scale, timing_ms);
     return compute_t<double>(ctx, (const double*)x, B, T, F, (const double*)D, K, W, (const double*)a_init, energy, *params,
                              (double*)coefficients, (double*)residual, iterations, stop, snr, residual_scale, timing_ms);
+}
+
+// The learner (hsc/modeling.py:330-417): per chunk of learners, each iteration is the W steps, R = X/|recon| (updated A,
+// old D) into the residual buffer, the tile partials, the dictionary update, then the residual and the stop decision with
+// the new D.  Every learner owns its D ([B][K][W][F], stride K*W*F); a finished learner's D stays as it was.
+template <typename T>
+static int learn_t(hscnmf_ctx* ctx, const T* x, int B, int Tn, int F, const T* D_init, int K, int W, const T* a_init,
+                   const double* energy, const hscnmf_params& p, T* D_out, int32_t* iters, int32_t* stop, double* snr,
+                   double* rscale, double* timing)
+{
+    int rc = HSCNMF_OK;
+    const int L = Tn - W + 1, ntl = (L + kRows - 1) / kRows, ntt = (Tn + kRows - 1) / kRows, NW = W * F;
+    const size_t dsz = (size_t)K * NW, psz = (size_t)ntl * K * (NW + 1);
+    const bool need_flags = p.has_residual_scale || p.has_snr;
+    const size_t lds_part = (size_t)(kRows + W - 1) * F * sizeof(T), lds_upd = (size_t)(kThreads + NW + 1) * sizeof(T);
+    int PR = 0, slab = 0;
+    size_t lds = 0;
+    T *dA[2] = {nullptr, nullptr}, *dX = nullptr, *dR = nullptr, *dD = nullptr, *dPD = nullptr;
+    double *dPart = nullptr, *dEn = nullptr, *dSnr = nullptr, *dRs = nullptr;
+    int *dDone = nullptr, *dIt = nullptr, *dStop = nullptr;
+    size_t freeb = 0, totalb = 0, per = 0, budget = 0;
+    int Bc = 0;
+    std::vector<int> hdone;
+    double tm[5] = {0, 0, 0, 0, 0};
+    if (!lds_plan<T>(W, F, PR, slab, lds) || lds_part > (size_t)kLdsBytes || lds_upd > (size_t)kLdsBytes)
+        return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_learn: W = %d, F = %d needs more than %d bytes of LDS per workgroup",
+                    W, F, kLdsBytes);
+    NMF_TRY(hipSetDevice(ctx->device));
+    NMF_TRY(hipMemGetInfo(&freeb, &totalb));
+    per = (2 * (size_t)L * K + 2 * (size_t)Tn * F + dsz + psz) * sizeof(T) + (size_t)ntt * 2 * sizeof(double) +
+          3 * sizeof(double) + 3 * sizeof(int);
+    budget = p.memory_budget ? (size_t)p.memory_budget : freeb / 10 * 6;
+    Bc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)B, budget / per, (size_t)65535}));
+    NMF_TRY(hipMalloc(&dA[0], (size_t)Bc * L * K * sizeof(T)));
+    NMF_TRY(hipMalloc(&dA[1], (size_t)Bc * L * K * sizeof(T)));
+    NMF_TRY(hipMalloc(&dX, (size_t)Bc * Tn * F * sizeof(T)));
+    NMF_TRY(hipMalloc(&dR, (size_t)Bc * Tn * F * sizeof(T)));
+    NMF_TRY(hipMalloc(&dD, (size_t)Bc * dsz * sizeof(T)));
+    NMF_TRY(hipMalloc(&dPD, (size_t)Bc * psz * sizeof(T)));
+    NMF_TRY(hipMalloc(&dPart, (size_t)Bc * ntt * 2 * sizeof(double)));
+    NMF_TRY(hipMalloc(&dEn, (size_t)Bc * sizeof(double)));
+    NMF_TRY(hipMalloc(&dSnr, (size_t)Bc * sizeof(double)));
+    NMF_TRY(hipMalloc(&dRs, (size_t)Bc * sizeof(double)));
+    NMF_TRY(hipMalloc(&dDone, (size_t)Bc * sizeof(int)));
+    NMF_TRY(hipMalloc(&dIt, (size_t)Bc * sizeof(int)));
+    NMF_TRY(hipMalloc(&dStop, (size_t)Bc * sizeof(int)));
+    hdone.resize(Bc);
+    for (int c0 = 0; c0 < B; c0 += Bc) {
+        const int nb = std::min(Bc, B - c0);
+        NMF_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+        NMF_TRY(hipMemcpyAsync(dX, x + (size_t)c0 * Tn * F, (size_t)nb * Tn * F * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+        NMF_TRY(hipMemcpy2DAsync(dA[0], (size_t)L * K * sizeof(T), a_init + (size_t)c0 * Tn * K, (size_t)Tn * K * sizeof(T),
+                                 (size_t)L * K * sizeof(T), nb, hipMemcpyHostToDevice, ctx->stream));
+        NMF_TRY(hipMemcpyAsync(dD, D_init + (size_t)c0 * dsz, (size_t)nb * dsz * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+        NMF_TRY(hipMemcpyAsync(dEn, energy + c0, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        NMF_TRY(hipMemsetAsync(dDone, 0, (size_t)nb * sizeof(int), ctx->stream));
+        NMF_TRY(hipMemsetAsync(dIt, 0, (size_t)nb * sizeof(int), ctx->stream));
+        NMF_TRY(hipMemsetAsync(dStop, 0, (size_t)nb * sizeof(int), ctx->stream));
+        NMF_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+        int it = 0;
+        for (; it < p.max_iterations; ++it) {
+            for (int t = 0; t < W; ++t) {
+                const int g = it * W + t;
+                hipLaunchKernelGGL(nmf_step_kernel<T>, dim3(ntl, nb), dim3(kThreads), lds, ctx->stream, dA[g & 1],
+                                   dA[(g + 1) & 1], dX, dD, dsz, dDone, L, Tn, K, W, F, t, PR, slab);
+            }
+            const T* dAn = dA[((it + 1) * W) & 1];
+            hipLaunchKernelGGL(nmf_ratio_kernel<T>, dim3(ntt, nb), dim3(kThreads), lds, ctx->stream, dAn, dX, dD, dsz, dDone,
+                               dR, L, Tn, K, W, F, PR, slab);
+            hipLaunchKernelGGL(nmf_dpart_kernel<T>, dim3(ntl, nb), dim3(kThreads), lds_part, ctx->stream, dAn, dR, dDone,
+                               dPD, L, Tn, K, W, F);
+            hipLaunchKernelGGL(nmf_dupdate_kernel<T>, dim3(K, nb), dim3(kThreads), lds_upd, ctx->stream, dPD, ntl, dDone, dD,
+                               K, NW);
+            hipLaunchKernelGGL(nmf_residual_kernel<T>, dim3(ntt, nb), dim3(kThreads), lds, ctx->stream, dAn, dX, dD, dsz,
+                               dDone, dR, dPart, L, Tn, K, W, F, PR, slab);
+            hipLaunchKernelGGL(nmf_decide_kernel, dim3(nb), dim3(64), 0, ctx->stream, dPart, ntt, dEn, dDone, dIt, dStop, dSnr,
+                               dRs, it + 1, p);
+            NMF_TRY(hipGetLastError());
+            if (need_flags && it + 1 < p.max_iterations) {       // one read of the flags per iteration, only with tolerances
+                NMF_TRY(hipMemcpyAsync(hdone.data(), dDone, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+                NMF_TRY(hipStreamSynchronize(ctx->stream));
+                if (std::all_of(hdone.begin(), hdone.begin() + nb, [](int v) { return v != 0; })) { ++it; break; }
+            }
+        }
+        NMF_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+        NMF_TRY(hipMemcpyAsync(iters + c0, dIt, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        NMF_TRY(hipMemcpyAsync(stop + c0, dStop, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        NMF_TRY(hipMemcpyAsync(snr + c0, dSnr, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        NMF_TRY(hipMemcpyAsync(rscale + c0, dRs, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        NMF_TRY(hipMemcpyAsync(D_out + (size_t)c0 * dsz, dD, (size_t)nb * dsz * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+        NMF_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
+        NMF_TRY(hipStreamSynchronize(ctx->stream));
+        for (int b = 0; b < nb; ++b)
+            if (iters[c0 + b] < 1 || iters[c0 + b] > it) {
+                rc = fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: learner %d has no result", c0 + b);
+                goto done;
+            }
+        float ms[3] = {0, 0, 0};
+        for (int i = 0; i < 3; ++i) NMF_TRY(hipEventElapsedTime(&ms[i], ctx->ev[i], ctx->ev[i + 1]));
+        tm[0] += ms[0];
+        tm[1] += ms[1];
+        tm[2] += ms[2];
+        tm[3] += 1;
+        tm[4] += it;
+    }
+    if (timing) std::memcpy(timing, tm, sizeof(tm));
+done:
+    (void)hipStreamSynchronize(ctx->stream);
+    void* ptrs[] = {dA[0], dA[1], dX, dR, dD, dPD, dPart, dEn, dSnr, dRs, dDone, dIt, dStop};
+    for (void* q : ptrs) if (q) (void)hipFree(q);
+    return rc;
+}
+
+extern "C" int hscnmf_learn(hscnmf_ctx* ctx, int dtype, const void* x, int B, int T, int F, const void* D_init, int K, int W,
+                            const void* a_init, const double* energy, const hscnmf_params* params, void* D_out,
+                            int32_t* iterations, int32_t* stop, double* snr, double* residual_scale, double* timing_ms)
+{
+    if (!ctx) return fail(nullptr, HSCNMF_ERR_INVALID, "hscnmf_learn: ctx is NULL");
+    if (!x || !D_init || !a_init || !energy || !params || !D_out || !iterations || !stop || !snr || !residual_scale)
+        return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: NULL argument");
+    if (dtype != HSCNMF_F32 && dtype != HSCNMF_F64) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: unknown dtype %d", dtype);
+    if (B < 1 || K < 1 || F < 1) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: B = %d, K = %d, F = %d", B, K, F);
+    if (W < 2) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: filter width %d (the reference needs W >= 2)", W);
+    if (T < W) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: signal length %d is shorter than the filter width %d", T, W);
+    if (params->max_iterations < 1) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: max_iterations = %d", params->max_iterations);
+    if ((int64_t)W * F > (1 << 24) || (int64_t)(T - W + 1) * K > ((int64_t)1 << 31) / 8 || K > 65535)
+        return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_learn: shape out of range");
+    if (dtype == HSCNMF_F32)
+        return learn_t<float>(ctx, (const float*)x, B, T, F, (const float*)D_init, K, W, (const float*)a_init, energy, *params,
+                              (float*)D_out, iterations, stop, snr, residual_scale, timing_ms);
+    return learn_t<double>(ctx, (const double*)x, B, T, F, (const double*)D_init, K, W, (const double*)a_init, energy, *params,
+                           (double*)D_out, iterations, stop, snr, residual_scale, timing_ms);
 }

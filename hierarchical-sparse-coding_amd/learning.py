@@ -6,7 +6,7 @@ correlate -> arg-max pattern as the matching pursuit, over a batch of 2W-sample 
 runs on the GPU (hscmp_assign_windows); window extraction, the centroid update and the resets stay on
 the host and draw from numpy's RandomState in the reference's order, so a seeded run reproduces the
 reference's dictionary.  K-SVD (modeling.py:526-641) is provided on top of the GPU sparse coders.
-The multiplicative NMF learner (:330-417) is a different algorithm and out of scope.
+The multiplicative NMF learner (:330-417) is hsc_amd.nmf.ConvolutionalNMFLearner (not routed through this class).
 """
 import logging
 
@@ -194,5 +194,6 @@ class ConvolutionalDictionaryLearner(object):
         if self.algorithm == 'ksvd':
             return self._train_ksvd(X, *args, **kwargs)
         if self.algorithm == 'nmf':
-            raise NotImplementedError("algorithm='nmf' (multiplicative NMF, hsc/modeling.py:330-417) is not part of the matching-pursuit path")
+            raise NotImplementedError("algorithm='nmf' (multiplicative NMF, hsc/modeling.py:330-417) is not part of the matching-pursuit "
+                                      "path: use hsc_amd.nmf.ConvolutionalNMFLearner")
         raise Exception('Unknown training algorithm: %s' % (self.algorithm))
