@@ -25,6 +25,23 @@
 
 using namespace hscmp;
 
+// The kernels of one encode, chosen once by plan_encode before anything is queued: run_encode queues them (launch_init,
+// launch_loop) and hscmp_continue resumes the batch with the same loop.
+struct EncodePlan {
+    enum Init { kInitMfma, kInitBound, kInitSparse, kInitOwn, kInitGeneric };
+    enum Loop { kLoopMfma, kLoopSparse, kLoopGeneric, kLoopLocomp, kLoopLocompSparse, kLoopLocompMfma };
+    Init init = kInitGeneric;
+    Loop loop = kLoopGeneric;
+    bool rp = false;          // the round-parallel form of the loop (hscmp_rp.h, hscmp_rp_sparse.h)
+    int group = 1;            // signals per workgroup of the loop
+    bool packed = false;      // the four-workgroups-per-CU build of the sparse loop
+    bool f64 = false;
+    bool dict_lists = false;  // the dictionary has per-atom lists ("dictlist" kernels; "sparse" / "gathered" without)
+    bool row_lists = false;   // per-row feature lists of the input's non-zero cells (the level chaining or the init writes them)
+    bool kept_lists = false;  // ... and the loop keeps them current: it enters every cell it writes
+    bool init_only = false;   // HSCMP_INIT_ONLY (tests): stop behind the initial correlation
+};
+
 struct hscmp_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -55,7 +72,6 @@ struct hscmp_ctx {
     // d_rl_cnt / d_rl_f: the next chained encode clears those cells instead of the whole buffer (0: clear everything)
     int64_t listed_rows = 0;
     int listed_F = 0;
-    bool loop_kept_lists = false;   // the last encode ran the sparse loop with row lists (it enters every cell it writes)
     unsigned char* d_rowflag = nullptr;  // [B][T] non-zero input rows handed over by the level chaining
     bool rowflag_valid = false;
     size_t Dfrag_bytes = 0;
@@ -79,13 +95,8 @@ struct hscmp_ctx {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool timed = false;
     bool timed_loop_only = false;   // the last timed launch was a hscmp_continue (no prepare / initial correlation)
-    bool mfma_state = false;        // the batch's table-free state is the score-only form of the MFMA kernels
-    bool bound_state = false;       // ... and positions with best_k == -1 hold upper bounds (hscmp_bound.h)
-    bool rp_last = false;           // the last loop launch was the round-parallel form (hscmp_rp.h)
     int method = 0;                 // hscmp_set_method: 0 = greedy pursuit (modeling.py:1053), 1 = LoCOMP (:1267)
-    bool locomp_state = false;      // the batch was encoded by the LoCOMP loop (hscmp_continue resumes it)
-    bool locomp_sparse = false;     // ... on the sparse policy (LocompSparse)
-    bool locomp_mfma = false;       // ... with the re-correlations on the matrix cores (LocompMfma)
+    EncodePlan plan;                // the kernels of the last encode (hscmp_continue resumes its loop)
     const void* last_x_dev = nullptr;   // device address of the signals of the last encode (hscmp_hierarchy_epilogue reads them)
     // workspace arena of the entry points outside the batch encode (grow-only, lives as long as the context): slots
     // 0-7 the hierarchical epilogue, 8-15 the row-level entry points and the device-resident table
@@ -402,7 +413,7 @@ struct BufCap { void** p; size_t* cap; size_t bytes; };
 constexpr int kRowListCap = 8;
 static bool use_row_lists(const hscmp_ctx* ctx)
 {
-    return ctx->F > 1 && ctx->d_nzptr != nullptr && !getenv("HSCMP_NO_ROW_LISTS") && !getenv("HSCMP_FORCE_DENSE");
+    return ctx->F > 1 && ctx->d_nzptr != nullptr && !getenv("HSCMP_NO_ROW_LISTS");
 }
 
 // Workgroups per signal of the sparse initial correlation: enough to fill the chip at small batches.
@@ -413,9 +424,9 @@ static int sparse_init_split(int B, int T, int W)
 }
 
 static int ensure_workspace_g(hscmp_ctx* ctx, const DevParams& P, bool need_x, size_t es, bool multi_feature, bool row_lists);
-static int ensure_workspace(hscmp_ctx* ctx, const DevParams& P, bool need_x)
+static int ensure_workspace(hscmp_ctx* ctx, const DevParams& P, bool need_x, bool row_lists)
 {
-    return ensure_workspace_g(ctx, P, need_x, esize(ctx->dtype), ctx->F > 1, use_row_lists(ctx));
+    return ensure_workspace_g(ctx, P, need_x, esize(ctx->dtype), ctx->F > 1, row_lists);
 }
 // (element size and feature layout given explicitly: see make_params_g)
 static int ensure_workspace_g(hscmp_ctx* ctx, const DevParams& P, bool need_x, size_t es, bool multi_feature, bool row_lists)
@@ -474,60 +485,7 @@ template <typename R> static State<R> make_state(hscmp_ctx* c)
     return S;
 }
 
-static bool use_mfma(const hscmp_ctx* ctx, int T)
-{
-    if (getenv("HSCMP_FORCE_GENERIC")) return false;
-    // the score-only MFMA path assumes single-bounce reflection at the edges (T >= 3W-2)
-    return ctx->d_Dfrag != nullptr && T >= 3 * ctx->W - 2;
-}
-
-// Round-parallel loop (hscmp_rp.h: a 1024-thread workgroup per signal, the atoms of a blocked round side by side).
-// HSCMP_RP=0/1 forces the choice (tests run both; the results are bit-identical).
-static bool use_rp(const DevParams& P, bool level_loop)
-{
-    if (!P.blocked) return false;
-    if (const char* e = getenv("HSCMP_RP")) return atoi(e) != 0;
-    // measured at the config-4 shape (profiles/r03_*): the level loops gain at every batch size (1024 signals: 28.9 ->
-    // 14.5 ms); on the matrix cores the four-signal loop catches up once every CU holds four signals (1024: 117.2 vs 117.6 ms;
-    // 512: 66.0 vs 60.7 ms)
-    return level_loop || P.B <= 3 * mfma_device_cus();
-}
-
-// the MFMA loop of a float32 batch: round-parallel when the batch is small and the round is blocked, else iterate_kernel
-template <typename R> static int launch_mfma_loop(hscmp_ctx* ctx, const DevParams& P, const State<R>& S)
-{
-    ctx->rp_last = false;
-    if constexpr (sizeof(R) == 4) {
-        if (use_rp(P, false) && rp_mfma_launch(ctx->stream, P, S, (const float*)ctx->d_Dfrag, true) == 0) {
-            if (rp_mfma_launch(ctx->stream, P, S, (const float*)ctx->d_Dfrag) != 0) return -1;
-            ctx->rp_last = true;
-            return 0;
-        }
-    }
-    return mfma_launch_iterate<R>(ctx->stream, P, S, (const R*)ctx->d_Dfrag);
-}
-
-// Loop policy for multi-feature inputs (hierarchical levels >= 1): SparseRecorr gathers the non-zeros
-// of the window into LDS and reads the transposed dictionary coalesced.
-static bool use_sparse_loop(const hscmp_ctx* ctx)
-{
-    if (getenv("HSCMP_FORCE_DENSE")) return false;
-    // multi-feature inputs only (measured: for dense single-feature windows the dense chain is 3x faster), and
-    // only with a sparse dictionary: subtracting dense atoms fills the residual, the windows then overflow the
-    // gathered lists and the dense LDS-staged chain of GenericRecorr is several times faster (a k-means
-    // dictionary with ~150 of 528 non-zeros per atom: 1.3 ms vs 0.37 ms per atom)
-    if (ctx->d_nzptr == nullptr && !getenv("HSCMP_FORCE_GATHERED")) return false;
-    return ctx->F > 1 && ctx->d_Dt != nullptr && ctx->W <= 16384 && ctx->F <= 32767;   // (f << 16) | row key
-}
-// Sparse INITIAL correlation: only for multi-feature inputs (hierarchical levels >= 1, almost all
-// zero); a dense single-feature signal is cheaper through the dense generic kernel.
-static bool use_sparse_init(const hscmp_ctx* ctx, int T)
-{
-    if (getenv("HSCMP_FORCE_DENSE")) return false;
-    return ctx->F > 1 && ctx->d_Dt != nullptr && ctx->W <= 16384 && ctx->F <= 32767 && T <= 262144;
-}
-
-template <typename R> static SparseArgs<R> sparse_args(hscmp_ctx* ctx, int T, bool packed = false)
+template <typename R> static SparseArgs<R> sparse_args(hscmp_ctx* ctx, const EncodePlan& plan, int T, bool packed = false)
 {
     SparseArgs<R> A;
     A.Dt = (const R*)ctx->d_Dt; A.scratch = (R*)ctx->d_scratch;
@@ -537,154 +495,220 @@ template <typename R> static SparseArgs<R> sparse_args(hscmp_ctx* ctx, int T, bo
     A.fptr = getenv("HSCMP_NO_PAIRING") ? nullptr : ctx->d_fptr; A.fkw = ctx->d_fkw; A.fval = (const R*)ctx->d_fval;
     A.nnz = ctx->dict_nnz; A.wts = (const R*)ctx->d_w;
     A.caps = sparse_caps(ctx->W, packed);
-    const bool lists = use_row_lists(ctx) && ctx->d_rl_cnt != nullptr;
-    A.rl_cnt = lists ? ctx->d_rl_cnt : nullptr; A.rl_f = ctx->d_rl_f; A.rl_cap = kRowListCap; A.rl_filled = ctx->rl_filled ? 1 : 0;
+    A.rl_cnt = plan.row_lists ? ctx->d_rl_cnt : nullptr; A.rl_f = ctx->d_rl_f; A.rl_cap = kRowListCap; A.rl_filled = ctx->rl_filled ? 1 : 0;
     return A;
 }
 
-// More signals than two per CU: the four-workgroups-per-CU form of the loop (see SparseRecorr) when its LDS fits.
-static bool sparse_loop_packed(const DevParams& P, size_t lds_packed)
+template <typename Pol> static size_t policy_lds_bytes(const DevParams& P0, const typename Pol::Args& A)
 {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    }
-    if (getenv("HSCMP_SPARSE_PACKED")) return atoi(getenv("HSCMP_SPARSE_PACKED")) != 0;
-    return P.B > 2 * cus && lds_packed <= (size_t)40 * 1024;
-}
-
-template <typename R, bool PACKED> static int launch_iterate_sparse_t(hscmp_ctx* ctx, const DevParams& P0, bool dry, size_t* lds_out)
-{
-    using Pol = SparseRecorr<R, PACKED>;
-    State<R> S = make_state<R>(ctx);
     DevParams P = P0;
     set_segments(P, Pol::kMaxSegments);
-    const SparseArgs<R> A = sparse_args<R>(ctx, P.T, PACKED);
-    const size_t lds = ((sizeof(typename Pol::Shared) + 15) / 16) * 16 + Pol::extra_lds_bytes(P, A);
-    if (lds_out) *lds_out = lds;
-    if (dry) return HSCMP_OK;
-    auto kern = iterate_kernel<R, Pol>;
-    HIP_TRY(ctx, set_dyn_lds((const void*)kern, lds));
-    hipLaunchKernelGGL(kern, dim3(P.B), dim3(kThreads), lds, ctx->stream, P, S, A);
-    return HSCMP_OK;
+    return Pol::total_lds_bytes(P, A);
 }
 
-template <typename R> static int launch_iterate_sparse(hscmp_ctx* ctx, const DevParams& P0)
+// The loop of policy Pol (iterate_kernel), `signals_per_wg` signals per workgroup.  dry: only tell whether its LDS fits (158 KB:
+// the kernel's own static bytes count too), queue nothing.  0: launched (or fits); -1: it cannot run this shape.
+template <typename R, typename Pol>
+static int launch_policy(hscmp_ctx* ctx, const DevParams& P0, const typename Pol::Args& A, int signals_per_wg, bool dry)
 {
-    ctx->rp_last = false;
-    if constexpr (sizeof(R) == 8) {
-        // small batches of blocked rounds: the round-parallel loop (hscmp_rp_sparse.h), one wave per atom of the round
-        if (use_rp(P0, true)) {
-            State<R> S = make_state<R>(ctx);
-            const SparseArgs<R> A = sparse_args<R>(ctx, P0.T, false);
-            if (rp_sparse_launch<R>(ctx->stream, P0, S, A, true) == 0) {
-                if (rp_sparse_launch<R>(ctx->stream, P0, S, A, false) != 0) return fail(ctx, HSCMP_ERR_HIP, "the round-parallel level loop could not be launched");
-                ctx->rp_last = true;
-                return HSCMP_OK;
-            }
-        }
-    }
-    size_t lds_packed = 0;
-    (void)launch_iterate_sparse_t<R, true>(ctx, P0, true, &lds_packed);
-    if (sparse_loop_packed(P0, lds_packed)) return launch_iterate_sparse_t<R, true>(ctx, P0, false, nullptr);
-    return launch_iterate_sparse_t<R, false>(ctx, P0, false, nullptr);
-}
-
-template <typename R> static int launch_corr_init_sparse(hscmp_ctx* ctx, const DevParams& P)
-{
-    State<R> S = make_state<R>(ctx);
-    const SparseArgs<R> A = sparse_args<R>(ctx, P.T);
-    const size_t lds = sparse_lds_bytes<R>(A.caps) + staged_dict_bytes(P, A) + (size_t)((P.T + 31) / 32) * sizeof(unsigned);
-    auto kern = corr_init_sparse_kernel<R>;
-    HIP_TRY(ctx, set_dyn_lds((const void*)kern, lds));
-    hipLaunchKernelGGL(kern, dim3(P.B, sparse_init_split(P.B, P.T, P.W)), dim3(kThreads), lds, ctx->stream, P, S, A);
-    return HSCMP_OK;
-}
-
-template <typename R> static int launch_iterate(hscmp_ctx* ctx, const DevParams& P0)
-{
-    State<R> S = make_state<R>(ctx);
-    DevParams P = P0;
-    set_segments(P, GenericRecorr<R>::kMaxSegments);
-    const size_t lds = ((sizeof(typename GenericRecorr<R>::Shared) + 15) / 16) * 16 + GenericRecorr<R>::extra_lds_bytes(P);
-    auto kern = iterate_kernel<R, GenericRecorr<R>>;
-    HIP_TRY(ctx, set_dyn_lds((const void*)kern, lds));
-    hipLaunchKernelGGL(kern, dim3(P.B), dim3(kThreads), lds, ctx->stream, P, S, typename GenericRecorr<R>::Args{});
-    return HSCMP_OK;
-}
-
-// LoCOMP (hscmp_locomp.h): the table-free dense loop with the group re-fit as its atom body
-template <typename R> static int launch_iterate_locomp(hscmp_ctx* ctx, const DevParams& P0)
-{
-    using Pol = LocompRecorr<R>;
-    State<R> S = make_state<R>(ctx);
     DevParams P = P0;
     set_segments(P, Pol::kMaxSegments);
-    const size_t lds = ((sizeof(typename Pol::Shared) + 15) / 16) * 16 + Pol::extra_lds_bytes(P);
-    auto kern = iterate_kernel<R, Pol>;
-    HIP_TRY(ctx, set_dyn_lds((const void*)kern, lds));
-    hipLaunchKernelGGL(kern, dim3(P.B), dim3(kThreads), lds, ctx->stream, P, S, typename Pol::Args{});
-    return HSCMP_OK;
-}
-
-// single-feature float32 with a dictionary image (hscmp_set_dictionary built it): the re-correlations on the matrix cores.
-// Two signals per workgroup (one image per CU, two signals on its matrix pipe) when the batch has more signals than the chip has CUs.
-template <int S4C, bool HAS_W, int GS> static int launch_iterate_locomp_mfma_g(hscmp_ctx* ctx, const DevParams& P0, bool dry)
-{
-    using Pol = LocompMfma<S4C, HAS_W, GS>;
-    State<float> S = make_state<float>(ctx);
-    DevParams P = P0;
-    set_segments(P, Pol::kMaxSegments);
-    MfmaArgs A;
-    A.dimg = (const float*)ctx->d_Dfrag; A.G = mfma_groups(P.K); A.S4 = S4C; A.has_w = HAS_W ? 1 : 0;
     const size_t lds = Pol::total_lds_bytes(P, A);
-    if (lds > (size_t)158 * 1024) return -1;
-    if (dry) return 0;
-    auto kern = iterate_kernel<float, Pol>;
-    HIP_TRY(ctx, set_dyn_lds((const void*)kern, lds));
-    hipLaunchKernelGGL(kern, dim3((P.B + GS - 1) / GS), dim3(GS * kThreads), lds, ctx->stream, P, S, A);
-    return HSCMP_OK;
+    if (dry) return lds <= (size_t)158 * 1024 ? 0 : -1;
+    auto kern = iterate_kernel<R, Pol>;
+    if (set_dyn_lds((const void*)kern, lds) != hipSuccess) return -1;
+    hipLaunchKernelGGL(kern, dim3((P.B + signals_per_wg - 1) / signals_per_wg), dim3(signals_per_wg * kThreads), lds, ctx->stream, P,
+                       make_state<R>(ctx), A);
+    return 0;
 }
-template <int S4C, bool HAS_W> static int launch_iterate_locomp_mfma_t(hscmp_ctx* ctx, const DevParams& P, bool dry)
+
+// LoCOMP with the re-correlations on the matrix cores (LocompMfma: single-feature float32 with a dictionary image), `group`
+// signals per workgroup around one image.  -1: no such form for this shape.
+template <int S4C, bool HAS_W> static int launch_locomp_mfma_t(hscmp_ctx* ctx, const DevParams& P, const MfmaArgs& A, int group, bool dry)
 {
-    // signals per workgroup: as many as it takes to put the whole batch on the chip at once -- two or four around one dictionary
-    // image, their tiles sharing the CU's matrix pipe (HSCMP_LOCOMP_PACK = 1 / 2 / 4 overrides)
-    const char* e = getenv("HSCMP_LOCOMP_PACK");
-    const int cus = mfma_device_cus();
-    const int pack = e ? atoi(e) : P.B > 2 * cus ? 4 : P.B > cus ? 2 : 1;
-    if (pack >= 4 && launch_iterate_locomp_mfma_g<S4C, HAS_W, 4>(ctx, P, true) == 0) return launch_iterate_locomp_mfma_g<S4C, HAS_W, 4>(ctx, P, dry);
-    if (pack >= 2 && launch_iterate_locomp_mfma_g<S4C, HAS_W, 2>(ctx, P, true) == 0) return launch_iterate_locomp_mfma_g<S4C, HAS_W, 2>(ctx, P, dry);
-    return launch_iterate_locomp_mfma_g<S4C, HAS_W, 1>(ctx, P, dry);
+    switch (group) {
+    case 4: return launch_policy<float, LocompMfma<S4C, HAS_W, 4>>(ctx, P, A, 4, dry);
+    case 2: return launch_policy<float, LocompMfma<S4C, HAS_W, 2>>(ctx, P, A, 2, dry);
+    default: return launch_policy<float, LocompMfma<S4C, HAS_W, 1>>(ctx, P, A, 1, dry);
+    }
 }
-static int launch_iterate_locomp_mfma(hscmp_ctx* ctx, const DevParams& P, bool dry)
+static int launch_locomp_mfma(hscmp_ctx* ctx, const DevParams& P, int group, bool dry)
 {
-    if (ctx->dtype != HSCMP_F32 || ctx->F != 1 || !ctx->d_Dfrag || getenv("HSCMP_LOCOMP_NO_MFMA")) return -1;
-    const bool w = ctx->d_w != nullptr;
-    switch (mfma_chunks(P.W)) {
-    case 8: return w ? launch_iterate_locomp_mfma_t<8, true>(ctx, P, dry) : launch_iterate_locomp_mfma_t<8, false>(ctx, P, dry);
-    case 4: return w ? launch_iterate_locomp_mfma_t<4, true>(ctx, P, dry) : launch_iterate_locomp_mfma_t<4, false>(ctx, P, dry);
-    case 2: return w ? launch_iterate_locomp_mfma_t<2, true>(ctx, P, dry) : launch_iterate_locomp_mfma_t<2, false>(ctx, P, dry);
+    MfmaArgs A;
+    A.dimg = (const float*)ctx->d_Dfrag; A.G = mfma_groups(P.K); A.S4 = mfma_chunks(P.W); A.has_w = ctx->d_w != nullptr ? 1 : 0;
+    const bool w = A.has_w != 0;
+    switch (A.S4) {
+    case 8: return w ? launch_locomp_mfma_t<8, true>(ctx, P, A, group, dry) : launch_locomp_mfma_t<8, false>(ctx, P, A, group, dry);
+    case 4: return w ? launch_locomp_mfma_t<4, true>(ctx, P, A, group, dry) : launch_locomp_mfma_t<4, false>(ctx, P, A, group, dry);
+    case 2: return w ? launch_locomp_mfma_t<2, true>(ctx, P, A, group, dry) : launch_locomp_mfma_t<2, false>(ctx, P, A, group, dry);
     default: return -1;
     }
 }
 
-// (dry: only tells whether the policy's LDS fits -- staged dictionary lists can be too long; the dense form runs then)
-template <typename R> static int launch_iterate_locomp_sparse(hscmp_ctx* ctx, const DevParams& P0, bool dry = false)
+// The one place that chooses the kernels of an encode: every knob that selects a kernel is read here, once per encode, and every
+// LDS-fit check runs here.  row_lists: the encode keeps per-row feature lists where its kernels can use them (use_row_lists).
+template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const DevParams& P, bool row_lists)
 {
-    using Pol = LocompSparse<R>;
-    State<R> S = make_state<R>(ctx);
-    DevParams P = P0;
-    set_segments(P, Pol::kMaxSegments);
-    const SparseArgs<R> A = sparse_args<R>(ctx, P.T, false);
-    const size_t lds = ((sizeof(typename Pol::Shared) + 15) / 16) * 16 + Pol::extra_lds_bytes(P, A);
-    if (lds > (size_t)158 * 1024) return -1;
-    if (dry) return 0;
-    auto kern = iterate_kernel<R, Pol>;
-    HIP_TRY(ctx, set_dyn_lds((const void*)kern, lds));
-    hipLaunchKernelGGL(kern, dim3(P.B), dim3(kThreads), lds, ctx->stream, P, S, A);
+    EncodePlan plan;
+    plan.f64 = sizeof(R) == 8;
+    plan.dict_lists = ctx->d_nzptr != nullptr;
+    const State<R> S = make_state<R>(ctx);
+    const R* dimg = (const R*)ctx->d_Dfrag;
+    const int cus = mfma_device_cus();
+    const bool locomp = ctx->method == HSCMP_METHOD_LOCOMP;      // (its loop keeps coefficient + atom per position: no score-only state)
+    // Round-parallel loops for blocked rounds (HSCMP_RP=0/1 forces the choice; tests run both, the results are bit-identical).
+    // Measured at the config-4 shape (profiles/r03_*): the level loops gain at every batch size (1024 signals: 28.9 -> 14.5 ms);
+    // on the matrix cores the four-signal loop catches up once every CU holds four signals (1024: 117.2 vs 117.6 ms; 512: 66.0
+    // vs 60.7 ms).
+    const char* rp_env = getenv("HSCMP_RP");
+    const bool rp_level = P.blocked && (rp_env ? atoi(rp_env) != 0 : true);
+    const bool rp_mfma = P.blocked && (rp_env ? atoi(rp_env) != 0 : P.B <= 3 * cus);
+    // Sparsity-aware kernels for multi-feature inputs (hierarchical levels >= 1).  The loop only with a sparse dictionary
+    // (measured: for dense single-feature windows the dense chain is 3x faster; subtracting dense atoms fills the residual, the
+    // windows then overflow the gathered lists and the dense LDS-staged chain of GenericRecorr is several times faster -- a k-means
+    // dictionary with ~150 of 528 non-zeros per atom: 1.3 ms vs 0.37 ms per atom).  ((f << 16) | row keys: W <= 16384, F <= 32767)
+    const bool sparse_shape = ctx->F > 1 && ctx->d_Dt != nullptr && ctx->W <= 16384 && ctx->F <= 32767;
+    const bool sparse_loop = sparse_shape && (ctx->d_nzptr != nullptr || getenv("HSCMP_FORCE_GATHERED"));
+    plan.row_lists = row_lists && sparse_loop;
+
+    // The matrix-core kernels come as a pair: the score-only state the initial correlation leaves is what the MFMA loop reads (the
+    // generic / sparse kernels keep coefficient + atom instead).  The score-only path assumes single-bounce reflection at the
+    // edges (T >= 3W-2).  Four signals per workgroup pay off once a CU would otherwise hold more than two signals in turn
+    // (B > 2 x CUs); HSCMP_MFMA_QUAD=0/1 forces the choice (tests run both; the results are bit-identical).
+    bool mf = false;
+    if (!locomp && !getenv("HSCMP_FORCE_GENERIC") && dimg && P.T >= 3 * ctx->W - 2 && mfma_launch_corr_init<R>(ctx->stream, P, S, dimg, true) == 0) {
+        bool quad = sizeof(R) == 4 && P.B > 2 * cus;
+        if (const char* e = getenv("HSCMP_MFMA_QUAD")) quad = atoi(e) != 0;
+        if (quad && mfma_launch_iterate<R>(ctx->stream, P, S, dimg, 4, true) == 0) plan.group = 4;
+        mf = plan.group == 4 || mfma_launch_iterate<R>(ctx->stream, P, S, dimg, 1, true) == 0;
+    }
+    if (mf) {
+        plan.init = EncodePlan::kInitMfma;
+        plan.loop = EncodePlan::kLoopMfma;
+        plan.init_only = getenv("HSCMP_INIT_ONLY") != nullptr;
+        if constexpr (sizeof(R) == 4) {
+            // float32 single-arg-max encodes: the initial correlation as upper bounds on the bf16 matrix cores, refined by the loop
+            // where a selection needs it (hscmp_bound.h).  HSCMP_EXACT_INIT=1: the exact pass everywhere.
+            if (!P.blocked && !P.select_only && ctx->d_Bimg && !getenv("HSCMP_EXACT_INIT") &&
+                bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->d_Bimg, ctx->bound_cmax, true) == 0)
+                plan.init = EncodePlan::kInitBound;
+            plan.rp = rp_mfma && rp_mfma_launch(ctx->stream, P, S, dimg, true) == 0;
+        }
+        return plan;
+    }
+    // (a dense single-feature signal is cheaper through the dense generic kernel)
+    if (sparse_shape && P.T <= 262144) plan.init = EncodePlan::kInitSparse;
+    if (locomp) {
+        // LoCOMP on the matrix cores: its loop kernel starts with the initial correlation (LocompMfma::prologue).  Signals per
+        // workgroup: as many as it takes to put the whole batch on the chip at once -- two or four around one dictionary image,
+        // their tiles sharing the CU's matrix pipe (HSCMP_LOCOMP_PACK = 1 / 2 / 4 overrides).  The sparse form when its staged
+        // dictionary lists fit (else the dense form runs).
+        const char* pack_env = getenv("HSCMP_LOCOMP_PACK");
+        const int pack = pack_env ? atoi(pack_env) : P.B > 2 * cus ? 4 : P.B > cus ? 2 : 1;
+        if (sparse_loop && launch_policy<R, LocompSparse<R>>(ctx, P, sparse_args<R>(ctx, plan, P.T), 1, true) == 0) {
+            plan.loop = EncodePlan::kLoopLocompSparse;
+            plan.kept_lists = plan.row_lists;
+        } else if (sizeof(R) == 4 && ctx->F == 1 && dimg && !getenv("HSCMP_LOCOMP_NO_MFMA")) {
+            for (int g : {4, 2, 1})
+                if ((pack >= g || g == 1) && launch_locomp_mfma(ctx, P, g, true) == 0) {
+                    plan.init = EncodePlan::kInitOwn; plan.loop = EncodePlan::kLoopLocompMfma; plan.group = g;
+                    break;
+                }
+        }
+        if (plan.loop == EncodePlan::kLoopGeneric) plan.loop = EncodePlan::kLoopLocomp;
+        return plan;
+    }
+    if (sparse_loop) {
+        plan.loop = EncodePlan::kLoopSparse;
+        plan.kept_lists = plan.row_lists;
+        // small batches of blocked rounds: the round-parallel level loop (hscmp_rp_sparse.h), one wave per atom of the round
+        if constexpr (sizeof(R) == 8) plan.rp = rp_level && rp_sparse_launch<R>(ctx->stream, P, S, sparse_args<R>(ctx, plan, P.T), true) == 0;
+        // more signals than two per CU: the four-workgroups-per-CU form of the loop (see SparseRecorr) when its LDS fits
+        const char* packed_env = getenv("HSCMP_SPARSE_PACKED");
+        if (!plan.rp)
+            plan.packed = packed_env ? atoi(packed_env) != 0
+                                     : P.B > 2 * cus && policy_lds_bytes<SparseRecorr<R, true>>(P, sparse_args<R>(ctx, plan, P.T, true)) <= (size_t)40 * 1024;
+    }
+    return plan;
+}
+
+// What hscmp_last_variant reports: "<init>_init+<loop>_loop_<dtype>" and the loop's form.
+static std::string variant_of(const EncodePlan& plan)
+{
+    const bool bound = plan.init == EncodePlan::kInitBound;
+    if (plan.init_only) return bound ? "bound_init" : "mfma_init";
+    static const char* const inits[] = {"mfma", "mfma", "sparse", "own", "generic"};
+    static const char* const loops[] = {"mfma", "gathered", "generic", "locomp", "locomp_dictlist", "locomp_mfma"};
+    const char* init = plan.init == EncodePlan::kInitSparse && plan.dict_lists ? "dictlist" : inits[plan.init];
+    const char* loop = plan.loop == EncodePlan::kLoopSparse && plan.dict_lists ? "dictlist" : loops[plan.loop];
+    std::string v = std::string(init) + "_init+" + loop + "_loop_" + (plan.f64 ? "f64" : "f32") + (bound ? "_bound" : "");
+    if (plan.rp) v += "_rp";
+    else if (plan.loop == EncodePlan::kLoopMfma && plan.group > 1) v += "_x" + std::to_string(plan.group);
+    return v;
+}
+
+// Queue the initial correlation of the plan (behind the prepare), and first the per-row lists of the input's non-zero cells
+// where the loop uses them and the level chaining has not written them while it scattered.
+template <typename R> static int launch_init(hscmp_ctx* ctx, const EncodePlan& plan, const DevParams& P, const void* x_dev)
+{
+    const State<R> S = make_state<R>(ctx);
+    const R* dimg = (const R*)ctx->d_Dfrag;
+    if (plan.row_lists && !ctx->rl_filled) {
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_rl_cnt, 0, (size_t)P.B * P.T * sizeof(int), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_rl_f, 0xff, (size_t)P.B * P.T * kRowListCap * sizeof(int), ctx->stream));
+        const int split = std::max(1, std::min(256, 4096 / P.B));
+        hipLaunchKernelGGL((build_row_lists_kernel<R>), dim3(P.B, split), dim3(kThreads), 0, ctx->stream, (const R*)x_dev, P.T, P.F,
+                           ctx->d_rl_cnt, ctx->d_rl_f, kRowListCap);
+    }
+    int rc = 0;
+    switch (plan.init) {
+    case EncodePlan::kInitMfma: rc = mfma_launch_corr_init<R>(ctx->stream, P, S, dimg); break;
+    case EncodePlan::kInitBound:
+        if constexpr (sizeof(R) == 4) rc = bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->d_Bimg, ctx->bound_cmax);
+        break;
+    case EncodePlan::kInitSparse: {
+        const SparseArgs<R> A = sparse_args<R>(ctx, plan, P.T);
+        const size_t lds = sparse_lds_bytes<R>(A.caps) + staged_dict_bytes(P, A) + (size_t)((P.T + 31) / 32) * sizeof(unsigned);
+        auto kern = corr_init_sparse_kernel<R>;
+        HIP_TRY(ctx, set_dyn_lds((const void*)kern, lds));
+        hipLaunchKernelGGL(kern, dim3(P.B, sparse_init_split(P.B, P.T, P.W)), dim3(kThreads), lds, ctx->stream, P, S, A);
+        break;
+    }
+    case EncodePlan::kInitOwn: break;
+    case EncodePlan::kInitGeneric:
+        hipLaunchKernelGGL((corr_init_generic_kernel<R, false>), dim3((P.T + kThreads - 1) / kThreads, P.B), dim3(kThreads), 0, ctx->stream,
+                           P, S, (const R*)ctx->d_resid, P.off, P.T, (R*)nullptr);
+        break;
+    }
+    if (rc != 0) return fail(ctx, HSCMP_ERR_HIP, "the initial correlation of %s could not be launched", variant_of(plan).c_str());
+    return HSCMP_OK;
+}
+
+// Queue the loop of the plan: run_encode behind the initial correlation, hscmp_continue on the state an earlier launch left.
+template <typename R> static int launch_loop(hscmp_ctx* ctx, const EncodePlan& plan, const DevParams& P)
+{
+    const R* dimg = (const R*)ctx->d_Dfrag;
+    int rc = -1;
+    switch (plan.loop) {
+    case EncodePlan::kLoopMfma:
+        if constexpr (sizeof(R) == 4)
+            if (plan.rp) { rc = rp_mfma_launch(ctx->stream, P, make_state<float>(ctx), dimg); break; }
+        rc = mfma_launch_iterate<R>(ctx->stream, P, make_state<R>(ctx), dimg, plan.group);
+        break;
+    case EncodePlan::kLoopSparse:
+        if constexpr (sizeof(R) == 8)
+            if (plan.rp) { rc = rp_sparse_launch<R>(ctx->stream, P, make_state<R>(ctx), sparse_args<R>(ctx, plan, P.T), false); break; }
+        rc = plan.packed ? launch_policy<R, SparseRecorr<R, true>>(ctx, P, sparse_args<R>(ctx, plan, P.T, true), 1, false)
+                         : launch_policy<R, SparseRecorr<R, false>>(ctx, P, sparse_args<R>(ctx, plan, P.T), 1, false);
+        break;
+    case EncodePlan::kLoopGeneric: rc = launch_policy<R, GenericRecorr<R>>(ctx, P, {}, 1, false); break;
+    case EncodePlan::kLoopLocomp: rc = launch_policy<R, LocompRecorr<R>>(ctx, P, {}, 1, false); break;
+    case EncodePlan::kLoopLocompSparse: rc = launch_policy<R, LocompSparse<R>>(ctx, P, sparse_args<R>(ctx, plan, P.T), 1, false); break;
+    case EncodePlan::kLoopLocompMfma:
+        if constexpr (sizeof(R) == 4) rc = launch_locomp_mfma(ctx, P, plan.group, false);
+        break;
+    }
+    if (rc != 0) return fail(ctx, HSCMP_ERR_HIP, "the loop of %s could not be launched", variant_of(plan).c_str());
     return HSCMP_OK;
 }
 
@@ -692,7 +716,8 @@ template <typename R> static int launch_iterate_locomp_sparse(hscmp_ctx* ctx, co
 // residual buffer and prepare only needs the energy.
 struct ChainSource { const int* slot_t; const int* slot_k; const double* slot_a; const int* stats; int cap, first, has_min; double minc; bool lists; int max_slots; };
 
-template <typename R> static int run_encode(hscmp_ctx* ctx, const DevParams& P, const void* x_dev, const ChainSource* chain = nullptr)
+template <typename R>
+static int run_encode(hscmp_ctx* ctx, const EncodePlan& plan, const DevParams& P, const void* x_dev, const ChainSource* chain = nullptr)
 {
     State<R> S = make_state<R>(ctx);
     HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
@@ -716,87 +741,20 @@ template <typename R> static int run_encode(hscmp_ctx* ctx, const DevParams& P, 
     } else
         hipLaunchKernelGGL((prepare_kernel<R>), dim3(P.B), dim3(kThreads), 0, ctx->stream, P, S, (const R*)x_dev);
     HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    // The matrix-core kernels come as a pair: the score-only state the initial correlation leaves is what the MFMA loop
-    // reads (the generic / sparse kernels keep coefficient + atom instead).  Both are configured before anything is
-    // queued; if either cannot run this shape, neither does.
-    bool mf = false;
-    const bool loc = ctx->method == HSCMP_METHOD_LOCOMP;       // (its loop keeps coefficient + atom per position: no score-only state)
-    if (!loc && use_mfma(ctx, P.T) && mfma_launch_corr_init<R>(ctx->stream, P, S, (const R*)ctx->d_Dfrag, true) == 0 &&
-        mfma_launch_iterate<R>(ctx->stream, P, S, (const R*)ctx->d_Dfrag, true) == 0) {
-        mf = true;
-    }
-    // float32 single-arg-max encodes: the initial correlation as upper bounds on the bf16 matrix cores, refined by the loop
-    // where a selection needs it (hscmp_bound.h).  HSCMP_EXACT_INIT=1: the exact pass everywhere.
-    bool bnd = false;
-    if constexpr (sizeof(R) == 4) {
-        if (mf && !P.blocked && !P.select_only && ctx->d_Bimg && !getenv("HSCMP_EXACT_INIT") &&
-            bound_launch_corr_init(ctx->stream, P, S, (const float*)ctx->d_Dfrag, ctx->d_Bimg, ctx->bound_cmax, true) == 0)
-            bnd = true;
-    }
-    if (mf) {
-        int rc;
-        if constexpr (sizeof(R) == 4) rc = bnd ? bound_launch_corr_init(ctx->stream, P, S, (const float*)ctx->d_Dfrag, ctx->d_Bimg, ctx->bound_cmax)
-                                               : mfma_launch_corr_init<R>(ctx->stream, P, S, (const R*)ctx->d_Dfrag);
-        else rc = mfma_launch_corr_init<R>(ctx->stream, P, S, (const R*)ctx->d_Dfrag);
-        if (rc != 0) return fail(ctx, HSCMP_ERR_HIP, "the MFMA initial correlation could not be launched");
-    }
-    ctx->P.bound_init = bnd ? 1 : 0;                  // (hscmp_continue resumes on the same state)
-    DevParams PL = P;
-    PL.bound_init = ctx->P.bound_init;
-    ctx->mfma_state = mf;
-    ctx->bound_state = bnd;
-    if (!mf && use_sparse_loop(ctx) && use_row_lists(ctx) && !ctx->rl_filled) {
-        // per-row lists of the input's non-zero cells (the level chaining writes them while it scatters)
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_rl_cnt, 0, (size_t)P.B * P.T * sizeof(int), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_rl_f, 0xff, (size_t)P.B * P.T * kRowListCap * sizeof(int), ctx->stream));
-        const int split = std::max(1, std::min(256, 4096 / P.B));
-        hipLaunchKernelGGL((build_row_lists_kernel<R>), dim3(P.B, split), dim3(kThreads), 0, ctx->stream, (const R*)x_dev, P.T, P.F,
-                           ctx->d_rl_cnt, ctx->d_rl_f, kRowListCap);
-    }
-    const bool spi = !mf && use_sparse_init(ctx, P.T);
-    // (LoCOMP on the matrix cores: its loop kernel starts with the initial correlation -- see LocompMfma::prologue)
-    const bool own_init = loc && !spi && !use_sparse_loop(ctx) && launch_iterate_locomp_mfma(ctx, P, true) == 0;
-    if (spi) { int rc = launch_corr_init_sparse<R>(ctx, P); if (rc) return rc; }
-    if (!mf && !spi && !own_init) {
-        dim3 grid((P.T + kThreads - 1) / kThreads, P.B);
-        hipLaunchKernelGGL((corr_init_generic_kernel<R, false>), grid, dim3(kThreads), 0, ctx->stream, P, S,
-                           (const R*)ctx->d_resid, P.off, P.T, (R*)nullptr);
-    }
+    ctx->plan = plan;
+    ctx->P.bound_init = plan.init == EncodePlan::kInitBound ? 1 : 0;     // (the loop reads it; hscmp_continue resumes on the same state)
+    int rc = launch_init<R>(ctx, plan, P, x_dev);
+    if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-    bool mfi = false;
-    if (mf && getenv("HSCMP_INIT_ONLY")) {
-        // diagnostic / test knob: stop behind the initial correlation (its best_c / best_k through hscmp_get_device_view)
-        HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
-        ctx->timed = true; ctx->timed_loop_only = false;
-        ctx->variant = bnd ? "bound_init" : "mfma_init";
-        return HSCMP_OK;
+    if (!plan.init_only) {          // (HSCMP_INIT_ONLY: best_c / best_k of the initial correlation through hscmp_get_device_view)
+        DevParams PL = P;
+        PL.bound_init = ctx->P.bound_init;
+        if ((rc = launch_loop<R>(ctx, plan, PL))) return rc;
     }
-    if (mf) {
-        if (launch_mfma_loop<R>(ctx, PL, S) != 0)
-            return fail(ctx, HSCMP_ERR_HIP, "the MFMA loop could not be launched on the state of the MFMA initial correlation");
-        mfi = true;
-    }
-    const bool spl = !mfi && !loc && use_sparse_loop(ctx);
-    ctx->loop_kept_lists = spl && use_row_lists(ctx);
-    ctx->locomp_state = loc;
-    const bool locs = loc && use_sparse_loop(ctx) && launch_iterate_locomp_sparse<R>(ctx, P, true) == 0;
-    ctx->locomp_sparse = locs;
-    if (loc) ctx->loop_kept_lists = locs && use_row_lists(ctx);
-    const bool locm = loc && !locs && own_init;
-    ctx->locomp_mfma = locm;
-    if (loc) {
-        ctx->rp_last = false;
-        int rc = locs ? launch_iterate_locomp_sparse<R>(ctx, P) : locm ? launch_iterate_locomp_mfma(ctx, P, false) : launch_iterate_locomp<R>(ctx, P);
-        if (rc) return rc;
-    }
-    else if (spl) { int rc = launch_iterate_sparse<R>(ctx, P); if (rc) return rc; }
-    else if (!mfi) { int rc = launch_iterate<R>(ctx, P); if (rc) return rc; }
     HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
     HIP_TRY(ctx, hipGetLastError());
     ctx->timed = true; ctx->timed_loop_only = false;
-    ctx->variant = std::string(mf ? "mfma" : own_init ? "own" : spi ? (ctx->d_nzptr ? "dictlist" : "sparse") : "generic") + "_init+" + (loc ? (locs ? "locomp_dictlist" : locm ? "locomp_mfma" : "locomp") : mfi ? "mfma" : spl ? (ctx->d_nzptr ? "dictlist" : "gathered") : "generic") +
-                   "_loop_" + (sizeof(R) == 4 ? "f32" : "f64") + (bnd ? "_bound" : "") +
-                   ((mfi || spl) && ctx->rp_last ? std::string("_rp") : mfi && mfma_last_group() > 1 ? "_x" + std::to_string(mfma_last_group()) : std::string());
+    ctx->variant = variant_of(plan);
     return HSCMP_OK;
 }
 
@@ -809,7 +767,9 @@ static int encode_common(hscmp_ctx* ctx, const void* x, bool host, int B, int T,
     DevParams P;
     int rc = make_params(ctx, B, T, params, &P);
     if (rc) return rc;
-    if ((rc = ensure_workspace(ctx, P, host))) return rc;
+    const bool row_lists = use_row_lists(ctx);
+    if ((rc = ensure_workspace(ctx, P, host, row_lists))) return rc;
+    const EncodePlan plan = ctx->dtype == HSCMP_F32 ? plan_encode<float>(ctx, P, row_lists) : plan_encode<double>(ctx, P, row_lists);
     const void* xd = x;
     if (host) {
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_x, x, (size_t)B * T * ctx->F * esize(ctx->dtype), hipMemcpyHostToDevice, ctx->stream));
@@ -818,7 +778,7 @@ static int encode_common(hscmp_ctx* ctx, const void* x, bool host, int B, int T,
     ctx->P = P; ctx->last = *params; ctx->B = B; ctx->T = T; ctx->cap = P.cap; ctx->maxsel = P.maxsel;
     ctx->listed_rows = 0;                       // the residual buffer is overwritten with a dense input
     ctx->last_x_dev = xd;
-    rc = ctx->dtype == HSCMP_F32 ? run_encode<float>(ctx, P, xd) : run_encode<double>(ctx, P, xd);
+    rc = ctx->dtype == HSCMP_F32 ? run_encode<float>(ctx, plan, P, xd) : run_encode<double>(ctx, plan, P, xd);
     if (rc) return rc;
     ctx->have_batch = true;
     if (host) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -850,9 +810,11 @@ extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, in
     DevParams P;
     int rc = make_params(ctx, count, T, params, &P);
     if (rc) return rc;
-    if ((rc = ensure_workspace(ctx, P, false))) return rc;        // no input buffer: the slots are scattered straight into the residual
+    const bool row_lists = use_row_lists(ctx);
+    if ((rc = ensure_workspace(ctx, P, false, row_lists))) return rc;        // no input buffer: the slots are scattered straight into the residual
+    const EncodePlan plan = plan_encode<double>(ctx, P, row_lists);
+    const bool lists = plan.row_lists;          // (the scatter writes them)
     const size_t bytes = (size_t)count * T * ctx->F * sizeof(double);
-    const bool lists = use_sparse_loop(ctx) && use_row_lists(ctx);
     if (ctx->listed_rows > 0 && ctx->listed_F == ctx->F && !getenv("HSCMP_NO_LAZY_CLEAR")) {
         // the buffer still holds the previous chained batch; its lists say where
         hipLaunchKernelGGL((clear_listed_cells_kernel<double>), dim3((unsigned)((ctx->listed_rows + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream,
@@ -884,13 +846,13 @@ extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, in
     }
     const ChainSource chain{prev->d_slot_t, prev->d_slot_k, prev->d_slot_a, prev->d_stats, prev->cap, first, has_min,
                             has_min ? min_coefficients : 0.0, lists, max_slots};
-    rc = run_encode<double>(ctx, P, ctx->d_resid, &chain);
+    rc = run_encode<double>(ctx, plan, P, ctx->d_resid, &chain);
     ctx->rowflag_valid = false; ctx->rl_filled = false;
     if (rc) return rc;
     ctx->have_batch = true;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // (only now: a failed launch leaves the buffer in an unknown state, and so does any other writer -- see the resets)
-    if (lists && ctx->loop_kept_lists) { ctx->listed_rows = (int64_t)count * T; ctx->listed_F = ctx->F; }
+    if (plan.kept_lists) { ctx->listed_rows = (int64_t)count * T; ctx->listed_F = ctx->F; }
     return HSCMP_OK;
 }
 
@@ -901,33 +863,11 @@ extern "C" int hscmp_continue(hscmp_ctx* ctx, int max_rounds)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevParams P = ctx->P;
     P.max_rounds = max_rounds;
-    bool mfi = false;
     HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));       // hscmp_last_kernel_ms: [2] = this launch, [0] = [1] = 0
     ctx->timed_loop_only = true;
-    if (ctx->mfma_state) {          // the loop must be the one that understands the state the encode left
-        int rc;
-        if (ctx->dtype == HSCMP_F32) {
-            State<float> S = make_state<float>(ctx);
-            rc = launch_mfma_loop<float>(ctx, P, S);
-        } else {
-            State<double> S = make_state<double>(ctx);
-            rc = launch_mfma_loop<double>(ctx, P, S);
-        }
-        if (rc != 0) return fail(ctx, HSCMP_ERR_HIP, "hscmp_continue: the MFMA loop could not be launched");
-        mfi = true;
-    }
-    if (ctx->locomp_state) {
-        int rc = ctx->locomp_mfma ? launch_iterate_locomp_mfma(ctx, P, false) :
-                 ctx->locomp_sparse ? (ctx->dtype == HSCMP_F32 ? launch_iterate_locomp_sparse<float>(ctx, P) : launch_iterate_locomp_sparse<double>(ctx, P))
-                                    : (ctx->dtype == HSCMP_F32 ? launch_iterate_locomp<float>(ctx, P) : launch_iterate_locomp<double>(ctx, P));
-        if (rc) return rc;
-    } else if (!mfi && use_sparse_loop(ctx)) {
-        int rc = ctx->dtype == HSCMP_F32 ? launch_iterate_sparse<float>(ctx, P) : launch_iterate_sparse<double>(ctx, P);
-        if (rc) return rc;
-    } else if (!mfi) {
-        int rc = ctx->dtype == HSCMP_F32 ? launch_iterate<float>(ctx, P) : launch_iterate<double>(ctx, P);
-        if (rc) return rc;
-    }
+    // the loop the encode chose: the one that understands the state it left
+    const int rc = ctx->plan.f64 ? launch_loop<double>(ctx, ctx->plan, P) : launch_loop<float>(ctx, ctx->plan, P);
+    if (rc) return rc;
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1504,8 +1444,8 @@ extern "C" int hscmp_update_inner_products(hscmp_ctx* ctx, void* ip, const void*
 // _selectBestAtoms (:899-982) on the resident table, update = the caller's new residual samples + _updateInnerProducts
 // (:1018-1051) for every atom of the re-fitted group, in place.  Per iteration the host moves O(W) samples, not T*K.
 // Multi-feature tables (hierarchical levels >= 1) are built row by row from the non-zero cells of each row's window
-// (table_rows_sparse_kernel); single-feature inputs are dense and keep the dense kernels.  HSCMP_FORCE_DENSE: dense always.
-static bool table_rows_are_sparse(const hscmp_ctx* ctx) { return ctx->F > 1 && ctx->W <= 32767 && ctx->F <= 65535 && !getenv("HSCMP_FORCE_DENSE"); }
+// (table_rows_sparse_kernel); single-feature inputs are dense and keep the dense kernels.
+static bool table_rows_are_sparse(const hscmp_ctx* ctx) { return ctx->F > 1 && ctx->W <= 32767 && ctx->F <= 65535; }
 constexpr int kTableRowCap = 1024;             // listed non-zeros per row window (12 KB of LDS in float64); more: dense chain
 template <typename R> static void launch_table_rows_sparse(hscmp_ctx* ctx, const R* d_r, int T, int row0, int nrows, int p, R* d_table)
 {

@@ -906,6 +906,7 @@ template <typename R> struct GenericRecorr {
     static __device__ __forceinline__ bool residual_copy_in_lds(const Args&, char*) { return false; }
     static constexpr int kWinBytes = 16384;            // LDS window of the residual span, when it fits
     static size_t extra_lds_bytes(const DevParams&) { return kWinBytes; }
+    static size_t total_lds_bytes(const DevParams& P, const Args&) { return ((sizeof(Shared) + 15) / 16) * 16 + extra_lds_bytes(P); }
     static __device__ __forceinline__ void prologue(const DevParams&, const State<R>&, const Args&, char*, int, Sync&) {}
     template <typename SH>
     static __device__ __forceinline__ void run(const DevParams& P, const State<R>& S, const Sig<R>& G,

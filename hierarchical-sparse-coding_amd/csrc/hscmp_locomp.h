@@ -81,6 +81,7 @@ template <typename R> struct LocompRecorr : GenericRecorr<R> {
     static __device__ __forceinline__ void lrun_span(const DevParams&, const State<R>&, const Sig<R>&, const Args&, char*, int, int, SY&) {}
     static __device__ __forceinline__ bool atom_lists(const DevParams&, const Args&, char*, const int*&, const int*&, const R*&) { return false; }
     static size_t extra_lds_bytes(const DevParams& P) { return Base::extra_lds_bytes(P) + sizeof(LocompLds<R>) + 16; }
+    static size_t total_lds_bytes(const DevParams& P, const Args&) { return ((sizeof(typename Base::Shared) + 15) / 16) * 16 + extra_lds_bytes(P); }
     static __device__ __forceinline__ LocompLds<R>& group(const DevParams&, const Args&, char* lds)
     {
         return *reinterpret_cast<LocompLds<R>*>(lds + ((Base::kWinBytes + 15) / 16) * 16);
@@ -365,6 +366,7 @@ template <typename R> struct LocompSparse : SparseRecorr<R, false> {
     }
     static size_t policy_bytes(const DevParams& P, const Args& A) { return ((Base::extra_lds_bytes(P, A) + 15) / 16) * 16; }
     static size_t extra_lds_bytes(const DevParams& P, const Args& A) { return policy_bytes(P, A) + sizeof(LocompLds<R>) + 16; }
+    static size_t total_lds_bytes(const DevParams& P, const Args& A) { return ((sizeof(typename Base::Shared) + 15) / 16) * 16 + extra_lds_bytes(P, A); }
     static __device__ __forceinline__ LocompLds<R>& group(const DevParams& P, const Args& A, char* lds)
     {
         const size_t off = ((Base::bits_offset(P, A) + (Base::has_bits(P, A) ? (size_t)((P.T + 31) / 32) * sizeof(unsigned) : 0) + 15) / 16) * 16;

@@ -1383,9 +1383,6 @@ static int mfma_launch_corr_init_t(hipStream_t stream, const DevParams& P, const
     return 0;
 }
 
-// signals per workgroup of the last MFMA loop this thread launched (reported by hscmp_last_variant)
-inline int& mfma_last_group() { static thread_local int g = 1; return g; }
-
 template <typename Tile, int S4C, bool HAS_W, int GS>
 static int mfma_launch_iterate_g(hipStream_t stream, const DevParams& P0, const State<typename Tile::R>& S,
                                  const MfmaArgsT<typename Tile::R>& A, bool dry)
@@ -1407,24 +1404,18 @@ static int mfma_launch_iterate_g(hipStream_t stream, const DevParams& P0, const 
                 hipGetErrorString(e), P.seg, P.nseg);
     }
     hipLaunchKernelGGL(kern, dim3((P.B + GS - 1) / GS), dim3(GS * kThreads), lds, stream, P, S, A);
-    mfma_last_group() = GS;
     return 0;
 }
 
-// Four signals per workgroup pay off once a CU would otherwise hold more than two signals in turn (B > 2 x CUs):
-// one round of four overlapping signals per CU instead of two rounds of two.  HSCMP_MFMA_QUAD=0/1 forces the choice
-// (tests run both; the results are bit-identical).  Returns the signals per workgroup that `dry == false` launched.
+// The loop with `group` signals per workgroup: 1, or 4 (float32 with a compile-time chunk count: one round of four overlapping
+// signals per CU instead of two rounds of two).  0: launched (or, dry, could be); -1: no such form for this shape.
 template <typename Tile, int S4C, bool HAS_W>
 static int mfma_launch_iterate_t(hipStream_t stream, const DevParams& P, const State<typename Tile::R>& S,
-                                 const MfmaArgsT<typename Tile::R>& A, bool dry = false)
+                                 const MfmaArgsT<typename Tile::R>& A, int group, bool dry)
 {
-    bool quad = false;
-    if constexpr (sizeof(typename Tile::R) == 4 && S4C > 0) {
-        quad = P.B > 2 * mfma_device_cus();
-        if (const char* e = getenv("HSCMP_MFMA_QUAD")) quad = atoi(e) != 0;
-        if (quad && mfma_launch_iterate_g<Tile, S4C, HAS_W, 4>(stream, P, S, A, dry) == 0) return 0;
-    }
-    return mfma_launch_iterate_g<Tile, S4C, HAS_W, 1>(stream, P, S, A, dry);
+    if constexpr (sizeof(typename Tile::R) == 4 && S4C > 0)
+        if (group == 4) return mfma_launch_iterate_g<Tile, S4C, HAS_W, 4>(stream, P, S, A, dry);
+    return group == 1 ? mfma_launch_iterate_g<Tile, S4C, HAS_W, 1>(stream, P, S, A, dry) : -1;
 }
 
 template <typename R> inline MfmaArgsT<R> mfma_args(const DevParams& P, const State<R>& S, const R* dimg)
@@ -1435,15 +1426,15 @@ template <typename R> inline MfmaArgsT<R> mfma_args(const DevParams& P, const St
     return A;
 }
 
-#define HSCMP_MFMA_DISPATCH(FN)                                                                       \
-    do {                                                                                              \
-        const bool hw = A.has_w != 0;                                                                 \
-        switch (A.S4) {                                                                               \
-        case 8: return hw ? FN<Tile, 8, true>(stream, P, S, A, dry) : FN<Tile, 8, false>(stream, P, S, A, dry);  \
-        case 4: return hw ? FN<Tile, 4, true>(stream, P, S, A, dry) : FN<Tile, 4, false>(stream, P, S, A, dry);  \
-        case 2: return hw ? FN<Tile, 2, true>(stream, P, S, A, dry) : FN<Tile, 2, false>(stream, P, S, A, dry);  \
-        default: return hw ? FN<Tile, 0, true>(stream, P, S, A, dry) : FN<Tile, 0, false>(stream, P, S, A, dry); \
-        }                                                                                             \
+#define HSCMP_MFMA_DISPATCH(FN, ...)                                                                                          \
+    do {                                                                                                                      \
+        const bool hw = A.has_w != 0;                                                                                         \
+        switch (A.S4) {                                                                                                       \
+        case 8: return hw ? FN<Tile, 8, true>(stream, P, S, A, __VA_ARGS__) : FN<Tile, 8, false>(stream, P, S, A, __VA_ARGS__);  \
+        case 4: return hw ? FN<Tile, 4, true>(stream, P, S, A, __VA_ARGS__) : FN<Tile, 4, false>(stream, P, S, A, __VA_ARGS__);  \
+        case 2: return hw ? FN<Tile, 2, true>(stream, P, S, A, __VA_ARGS__) : FN<Tile, 2, false>(stream, P, S, A, __VA_ARGS__);  \
+        default: return hw ? FN<Tile, 0, true>(stream, P, S, A, __VA_ARGS__) : FN<Tile, 0, false>(stream, P, S, A, __VA_ARGS__); \
+        }                                                                                                                     \
     } while (0)
 
 // dry: only check that the kernel can be configured for this shape (LDS attribute), queue nothing
@@ -1451,14 +1442,15 @@ template <typename R> inline int mfma_launch_corr_init(hipStream_t stream, const
 {
     using Tile = typename TileOf<R>::type;
     const MfmaArgsT<R> A = mfma_args<R>(P, S, dimg);
-    HSCMP_MFMA_DISPATCH(mfma_launch_corr_init_t);
+    HSCMP_MFMA_DISPATCH(mfma_launch_corr_init_t, dry);
 }
 
-template <typename R> inline int mfma_launch_iterate(hipStream_t stream, const DevParams& P, const State<R>& S, const R* dimg, bool dry = false)
+template <typename R>
+inline int mfma_launch_iterate(hipStream_t stream, const DevParams& P, const State<R>& S, const R* dimg, int group, bool dry = false)
 {
     using Tile = typename TileOf<R>::type;
     const MfmaArgsT<R> A = mfma_args<R>(P, S, dimg);
-    HSCMP_MFMA_DISPATCH(mfma_launch_iterate_t);
+    HSCMP_MFMA_DISPATCH(mfma_launch_iterate_t, group, dry);
 }
 
 }  // namespace hscmp

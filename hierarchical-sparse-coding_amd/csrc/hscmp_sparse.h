@@ -639,6 +639,7 @@ template <typename R, bool PACKED = false> struct SparseRecorr {
     {
         return bits_offset(P, A) + (has_bits(P, A) ? (size_t)((P.T + 31) / 32) * sizeof(unsigned) : 0);
     }
+    static size_t total_lds_bytes(const DevParams& P, const Args& A) { return ((sizeof(Shared) + 15) / 16) * 16 + extra_lds_bytes(P, A); }
     static __device__ __forceinline__ unsigned* bits_of(const DevParams& P, const Args& A, char* lds) { return reinterpret_cast<unsigned*>(lds + bits_offset(P, A)); }
     static __device__ __forceinline__ const R* weights(const DevParams& P, const State<R>&, const Args& A, char* lds)
     {
