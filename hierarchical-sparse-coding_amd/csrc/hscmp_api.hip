@@ -18,6 +18,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <algorithm>
@@ -25,8 +26,44 @@
 
 using namespace hscmp;
 
+// The environment knobs (field x is HSCMP_X): tests and diagnostics force a path with them, every path
+// bit-identical.  read_knobs is the only reader of the environment: each entry point takes one snapshot when it is called and
+// passes it down, and an encode keeps its snapshot in its plan, so hscmp_continue resumes with it.
+struct Knobs {
+    bool no_dict_lists, no_row_lists, no_rowbits, no_pairing, force_gathered, force_generic;     // set or not
+    bool init_only, exact_init, locomp_no_mfma, no_sorted_prepare, no_lazy_clear;
+    int rp, mfma_quad, sparse_packed;     // 0 / 1 forces the choice; -1: not set, chosen by the shape
+    int locomp_pack;                      // at most this many signals per workgroup; 0: not set, by the batch size
+    int slot_hash_min, locomp_group_cap, locomp_ahead, sorted_prepare_min, lds_pad;     // the value, or the default
+    int epi_lds_keys;                     // the value if a power of two in 64..kEpiLdsKeys, else kEpiLdsKeys
+    bool epi_lds_keys_set;                // ... set at all, valid or not (the epilogue's LDS floor is then 8 KB instead of 64 KB)
+};
+
+static Knobs read_knobs()
+{
+    Knobs k;
+    const char* v;
+    k.no_dict_lists = getenv("HSCMP_NO_DICT_LISTS"); k.no_row_lists = getenv("HSCMP_NO_ROW_LISTS"); k.no_rowbits = getenv("HSCMP_NO_ROWBITS");
+    k.no_pairing = getenv("HSCMP_NO_PAIRING"); k.force_gathered = getenv("HSCMP_FORCE_GATHERED"); k.force_generic = getenv("HSCMP_FORCE_GENERIC");
+    k.init_only = getenv("HSCMP_INIT_ONLY"); k.exact_init = getenv("HSCMP_EXACT_INIT"); k.locomp_no_mfma = getenv("HSCMP_LOCOMP_NO_MFMA");
+    k.no_sorted_prepare = getenv("HSCMP_NO_SORTED_PREPARE"); k.no_lazy_clear = getenv("HSCMP_NO_LAZY_CLEAR");
+    k.rp = (v = getenv("HSCMP_RP")) ? atoi(v) != 0 : -1;
+    k.mfma_quad = (v = getenv("HSCMP_MFMA_QUAD")) ? atoi(v) != 0 : -1;
+    k.sparse_packed = (v = getenv("HSCMP_SPARSE_PACKED")) ? atoi(v) != 0 : -1;
+    k.locomp_pack = (v = getenv("HSCMP_LOCOMP_PACK")) ? std::max(1, atoi(v)) : 0;     // (0 and below pack like 1)
+    k.slot_hash_min = (v = getenv("HSCMP_SLOT_HASH_MIN")) ? std::max(0, atoi(v)) : kSlotHashMin;
+    k.locomp_group_cap = (v = getenv("HSCMP_LOCOMP_GROUP_CAP")) ? std::min(4096, std::max(2, atoi(v))) : kLocompGroupCap;
+    k.locomp_ahead = (v = getenv("HSCMP_LOCOMP_AHEAD")) ? atoi(v) & 7 : 7;
+    k.sorted_prepare_min = (v = getenv("HSCMP_SORTED_PREPARE_MIN")) ? atoi(v) : 2048;
+    k.lds_pad = (v = getenv("HSCMP_LDS_PAD")) ? atoi(v) : 0;
+    k.epi_lds_keys_set = (v = getenv("HSCMP_EPI_LDS_KEYS"));
+    const int n = v ? atoi(v) : 0;
+    k.epi_lds_keys = n >= 64 && n <= kEpiLdsKeys && (n & (n - 1)) == 0 ? n : kEpiLdsKeys;
+    return k;
+}
+
 // The kernels of one encode, chosen once by plan_encode before anything is queued: run_encode queues them (launch_init,
-// launch_loop) and hscmp_continue resumes the batch with the same loop.
+// launch_loop) and hscmp_continue resumes the batch with the same loop and the same knobs.
 struct EncodePlan {
     enum Init { kInitMfma, kInitBound, kInitSparse, kInitOwn, kInitGeneric };
     enum Loop { kLoopMfma, kLoopSparse, kLoopGeneric, kLoopLocomp, kLoopLocompSparse, kLoopLocompMfma };
@@ -40,6 +77,7 @@ struct EncodePlan {
     bool row_lists = false;   // per-row feature lists of the input's non-zero cells (the level chaining or the init writes them)
     bool kept_lists = false;  // ... and the loop keeps them current: it enters every cell it writes
     bool init_only = false;   // HSCMP_INIT_ONLY (tests): stop behind the initial correlation
+    Knobs knobs{};            // the encode's snapshot: the launches read pairing, row bitmaps and LDS pad from it
 };
 
 struct hscmp_ctx {
@@ -281,7 +319,7 @@ extern "C" int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W,
         HIP_TRY(ctx, hipMemcpy(ctx->d_Dc, dt.data(), nD, hipMemcpyHostToDevice));
         // per-atom list of non-zeros in chain order (f outer, w inner), kept when the dictionary is sparse
         // (level dictionaries built from decompositions + singletons, hsc/dataset.py:137-194, 826-860)
-        if (W <= 32767 && F <= 65535 && !getenv("HSCMP_NO_DICT_LISTS")) {
+        if (W <= 32767 && F <= 65535 && !read_knobs().no_dict_lists) {
             std::vector<int> ptr(K + 1, 0), wf;
             std::vector<char> val;
             const size_t limit = (size_t)kDictListMaxPerAtom * K;
@@ -359,7 +397,7 @@ extern "C" int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W,
 
 // geometry given explicitly (the row-level selection runs on a caller's table of any K, W: the context's dictionary is
 // not involved and is not touched)
-static int make_params_g(hscmp_ctx* ctx, int K, int W, int F, int B, int T, const hscmp_params* p, DevParams* out)
+static int make_params_g(hscmp_ctx* ctx, const Knobs& kn, int K, int W, int F, int B, int T, const hscmp_params* p, DevParams* out)
 {
     DevParams P{};
     P.B = B; P.T = T; P.K = K; P.W = W; P.F = F;
@@ -387,22 +425,19 @@ static int make_params_g(hscmp_ctx* ctx, int K, int W, int F, int B, int T, cons
     if (p->max_events <= 0) return fail(ctx, HSCMP_ERR_INVALID, "max_events must be > 0");
     P.cap = p->max_events;
     P.hmask = slot_hash_mask(P.cap);
-    P.hash_min = kSlotHashMin;
-    if (const char* v = getenv("HSCMP_SLOT_HASH_MIN")) P.hash_min = std::max(0, atoi(v));
+    P.hash_min = kn.slot_hash_min;
     if (ctx && ctx->method == HSCMP_METHOD_LOCOMP) P.hash_min = INT_MAX;        // (its atom body scans the slot list for the neighbourhood anyway)
     P.max_rounds = p->max_rounds;
-    P.lg_cap = kLocompGroupCap;
-    if (const char* v = getenv("HSCMP_LOCOMP_GROUP_CAP")) P.lg_cap = std::min(4096, std::max(2, atoi(v)));
-    P.lc_ahead = 7;          // bit 0: selections of a round side by side; bit 1: a group's rows re-correlated one wave per quarter (sparse policy);
-                             // bit 2: the rows of a batch of selections re-correlated behind its last one, one wave per selection
-    if (const char* v = getenv("HSCMP_LOCOMP_AHEAD")) P.lc_ahead = atoi(v) & 7;
+    P.lg_cap = kn.locomp_group_cap;
+    P.lc_ahead = kn.locomp_ahead;     // (default 7) bit 0: selections of a round side by side; bit 1: a group's rows re-correlated one wave per quarter (sparse policy);
+                                      // bit 2: the rows of a batch of selections re-correlated behind its last one, one wave per selection
     *out = P;
     return HSCMP_OK;
 }
 
-static int make_params(hscmp_ctx* ctx, int B, int T, const hscmp_params* p, DevParams* out)
+static int make_params(hscmp_ctx* ctx, const Knobs& kn, int B, int T, const hscmp_params* p, DevParams* out)
 {
-    return make_params_g(ctx, ctx->K, ctx->W, ctx->F, B, T, p, out);
+    return make_params_g(ctx, kn, ctx->K, ctx->W, ctx->F, B, T, p, out);
 }
 
 // every buffer tracks its own capacity in bytes (element size changes with the dictionary dtype)
@@ -411,9 +446,9 @@ struct BufCap { void** p; size_t* cap; size_t bytes; };
 // Per-row feature lists: multi-feature inputs with a sparse dictionary (the per-atom lists tell which cells an
 // atom touches).
 constexpr int kRowListCap = 8;
-static bool use_row_lists(const hscmp_ctx* ctx)
+static bool use_row_lists(const hscmp_ctx* ctx, const Knobs& kn)
 {
-    return ctx->F > 1 && ctx->d_nzptr != nullptr && !getenv("HSCMP_NO_ROW_LISTS");
+    return ctx->F > 1 && ctx->d_nzptr != nullptr && !kn.no_row_lists;
 }
 
 // Workgroups per signal of the sparse initial correlation: enough to fill the chip at small batches.
@@ -489,10 +524,10 @@ template <typename R> static SparseArgs<R> sparse_args(hscmp_ctx* ctx, const Enc
 {
     SparseArgs<R> A;
     A.Dt = (const R*)ctx->d_Dt; A.scratch = (R*)ctx->d_scratch;
-    A.rowflag = (T <= kRowBitsMaxT && !getenv("HSCMP_NO_ROWBITS")) ? ctx->d_rowflag : nullptr;
+    A.rowflag = (T <= kRowBitsMaxT && !plan.knobs.no_rowbits) ? ctx->d_rowflag : nullptr;
     A.rowflag_filled = ctx->rowflag_valid ? 1 : 0;
     A.nzptr = ctx->d_nzptr; A.nzwf = ctx->d_nzwf; A.nzval = (const R*)ctx->d_nzval;
-    A.fptr = getenv("HSCMP_NO_PAIRING") ? nullptr : ctx->d_fptr; A.fkw = ctx->d_fkw; A.fval = (const R*)ctx->d_fval;
+    A.fptr = plan.knobs.no_pairing ? nullptr : ctx->d_fptr; A.fkw = ctx->d_fkw; A.fval = (const R*)ctx->d_fval;
     A.nnz = ctx->dict_nnz; A.wts = (const R*)ctx->d_w;
     A.caps = sparse_caps(ctx->W, packed);
     A.rl_cnt = plan.row_lists ? ctx->d_rl_cnt : nullptr; A.rl_f = ctx->d_rl_f; A.rl_cap = kRowListCap; A.rl_filled = ctx->rl_filled ? 1 : 0;
@@ -545,11 +580,12 @@ static int launch_locomp_mfma(hscmp_ctx* ctx, const DevParams& P, int group, boo
     }
 }
 
-// The one place that chooses the kernels of an encode: every knob that selects a kernel is read here, once per encode, and every
-// LDS-fit check runs here.  row_lists: the encode keeps per-row feature lists where its kernels can use them (use_row_lists).
-template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const DevParams& P, bool row_lists)
+// The one place that chooses the kernels of an encode: every knob that selects a kernel is looked at here, and every LDS-fit
+// check runs here.  row_lists: the encode keeps per-row feature lists where its kernels can use them (use_row_lists).
+template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const Knobs& kn, const DevParams& P, bool row_lists)
 {
     EncodePlan plan;
+    plan.knobs = kn;
     plan.f64 = sizeof(R) == 8;
     plan.dict_lists = ctx->d_nzptr != nullptr;
     const State<R> S = make_state<R>(ctx);
@@ -560,15 +596,14 @@ template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const DevPar
     // Measured at the config-4 shape (profiles/r03_*): the level loops gain at every batch size (1024 signals: 28.9 -> 14.5 ms);
     // on the matrix cores the four-signal loop catches up once every CU holds four signals (1024: 117.2 vs 117.6 ms; 512: 66.0
     // vs 60.7 ms).
-    const char* rp_env = getenv("HSCMP_RP");
-    const bool rp_level = P.blocked && (rp_env ? atoi(rp_env) != 0 : true);
-    const bool rp_mfma = P.blocked && (rp_env ? atoi(rp_env) != 0 : P.B <= 3 * cus);
+    const bool rp_level = P.blocked && kn.rp != 0;
+    const bool rp_mfma = P.blocked && (kn.rp >= 0 ? kn.rp != 0 : P.B <= 3 * cus);
     // Sparsity-aware kernels for multi-feature inputs (hierarchical levels >= 1).  The loop only with a sparse dictionary
     // (measured: for dense single-feature windows the dense chain is 3x faster; subtracting dense atoms fills the residual, the
     // windows then overflow the gathered lists and the dense LDS-staged chain of GenericRecorr is several times faster -- a k-means
     // dictionary with ~150 of 528 non-zeros per atom: 1.3 ms vs 0.37 ms per atom).  ((f << 16) | row keys: W <= 16384, F <= 32767)
     const bool sparse_shape = ctx->F > 1 && ctx->d_Dt != nullptr && ctx->W <= 16384 && ctx->F <= 32767;
-    const bool sparse_loop = sparse_shape && (ctx->d_nzptr != nullptr || getenv("HSCMP_FORCE_GATHERED"));
+    const bool sparse_loop = sparse_shape && (ctx->d_nzptr != nullptr || kn.force_gathered);
     plan.row_lists = row_lists && sparse_loop;
 
     // The matrix-core kernels come as a pair: the score-only state the initial correlation leaves is what the MFMA loop reads (the
@@ -576,20 +611,19 @@ template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const DevPar
     // edges (T >= 3W-2).  Four signals per workgroup pay off once a CU would otherwise hold more than two signals in turn
     // (B > 2 x CUs); HSCMP_MFMA_QUAD=0/1 forces the choice (tests run both; the results are bit-identical).
     bool mf = false;
-    if (!locomp && !getenv("HSCMP_FORCE_GENERIC") && dimg && P.T >= 3 * ctx->W - 2 && mfma_launch_corr_init<R>(ctx->stream, P, S, dimg, true) == 0) {
-        bool quad = sizeof(R) == 4 && P.B > 2 * cus;
-        if (const char* e = getenv("HSCMP_MFMA_QUAD")) quad = atoi(e) != 0;
-        if (quad && mfma_launch_iterate<R>(ctx->stream, P, S, dimg, 4, true) == 0) plan.group = 4;
-        mf = plan.group == 4 || mfma_launch_iterate<R>(ctx->stream, P, S, dimg, 1, true) == 0;
+    if (!locomp && !kn.force_generic && dimg && P.T >= 3 * ctx->W - 2 && mfma_launch_corr_init<R>(ctx->stream, P, S, dimg, true) == 0) {
+        const bool quad = kn.mfma_quad >= 0 ? kn.mfma_quad != 0 : sizeof(R) == 4 && P.B > 2 * cus;
+        if (quad && mfma_launch_iterate<R>(ctx->stream, P, S, dimg, 4, kn.lds_pad, true) == 0) plan.group = 4;
+        mf = plan.group == 4 || mfma_launch_iterate<R>(ctx->stream, P, S, dimg, 1, kn.lds_pad, true) == 0;
     }
     if (mf) {
         plan.init = EncodePlan::kInitMfma;
         plan.loop = EncodePlan::kLoopMfma;
-        plan.init_only = getenv("HSCMP_INIT_ONLY") != nullptr;
+        plan.init_only = kn.init_only;
         if constexpr (sizeof(R) == 4) {
             // float32 single-arg-max encodes: the initial correlation as upper bounds on the bf16 matrix cores, refined by the loop
             // where a selection needs it (hscmp_bound.h).  HSCMP_EXACT_INIT=1: the exact pass everywhere.
-            if (!P.blocked && !P.select_only && ctx->d_Bimg && !getenv("HSCMP_EXACT_INIT") &&
+            if (!P.blocked && !P.select_only && ctx->d_Bimg && !kn.exact_init &&
                 bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->d_Bimg, ctx->bound_cmax, true) == 0)
                 plan.init = EncodePlan::kInitBound;
             plan.rp = rp_mfma && rp_mfma_launch(ctx->stream, P, S, dimg, true) == 0;
@@ -603,12 +637,11 @@ template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const DevPar
         // workgroup: as many as it takes to put the whole batch on the chip at once -- two or four around one dictionary image,
         // their tiles sharing the CU's matrix pipe (HSCMP_LOCOMP_PACK = 1 / 2 / 4 overrides).  The sparse form when its staged
         // dictionary lists fit (else the dense form runs).
-        const char* pack_env = getenv("HSCMP_LOCOMP_PACK");
-        const int pack = pack_env ? atoi(pack_env) : P.B > 2 * cus ? 4 : P.B > cus ? 2 : 1;
+        const int pack = kn.locomp_pack > 0 ? kn.locomp_pack : P.B > 2 * cus ? 4 : P.B > cus ? 2 : 1;
         if (sparse_loop && launch_policy<R, LocompSparse<R>>(ctx, P, sparse_args<R>(ctx, plan, P.T), 1, true) == 0) {
             plan.loop = EncodePlan::kLoopLocompSparse;
             plan.kept_lists = plan.row_lists;
-        } else if (sizeof(R) == 4 && ctx->F == 1 && dimg && !getenv("HSCMP_LOCOMP_NO_MFMA")) {
+        } else if (sizeof(R) == 4 && ctx->F == 1 && dimg && !kn.locomp_no_mfma) {
             for (int g : {4, 2, 1})
                 if ((pack >= g || g == 1) && launch_locomp_mfma(ctx, P, g, true) == 0) {
                     plan.init = EncodePlan::kInitOwn; plan.loop = EncodePlan::kLoopLocompMfma; plan.group = g;
@@ -624,10 +657,9 @@ template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const DevPar
         // small batches of blocked rounds: the round-parallel level loop (hscmp_rp_sparse.h), one wave per atom of the round
         if constexpr (sizeof(R) == 8) plan.rp = rp_level && rp_sparse_launch<R>(ctx->stream, P, S, sparse_args<R>(ctx, plan, P.T), true) == 0;
         // more signals than two per CU: the four-workgroups-per-CU form of the loop (see SparseRecorr) when its LDS fits
-        const char* packed_env = getenv("HSCMP_SPARSE_PACKED");
         if (!plan.rp)
-            plan.packed = packed_env ? atoi(packed_env) != 0
-                                     : P.B > 2 * cus && policy_lds_bytes<SparseRecorr<R, true>>(P, sparse_args<R>(ctx, plan, P.T, true)) <= (size_t)40 * 1024;
+            plan.packed = kn.sparse_packed >= 0 ? kn.sparse_packed != 0
+                                                : P.B > 2 * cus && policy_lds_bytes<SparseRecorr<R, true>>(P, sparse_args<R>(ctx, plan, P.T, true)) <= (size_t)40 * 1024;
     }
     return plan;
 }
@@ -693,7 +725,7 @@ template <typename R> static int launch_loop(hscmp_ctx* ctx, const EncodePlan& p
     case EncodePlan::kLoopMfma:
         if constexpr (sizeof(R) == 4)
             if (plan.rp) { rc = rp_mfma_launch(ctx->stream, P, make_state<float>(ctx), dimg); break; }
-        rc = mfma_launch_iterate<R>(ctx->stream, P, make_state<R>(ctx), dimg, plan.group);
+        rc = mfma_launch_iterate<R>(ctx->stream, P, make_state<R>(ctx), dimg, plan.group, plan.knobs.lds_pad);
         break;
     case EncodePlan::kLoopSparse:
         if constexpr (sizeof(R) == 8)
@@ -727,9 +759,8 @@ static int run_encode(hscmp_ctx* ctx, const EncodePlan& plan, const DevParams& P
         while ((1 << ibits) < std::max(2, chain->max_slots)) ++ibits;
         const long long cells256 = ((long long)P.T * P.F + 255) >> 8;
         const size_t lds = (size_t)std::max(1, chain->max_slots) * sizeof(unsigned);
-        const int sorted_min = getenv("HSCMP_SORTED_PREPARE_MIN") ? atoi(getenv("HSCMP_SORTED_PREPARE_MIN")) : 2048;
-        const bool sorted = chain->max_slots > sorted_min && lds <= (size_t)150 * 1024 && ibits < 31 && cells256 < (1ll << (32 - ibits)) &&
-                            !getenv("HSCMP_NO_SORTED_PREPARE") &&
+        const bool sorted = chain->max_slots > plan.knobs.sorted_prepare_min && lds <= (size_t)150 * 1024 && ibits < 31 &&
+                            cells256 < (1ll << (32 - ibits)) && !plan.knobs.no_sorted_prepare &&
                             set_dyn_lds((const void*)prepare_from_slots_sorted_kernel<R>, lds) == hipSuccess;
         if (sorted)
             hipLaunchKernelGGL((prepare_from_slots_sorted_kernel<R>), dim3(P.B), dim3(kThreads), lds, ctx->stream, P, S, chain->slot_t, chain->slot_k,
@@ -764,12 +795,13 @@ static int encode_common(hscmp_ctx* ctx, const void* x, bool host, int B, int T,
     if (ctx->dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_encode_batch: no dictionary set");
     if (!x || !params || B <= 0 || T <= 0) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch: bad arguments (B=%d T=%d)", B, T);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const Knobs kn = read_knobs();
     DevParams P;
-    int rc = make_params(ctx, B, T, params, &P);
+    int rc = make_params(ctx, kn, B, T, params, &P);
     if (rc) return rc;
-    const bool row_lists = use_row_lists(ctx);
+    const bool row_lists = use_row_lists(ctx, kn);
     if ((rc = ensure_workspace(ctx, P, host, row_lists))) return rc;
-    const EncodePlan plan = ctx->dtype == HSCMP_F32 ? plan_encode<float>(ctx, P, row_lists) : plan_encode<double>(ctx, P, row_lists);
+    const EncodePlan plan = ctx->dtype == HSCMP_F32 ? plan_encode<float>(ctx, kn, P, row_lists) : plan_encode<double>(ctx, kn, P, row_lists);
     const void* xd = x;
     if (host) {
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_x, x, (size_t)B * T * ctx->F * esize(ctx->dtype), hipMemcpyHostToDevice, ctx->stream));
@@ -807,15 +839,16 @@ extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, in
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(prev->stream));           // the previous level's results are final
     const int T = prev->T;
+    const Knobs kn = read_knobs();
     DevParams P;
-    int rc = make_params(ctx, count, T, params, &P);
+    int rc = make_params(ctx, kn, count, T, params, &P);
     if (rc) return rc;
-    const bool row_lists = use_row_lists(ctx);
+    const bool row_lists = use_row_lists(ctx, kn);
     if ((rc = ensure_workspace(ctx, P, false, row_lists))) return rc;        // no input buffer: the slots are scattered straight into the residual
-    const EncodePlan plan = plan_encode<double>(ctx, P, row_lists);
+    const EncodePlan plan = plan_encode<double>(ctx, kn, P, row_lists);
     const bool lists = plan.row_lists;          // (the scatter writes them)
     const size_t bytes = (size_t)count * T * ctx->F * sizeof(double);
-    if (ctx->listed_rows > 0 && ctx->listed_F == ctx->F && !getenv("HSCMP_NO_LAZY_CLEAR")) {
+    if (ctx->listed_rows > 0 && ctx->listed_F == ctx->F && !kn.no_lazy_clear) {
         // the buffer still holds the previous chained batch; its lists say where
         hipLaunchKernelGGL((clear_listed_cells_kernel<double>), dim3((unsigned)((ctx->listed_rows + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream,
                            (double*)ctx->d_resid, ctx->listed_rows, ctx->F, ctx->d_rl_cnt, ctx->d_rl_f, kRowListCap);
@@ -1245,8 +1278,8 @@ extern "C" int hscmp_hierarchy_epilogue(hscmp_ctx* last, hscmp_ctx* level0, int 
     }
     int nmax = 2;
     while (nmax < last->cap) nmax <<= 1;
-    int lds_keys = kEpiLdsKeys;                                  // (HSCMP_EPI_LDS_KEYS: tests force the chunked sort at small sizes)
-    if (const char* e = getenv("HSCMP_EPI_LDS_KEYS")) { const int v = atoi(e); if (v >= 64 && v <= kEpiLdsKeys && (v & (v - 1)) == 0) lds_keys = v; }
+    const Knobs kn = read_knobs();
+    const int lds_keys = kn.epi_lds_keys;                        // (HSCMP_EPI_LDS_KEYS: tests force the chunked sort at small sizes)
     const bool need_scratch = true;                              // (the t-sorted keys move there while the LDS holds residual tiles)
     const size_t nres = out_residual ? (size_t)count * T * Fd * sizeof(double) : 0;
     const size_t sizes[8] = {0, (size_t)(count + 1) * sizeof(long long), (size_t)count * sizeof(int), (size_t)count * (Ktot + 1) * sizeof(int),
@@ -1269,7 +1302,7 @@ extern "C" int hscmp_hierarchy_epilogue(hscmp_ctx* last, hscmp_ctx* level0, int 
         if ((rc = epi_buffer(last, kArenaEpiEnergy, (size_t)count * sizeof(double)))) return rc;
         A.out_energy = (double*)last->d_epi[kArenaEpiEnergy];
     }
-    const size_t lds = std::max<size_t>((size_t)std::min(nmax, lds_keys) * sizeof(unsigned long long), getenv("HSCMP_EPI_LDS_KEYS") ? 8192 : 65536);
+    const size_t lds = std::max<size_t>((size_t)std::min(nmax, lds_keys) * sizeof(unsigned long long), kn.epi_lds_keys_set ? 8192 : 65536);
     A.lds_keys = std::min(nmax, lds_keys); A.lds_bytes = (int)lds;
     const size_t xoff = (size_t)first * T * Fd * esize(level0->dtype);
     if (level0->dtype == HSCMP_F32) {
@@ -1320,14 +1353,14 @@ extern "C" int hscmp_debug_stamps(unsigned long long* out16, int reset)
 // One selection (modeling.py:899-982) on a table that is ON THE DEVICE: d_ip [T][K], d_w [K] or null.  Uses the batch
 // workspace of the context (a batch held by the context is gone afterwards) but none of its dictionary state.
 template <typename R>
-static int select_on_device(hscmp_ctx* ctx, const R* d_ip, const R* d_w, int T, int K, int W, int nb_blocks, int offset, double thres,
+static int select_on_device(hscmp_ctx* ctx, const Knobs& kn, const R* d_ip, const R* d_w, int T, int K, int W, int nb_blocks, int offset, double thres,
                             int32_t* out_t, int32_t* out_k, void* out_c, int max_out, int32_t* n_out, const char* who)
 {
     hscmp_params hp{};
     hp.nb_nonzero_coefs = -1; hp.nb_blocks = nb_blocks; hp.tolerance_snr = NAN; hp.tolerance_residual_scale = NAN;
     hp.null_coeff_thres = thres; hp.eps = 0.0; hp.max_events = 1; hp.max_rounds = 1;
     DevParams P;
-    int rc = make_params_g(ctx, K, W, 1, 1, T, &hp, &P);               // only T, K, W matter for the selection
+    int rc = make_params_g(ctx, kn, K, W, 1, 1, T, &hp, &P);               // only T, K, W matter for the selection
     if (rc == HSCMP_OK) rc = ensure_workspace_g(ctx, P, false, sizeof(R), false, false);
     if (rc != HSCMP_OK) return rc;
     ctx->have_batch = false;
@@ -1372,7 +1405,7 @@ template <typename R> static int upload_weights(hscmp_ctx* ctx, const void* weig
 }
 
 template <typename R>
-static int run_select(hscmp_ctx* ctx, const void* ip, int T, int K, int W, int nb_blocks, int offset, double thres,
+static int run_select(hscmp_ctx* ctx, const Knobs& kn, const void* ip, int T, int K, int W, int nb_blocks, int offset, double thres,
                       const void* weights, int32_t* out_t, int32_t* out_k, void* out_c, int max_out, int32_t* n_out)
 {
     int rc = epi_buffer(ctx, kArenaRowA, (size_t)T * K * sizeof(R));
@@ -1380,7 +1413,7 @@ static int run_select(hscmp_ctx* ctx, const void* ip, int T, int K, int W, int n
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_epi[kArenaRowA], ip, (size_t)T * K * sizeof(R), hipMemcpyHostToDevice, ctx->stream));
     const R* d_w;
     if ((rc = upload_weights<R>(ctx, weights, K, &d_w)) != HSCMP_OK) return rc;
-    return select_on_device<R>(ctx, (const R*)ctx->d_epi[kArenaRowA], d_w, T, K, W, nb_blocks, offset, thres, out_t, out_k, out_c, max_out, n_out,
+    return select_on_device<R>(ctx, kn, (const R*)ctx->d_epi[kArenaRowA], d_w, T, K, W, nb_blocks, offset, thres, out_t, out_k, out_c, max_out, n_out,
                                "hscmp_select_best_atoms");
 }
 
@@ -1393,9 +1426,10 @@ extern "C" int hscmp_select_best_atoms(hscmp_ctx* ctx, const void* ip, int T, in
         return fail(ctx, HSCMP_ERR_INVALID, "hscmp_select_best_atoms: bad arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const Knobs kn = read_knobs();
     return dtype == HSCMP_F32
-        ? run_select<float>(ctx, ip, T, K, W, nb_blocks, offset, null_coeff_thres, weights, out_t, out_k, out_c, max_out, n_out)
-        : run_select<double>(ctx, ip, T, K, W, nb_blocks, offset, null_coeff_thres, weights, out_t, out_k, out_c, max_out, n_out);
+        ? run_select<float>(ctx, kn, ip, T, K, W, nb_blocks, offset, null_coeff_thres, weights, out_t, out_k, out_c, max_out, n_out)
+        : run_select<double>(ctx, kn, ip, T, K, W, nb_blocks, offset, null_coeff_thres, weights, out_t, out_k, out_c, max_out, n_out);
 }
 
 template <typename R> static void launch_update_rows(hscmp_ctx* ctx, const R* d_r, int T, int p, R* d_rows, R* d_table)
@@ -1489,16 +1523,17 @@ extern "C" int hscmp_table_select(hscmp_ctx* ctx, int nb_blocks, int offset, dou
     if (ctx->tab_T <= 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_table_select: no table open (hscmp_table_open)");
     if (!out_t || !out_k || !out_c || !n_out) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_table_select: bad arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const Knobs kn = read_knobs();
     int rc;
     if (ctx->dtype == HSCMP_F32) {
         const float* d_w;
         if ((rc = upload_weights<float>(ctx, weights, ctx->K, &d_w)) != HSCMP_OK) return rc;
-        return select_on_device<float>(ctx, (const float*)ctx->d_epi[kArenaTable], d_w, ctx->tab_T, ctx->K, ctx->W, nb_blocks, offset, null_coeff_thres,
+        return select_on_device<float>(ctx, kn, (const float*)ctx->d_epi[kArenaTable], d_w, ctx->tab_T, ctx->K, ctx->W, nb_blocks, offset, null_coeff_thres,
                                        out_t, out_k, out_c, max_out, n_out, "hscmp_table_select");
     }
     const double* d_w;
     if ((rc = upload_weights<double>(ctx, weights, ctx->K, &d_w)) != HSCMP_OK) return rc;
-    return select_on_device<double>(ctx, (const double*)ctx->d_epi[kArenaTable], d_w, ctx->tab_T, ctx->K, ctx->W, nb_blocks, offset, null_coeff_thres,
+    return select_on_device<double>(ctx, kn, (const double*)ctx->d_epi[kArenaTable], d_w, ctx->tab_T, ctx->K, ctx->W, nb_blocks, offset, null_coeff_thres,
                                     out_t, out_k, out_c, max_out, n_out, "hscmp_table_select");
 }
 

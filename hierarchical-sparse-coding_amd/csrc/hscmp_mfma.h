@@ -26,8 +26,6 @@
 #include "hscmp_kernels.h"
 
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 #include <vector>
 
@@ -1376,33 +1374,25 @@ static int mfma_launch_corr_init_t(hipStream_t stream, const DevParams& P, const
     const int cus = mfma_device_cus();
     const int per_cu = cached_blocks_per_cu((const void*)kern, kThreads, lds);
     const int64_t nitems = (int64_t)((P.T + kMfmaChunk - 1) / kMfmaChunk) * P.B;
-    int64_t grid = (int64_t)cus * per_cu;
-    if (const char* e = getenv("HSCMP_INIT_PER_CU")) grid = (int64_t)cus * std::max(1, atoi(e));      // diagnostic: fewer resident workgroups
-    if (grid > nitems) grid = nitems;
+    const int64_t grid = std::min((int64_t)cus * per_cu, nitems);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), lds, stream, P, S, A);
     return 0;
 }
 
+// lds_pad: bytes of LDS added on top (HSCMP_LDS_PAD: forces a lower occupancy)
 template <typename Tile, int S4C, bool HAS_W, int GS>
 static int mfma_launch_iterate_g(hipStream_t stream, const DevParams& P0, const State<typename Tile::R>& S,
-                                 const MfmaArgsT<typename Tile::R>& A, bool dry)
+                                 const MfmaArgsT<typename Tile::R>& A, int lds_pad, bool dry)
 {
     using Pol = MfmaRecorr<Tile, S4C, HAS_W, GS>;
     DevParams P = P0;
     set_segments(P, Pol::kMaxSegments);
     size_t lds = Pol::total_lds_bytes(P, A);
     if (GS > 1 && lds > (size_t)160 * 1024) return -1;
-    if (const char* pad = getenv("HSCMP_LDS_PAD")) lds += (size_t)atoi(pad);      // diagnostic: force a lower occupancy
+    lds += (size_t)lds_pad;
     auto kern = iterate_kernel<typename Tile::R, Pol>;
     if (set_dyn_lds((const void*)kern, lds) != hipSuccess) return -1;
     if (dry) return 0;
-    if (getenv("HSCMP_DEBUG")) {
-        int per_cu = -1;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, GS * kThreads, lds);
-        fprintf(stderr, "[hscmp] iterate_kernel<mfma %s S4=%d w=%d, %d signal(s) per workgroup>: dynamic LDS %zu B (control %zu B), occupancy API %d blocks/CU (%s), seg=%d nseg=%d\n",
-                sizeof(typename Tile::R) == 4 ? "f32" : "f64", S4C, (int)HAS_W, GS, lds, sizeof(typename Pol::Shared), per_cu,
-                hipGetErrorString(e), P.seg, P.nseg);
-    }
     hipLaunchKernelGGL(kern, dim3((P.B + GS - 1) / GS), dim3(GS * kThreads), lds, stream, P, S, A);
     return 0;
 }
@@ -1411,11 +1401,11 @@ static int mfma_launch_iterate_g(hipStream_t stream, const DevParams& P0, const 
 // signals per CU instead of two rounds of two).  0: launched (or, dry, could be); -1: no such form for this shape.
 template <typename Tile, int S4C, bool HAS_W>
 static int mfma_launch_iterate_t(hipStream_t stream, const DevParams& P, const State<typename Tile::R>& S,
-                                 const MfmaArgsT<typename Tile::R>& A, int group, bool dry)
+                                 const MfmaArgsT<typename Tile::R>& A, int group, int lds_pad, bool dry)
 {
     if constexpr (sizeof(typename Tile::R) == 4 && S4C > 0)
-        if (group == 4) return mfma_launch_iterate_g<Tile, S4C, HAS_W, 4>(stream, P, S, A, dry);
-    return group == 1 ? mfma_launch_iterate_g<Tile, S4C, HAS_W, 1>(stream, P, S, A, dry) : -1;
+        if (group == 4) return mfma_launch_iterate_g<Tile, S4C, HAS_W, 4>(stream, P, S, A, lds_pad, dry);
+    return group == 1 ? mfma_launch_iterate_g<Tile, S4C, HAS_W, 1>(stream, P, S, A, lds_pad, dry) : -1;
 }
 
 template <typename R> inline MfmaArgsT<R> mfma_args(const DevParams& P, const State<R>& S, const R* dimg)
@@ -1446,11 +1436,11 @@ template <typename R> inline int mfma_launch_corr_init(hipStream_t stream, const
 }
 
 template <typename R>
-inline int mfma_launch_iterate(hipStream_t stream, const DevParams& P, const State<R>& S, const R* dimg, int group, bool dry = false)
+inline int mfma_launch_iterate(hipStream_t stream, const DevParams& P, const State<R>& S, const R* dimg, int group, int lds_pad, bool dry = false)
 {
     using Tile = typename TileOf<R>::type;
     const MfmaArgsT<R> A = mfma_args<R>(P, S, dimg);
-    HSCMP_MFMA_DISPATCH(mfma_launch_iterate_t, group, dry);
+    HSCMP_MFMA_DISPATCH(mfma_launch_iterate_t, group, lds_pad, dry);
 }
 
 }  // namespace hscmp

@@ -715,9 +715,6 @@ static int rp_sparse_launch(hipStream_t stream, const DevParams& P0, const State
     auto kern = iterate_rp_kernel<R, Pol>;
     if (set_dyn_lds((const void*)kern, lds) != hipSuccess) return -1;
     if (dry) return 0;
-    if (getenv("HSCMP_DEBUG"))
-        fprintf(stderr, "[hscmp] iterate_rp_kernel<sparse>: LDS %zu B, %d teams, lists nz %d rec %d, staged by-feature %d per-atom %d\n", lds,
-                A.caps.teams, A.caps.nz, A.caps.rec, A.caps.stage_lists, A.caps.stage_atoms);
     hipLaunchKernelGGL(kern, dim3(P.B), dim3(kRpThreads), lds, stream, P, S, A);
     return 0;
 }

@@ -146,3 +146,31 @@ def test_level_chained_encode(monkeypatch):
         _assert_same(_snapshot(e1), one)
     finally:
         e0.close(); e1.close()
+
+
+@pytest.mark.parametrize('name', ['f32_blocked_rp', 'f32_default', 'level_sparse', 'level_sparse_packed', 'level_sparse_rp',
+                                  'locomp_level_sparse'])
+def test_resume_keeps_the_encode_knobs(name, monkeypatch):
+    """hscmp_continue resumes with the knobs the encode read: knobs changed after the encode change neither the loop nor
+    its arguments."""
+    from hsc_amd import _native
+    problem, method, env, kw, expected = ROWS[name]
+    for key, val in env.items():
+        monkeypatch.setenv(key, val)
+    x, D = problem()
+    eps = float(np.finfo(x.dtype).eps)
+    eng = _native.Engine(0)
+    try:
+        eng.set_method(method)
+        eng.set_dictionary(D)
+        eng.encode_batch(x, _native.make_params(eps=eps, maxEvents=2048, **kw))
+        one = _snapshot(eng)
+        eng.encode_batch(x, _native.make_params(eps=eps, maxEvents=2048, maxRounds=2, **kw))
+        monkeypatch.setenv('HSCMP_NO_PAIRING', '1')
+        monkeypatch.setenv('HSCMP_NO_ROWBITS', '1')
+        monkeypatch.setenv('HSCMP_RP', '1' if env.get('HSCMP_RP') == '0' else '0')
+        _resume_until_stopped(eng)
+        assert eng.last_variant() == expected
+        _assert_same(_snapshot(eng), one)
+    finally:
+        eng.close()
