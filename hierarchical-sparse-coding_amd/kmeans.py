@@ -1,0 +1,281 @@
+"""Convolutional k-means dictionary learning on MI355X: the reference's ConvolutionalDictionaryLearner(algorithm='kmean')
+(hsc/modeling.py:420-524) with every iteration's data work on the GPU, through libhsckmeans.so (include/hsckmeans.h).
+DESIGN.md section 14.
+
+The signals and the window starts go to the device once.  Each iteration makes one hsckmeans_step call (one
+synchronise) for every learner still running: the assignment of every window (the arg-max of hscmp_assign_windows,
+bit for bit, on the matrix cores), the membership lists and, per centroid, the sum of its members' normalised
+patches in numpy's order.  The host finishes on those K x W x F sums with the reference's own expressions: the mean,
+the emptiness test (the reference's np.any() of the member indices: a centroid whose only member is window 0 is
+empty), the resets, the +1e-9 of zero-norm centroids, normalize() and alpha.  So the dtype rules are numpy's and the
+random draws are the host learner's, in the same order: the window starts, _init_D, then per iteration the resets
+in centroid order.
+
+There is no CPU path: without libhsckmeans.so or a visible GPU the calls raise hsc_amd._native.HscmpError.
+ConvolutionalDictionaryLearner(algorithm='kmean') keeps its host path and is not routed here.
+"""
+import ctypes
+import logging
+import os
+import time
+
+import numpy as np
+
+from . import _native
+from .utils import normalize
+
+logger = logging.getLogger(__name__)
+
+LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'kmeans', 'libhsckmeans.so')
+EXPORTS = ['hsckmeans_version', 'hsckmeans_create', 'hsckmeans_destroy', 'hsckmeans_last_error', 'hsckmeans_set_data',
+           'hsckmeans_step']
+INIT_METHODS = ('random_samples', 'noise')
+RESET_METHODS = ('random_samples', 'random_samples_average', 'noise')
+MAX_WINDOW_SIZE = 255                    # include/hsckmeans.h: W + 1 positions per workgroup column set
+F32, F64 = 0, 1                          # HSCKMEANS_F32 / _F64
+SKIP, ASSIGN_F32, ASSIGN_F64 = 0, 1, 2   # modes of hsckmeans_step
+TIMES = 4                                # upload, assignment, centroids, download
+
+_lib = None
+
+
+def load_library():
+    """Load libhsckmeans.so; raises (never falls back) when it is missing."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.isfile(LIB_PATH):
+        raise _native.HscmpError('libhsckmeans.so is not built (%s). Run `python __graft_entry__.py build` '
+                                 '(hipcc --offload-arch=gfx950). There is no CPU fallback.' % LIB_PATH)
+    lib = ctypes.CDLL(LIB_PATH)
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib.hsckmeans_version.restype = ci
+    lib.hsckmeans_create.argtypes = [ctypes.POINTER(vp), ci]
+    lib.hsckmeans_create.restype = ci
+    lib.hsckmeans_destroy.argtypes = [vp]
+    lib.hsckmeans_destroy.restype = None
+    lib.hsckmeans_last_error.argtypes = [vp]
+    lib.hsckmeans_last_error.restype = ctypes.c_char_p
+    lib.hsckmeans_set_data.argtypes = [vp, vp, ci, ci, ci, ci, vp, ci, ci]
+    lib.hsckmeans_set_data.restype = ci
+    lib.hsckmeans_step.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
+    lib.hsckmeans_step.restype = ci
+    _lib = lib
+    return lib
+
+
+class _Context(object):
+    def __init__(self, device):
+        self._lib = load_library()
+        h = ctypes.c_void_p()
+        rc = self._lib.hsckmeans_create(ctypes.byref(h), int(device))
+        if rc != 0:
+            ex = _native.HscmpError('hsckmeans_create failed (%d): %s' % (rc, self._lib.hsckmeans_last_error(None).decode()))
+            ex.code = int(rc)
+            raise ex
+        self._h = h
+
+    def _check(self, rc, what):
+        if rc != 0:
+            ex = _native.HscmpError('%s failed (%d): %s' % (what, rc, self._lib.hsckmeans_last_error(self._h).decode()))
+            ex.code = int(rc)
+            raise ex
+
+    def set_data(self, x, starts, W):
+        """x [B,T,F] float32/float64 C order, starts [B,N] int64."""
+        B, T, F = x.shape
+        N = starts.shape[1]
+        self.B, self.N, self.W, self.F, self.dtype = B, N, W, F, x.dtype
+        self._check(self._lib.hsckmeans_set_data(self._h, _native._ptr(x), F32 if x.dtype == np.float32 else F64, B, T, F,
+                                                 _native._ptr(starts), N, W), 'hsckmeans_set_data')
+
+    def step(self, D, mode):
+        """D [B,K,W,F] float64, mode [B] int32.  Returns t, k [B,N], count, nonzero [B,K], sums [B,K,W*F], timing [4]."""
+        B, K = D.shape[0], D.shape[1]
+        t = np.zeros((B, self.N), dtype=np.int32)
+        k = np.zeros((B, self.N), dtype=np.int32)
+        count = np.zeros((B, K), dtype=np.int32)
+        nonzero = np.zeros((B, K), dtype=np.int32)
+        sums = np.zeros((B, K, self.W * self.F), dtype=self.dtype)
+        timing = np.zeros((TIMES,), dtype=np.float64)
+        p = _native._ptr
+        self._check(self._lib.hsckmeans_step(self._h, p(D), K, p(mode), p(t), p(k), p(count), p(nonzero), p(sums), p(timing)),
+                    'hsckmeans_step')
+        return t, k, count, nonzero, sums, timing
+
+    def __del__(self):
+        if getattr(self, '_h', None):
+            self._lib.hsckmeans_destroy(self._h)
+            self._h = None
+
+
+_contexts = {}
+
+
+def _context(device):
+    if device not in _contexts:
+        _contexts[device] = _Context(device)
+    return _contexts[device]
+
+
+def _rng(rng):
+    return np.random if rng is None else rng
+
+
+def check_arguments(k, W, data_shape, dtype, nbRandomWindows, initMethod, resetMethod, batch=False):
+    """The argument checks of train / trainBatch (raised before any device call)."""
+    if initMethod not in INIT_METHODS:
+        raise Exception('Unsupported initialization method: %s' % (initMethod))
+    if resetMethod not in RESET_METHODS:
+        raise Exception('Unsupported reset method: %s' % (resetMethod))
+    lead = 1 if batch else 0
+    if len(data_shape) - lead not in (1, 2):
+        lead_dims = 'B,' if batch else ''
+        raise ValueError('k-means: the data must be [%sT] or [%sT,F] (got %d dimensions)' % (lead_dims, lead_dims, len(data_shape)))
+    if batch and data_shape[0] < 1:
+        raise ValueError('k-means: trainBatch needs at least one sequence')
+    if dtype not in (np.float32, np.float64):
+        raise ValueError('k-means: the data must be float32 or float64 (got %s)' % dtype)
+    if k < 1:
+        raise ValueError('k-means: k = %d, needs k >= 1' % k)
+    if W < 1 or W > MAX_WINDOW_SIZE:
+        raise NotImplementedError('k-means on the GPU: windowSize = %d is outside 1 .. %d' % (W, MAX_WINDOW_SIZE))
+    if nbRandomWindows < 1:
+        raise ValueError('k-means: nbRandomWindows = %d, needs at least one window' % nbRandomWindows)
+    T = data_shape[lead]
+    F = 1 if len(data_shape) - lead == 1 else data_shape[lead + 1]
+    if F < 1:
+        raise ValueError('k-means: no features')
+    if 2 * W >= T:
+        raise ValueError('k-means: windows of 2 * windowSize = %d samples need a longer signal (T = %d)' % (2 * W, T))
+    if W * F < 2:
+        raise NotImplementedError('k-means on the GPU: atoms of a single sample (W * F = 1) are not supported')
+    return T, F
+
+
+class ConvolutionalKMeansLearner(object):
+    """The reference's convolutional k-means learner (ConvolutionalDictionaryLearner._train_kmean, hsc/modeling.py:420-524)
+    with each iteration on the GPU (one hsckmeans_step call), for one learner (train) or a batch (trainBatch).
+
+    lastStats (after train): one dict per iteration with alpha, nbResets, counts [K] (members per centroid, summing to
+    nbRandomWindows), step_ms (host wall clock of the synchronised call), assign_ms, centroid_ms and kernel_ms
+    (device time of the assignment, of the norms + lists + sums, and of both).  After trainBatch: one such list per
+    learner."""
+
+    def __init__(self, k, windowSize, device=0, rng=None):
+        self.k = int(k)
+        self.windowSize = int(windowSize)
+        self.device = device
+        self.rng = rng
+        self.lastStats = None
+
+    def train(self, data, nbRandomWindows, maxIterations=100, tolerance=0.0, initMethod='random_samples',
+              resetMethod='noise', nbAveragedPatches=8):
+        """hsc/modeling.py:420-524.  data [T] or [T,F] (np.matrix included) float32 / float64; returns D [K,W] or
+        [K,W,F] with the host learner's dtype.  Draws from `rng` or numpy's global generator, as the host learner."""
+        data = np.asarray(data)
+        check_arguments(self.k, self.windowSize, data.shape, data.dtype, nbRandomWindows, initMethod, resetMethod)
+        load_library()                                       # no CPU path: fail before the first draw
+        Ds, stats = self._run(data[np.newaxis], [self.rng], int(nbRandomWindows), maxIterations, tolerance, initMethod,
+                              resetMethod, nbAveragedPatches)
+        self.lastStats = stats[0]
+        return Ds[0]
+
+    def trainBatch(self, sequences, nbRandomWindows, maxIterations=100, tolerance=0.0, initMethod='random_samples',
+                   resetMethod='noise', nbAveragedPatches=8, rngs=None):
+        """B independent learners, learner b on sequences[b] ([B,T] or [B,T,F]).  rngs: a list of B generators
+        (learner b then reproduces train() with rngs[b]), or one generator / None (numpy's global generator) shared
+        by all: every learner's window starts then its D, in batch order, then per iteration the resets of the
+        learners still running, learner by learner.  Each learner stops on its own (n < maxIterations and
+        alpha > tolerance); a stopped learner is neither updated nor draws.
+        Returns (D [B,K,W(,F)] in the learners' common result dtype, per-learner lastStats lists)."""
+        sequences = np.asarray(sequences)
+        check_arguments(self.k, self.windowSize, sequences.shape, sequences.dtype, nbRandomWindows, initMethod,
+                        resetMethod, batch=True)
+        B = sequences.shape[0]
+        if isinstance(rngs, (list, tuple)):
+            if len(rngs) != B:
+                raise ValueError('k-means: %d generators for %d learners' % (len(rngs), B))
+            rngs = list(rngs)
+        else:
+            rngs = [rngs] * B
+        load_library()
+        Ds, stats = self._run(sequences, rngs, int(nbRandomWindows), maxIterations, tolerance, initMethod, resetMethod,
+                              nbAveragedPatches)
+        self.lastStats = stats
+        return np.stack(Ds), stats
+
+    # ---- the shared loop ---------------------------------------------------------------------------
+    def _run(self, seqs, rngs, N, maxIterations, tolerance, initMethod, resetMethod, nbAveragedPatches):
+        from .learning import ConvolutionalDictionaryLearner
+        from .modeling import _compute_dtype
+        B, T = seqs.shape[0], seqs.shape[1]
+        W, K = self.windowSize, self.k
+        x = np.ascontiguousarray(seqs.reshape((B, T, -1)))
+        F = x.shape[2]
+        pshape = (W,) if seqs.ndim == 2 else (W, F)
+        starts = np.zeros((B, N), dtype=np.int64)
+        Ds = []
+        for b in range(B):                                   # extractRandomWindows, then _init_D (modeling.py:426-429)
+            starts[b] = _rng(rngs[b]).randint(low=0, high=T - 2 * W, size=(N,))
+            Ds.append(ConvolutionalDictionaryLearner(K, W, rng=rngs[b])._init_D(seqs[b], initMethod))
+        ctx = _context(self.device)
+        ctx.set_data(x, starts, W)
+        n = [0] * B
+        alpha = [tolerance + 1.0] * B
+        stats = [[] for _ in range(B)]
+        while True:
+            running = [b for b in range(B) if n[b] < maxIterations and alpha[b] > tolerance]
+            if not running:
+                break
+            mode = np.zeros((B,), dtype=np.int32)
+            D64 = np.zeros((B, K, W, F), dtype=np.float64)
+            for b in running:
+                mode[b] = ASSIGN_F32 if _compute_dtype(x.dtype, Ds[b].dtype) == np.float32 else ASSIGN_F64
+                D64[b] = Ds[b].reshape((K, W, F))
+            t0 = time.perf_counter()
+            at, ak, count, nonzero, sums, timing = ctx.step(D64, mode)
+            step_ms = 1e3 * (time.perf_counter() - t0)
+            for b in running:
+                newD, nbResets = self._finish(seqs[b], starts[b], at[b], count[b], nonzero[b], sums[b], Ds[b], pshape,
+                                              _rng(rngs[b]), resetMethod, nbAveragedPatches)
+                alpha[b] = np.sqrt(np.sum(np.square(Ds[b] - newD)))
+                logger.debug('K-mean iteration %d: tolerance = %f, nb resets = %d' % (n[b], alpha[b], nbResets))
+                stats[b].append(dict(alpha=float(alpha[b]), nbResets=int(nbResets), counts=count[b].astype(np.int64),
+                                     step_ms=step_ms, assign_ms=float(timing[1]), centroid_ms=float(timing[2]),
+                                     kernel_ms=float(timing[1] + timing[2]), assignment=(at[b].astype(np.int64), ak[b].astype(np.int64))))
+                Ds[b] = newD
+                n[b] += 1
+        return Ds, stats
+
+    @staticmethod
+    def _finish(data, starts, t, count, nonzero, sums, D, pshape, rng, resetMethod, nbAveragedPatches):
+        """The reference's computeCentroid (modeling.py:474-503) on the device's sums; resets cut their patches from
+        the host's data at start + t."""
+        W = pshape[0]
+        N = starts.shape[0]
+
+        def patch(i):
+            s = int(starts[i]) + int(t[i])
+            return data[s:s + W]
+
+        centroids, nbResets = [], 0
+        for c in range(D.shape[0]):
+            if nonzero[c]:
+                # np.mean(normalize(patches[members]), axis=0): the device's sequential sum over m, divided as np.mean does
+                S = sums[c].reshape(pshape)
+                centroid = np.empty_like(S)
+                np.true_divide(S, np.intp(count[c]), out=centroid, casting='unsafe')
+            else:
+                nbResets += 1
+                if resetMethod == 'random_samples':
+                    centroid = patch(rng.randint(low=0, high=N))
+                elif resetMethod == 'random_samples_average':
+                    idx = rng.randint(low=0, high=N, size=(nbAveragedPatches,))
+                    centroid = np.mean(np.stack([patch(i) for i in idx]), axis=0)
+                else:
+                    centroid = rng.uniform(low=-1.0, high=1.0, size=pshape)
+            if np.sqrt(np.sum(np.square(centroid))) == 0.0:
+                centroid = centroid + 1e-9
+            centroids.append(centroid)
+        return normalize(np.stack(centroids)), nbResets

@@ -1,13 +1,16 @@
 """Own counterpart of scripts/learn_mlcsc_dataset.py:84-116: per level, learn a dictionary by convolutional
 k-means on the current representation (window assignment on the GPU), encode the training signal with the
 hierarchical matching pursuit built so far, and hand the last level's coefficients to the next level.
-Prints the time of each stage.  Data: tools/generate_dataset.py (Perlin dictionary, Poisson events)."""
+Prints the time of each stage.  Data: tools/generate_dataset.py (Perlin dictionary, Poisson events).
+KMEANS=device learns with hsc_amd.kmeans.ConvolutionalKMeansLearner (every iteration on the GPU, the same dictionary);
+the default is the host learner."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import generate_dataset as gd
 from hsc_amd.dataset import MultilevelDictionary, addSingletonBases, scalesToWindowSizes
+from hsc_amd.kmeans import ConvolutionalKMeansLearner
 from hsc_amd.learning import ConvolutionalDictionaryLearner
 from hsc_amd.modeling import HierarchicalConvolutionalMatchingPursuit, HierarchicalConvolutionalSparseCoder
 
@@ -22,8 +25,11 @@ dictionaries, inp, coefficients = [], train, None
 for level, (k, w) in enumerate(zip(counts, widths)):
     nfeat = 1 if inp.ndim == 1 else inp.shape[1]
     t0 = time.perf_counter()
-    D = ConvolutionalDictionaryLearner(k, w, algorithm='kmean').train(inp, nbRandomWindows=10000, maxIterations=10, tolerance=0.0,
-                                                                      resetMethod='random_samples')
+    if os.environ.get('KMEANS', 'host') == 'device':
+        learner = ConvolutionalKMeansLearner(k, w)
+    else:
+        learner = ConvolutionalDictionaryLearner(k, w, algorithm='kmean')
+    D = learner.train(inp, nbRandomWindows=10000, maxIterations=10, tolerance=0.0, resetMethod='random_samples')
     t1 = time.perf_counter()
     dictionaries.append(D)
     if level > 0:
