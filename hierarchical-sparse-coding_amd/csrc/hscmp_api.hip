@@ -31,7 +31,7 @@ using namespace hscmp;
 // passes it down, and an encode keeps its snapshot in its plan, so hscmp_continue resumes with it.
 struct Knobs {
     bool no_dict_lists, no_row_lists, no_rowbits, no_pairing, force_gathered, force_generic;     // set or not
-    bool init_only, exact_init, locomp_no_mfma, no_sorted_prepare, no_lazy_clear;
+    bool init_only, exact_init, exact_recorr, locomp_no_mfma, no_sorted_prepare, no_lazy_clear;
     int rp, mfma_quad, sparse_packed;     // 0 / 1 forces the choice; -1: not set, chosen by the shape
     int locomp_pack;                      // at most this many signals per workgroup; 0: not set, by the batch size
     int slot_hash_min, locomp_group_cap, locomp_ahead, sorted_prepare_min, lds_pad;     // the value, or the default
@@ -45,7 +45,7 @@ static Knobs read_knobs()
     const char* v;
     k.no_dict_lists = getenv("HSCMP_NO_DICT_LISTS"); k.no_row_lists = getenv("HSCMP_NO_ROW_LISTS"); k.no_rowbits = getenv("HSCMP_NO_ROWBITS");
     k.no_pairing = getenv("HSCMP_NO_PAIRING"); k.force_gathered = getenv("HSCMP_FORCE_GATHERED"); k.force_generic = getenv("HSCMP_FORCE_GENERIC");
-    k.init_only = getenv("HSCMP_INIT_ONLY"); k.exact_init = getenv("HSCMP_EXACT_INIT"); k.locomp_no_mfma = getenv("HSCMP_LOCOMP_NO_MFMA");
+    k.init_only = getenv("HSCMP_INIT_ONLY"); k.exact_init = getenv("HSCMP_EXACT_INIT"); k.exact_recorr = getenv("HSCMP_EXACT_RECORR"); k.locomp_no_mfma = getenv("HSCMP_LOCOMP_NO_MFMA");
     k.no_sorted_prepare = getenv("HSCMP_NO_SORTED_PREPARE"); k.no_lazy_clear = getenv("HSCMP_NO_LAZY_CLEAR");
     k.rp = (v = getenv("HSCMP_RP")) ? atoi(v) != 0 : -1;
     k.mfma_quad = (v = getenv("HSCMP_MFMA_QUAD")) ? atoi(v) != 0 : -1;
@@ -77,6 +77,7 @@ struct EncodePlan {
     bool row_lists = false;   // per-row feature lists of the input's non-zero cells (the level chaining or the init writes them)
     bool kept_lists = false;  // ... and the loop keeps them current: it enters every cell it writes
     bool init_only = false;   // HSCMP_INIT_ONLY (tests): stop behind the initial correlation
+    bool bound_loop = false;  // the four-signal loop re-correlates as upper bounds (MfmaRecorr BOUND)
     Knobs knobs{};            // the encode's snapshot: the launches read pairing, row bitmaps and LDS pad from it
 };
 
@@ -91,8 +92,9 @@ struct hscmp_ctx {
     void* d_D = nullptr;
     void* d_w = nullptr;      // nullptr when no weights
     void* d_Dfrag = nullptr;  // MFMA fragment-ordered copy (f32, F == 1)
-    unsigned short* d_Bimg = nullptr;   // bf16 hi / lo images of the bound pass (f32, F == 1, dictionary inside its model: hscmp_bound.h)
+    unsigned short* d_Bimg = nullptr;   // bf16 hi / lo (/ rem) planes of the bound passes (f32, F == 1, dictionary inside its model: hscmp_bound.h)
     float bound_cmax = 0.0f;            // >= max_k ||d_k|| |w_k|
+    bool bound_loop_image = false;      // d_Bimg also holds the rem plane: hi, lo, rem rebuild every element (the bound loop's image)
     void* d_Dt = nullptr;     // [W][F][K] transposed copy for the sparsity-aware kernels (F > 1)
     void* d_Dc = nullptr;     // [K][F][W] chain-ordered copy for the dense chains (F > 1)
     void* d_scratch = nullptr;
@@ -277,6 +279,7 @@ extern "C" int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W,
     if (ctx->d_w) { (void)hipFree(ctx->d_w); ctx->d_w = nullptr; }
     if (ctx->d_Dfrag) { (void)hipFree(ctx->d_Dfrag); ctx->d_Dfrag = nullptr; ctx->Dfrag_bytes = 0; }
     if (ctx->d_Bimg) { (void)hipFree(ctx->d_Bimg); ctx->d_Bimg = nullptr; }
+    ctx->bound_loop_image = false;
     if (ctx->d_Dt) { (void)hipFree(ctx->d_Dt); ctx->d_Dt = nullptr; }
     if (ctx->d_Dc) { (void)hipFree(ctx->d_Dc); ctx->d_Dc = nullptr; }
     if (ctx->d_nzptr) { (void)hipFree(ctx->d_nzptr); ctx->d_nzptr = nullptr; }
@@ -377,13 +380,16 @@ extern "C" int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W,
         HIP_TRY(ctx, hipMemcpy(ctx->d_Dfrag, frag.data(), ctx->Dfrag_bytes, hipMemcpyHostToDevice));
         // the bound pass of the initial correlation (hscmp_bound.h): bf16 images no larger than the float32 one, and a
         // dictionary and weights inside the error model; otherwise every encode runs the exact initial correlation
+        // (the third plane, rem, is for the four-signal loop's own bound tile: only if it rebuilds every element exactly)
         std::vector<unsigned short> bimg;
         float cmax = 0.0f;
+        bool rem_exact = false;
         if ((size_t)2 * mfma_groups(K) * bound_steps(W) * 1024 <= TileF32::kMaxImageBytes &&
-            bound_build_dict_image((const float*)D, (const float*)weights, K, W, bimg, cmax)) {
+            bound_build_dict_image((const float*)D, (const float*)weights, K, W, bimg, cmax, rem_exact)) {
             HIP_TRY(ctx, hipMalloc((void**)&ctx->d_Bimg, bimg.size() * sizeof(unsigned short)));
             HIP_TRY(ctx, hipMemcpy(ctx->d_Bimg, bimg.data(), bimg.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
             ctx->bound_cmax = cmax;
+            ctx->bound_loop_image = rem_exact;
         }
     } else if (dtype == HSCMP_F64 && mfma_supported<double>(K, W, F)) {
         std::vector<double> frag;
@@ -626,6 +632,11 @@ template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const Knobs&
             if (!P.blocked && !P.select_only && ctx->d_Bimg && !kn.exact_init &&
                 bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->d_Bimg, ctx->bound_cmax, true) == 0)
                 plan.init = EncodePlan::kInitBound;
+            // ... and the four-signal loop re-correlates as upper bounds too, on the bf16 planes (HSCMP_EXACT_RECORR=1: the
+            // exact re-correlation behind the bound pass; HSCMP_EXACT_INIT=1 keeps both exact)
+            if (plan.init == EncodePlan::kInitBound && plan.group == 4 && ctx->bound_loop_image && !kn.exact_recorr &&
+                mfma_launch_iterate<R>(ctx->stream, P, S, dimg, 4, kn.lds_pad, true, ctx->d_Bimg, ctx->bound_cmax) == 0)
+                plan.bound_loop = true;
             plan.rp = rp_mfma && rp_mfma_launch(ctx->stream, P, S, dimg, true) == 0;
         }
         return plan;
@@ -725,7 +736,8 @@ template <typename R> static int launch_loop(hscmp_ctx* ctx, const EncodePlan& p
     case EncodePlan::kLoopMfma:
         if constexpr (sizeof(R) == 4)
             if (plan.rp) { rc = rp_mfma_launch(ctx->stream, P, make_state<float>(ctx), dimg); break; }
-        rc = mfma_launch_iterate<R>(ctx->stream, P, make_state<R>(ctx), dimg, plan.group, plan.knobs.lds_pad);
+        rc = mfma_launch_iterate<R>(ctx->stream, P, make_state<R>(ctx), dimg, plan.group, plan.knobs.lds_pad, false,
+                                    plan.bound_loop ? ctx->d_Bimg : nullptr, ctx->bound_cmax);
         break;
     case EncodePlan::kLoopSparse:
         if constexpr (sizeof(R) == 8)

@@ -44,6 +44,11 @@
 //   a dictionary (or weights) with a non-zero magnitude outside [2^-30, 2^30] does not get a bf16 image at all
 //   (hscmp_set_dictionary), and the encode runs corr_init_mfma_kernel.
 // tools/bf16_bound_probe.hip checks assumption (2) on the hardware (profiles/r05_bf16_probe.txt).
+//
+// The four-signal loop (MfmaRecorr with BOUND) re-correlates the rows around an applied atom with the same tile
+// (bound_tile, hscmp_mfma.h) over its reflect-padded window: the derivation above holds unchanged whenever every
+// sample the tile reads is inside the model, and a tile whose window holds one outside it (a wave-wide vote, every atom)
+// runs the exact float32 tile on the planes (planes_tile_score).  Split, epilogue and constants have one definition.
 #pragma once
 
 #include "hscmp_mfma.h"
@@ -53,42 +58,53 @@
 
 namespace hscmp {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float kBoundEps = 0x1p-13f;        // >= 1.67 eps_0 (see above)
-constexpr float kBoundRel = 1.0f + 0x1p-20f;
-constexpr float kBoundAbs = 0x1p-80f;
-constexpr float kBoundXMin = 0x1p-60f, kBoundXMax = 0x1p60f;     // signal samples (per chunk, on the device)
-constexpr double kBoundDMin = 0x1p-30, kBoundDMax = 0x1p30;     // dictionary entries and weights (host)
-
-// bf16 round-to-nearest-even of a finite float32 whose magnitude is far from FLT_MAX: the bits of the bf16 value as a float32
-__host__ __device__ inline unsigned bf16_rn_bits(unsigned b) { return (b + 0x7fffu + ((b >> 16) & 1u)) & 0xffff0000u; }
-__host__ __device__ inline void bf16_split(float v, unsigned short& hi, unsigned short& lo)
-{
-    unsigned b;
-    memcpy(&b, &v, 4);
-    const unsigned hb = bf16_rn_bits(b);
-    float hf;
-    memcpy(&hf, &hb, 4);
-    const float r = v - hf;                                     // exact
-    unsigned rb;
-    memcpy(&rb, &r, 4);
-    hi = (unsigned short)(hb >> 16);
-    lo = (unsigned short)(bf16_rn_bits(rb) >> 16);
-}
-
 // k-steps of 16 taps for the filter width (the bound pass is built for SB = 1, 2, 4: the float32 chunk counts 2, 4, 8)
 inline int bound_steps(int W) { return (W + 15) / 16; }
 
-// host: the two bf16 images Bimg[img][g][s][lane][8] (img 0 = hi, 1 = lo): element j of lane l in (group g, k-step s) is
-// D[32g + (l&31)][16s + 8(l>>5) + j] -- the A-operand map of v_mfma_f32_32x32x16_bf16; zero padded.  Also
+// The third plane (the four-signal loop): rem = (v - hi) - lo, so that every float32 tap the exact
+// chains need is rebuilt from the bf16 image as (hi + lo) + rem, and the loop keeps no float32 image at all (three bf16
+// planes are 96 KB at K = 256, W = 64; the float32 image and two bf16 planes would not fit a CU's 160 KB beside four
+// signals).  Why the rebuild is exact for v inside the model (|v| in [2^-30, 2^30], or 0): let e be the exponent of v,
+// so v is a multiple of 2^(e-23).  hi = rn(v) has 8 significant bits and is a multiple of 2^(e-7) (or of 2^(e-6) after
+// a carry), so r = v - hi is a multiple of 2^(e-23) with |r| <= 2^(e-8): at most 16 significant bits, exact in float32.
+// lo = rn(r) is a multiple of 2^(e-23) too (rounding r to 8 bits never goes below r's own last bit), so
+// rem = r - lo is exact, a multiple of 2^(e-23) with |rem| <= 2^-8 |r| <= 2^(e-16): at most 8 significant bits, a
+// bf16 (its exponent, >= -30 - 23, is far inside bf16's normal range).  hi + lo = v - rem is a multiple of 2^(e-23) of
+// magnitude at most 2^(e+1) (it passes |v| only if hi rounded up to 2^(e+1), and then lo <= 0): exact in float32, and
+// (hi + lo) + rem = v exactly.  The argument is what makes the plane possible;
+// what the engine relies on is the check below, element by element (tests/test_bound_planes.py runs it over every
+// float32 of the model range).
+__host__ __device__ inline bool bf16_rem(float v, unsigned short hi, unsigned short lo, unsigned short& rem)
+{
+    const unsigned hb = (unsigned)hi << 16, lb = (unsigned)lo << 16;
+    float hf, lf;
+    memcpy(&hf, &hb, 4);
+    memcpy(&lf, &lb, 4);
+    const float rf = (v - hf) - lf;
+    unsigned rb;
+    memcpy(&rb, &rf, 4);
+    rem = (unsigned short)(rb >> 16);
+    const unsigned qb = (unsigned)rem << 16;
+    float q;
+    memcpy(&q, &qb, 4);
+    const float back = (hf + lf) + q;                           // the rebuild of the exact chains (bf16_tap)
+    unsigned vb, bb;
+    memcpy(&vb, &v, 4);
+    memcpy(&bb, &back, 4);
+    return (rb & 0xffffu) == 0u && bb == vb;
+}
+
+// host: the bf16 planes Bimg[plane][g][s][lane][8] (plane 0 = hi, 1 = lo, 2 = rem): element j of lane l in (group g,
+// k-step s) is D[32g + (l&31)][16s + 8(l>>5) + j] -- the A-operand map of v_mfma_f32_32x32x16_bf16; zero padded.  Also
 // cmax >= max_k ||d_k|| |w_k| (rounded up).  Returns false when the dictionary or the weights lie outside the model.
-inline bool bound_build_dict_image(const float* D, const float* wts, int K, int W, std::vector<unsigned short>& out, float& cmax)
+// rem_exact: every element is rebuilt bitwise by (hi + lo) + rem (else the loop keeps its float32 image).
+inline bool bound_build_dict_image(const float* D, const float* wts, int K, int W, std::vector<unsigned short>& out, float& cmax,
+                                   bool& rem_exact)
 {
     const int G = mfma_groups(K), SB = bound_steps(W);
     const size_t per = (size_t)G * SB * 64 * 8;
-    out.assign(2 * per, 0);
+    out.assign(3 * per, 0);
+    rem_exact = true;
     double cm = 0.0;
     auto in_model = [](double a) { return std::isfinite(a) && (a == 0.0 || (std::fabs(a) >= kBoundDMin && std::fabs(a) <= kBoundDMax)); };
     for (int k = 0; k < K; ++k) {
@@ -108,11 +124,14 @@ inline bool bound_build_dict_image(const float* D, const float* wts, int K, int 
                 for (int j = 0; j < 8; ++j) {
                     const int k = 32 * g + (lane & 31), w = 16 * s + 8 * (lane >> 5) + j;
                     if (k >= K || w >= W) continue;
-                    unsigned short hi, lo;
-                    bf16_split(D[(size_t)k * W + w], hi, lo);
+                    const float v = D[(size_t)k * W + w];
+                    unsigned short hi, lo, rem;
+                    bf16_split(v, hi, lo);
+                    rem_exact = bf16_rem(v, hi, lo, rem) && rem_exact;
                     const size_t i = (((size_t)g * SB + s) * 64 + lane) * 8 + j;
                     out[i] = hi;
                     out[per + i] = lo;
+                    out[2 * per + i] = rem;
                 }
     cm *= 1.0 + 0x1p-30;                                        // (the double sum and sqrt: relative error < 2^-45)
     float f = (float)cm;
@@ -121,87 +140,6 @@ inline bool bound_build_dict_image(const float* D, const float* wts, int K, int 
     return true;
 }
 
-__device__ __forceinline__ float bf16_lo_f(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf16_hi_f(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
-
-// One 32-position tile against all atom groups: the bound of every position (lanes 0..31: position = lane).
-//   bimg: LDS [hi image][lo image];  xh, xl: the chunk's bf16 halves in LDS, 4-byte aligned, index 0 = the first tap
-//   of the tile's first position.  B operand of k-step s, lane (r, h): samples r + 16s + 8h + j, j = 0..7 -- 8
-//   consecutive bf16 at an odd or even start: five aligned dwords and v_alignbit.
-template <int SB, bool HAS_W>
-__device__ __forceinline__ float bound_tile(const bf16x8* __restrict__ bimg_h, const bf16x8* __restrict__ bimg_l,
-                                            const unsigned short* __restrict__ xh, const unsigned short* __restrict__ xl,
-                                            const float* __restrict__ wts, int G, int lane, float cmax)
-{
-    const int r = lane & 31, h = lane >> 5;
-    const unsigned* xh32 = reinterpret_cast<const unsigned*>(xh);
-    const unsigned* xl32 = reinterpret_cast<const unsigned*>(xl);
-    const unsigned sh = 16u * (unsigned)(r & 1);
-    u32x4 bh[SB], bl[SB];
-    float ss = 0.0f;
-#pragma unroll
-    for (int s = 0; s < SB; ++s) {
-        const int w0 = (r >> 1) + 8 * s + 4 * h;
-        unsigned a[5], b[5];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) { a[i] = xh32[w0 + i]; b[i] = xl32[w0 + i]; }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            bh[s][i] = __builtin_amdgcn_alignbit(a[i + 1], a[i], sh);
-            bl[s][i] = __builtin_amdgcn_alignbit(b[i + 1], b[i], sh);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {                           // ||xh + xl||^2 over this half-wave's taps (xh + xl exact)
-            const float y0 = bf16_lo_f(bh[s][i]) + bf16_lo_f(bl[s][i]);
-            const float y1 = bf16_hi_f(bh[s][i]) + bf16_hi_f(bl[s][i]);
-            ss = fmaf(y0, y0, ss);
-            ss = fmaf(y1, y1, ss);
-        }
-    }
-    ss = ss + swap_halves_f(ss, h);                             // both halves of the window (taps 16s + 0..15)
-    float bs = 0.0f;
-    auto katom = [&](int kbase, int e) { return kbase + (e & 3) + 8 * (e >> 2); };
-    auto chain = [&](int g, f32x16& acc) {
-        f32x16 z;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) z[e] = 0.0f;
-        acc = z;
-#pragma unroll
-        for (int s = 0; s < SB; ++s) {
-            const bf16x8 ah = bimg_h[(g * SB + s) * 64 + lane], al = bimg_l[(g * SB + s) * 64 + lane];
-            const bf16x8 xbh = __builtin_bit_cast(bf16x8, bh[s]), xbl = __builtin_bit_cast(bf16x8, bl[s]);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xbh, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xbl, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xbh, acc, 0, 0, 0);
-        }
-    };
-    auto reduce = [&](const f32x16& acc, int g) {
-        const int kbase = 32 * g + 4 * h;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) mfma_reduce_pair<HAS_W>(acc[2 * e], acc[2 * e + 1], katom(kbase, 2 * e), katom(kbase, 2 * e + 1), wts, bs);
-    };
-    // two accumulators: the reduction of group g-1 runs beside the MFMAs of group g
-    f32x16 acc0, acc1;
-    chain(0, acc0);
-    int g = 1;
-    for (; g + 1 < G; g += 2) {
-        chain(g, acc1);
-        reduce(acc0, g - 1);
-        chain(g + 1, acc0);
-        reduce(acc1, g);
-    }
-    if (g < G) {
-        chain(g, acc1);
-        reduce(acc0, g - 1);
-        reduce(acc1, g);
-    } else {
-        reduce(acc0, G - 1);
-    }
-    bs = fmaxf(bs, swap_halves_f(bs, h));
-    if (ss == 0.0f) return bs;                                  // all-zero window: every product and sum is an exact 0
-    const float e = __fmul_rn(__fmul_rn(kBoundEps, __fsqrt_rn(ss)), cmax) + kBoundAbs;
-    return fmaf(bs, kBoundRel, e);
-}
 
 // ------------------------------------------------------------------------------------------------
 // The bound pass: the persistent grid of corr_init_mfma_kernel over (signal, 2048-position chunk) items.
@@ -254,10 +192,7 @@ __global__ __launch_bounds__(kThreads) void corr_bound_kernel(DevParams P, State
     for (; item < nitems; item += gridDim.x) {
         bool out = false;
 #pragma unroll
-        for (int u = 0; u < kMfmaChunkLoads; ++u) {
-            const float a = fabsf(xr[u]);
-            out |= !(a <= kBoundXMax) || (a != 0.0f && a < kBoundXMin);      // (NaN fails the first test)
-        }
+        for (int u = 0; u < kMfmaChunkLoads; ++u) out |= bound_sample_out(xr[u]);
         const bool exact = __syncthreads_or(out) != 0;  // (also: every tile of the previous chunk has read the buffer)
 #pragma unroll
         for (int u = 0; u < kMfmaChunkLoads; ++u) {

@@ -26,6 +26,8 @@
 #include "hscmp_kernels.h"
 
 #include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <type_traits>
 #include <vector>
 
@@ -44,6 +46,8 @@ template <typename R> struct MfmaArgsT {
     int G;               // atom groups (32 atoms for float32, 16 for float64)
     int S4;              // chunks of 8 taps (one 16-byte A-operand word per lane)
     int has_w;
+    const unsigned short* bimg = nullptr;   // the bound loop (MfmaRecorr, BOUND): bf16 planes hi, lo, rem (hscmp_bound.h)
+    float cmax = 0.0f;                      // ... and its cmax >= max_k ||d_k|| |w_k|
 };
 using MfmaArgs = MfmaArgsT<float>;
 
@@ -305,6 +309,208 @@ __device__ __forceinline__ float mfma_tile_score_lean(const float* __restrict__ 
         reduce_all(acc1, g);
     } else {
         reduce_all(acc0, G - 1);
+    }
+    mfma_merge_halves(bs, bg, h);
+    grp = bg;
+    return bs;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The bound tile: certified UPPER BOUNDS of a 32-position tile's scores on the bf16 matrix cores (float32 operands
+// split into bf16 hi + lo; hi.hi + hi.lo + lo.hi on v_mfma_f32_32x32x16_bf16).  One definition for the bound pass of
+// the initial correlation (corr_bound_kernel) and the re-correlation of the four-signal loop (MfmaRecorr, BOUND):
+// hscmp_bound.h derives the constants and states the model the inputs must lie in.
+// ------------------------------------------------------------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr float kBoundEps = 0x1p-13f;        // >= 1.67 eps_0 (hscmp_bound.h)
+constexpr float kBoundRel = 1.0f + 0x1p-20f;
+constexpr float kBoundAbs = 0x1p-80f;
+constexpr float kBoundXMin = 0x1p-60f, kBoundXMax = 0x1p60f;     // signal samples (per chunk, on the device)
+constexpr double kBoundDMin = 0x1p-30, kBoundDMax = 0x1p30;     // dictionary entries and weights (host)
+
+// bf16 round-to-nearest-even of a finite float32 whose magnitude is far from FLT_MAX: the bits of the bf16 value as a float32
+__host__ __device__ inline unsigned bf16_rn_bits(unsigned b) { return (b + 0x7fffu + ((b >> 16) & 1u)) & 0xffff0000u; }
+__host__ __device__ inline void bf16_split(float v, unsigned short& hi, unsigned short& lo)
+{
+    unsigned b;
+    memcpy(&b, &v, 4);
+    const unsigned hb = bf16_rn_bits(b);
+    float hf;
+    memcpy(&hf, &hb, 4);
+    const float r = v - hf;                                     // exact
+    unsigned rb;
+    memcpy(&rb, &r, 4);
+    hi = (unsigned short)(hb >> 16);
+    lo = (unsigned short)(bf16_rn_bits(rb) >> 16);
+}
+
+__device__ __forceinline__ float bf16_lo_f(unsigned w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf16_hi_f(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
+
+// One 32-position tile against all atom groups: the bound of every position (lanes 0..31: position = lane).
+//   bimg: LDS [hi image][lo image];  xh, xl: the chunk's bf16 halves in LDS, 4-byte aligned, index 0 = the first tap
+//   of the tile's first position.  B operand of k-step s, lane (r, h): samples r + 16s + 8h + j, j = 0..7 -- 8
+//   consecutive bf16 at an odd or even start: five aligned dwords and v_alignbit.
+template <int SB, bool HAS_W>
+__device__ __forceinline__ float bound_tile(const bf16x8* __restrict__ bimg_h, const bf16x8* __restrict__ bimg_l,
+                                            const unsigned short* __restrict__ xh, const unsigned short* __restrict__ xl,
+                                            const float* __restrict__ wts, int G, int lane, float cmax)
+{
+    const int r = lane & 31, h = lane >> 5;
+    const unsigned* xh32 = reinterpret_cast<const unsigned*>(xh);
+    const unsigned* xl32 = reinterpret_cast<const unsigned*>(xl);
+    const unsigned sh = 16u * (unsigned)(r & 1);
+    u32x4 bh[SB], bl[SB];
+    float ss = 0.0f;
+#pragma unroll
+    for (int s = 0; s < SB; ++s) {
+        const int w0 = (r >> 1) + 8 * s + 4 * h;
+        unsigned a[5], b[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) { a[i] = xh32[w0 + i]; b[i] = xl32[w0 + i]; }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            bh[s][i] = __builtin_amdgcn_alignbit(a[i + 1], a[i], sh);
+            bl[s][i] = __builtin_amdgcn_alignbit(b[i + 1], b[i], sh);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {                           // ||xh + xl||^2 over this half-wave's taps (xh + xl exact)
+            const float y0 = bf16_lo_f(bh[s][i]) + bf16_lo_f(bl[s][i]);
+            const float y1 = bf16_hi_f(bh[s][i]) + bf16_hi_f(bl[s][i]);
+            ss = fmaf(y0, y0, ss);
+            ss = fmaf(y1, y1, ss);
+        }
+    }
+    ss = ss + swap_halves_f(ss, h);                             // both halves of the window (taps 16s + 0..15)
+    float bs = 0.0f;
+    auto katom = [&](int kbase, int e) { return kbase + (e & 3) + 8 * (e >> 2); };
+    auto chain = [&](int g, f32x16& acc) {
+        f32x16 z;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) z[e] = 0.0f;
+        acc = z;
+#pragma unroll
+        for (int s = 0; s < SB; ++s) {
+            const bf16x8 ah = bimg_h[(g * SB + s) * 64 + lane], al = bimg_l[(g * SB + s) * 64 + lane];
+            const bf16x8 xbh = __builtin_bit_cast(bf16x8, bh[s]), xbl = __builtin_bit_cast(bf16x8, bl[s]);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xbh, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xbl, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xbh, acc, 0, 0, 0);
+        }
+    };
+    auto reduce = [&](const f32x16& acc, int g) {
+        const int kbase = 32 * g + 4 * h;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) mfma_reduce_pair<HAS_W>(acc[2 * e], acc[2 * e + 1], katom(kbase, 2 * e), katom(kbase, 2 * e + 1), wts, bs);
+    };
+    // two accumulators: the reduction of group g-1 runs beside the MFMAs of group g
+    f32x16 acc0, acc1;
+    chain(0, acc0);
+    int g = 1;
+    for (; g + 1 < G; g += 2) {
+        chain(g, acc1);
+        reduce(acc0, g - 1);
+        chain(g + 1, acc0);
+        reduce(acc1, g);
+    }
+    if (g < G) {
+        chain(g, acc1);
+        reduce(acc0, g - 1);
+        reduce(acc1, g);
+    } else {
+        reduce(acc0, G - 1);
+    }
+    bs = fmaxf(bs, swap_halves_f(bs, h));
+    if (ss == 0.0f) return bs;                                  // all-zero window: every product and sum is an exact 0
+    const float e = __fmul_rn(__fmul_rn(kBoundEps, __fsqrt_rn(ss)), cmax) + kBoundAbs;
+    return fmaf(bs, kBoundRel, e);
+}
+
+// A signal sample outside the model of the bound tile: not finite, or a non-zero magnitude outside [2^-60, 2^60].
+// A tile (or a chunk of the bound pass) that reads one runs the exact float32 tile instead.
+__device__ __forceinline__ bool bound_sample_out(float x)
+{
+    const float a = fabsf(x);
+    return !(a <= kBoundXMax) || (a != 0.0f && a < kBoundXMin);      // (NaN fails the first test)
+}
+
+// ---- the bf16 planes as the float32 dictionary ---------------------------------------------------------------
+// The bound loop keeps no float32 image: its exact chains rebuild every tap as (hi + lo) + rem from the three planes
+// Bimg[plane][g][s][lane][8] (hscmp_bound.h: bitwise the float32 value, checked for every element on the host).
+// Element of D[k][w] in a plane: lane (k & 31) + 32 ((w >> 3) & 1), k-step w >> 4, element w & 7.
+__device__ __forceinline__ int bf16_plane_index(int k, int w, int SB)
+{
+    return (((k >> 5) * SB + (w >> 4)) * 64 + (k & 31) + 32 * ((w >> 3) & 1)) * 8 + (w & 7);
+}
+__device__ __forceinline__ float bf16_tap(unsigned hi, unsigned lo, unsigned rem)      // (the bf16 bits in the low half)
+{
+    return (__uint_as_float(hi << 16) + __uint_as_float(lo << 16)) + __uint_as_float(rem << 16);
+}
+// the taps 2i + h of a dword pair of elements (2i, 2i + 1) of the three planes
+__device__ __forceinline__ float bf16_tap_of(unsigned h, unsigned l, unsigned r, int odd)
+{
+    return odd ? (bf16_hi_f(h) + bf16_hi_f(l)) + bf16_hi_f(r) : (bf16_lo_f(h) + bf16_lo_f(l)) + bf16_lo_f(r);
+}
+
+// resolve_chain on the planes: D[k][.] . rwin[.] as the pinned sequential fma chain, taps ascending.  Chunk c of 8
+// taps is one 16-byte word per plane (lane (k & 31) + 32 (c & 1) of k-step c >> 1).  Bit-identical to resolve_chain.
+template <int SB>
+__device__ __forceinline__ float resolve_chain_planes(const unsigned short* __restrict__ img, int nplane, const float* __restrict__ rwin, int k)
+{
+    const u32x4* p0 = reinterpret_cast<const u32x4*>(img) + ((k >> 5) * SB) * 64 + (k & 31);
+    const u32x4* p1 = p0 + nplane / 8;
+    const u32x4* p2 = p1 + nplane / 8;
+    float acc = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 2 * SB; ++c) {
+        const int o = (c >> 1) * 64 + 32 * (c & 1);
+        const u32x4 h = p0[o], l = p1[o], r = p2[o];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            acc = fmaf(rwin[8 * c + 2 * i], (bf16_lo_f(h[i]) + bf16_lo_f(l[i])) + bf16_lo_f(r[i]), acc);
+            acc = fmaf(rwin[8 * c + 2 * i + 1], (bf16_hi_f(h[i]) + bf16_hi_f(l[i])) + bf16_hi_f(r[i]), acc);
+        }
+    }
+    return acc;
+}
+
+// The exact float32 tile on the planes (the bound loop's tile for a window outside the model): mfma_tile_score's
+// products in mfma_tile_score's order -- lane (j, h) of k-step 4c + i needs tap 8c + 2i + h, element 2i + h of the
+// word of chunk c -- so score and group hint are bit for bit the float32 tile's.  One accumulator, no operand
+// prefetch: the rare path, kept small in registers.
+template <int SB, bool HAS_W>
+__device__ __forceinline__ float planes_tile_score(const unsigned short* __restrict__ img, int nplane, const float* __restrict__ win,
+                                                   const float* __restrict__ wts, int G, int lane, int& grp)
+{
+    const int j = lane & 31, h = lane >> 5;
+    const float* wb = win + j + h;
+    const u32x4* p0 = reinterpret_cast<const u32x4*>(img) + j;
+    const u32x4* p1 = p0 + nplane / 8;
+    const u32x4* p2 = p1 + nplane / 8;
+    float bs = 0.0f;
+    int bg = 0;
+    auto katom = [&](int kbase, int r) { return kbase + (r & 3) + 8 * (r >> 2); };
+#pragma unroll 1
+    for (int g = 0; g < G; ++g) {
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 2 * SB; ++c) {
+            const int o = (g * SB + (c >> 1)) * 64 + 32 * (c & 1);
+            const u32x4 wh = p0[o], wl = p1[o], wr = p2[o];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bf16_tap_of(wh[i], wl[i], wr[i], h), wb[8 * c + 2 * i], acc, 0, 0, 0);
+        }
+        const int kbase = 32 * g + 4 * h;
+        const float before = bs;
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            mfma_reduce_pair<HAS_W>(acc[2 * e], acc[2 * e + 1], katom(kbase, 2 * e), katom(kbase, 2 * e + 1), wts, bs);
+        bg = bs > before ? g : bg;
     }
     mfma_merge_halves(bs, bg, h);
     grp = bg;
@@ -681,11 +887,16 @@ template <typename R> inline bool mfma_supported(int K, int W, int F)
 // 4: four signals share a 1024-thread workgroup and ONE image (float32 only): four waves per SIMD, each from a
 // different signal, so that while one signal is in its serial phases (loads, resolve, residual update, maxima, stop
 // rules) the matrix pipe has three other signals' tiles to run.  The waves of a signal meet at SoftSync barriers.
-template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
+// BOUND (four signals, float32, compile-time chunk count): the re-correlation writes upper bounds on the bf16 matrix cores
+// (bound_tile, as the bound pass of the initial correlation) and the selection refines the rows that win; the workgroup
+// holds the dictionary as the three bf16 planes of hscmp_bound.h instead of the float32 image.
+template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> struct MfmaRecorr {
     static constexpr int kMaxSegments = kMfmaMaxSeg;
     static constexpr bool kFused = true;
     static constexpr bool kLocomp = false;
     static constexpr int kGroup = GS;
+    static_assert(!BOUND || (GS == 4 && S4C > 0 && std::is_same<Tile, TileF32>::value), "the bound loop: four signals, float32, W <= 8 S4C");
+    static constexpr int SB = S4C / 2;          // (BOUND) k-steps of 16 taps of the bf16 tile
     // -DHSCMP_QUAD_LOCKSTEP=1 (measurement only): barriers B1 and B4 of the atom body become hardware barriers across
     // the four signals of the workgroup, which lines their tiles up -- all serial phases then run together without a
     // matrix instruction beside them, all tiles together.  Measured 10.1-10.2 ms against 9.6 ms for the greedy loop of
@@ -723,7 +934,8 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
     struct Layout {
         R* dimg; R* wts; R* win; R* esq; R* sbs; unsigned* bloom;
         R* rwin; R* rwin_w; unsigned long long* edge;
-        int nwin, wp, nsbmax;
+        unsigned short* bimg; unsigned short* xh; unsigned short* xl;      // (BOUND) the planes; the window's bf16 hi / lo
+        int nwin, wp, nsbmax, nplane;
     };
 
     static __host__ __device__ int window_floats(int W, int S4) { return ((2 * W - 1 + TP - 1) / TP) * TP + 8 * S4 + 32; }
@@ -732,14 +944,20 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
     static __host__ __device__ int segbuf_len_p(const DevParams& P) { return (((2 * P.W - 2) >> P.seg_shift) + 2) << P.seg_shift; }
     // LDS: what the signals of a workgroup share (dictionary image, weights), then per signal the control block and
     // its windows.  GS == 1: [control][image | weights | windows ...] as one region behind the control block.
+    static __host__ __device__ size_t image_lds_bytes(const Args& A)
+    {
+        if constexpr (BOUND) return (size_t)3 * A.G * SB * 1024;                    // three bf16 planes
+        else return (size_t)A.G * A.S4 * Tile::kChunkElems * sizeof(R);
+    }
     static __host__ __device__ size_t shared_lds_bytes(const Args& A)
     {
-        return ((size_t)A.G * A.S4 * Tile::kChunkElems + (HAS_W ? Tile::GA * A.G : 0)) * sizeof(R);      // (a multiple of 16)
+        return image_lds_bytes(A) + (HAS_W ? Tile::GA * A.G : 0) * sizeof(R);      // (a multiple of 16)
     }
     static __host__ __device__ size_t private_lds_bytes(const DevParams& P, const Args& A)
     {
         const size_t relems = (size_t)window_floats(P.W, A.S4) + 2 * 8 * A.S4 + (size_t)segbuf_len_p(P) + 8 * A.S4 + kWaves * 8 * A.S4;
-        return relems * sizeof(R) + kBloomWords * sizeof(unsigned) + kEdgeWords * sizeof(unsigned long long);
+        return relems * sizeof(R) + kBloomWords * sizeof(unsigned) + kEdgeWords * sizeof(unsigned long long) +
+               (BOUND ? (size_t)2 * window_floats(P.W, A.S4) * sizeof(unsigned short) : 0);
     }
     static __host__ __device__ size_t per_signal_lds_bytes(const DevParams& P, const Args& A)
     {
@@ -763,7 +981,9 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
         const int S4 = S4C > 0 ? S4C : A.S4;
         Layout L;
         L.dimg = reinterpret_cast<R*>(GS == 1 ? lds : dyn_lds());
-        L.wts = L.dimg + A.G * S4 * Tile::kChunkElems;
+        L.bimg = reinterpret_cast<unsigned short*>(L.dimg);
+        L.nplane = A.G * SB * 512;
+        L.wts = reinterpret_cast<R*>(reinterpret_cast<char*>(L.dimg) + image_lds_bytes(A));
         L.nwin = window_floats(P.W, S4);
         L.wp = 8 * S4;
         L.nsbmax = segbuf_len_p(P);
@@ -774,6 +994,8 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
         L.rwin = reinterpret_cast<R*>(L.bloom + kBloomWords);
         L.rwin_w = L.rwin + L.wp;
         L.edge = reinterpret_cast<unsigned long long*>(L.rwin_w + kWaves * L.wp);
+        L.xh = reinterpret_cast<unsigned short*>(L.edge + kEdgeWords);
+        L.xl = L.xh + L.nwin;
         return L;
     }
 
@@ -784,8 +1006,9 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
         if constexpr (GS > 1) {
             const int S4 = S4C > 0 ? S4C : A.S4;
             R* dimg = reinterpret_cast<R*>(smem);
-            R* wts = dimg + A.G * S4 * Tile::kChunkElems;
-            lds_copy16(dimg, A.dimg, A.G * S4 * Tile::kChunkElems * (int)sizeof(R), (int)threadIdx.x, GS * kThreads);
+            R* wts = reinterpret_cast<R*>(smem + image_lds_bytes(A));
+            if constexpr (BOUND) lds_copy16(dimg, A.bimg, (int)image_lds_bytes(A), (int)threadIdx.x, GS * kThreads);
+            else lds_copy16(dimg, A.dimg, A.G * S4 * Tile::kChunkElems * (int)sizeof(R), (int)threadIdx.x, GS * kThreads);
             if (HAS_W) for (int i = threadIdx.x; i < Tile::GA * A.G; i += GS * kThreads) wts[i] = i < P.K ? S.weights[i] : (R)0;
             if (ltid() == 0) {
                 Shared* sh = reinterpret_cast<Shared*>(smem + signal_lds_offset(P, A));
@@ -805,6 +1028,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
             if (HAS_W) for (int i = tid; i < Tile::GA * A.G; i += kThreads) L.wts[i] = i < P.K ? S.weights[i] : (R)0;
         }
         for (int i = tid; i < L.nwin; i += kThreads) L.win[i] = (R)0;   // the tail behind the span stays zero
+        if constexpr (BOUND) for (int i = tid; i < L.nwin; i += kThreads) { L.xh[i] = 0; L.xl[i] = 0; }
         for (int i = tid; i < kBloomWords; i += kThreads) L.bloom[i] = 0u;
         for (int i = tid; i < (1 + kWaves) * L.wp; i += kThreads) L.rwin[i] = (R)0;   // padded taps stay zero
         if (tid < kEdgeWords) L.edge[tid] = S.edge[kEdgeWords * b + tid];
@@ -829,6 +1053,31 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
     // never reached: iterate_kernel hands the whole atom body to apply_atom() when kFused
     template <typename SH>
     static __device__ __forceinline__ void run(const DevParams&, const State<R>&, const Sig<R>&, SH&, const Args&, char*, int, int) {}
+
+    // The float32 tap D[k][w] and the pinned chain of atom k over a window: from the float32 image, or (BOUND) rebuilt
+    // from the bf16 planes as (hi + lo) + rem -- the same float32 values, so the same chains bit for bit.
+    static __device__ __forceinline__ R dtap(const Layout& L, int k, int w, int S4)
+    {
+        if constexpr (BOUND) {
+            const int i = bf16_plane_index(k, w, SB);
+            return bf16_tap(L.bimg[i], L.bimg[L.nplane + i], L.bimg[2 * L.nplane + i]);
+        } else {
+            return L.dimg[Tile::dindex(k, w, S4)];
+        }
+    }
+    // (BOUND) sample i of the re-correlation's window as bf16 hi / lo, the bound tile's B operands
+    static __device__ __forceinline__ void window_split(const Layout& L, int i, R v)
+    {
+        unsigned short hi, lo;
+        bf16_split(v, hi, lo);
+        L.xh[i] = hi;
+        L.xl[i] = lo;
+    }
+    static __device__ __forceinline__ R dchain(const Layout& L, const R* rw, int k, int S4)
+    {
+        if constexpr (BOUND) return resolve_chain_planes<SB>(L.bimg, L.nplane, rw, k);
+        else return Tile::template resolve<S4C>(L.dimg, rw, k, S4);
+    }
 
     // (k, c) of position t by ONE wave (blocked selection, modeling.py:935-946): the window goes to
     // this wave's private LDS strip, lanes stride over the atoms, first k wins ties.
@@ -860,7 +1109,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
         Cand<R> best; best.s = (R)-1; best.i = INT_MAX;
         R bc = (R)0;
         if (lane < Tile::GA && k < P.K) {
-            bc = Tile::template resolve<S4C>(L.dimg, rw, k, S4);
+            bc = dchain(L, rw, k, S4);
             if (HAS_W) { const R sw = bc * L.wts[k]; best.s = rabs(sw); } else best.s = rabs(bc);
             // (a NaN -- diverged pursuit -- must not reach the reduction of the float64 build, whose comparisons would leave
             //  the lanes with different winners; the float32 reduction orders bit patterns, where a NaN is the largest)
@@ -874,12 +1123,16 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
 
     // ---- refining a bound --------------------------------------------------------------
     // Position t holds an upper bound (best_k[t] == -1): its exact score and group hint, by every wave for itself.
-    // Exactness: a position still holding a bound has never been re-correlated, so no applied atom overlaps its window
-    // (an atom at p changes samples p - off .. p - off + W - 1 and re-correlates every row whose window holds one of
-    // them, p - (W-1) .. p + (W-1), clipped), and its window outside the signal is still the ZERO padding of the initial
-    // table (the edge bits of DESIGN.md section 2 are set only by a re-correlation; the stale row T-1 is a re-correlated
-    // row).  So the residual, zero padded, IS the window the initial correlation saw, and the pinned chain of every atom
-    // over it (resolve_chain: bit for bit the MFMA chain) reproduces the score and the hint of corr_init_mfma_kernel.
+    // Two passes write bounds: the initial correlation (over the zero-padded signal) and, in the bound loop, the
+    // re-correlation of an applied atom (over the reflect-padded window of the moment).  Exactness: the window of a row
+    // that holds a bound has not changed since the bound was written.  Every later atom whose support overlaps the
+    // window (an atom at p changes samples p - off .. p - off + W - 1) re-correlates every row whose window holds one of
+    // them, p - (W-1) .. p + (W-1), clipped, and so replaces the bound -- with one exception, the stale sample of row
+    // T-1 with an even W (edge_window_value), which the edge history records.  Outside the signal, the window of a row
+    // that was never re-correlated is the ZERO padding of the initial table, and the reflection once it was (the edge
+    // bits of DESIGN.md section 2 are set by the atom whose tile wrote the row).  So edge_window_value gives, for either
+    // kind of row, exactly the window the pass that wrote the bound saw, and the pinned chain of every atom over it
+    // (bit for bit the MFMA chain) reproduces the score and the hint the exact tile would have written there.
     // The residual is the engine's own buffer: a caller's input that changes between resumed rounds does not matter.
     static __device__ __forceinline__ void refine(const DevParams& P, const Sig<R>& Gs, const Args& A, char* lds, int t, int lane,
                                                   R& s_out, int& g_out)
@@ -888,10 +1141,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
         const int S4 = S4C > 0 ? S4C : A.S4;
         R* rw = L.rwin_w + (ltid() >> 6) * L.wp;            // this wave's strip (taps past W stay zero)
         __builtin_amdgcn_wave_barrier();
-        for (int w = lane; w < P.W; w += 64) {
-            const int g = t - P.off + w;
-            rw[w] = (g >= 0 && g < P.T) ? Gs.r[g] : (R)0;
-        }
+        for (int w = lane; w < P.W; w += 64) rw[w] = edge_window_value(Gs.r, P.T, t - P.off + w, t, L.edge);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
         // lane l: atoms l, l + 64, ...; the score of the tile (|c * w_k|, max over atoms) and the lowest atom attaining it,
@@ -899,7 +1149,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
         R best = (R)-1;
         int bk = INT_MAX;
         for (int k = lane; k < P.K; k += 64) {
-            const R c = Tile::template resolve<S4C>(L.dimg, rw, k, S4);
+            const R c = dchain(L, rw, k, S4);
             const R v = HAS_W ? rabs(c * L.wts[k]) : rabs(c);
             if (v > best) { best = v; bk = k; }
         }
@@ -919,6 +1169,9 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
         R s_ex;
         int g_ex;
         refine(P, Gs, A, lds, t, lane, s_ex, g_ex);
+#ifdef HSCMP_DBG_STAMPS
+        if (blockIdx.x == 0 && threadIdx.x == 0) g_stamps[13] += 1;       // refines of signal 0 (g_stamps[15]: its atoms)
+#endif
         const int i = rl.n;
         const int sg = t >> P.seg_shift;
         // (constant indices only: the list stays in registers)
@@ -1121,7 +1374,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
                     R v = rv[u];
                     const int q = rm[u] - s;
                     if (q >= 0 && q < e - s) {
-                        const R prod = nc * L.dimg[Tile::dindex(k, es + q, S4)];   // -c*D[k] rounded, then += (utils.py:120,129)
+                        const R prod = nc * dtap(L, k, es + q, S4);   // -c*D[k] rounded, then += (utils.py:120,129)
                         const R vn = v + prod;
                         // (W = 2 only: the atom at T-1-W is an interior one, see the stale-sample note below)
                         if (!(W & 1) && p == T - 1 - W && rm[u] == T - 1 - W / 2 && (L.edge[1] & 1ull) && L.edge[2] == 0ull) {
@@ -1134,6 +1387,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
                         v = vn;
                     }
                     L.win[i] = v;
+                    if constexpr (BOUND) window_split(L, i, v);
                     rv[u] = v;
                 }
             }
@@ -1146,7 +1400,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
                 const int m = rm[u];
                 if (m >= s && m < e) {
                     const int q = m - s;
-                    const R prod = nc * L.dimg[Tile::dindex(k, es + q, S4)];   // -c*D[k] rounded, then += (utils.py:120,129)
+                    const R prod = nc * dtap(L, k, es + q, S4);   // -c*D[k] rounded, then += (utils.py:120,129)
                     const R vn = v + prod;
                     if (tstart + i == m) {                    // the sample itself (not a reflected copy)
                         // even W: an atom at T-1-W changes the sample that row T-1 reads through the reflection
@@ -1162,6 +1416,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
                     v = vn;
                 }
                 L.win[i] = v;
+                if constexpr (BOUND) window_split(L, i, v);
                 rv[u] = v;
             }
         }
@@ -1208,12 +1463,27 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
         for (int q = wv; q < ntiles; q += kWaves) {
             R sc;
             int grp;
-            if constexpr (GS > 1 && S4C > 0) sc = Tile::template tile_score_lean<S4C, HAS_W>(L.dimg, L.win + TP * q, L.wts, A.G, S4, lane, grp);
+            if constexpr (BOUND) {
+                // upper bounds on the bf16 matrix cores (bound_tile), unless the tile reads a sample outside the model: rows
+                // TP q .. TP q + TP-1, taps 0 .. 16 SB - 1 (past W the planes are zero, but zero times a non-finite sample is
+                // not).  A wave-wide vote; the window changes with every atom.
+                bool out = false;
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+                    if (lane + 64 * u < TP - 1 + 16 * SB) out |= bound_sample_out(L.win[TP * q + lane + 64 * u]);
+                if (__builtin_amdgcn_ballot_w64(out) != 0) {
+                    sc = planes_tile_score<SB, HAS_W>(L.bimg, L.nplane, L.win + TP * q, L.wts, A.G, lane, grp);
+                } else {
+                    const bf16x8* ph = reinterpret_cast<const bf16x8*>(L.bimg);
+                    sc = bound_tile<SB, HAS_W>(ph, ph + L.nplane / 8, L.xh + TP * q, L.xl + TP * q, L.wts, A.G, lane, A.cmax);
+                    grp = sc == 0.0f ? 0 : -1;                  // an exact 0 is a score (hint 0, as the exact tile); else a bound
+                }
+            } else if constexpr (GS > 1 && S4C > 0) sc = Tile::template tile_score_lean<S4C, HAS_W>(L.dimg, L.win + TP * q, L.wts, A.G, S4, lane, grp);
             else sc = Tile::template tile_score<S4C, HAS_W>(L.dimg, L.win + TP * q, L.wts, A.G, S4, lane, grp);
             const int row = TP * q + lane, t = p - (W - 1) + row;
             if (lane < TP && row < nrows && t >= 0 && t < T) {  // overlapReplace clipping (utils.py:133-161)
                 Gs.bc[t] = sc;
-                Gs.bk[t] = grp;                                 // the group hint of the row (resolve_group)
+                Gs.bk[t] = grp;                                 // the group hint of the row (resolve_group), or -1: a bound
                 L.sbs[t - segbase] = sc;
             }
         }
@@ -1312,12 +1582,12 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1> struct MfmaRecorr {
                 for (int kk = 0; kk < P.K; ++kk) {
                     float acc = 0.0f;
                     for (int w = 0; w < W; ++w)
-                        acc = fmaf((float)edge_window_value(Gs.r, T, t - P.off + w, t, L.edge), (float)L.dimg[Tile::dindex(kk, w, S4)], acc);
+                        acc = fmaf((float)edge_window_value(Gs.r, T, t - P.off + w, t, L.edge), (float)dtap(L, kk, w, S4), acc);
                     if (HAS_W) acc = acc * (float)L.wts[kk];
                     best = fmaxf(best, fabsf(acc));
                 }
                 const float kept = (float)Gs.bc[t];
-                if (best != kept) {
+                if (Gs.bk[t] == -1 ? !(kept >= best) : best != kept) {      // (a bound row: at least the score)
                     const unsigned long long n = atomicAdd(&g_cnt[1], 1ull);
                     if (n < 3) {
                         g_cnt[4 + 4 * n + 0] = ((unsigned long long)(blockIdx.x * GS + gsig()) << 32) | (unsigned)t | 0x80000000u;
@@ -1380,11 +1650,11 @@ static int mfma_launch_corr_init_t(hipStream_t stream, const DevParams& P, const
 }
 
 // lds_pad: bytes of LDS added on top (HSCMP_LDS_PAD: forces a lower occupancy)
-template <typename Tile, int S4C, bool HAS_W, int GS>
+template <typename Tile, int S4C, bool HAS_W, int GS, bool BOUND = false>
 static int mfma_launch_iterate_g(hipStream_t stream, const DevParams& P0, const State<typename Tile::R>& S,
                                  const MfmaArgsT<typename Tile::R>& A, int lds_pad, bool dry)
 {
-    using Pol = MfmaRecorr<Tile, S4C, HAS_W, GS>;
+    using Pol = MfmaRecorr<Tile, S4C, HAS_W, GS, BOUND>;
     DevParams P = P0;
     set_segments(P, Pol::kMaxSegments);
     size_t lds = Pol::total_lds_bytes(P, A);
@@ -1399,12 +1669,16 @@ static int mfma_launch_iterate_g(hipStream_t stream, const DevParams& P0, const 
 
 // The loop with `group` signals per workgroup: 1, or 4 (float32 with a compile-time chunk count: one round of four overlapping
 // signals per CU instead of two rounds of two).  0: launched (or, dry, could be); -1: no such form for this shape.
+// A.bimg set (four signals only): the bound loop on the bf16 planes.
 template <typename Tile, int S4C, bool HAS_W>
 static int mfma_launch_iterate_t(hipStream_t stream, const DevParams& P, const State<typename Tile::R>& S,
                                  const MfmaArgsT<typename Tile::R>& A, int group, int lds_pad, bool dry)
 {
-    if constexpr (sizeof(typename Tile::R) == 4 && S4C > 0)
+    if constexpr (sizeof(typename Tile::R) == 4 && S4C > 0) {
+        if (group == 4 && A.bimg) return mfma_launch_iterate_g<Tile, S4C, HAS_W, 4, true>(stream, P, S, A, lds_pad, dry);
         if (group == 4) return mfma_launch_iterate_g<Tile, S4C, HAS_W, 4>(stream, P, S, A, lds_pad, dry);
+    }
+    if (A.bimg) return -1;
     return group == 1 ? mfma_launch_iterate_g<Tile, S4C, HAS_W, 1>(stream, P, S, A, lds_pad, dry) : -1;
 }
 
@@ -1435,11 +1709,15 @@ template <typename R> inline int mfma_launch_corr_init(hipStream_t stream, const
     HSCMP_MFMA_DISPATCH(mfma_launch_corr_init_t, dry);
 }
 
+// bimg, cmax: the bound loop's planes (hscmp_bound.h), or nullptr for the exact loop
 template <typename R>
-inline int mfma_launch_iterate(hipStream_t stream, const DevParams& P, const State<R>& S, const R* dimg, int group, int lds_pad, bool dry = false)
+inline int mfma_launch_iterate(hipStream_t stream, const DevParams& P, const State<R>& S, const R* dimg, int group, int lds_pad, bool dry = false,
+                               const unsigned short* bimg = nullptr, float cmax = 0.0f)
 {
     using Tile = typename TileOf<R>::type;
-    const MfmaArgsT<R> A = mfma_args<R>(P, S, dimg);
+    MfmaArgsT<R> A = mfma_args<R>(P, S, dimg);
+    A.bimg = bimg;
+    A.cmax = cmax;
     HSCMP_MFMA_DISPATCH(mfma_launch_iterate_t, group, lds_pad, dry);
 }
 

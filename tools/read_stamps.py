@@ -24,6 +24,7 @@ for i, nm in enumerate(names):
 for i, nm in ((8, 'phase A issue'), (9, 'resolve (Bx..By)'), (10, '[return -> next round]'), (11, '[selection + round checks]'), (12, '[atom body incl. entry]')):
     print('  %-18s %8.0f cycles/atom' % (nm, v[i] / n))
 print('  %-18s %8.0f cycles/atom (sum; the select between atoms is not stamped)' % ('total', (v[:8].sum() + v[8] + v[9]) / n))
+print('  refines per selection %.3f (%d; bound pass of the initial correlation and bound loop)' % (v[13] / n, v[13]))
 
 # per-workgroup residency (diagnostic build)
 try:
