@@ -128,6 +128,53 @@ def load_library():
     return lib
 
 
+def load_satellite(path, prefix, argtypes):
+    """Load lib<prefix>.so from `path` (one of the libraries beside libhscmp: nmf.py, ksvd.py, kmeans.py) and set the
+    types of <prefix>_version / _create / _destroy / _last_error and of `argtypes` ({entry point: argument types},
+    each returning int).  Raises (never falls back) when it is missing."""
+    if not os.path.isfile(path):
+        raise HscmpError('lib%s.so is not built (%s). Run `python __graft_entry__.py build` '
+                         '(hipcc --offload-arch=gfx950). There is no CPU fallback.' % (prefix, path))
+    lib = ctypes.CDLL(path)
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    types = {prefix + '_version': ([], ci), prefix + '_create': ([ctypes.POINTER(vp), ci], ci),
+             prefix + '_destroy': ([vp], None), prefix + '_last_error': ([vp], ctypes.c_char_p)}
+    types.update((name, (args, ci)) for name, args in argtypes.items())
+    for name, (args, res) in types.items():
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = res
+    return lib
+
+
+class LibraryContext(object):
+    """A context of a library loaded by load_satellite: <prefix>_create on `device`, <prefix>_destroy when collected."""
+
+    def __init__(self, lib, prefix, device):
+        self._lib, self._prefix, self._h = lib, prefix, None
+        h = ctypes.c_void_p()
+        self._check(getattr(lib, prefix + '_create')(ctypes.byref(h), int(device)), prefix + '_create')
+        self._h = h
+
+    def _check(self, rc, what):
+        """A status other than 0 raises HscmpError('<what> failed (<rc>): <last error>') with .code = rc."""
+        if rc != 0:
+            last = getattr(self._lib, self._prefix + '_last_error')(self._h).decode()
+            ex = HscmpError('%s failed (%d): %s' % (what, rc, last))
+            ex.code = int(rc)
+            raise ex
+
+    def call(self, name, *args):
+        """<prefix>_<name>(context, *args), checked."""
+        fn = '%s_%s' % (self._prefix, name)
+        self._check(getattr(self._lib, fn)(self._h, *args), fn)
+
+    def __del__(self):
+        if getattr(self, '_h', None):
+            getattr(self._lib, self._prefix + '_destroy')(self._h)
+            self._h = None
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 

@@ -15,16 +15,14 @@
 //   4. sum_kernel: one thread per (centroid, element) sums patch / ||patch|| over the members in list order.
 // Compiled with -ffp-contract=off: no product is fused into a sum outside the explicit MFMA chains.
 #include "../../../include/hsckmeans.h"
+#include "../common/hsc_lib.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <string>
 #include <vector>
 
 namespace {
@@ -291,13 +289,13 @@ __global__ __launch_bounds__(256) void sum_kernel(const X* __restrict__ x, int T
     S[(size_t)b * K * Q + e] = acc;
 }
 
-thread_local std::string g_err;
-
 }  // namespace
 
-struct hsckmeans_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
+static_assert(HSCKMEANS_OK == hsc::OK && HSCKMEANS_ERR_INVALID == hsc::ERR_INVALID && HSCKMEANS_ERR_NO_DEVICE == hsc::ERR_NO_DEVICE &&
+              HSCKMEANS_ERR_HIP == hsc::ERR_HIP && HSCKMEANS_ERR_UNSUPPORTED == hsc::ERR_UNSUPPORTED &&
+              HSCKMEANS_ERR_ALLOC == hsc::ERR_ALLOC, "include/hsckmeans.h and common/hsc_lib.h disagree on a status");
+
+struct HSC_HIDDEN hsckmeans_ctx : hsc::CtxBase {
     hipEvent_t ev[5] = {};
     // data (set_data)
     int dtype = -1, B = 0, T = 0, F = 0, N = 0, W = 0;
@@ -305,82 +303,26 @@ struct hsckmeans_ctx {
     int* d_starts = nullptr;
     // step buffers (grown, never shrunk)
     enum { kImg32, kImg64, kMode, kT, kK, kNorm, kPofs, kMembers, kCount, kNonzero, kSums, kBufs };
-    void* buf[kBufs] = {};
-    size_t cap[kBufs] = {};
+    hsc::Buffers<kBufs> buf;
     std::vector<float> img32;
     std::vector<double> img64;
-    std::string err;
+
+    ~hsckmeans_ctx()
+    {
+        if (d_x) (void)hipFree(d_x);
+        if (d_starts) (void)hipFree(d_starts);
+    }
 };
 
-static int fail(hsckmeans_ctx* ctx, int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    (ctx ? ctx->err : g_err) = buf;
-    return code;
-}
-
-static hipError_t ensure(hsckmeans_ctx* ctx, int i, size_t bytes)
-{
-    bytes = std::max<size_t>(bytes, 256);
-    if (ctx->cap[i] >= bytes) return hipSuccess;
-    if (ctx->buf[i]) (void)hipFree(ctx->buf[i]);
-    ctx->buf[i] = nullptr;
-    ctx->cap[i] = 0;
-    hipError_t e = hipMalloc(&ctx->buf[i], bytes);
-    if (e == hipSuccess) ctx->cap[i] = bytes;
-    return e;
-}
-
-#define KM_TRY(expr)                                                                                          \
-    do {                                                                                                      \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess) return fail(ctx, HSCKMEANS_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));    \
-    } while (0)
+using hsc::fail;
 
 extern "C" int hsckmeans_version(void) { return 1; }
 
-extern "C" const char* hsckmeans_last_error(hsckmeans_ctx* ctx) { return ctx ? ctx->err.c_str() : g_err.c_str(); }
+extern "C" const char* hsckmeans_last_error(hsckmeans_ctx* ctx) { return hsc::last_error(ctx); }
 
-extern "C" int hsckmeans_create(hsckmeans_ctx** out, int device_id)
-{
-    if (!out) return fail(nullptr, HSCKMEANS_ERR_INVALID, "hsckmeans_create: out is NULL");
-    *out = nullptr;
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0)
-        return fail(nullptr, HSCKMEANS_ERR_NO_DEVICE, "hsckmeans_create: no HIP device visible (%s)", hipGetErrorString(e));
-    if (device_id < 0 || device_id >= n)
-        return fail(nullptr, HSCKMEANS_ERR_INVALID, "hsckmeans_create: device %d out of range (%d devices)", device_id, n);
-    hsckmeans_ctx* ctx = new hsckmeans_ctx();
-    ctx->device = device_id;
-    e = hipSetDevice(device_id);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-    for (int i = 0; i < 5 && e == hipSuccess; ++i) e = hipEventCreate(&ctx->ev[i]);
-    if (e != hipSuccess) {
-        int rc = fail(nullptr, HSCKMEANS_ERR_HIP, "hsckmeans_create: %s", hipGetErrorString(e));
-        hsckmeans_destroy(ctx);
-        return rc;
-    }
-    *out = ctx;
-    return HSCKMEANS_OK;
-}
+extern "C" int hsckmeans_create(hsckmeans_ctx** out, int device_id) { return hsc::create(out, device_id, "hsckmeans_create"); }
 
-extern "C" void hsckmeans_destroy(hsckmeans_ctx* ctx)
-{
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (void* b : ctx->buf) if (b) (void)hipFree(b);
-    if (ctx->d_x) (void)hipFree(ctx->d_x);
-    if (ctx->d_starts) (void)hipFree(ctx->d_starts);
-    for (hipEvent_t ev : ctx->ev) if (ev) (void)hipEventDestroy(ev);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
-}
+extern "C" void hsckmeans_destroy(hsckmeans_ctx* ctx) { hsc::destroy(ctx); }
 
 extern "C" int hsckmeans_set_data(hsckmeans_ctx* ctx, const void* x, int dtype, int B, int T, int F, const int64_t* starts,
                                   int N, int W)
@@ -399,8 +341,8 @@ extern "C" int hsckmeans_set_data(hsckmeans_ctx* ctx, const void* x, int dtype, 
             return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_data: start %lld of window %zu is outside [0, %d]", (long long)starts[i], i, T - 2 * W);
         s32[i] = (int)starts[i];
     }
-    KM_TRY(hipSetDevice(ctx->device));
-    KM_TRY(hipStreamSynchronize(ctx->stream));
+    HSC_TRY(hipSetDevice(ctx->device));
+    HSC_TRY(hipStreamSynchronize(ctx->stream));
     if (ctx->d_x) (void)hipFree(ctx->d_x);
     if (ctx->d_starts) (void)hipFree(ctx->d_starts);
     ctx->d_x = nullptr;
@@ -410,9 +352,9 @@ extern "C" int hsckmeans_set_data(hsckmeans_ctx* ctx, const void* x, int dtype, 
     hipError_t e = hipMalloc(&ctx->d_x, bx);
     if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_starts, bs);
     if (e != hipSuccess) return fail(ctx, HSCKMEANS_ERR_ALLOC, "hsckmeans_set_data: hipMalloc failed (%s)", hipGetErrorString(e));
-    KM_TRY(hipMemcpyAsync(ctx->d_x, x, bx, hipMemcpyHostToDevice, ctx->stream));
-    KM_TRY(hipMemcpyAsync(ctx->d_starts, s32.data(), bs, hipMemcpyHostToDevice, ctx->stream));
-    KM_TRY(hipStreamSynchronize(ctx->stream));
+    HSC_TRY(hipMemcpyAsync(ctx->d_x, x, bx, hipMemcpyHostToDevice, ctx->stream));
+    HSC_TRY(hipMemcpyAsync(ctx->d_starts, s32.data(), bs, hipMemcpyHostToDevice, ctx->stream));
+    HSC_TRY(hipStreamSynchronize(ctx->stream));
     ctx->dtype = dtype;
     ctx->B = B; ctx->T = T; ctx->F = F; ctx->N = N; ctx->W = W;
     return HSCKMEANS_OK;
@@ -423,7 +365,7 @@ static int launch_assign(hsckmeans_ctx* ctx, const void* img, const AssignArgs& 
 {
     dim3 grid((ctx->N + WPB - 1) / WPB, ctx->B);
     hipLaunchKernelGGL((assign_kernel<X, R>), grid, dim3(kThreads), lds, ctx->stream, (const X*)ctx->d_x, (const R*)img, args);
-    KM_TRY(hipGetLastError());
+    HSC_TRY(hipGetLastError());
     return HSCKMEANS_OK;
 }
 
@@ -441,12 +383,12 @@ static int launch_centroids(hsckmeans_ctx* ctx, int K)
     int* nonzero = (int*)ctx->buf[hsckmeans_ctx::kNonzero];
     hipLaunchKernelGGL((norm_kernel<X>), dim3((N + 255) / 256, B), dim3(256), 0, ctx->stream, (const X*)ctx->d_x, ctx->T, ctx->F, N,
                        ctx->W, ctx->d_starts, mode, at, norm, pofs);
-    KM_TRY(hipGetLastError());
+    HSC_TRY(hipGetLastError());
     hipLaunchKernelGGL(member_kernel, dim3(K, B), dim3(64), 0, ctx->stream, N, K, mode, ak, members, count, nonzero);
-    KM_TRY(hipGetLastError());
+    HSC_TRY(hipGetLastError());
     hipLaunchKernelGGL((sum_kernel<X>), dim3((unsigned)(((size_t)K * Q + 255) / 256), B), dim3(256), 0, ctx->stream, (const X*)ctx->d_x,
                        ctx->T, ctx->F, N, ctx->W, K, mode, members, count, norm, pofs, (X*)ctx->buf[hsckmeans_ctx::kSums]);
-    KM_TRY(hipGetLastError());
+    HSC_TRY(hipGetLastError());
     return HSCKMEANS_OK;
 }
 
@@ -495,23 +437,19 @@ extern "C" int hsckmeans_step(hsckmeans_ctx* ctx, const double* D, int K, const 
                 }
     }
 
-    KM_TRY(hipSetDevice(ctx->device));
+    HSC_TRY(hipSetDevice(ctx->device));
     const size_t xs = ctx->dtype == HSCKMEANS_F32 ? 4 : 8;
     const size_t bytes[hsckmeans_ctx::kBufs] = {
         any32 ? per * B * 4 : 0, any64 ? per * B * 8 : 0, (size_t)B * sizeof(int), (size_t)B * N * sizeof(int),
         (size_t)B * N * sizeof(int), (size_t)B * N * xs, (size_t)B * N * sizeof(int), (size_t)B * K * N * sizeof(int),
         (size_t)B * K * sizeof(int), (size_t)B * K * sizeof(int), (size_t)B * K * Q * xs};
-    for (int i = 0; i < hsckmeans_ctx::kBufs; ++i) {
-        hipError_t e = ensure(ctx, i, bytes[i]);
-        if (e != hipSuccess)
-            return fail(ctx, HSCKMEANS_ERR_ALLOC, "hsckmeans_step: hipMalloc of %zu bytes failed (%s)", bytes[i], hipGetErrorString(e));
-    }
+    if (int rc = ctx->buf.ensure(ctx, bytes, "hsckmeans_step")) return rc;
     hipStream_t st = ctx->stream;
-    KM_TRY(hipEventRecord(ctx->ev[0], st));
-    if (any32) KM_TRY(hipMemcpyAsync(ctx->buf[hsckmeans_ctx::kImg32], ctx->img32.data(), per * B * 4, hipMemcpyHostToDevice, st));
-    if (any64) KM_TRY(hipMemcpyAsync(ctx->buf[hsckmeans_ctx::kImg64], ctx->img64.data(), per * B * 8, hipMemcpyHostToDevice, st));
-    KM_TRY(hipMemcpyAsync(ctx->buf[hsckmeans_ctx::kMode], mode, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
-    KM_TRY(hipEventRecord(ctx->ev[1], st));
+    HSC_TRY(hipEventRecord(ctx->ev[0], st));
+    if (any32) HSC_TRY(hipMemcpyAsync(ctx->buf[hsckmeans_ctx::kImg32], ctx->img32.data(), per * B * 4, hipMemcpyHostToDevice, st));
+    if (any64) HSC_TRY(hipMemcpyAsync(ctx->buf[hsckmeans_ctx::kImg64], ctx->img64.data(), per * B * 8, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[hsckmeans_ctx::kMode], mode, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+    HSC_TRY(hipEventRecord(ctx->ev[1], st));
 
     // launch shape: WPB windows per workgroup so that their columns fit 16 tiles; features staged FC at a time
     const int P = W + 1;
@@ -544,22 +482,17 @@ extern "C" int hsckmeans_step(hsckmeans_ctx* ctx, const double* D, int K, const 
         else rc = launch_assign<double, double>(ctx, ctx->buf[hsckmeans_ctx::kImg64], args, WPB, lds);
         if (rc != HSCKMEANS_OK) return rc;
     }
-    KM_TRY(hipEventRecord(ctx->ev[2], st));
+    HSC_TRY(hipEventRecord(ctx->ev[2], st));
     rc = ctx->dtype == HSCKMEANS_F32 ? launch_centroids<float>(ctx, K) : launch_centroids<double>(ctx, K);
     if (rc != HSCKMEANS_OK) return rc;
-    KM_TRY(hipEventRecord(ctx->ev[3], st));
-    KM_TRY(hipMemcpyAsync(out_t, ctx->buf[hsckmeans_ctx::kT], (size_t)B * N * sizeof(int), hipMemcpyDeviceToHost, st));
-    KM_TRY(hipMemcpyAsync(out_k, ctx->buf[hsckmeans_ctx::kK], (size_t)B * N * sizeof(int), hipMemcpyDeviceToHost, st));
-    KM_TRY(hipMemcpyAsync(out_count, ctx->buf[hsckmeans_ctx::kCount], (size_t)B * K * sizeof(int), hipMemcpyDeviceToHost, st));
-    KM_TRY(hipMemcpyAsync(out_nonzero, ctx->buf[hsckmeans_ctx::kNonzero], (size_t)B * K * sizeof(int), hipMemcpyDeviceToHost, st));
-    KM_TRY(hipMemcpyAsync(out_sums, ctx->buf[hsckmeans_ctx::kSums], (size_t)B * K * Q * xs, hipMemcpyDeviceToHost, st));
-    KM_TRY(hipEventRecord(ctx->ev[4], st));
-    KM_TRY(hipStreamSynchronize(st));
-    if (timing_ms)
-        for (int i = 0; i < HSCKMEANS_TIMES; ++i) {
-            float ms = 0.0f;
-            KM_TRY(hipEventElapsedTime(&ms, ctx->ev[i], ctx->ev[i + 1]));
-            timing_ms[i] = ms;
-        }
+    HSC_TRY(hipEventRecord(ctx->ev[3], st));
+    HSC_TRY(hipMemcpyAsync(out_t, ctx->buf[hsckmeans_ctx::kT], (size_t)B * N * sizeof(int), hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipMemcpyAsync(out_k, ctx->buf[hsckmeans_ctx::kK], (size_t)B * N * sizeof(int), hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipMemcpyAsync(out_count, ctx->buf[hsckmeans_ctx::kCount], (size_t)B * K * sizeof(int), hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipMemcpyAsync(out_nonzero, ctx->buf[hsckmeans_ctx::kNonzero], (size_t)B * K * sizeof(int), hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipMemcpyAsync(out_sums, ctx->buf[hsckmeans_ctx::kSums], (size_t)B * K * Q * xs, hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipEventRecord(ctx->ev[4], st));
+    HSC_TRY(hipStreamSynchronize(st));
+    if (timing_ms && (rc = hsc::add_times(ctx, HSCKMEANS_TIMES, timing_ms)) != HSCKMEANS_OK) return rc;     // (zeroed above)
     return HSCKMEANS_OK;
 }

@@ -17,15 +17,13 @@
 //      writes D[k] and the new coefficients c_i = P_i . u.
 // Compiled with -ffp-contract=off: no product is fused into a sum, which step 1 relies on.
 #include "../../../include/hscksvd.h"
+#include "../common/hsc_lib.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <string>
 #include <vector>
 
 namespace {
@@ -293,87 +291,26 @@ __global__ __launch_bounds__(kThreads) void ksvd_sweep_kernel(SweepArgs a)
     }
 }
 
-thread_local std::string g_err;
-
 }  // namespace
 
-struct hscksvd_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    void* buf[7] = {};                 // D, indptr, rows, vals, occ, occ_ptr + stats, P
-    size_t cap[7] = {};
-    std::string err;
+static_assert(HSCKSVD_OK == hsc::OK && HSCKSVD_ERR_INVALID == hsc::ERR_INVALID && HSCKSVD_ERR_NO_DEVICE == hsc::ERR_NO_DEVICE &&
+              HSCKSVD_ERR_HIP == hsc::ERR_HIP && HSCKSVD_ERR_UNSUPPORTED == hsc::ERR_UNSUPPORTED && HSCKSVD_ERR_ALLOC == hsc::ERR_ALLOC,
+              "include/hscksvd.h and common/hsc_lib.h disagree on a status");
+
+struct HSC_HIDDEN hscksvd_ctx : hsc::CtxBase {
+    hipEvent_t ev[4] = {};
+    hsc::Buffers<7> buf;               // D, indptr, rows, vals, occ, occ_ptr + stats, P
 };
 
-static int fail(hscksvd_ctx* ctx, int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    (ctx ? ctx->err : g_err) = buf;
-    return code;
-}
-
-// device buffer i of at least `bytes` (grown, never shrunk)
-static hipError_t ensure(hscksvd_ctx* ctx, int i, size_t bytes)
-{
-    bytes = std::max<size_t>(bytes, 256);
-    if (ctx->cap[i] >= bytes) return hipSuccess;
-    if (ctx->buf[i]) (void)hipFree(ctx->buf[i]);
-    ctx->buf[i] = nullptr;
-    ctx->cap[i] = 0;
-    hipError_t e = hipMalloc(&ctx->buf[i], bytes);
-    if (e == hipSuccess) ctx->cap[i] = bytes;
-    return e;
-}
-
-#define KSVD_TRY(expr)                                                                                        \
-    do {                                                                                                      \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess) return fail(ctx, HSCKSVD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));      \
-    } while (0)
+using hsc::fail;
 
 extern "C" int hscksvd_version(void) { return 1; }
 
-extern "C" const char* hscksvd_last_error(hscksvd_ctx* ctx) { return ctx ? ctx->err.c_str() : g_err.c_str(); }
+extern "C" const char* hscksvd_last_error(hscksvd_ctx* ctx) { return hsc::last_error(ctx); }
 
-extern "C" int hscksvd_create(hscksvd_ctx** out, int device_id)
-{
-    if (!out) return fail(nullptr, HSCKSVD_ERR_INVALID, "hscksvd_create: out is NULL");
-    *out = nullptr;
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0)
-        return fail(nullptr, HSCKSVD_ERR_NO_DEVICE, "hscksvd_create: no HIP device visible (%s)", hipGetErrorString(e));
-    if (device_id < 0 || device_id >= n)
-        return fail(nullptr, HSCKSVD_ERR_INVALID, "hscksvd_create: device %d out of range (%d devices)", device_id, n);
-    hscksvd_ctx* ctx = new hscksvd_ctx();
-    ctx->device = device_id;
-    e = hipSetDevice(device_id);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&ctx->ev[i]);
-    if (e != hipSuccess) {
-        int rc = fail(nullptr, HSCKSVD_ERR_HIP, "hscksvd_create: %s", hipGetErrorString(e));
-        hscksvd_destroy(ctx);
-        return rc;
-    }
-    *out = ctx;
-    return HSCKSVD_OK;
-}
+extern "C" int hscksvd_create(hscksvd_ctx** out, int device_id) { return hsc::create(out, device_id, "hscksvd_create"); }
 
-extern "C" void hscksvd_destroy(hscksvd_ctx* ctx)
-{
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (void* b : ctx->buf) if (b) (void)hipFree(b);
-    for (hipEvent_t ev : ctx->ev) if (ev) (void)hipEventDestroy(ev);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
-}
+extern "C" void hscksvd_destroy(hscksvd_ctx* ctx) { hsc::destroy(ctx); }
 
 extern "C" int hscksvd_update(hscksvd_ctx* ctx, int T, int K, int W, int F, double* D, const int32_t* indptr,
                               const int32_t* indices, double* data, int use_pca, double* out_atom_stats, double* timing_ms)
@@ -418,28 +355,23 @@ extern "C" int hscksvd_update(hscksvd_ctx* ctx, int T, int K, int W, int F, doub
         return HSCKSVD_OK;                                              // no atom occurs: nothing changes
     }
 
-    KSVD_TRY(hipSetDevice(ctx->device));
+    HSC_TRY(hipSetDevice(ctx->device));
     const size_t bD = (size_t)K * n * sizeof(double), bI = (size_t)(K + 1) * sizeof(int),
                  bR = (size_t)nnz * sizeof(int), bV = (size_t)nnz * sizeof(double), bO = occ.size() * sizeof(int),
                  bS = (size_t)K * kStats * sizeof(double), bP = (size_t)max_m * n * sizeof(double);
     const size_t bytes[7] = {bD, bI, bR, bV, bO, bI + bS + 16, bP};
-    for (int i = 0; i < 7; ++i) {
-        hipError_t e = ensure(ctx, i, bytes[i]);
-        if (e != hipSuccess)
-            return fail(ctx, HSCKSVD_ERR_ALLOC, "hscksvd_update: hipMalloc of %zu bytes failed (%s)", bytes[i],
-                        hipGetErrorString(e));
-    }
+    if (int rc = ctx->buf.ensure(ctx, bytes, "hscksvd_update")) return rc;
     int* d_occ_ptr = (int*)ctx->buf[5];
     double* d_stats = (double*)((char*)ctx->buf[5] + (bI + 15) / 16 * 16);
     hipStream_t st = ctx->stream;
-    KSVD_TRY(hipEventRecord(ctx->ev[0], st));
-    KSVD_TRY(hipMemcpyAsync(ctx->buf[0], D, bD, hipMemcpyHostToDevice, st));
-    KSVD_TRY(hipMemcpyAsync(ctx->buf[1], indptr, bI, hipMemcpyHostToDevice, st));
-    KSVD_TRY(hipMemcpyAsync(ctx->buf[2], indices, bR, hipMemcpyHostToDevice, st));
-    KSVD_TRY(hipMemcpyAsync(ctx->buf[3], data, bV, hipMemcpyHostToDevice, st));
-    KSVD_TRY(hipMemcpyAsync(ctx->buf[4], occ.data(), bO, hipMemcpyHostToDevice, st));
-    KSVD_TRY(hipMemcpyAsync(d_occ_ptr, occ_ptr.data(), bI, hipMemcpyHostToDevice, st));
-    KSVD_TRY(hipEventRecord(ctx->ev[1], st));
+    HSC_TRY(hipEventRecord(ctx->ev[0], st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[0], D, bD, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[1], indptr, bI, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[2], indices, bR, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[3], data, bV, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[4], occ.data(), bO, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(d_occ_ptr, occ_ptr.data(), bI, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipEventRecord(ctx->ev[1], st));
     SweepArgs args;
     args.T = T;
     args.K = K;
@@ -455,19 +387,15 @@ extern "C" int hscksvd_update(hscksvd_ctx* ctx, int T, int K, int W, int F, doub
     args.P = (double*)ctx->buf[6];
     args.stats = d_stats;
     hipLaunchKernelGGL(ksvd_sweep_kernel, dim3(1), dim3(kThreads), 0, st, args);
-    KSVD_TRY(hipGetLastError());
-    KSVD_TRY(hipEventRecord(ctx->ev[2], st));
-    KSVD_TRY(hipMemcpyAsync(D, ctx->buf[0], bD, hipMemcpyDeviceToHost, st));
-    KSVD_TRY(hipMemcpyAsync(data, ctx->buf[3], bV, hipMemcpyDeviceToHost, st));
-    KSVD_TRY(hipMemcpyAsync(stats.data(), d_stats, bS, hipMemcpyDeviceToHost, st));
-    KSVD_TRY(hipEventRecord(ctx->ev[3], st));
-    KSVD_TRY(hipStreamSynchronize(st));
+    HSC_TRY(hipGetLastError());
+    HSC_TRY(hipEventRecord(ctx->ev[2], st));
+    HSC_TRY(hipMemcpyAsync(D, ctx->buf[0], bD, hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipMemcpyAsync(data, ctx->buf[3], bV, hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipMemcpyAsync(stats.data(), d_stats, bS, hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipEventRecord(ctx->ev[3], st));
+    HSC_TRY(hipStreamSynchronize(st));
     if (timing_ms)
-        for (int i = 0; i < 3; ++i) {
-            float ms = 0.f;
-            KSVD_TRY(hipEventElapsedTime(&ms, ctx->ev[i], ctx->ev[i + 1]));
-            timing_ms[i] = ms;
-        }
+        if (int rc = hsc::add_times(ctx, 3, timing_ms)) return rc;          // (zeroed above)
     if (out_atom_stats) std::memcpy(out_atom_stats, stats.data(), stats.size() * sizeof(double));
     return HSCKSVD_OK;
 }

@@ -12,15 +12,13 @@
 // the reference's stop decision per signal on the device; a finished signal's workgroups return at once.
 // hscnmf_learn (the dictionary learner) adds, per iteration, the ratio, partial and update kernels of section 12.
 #include "../../../include/hscnmf.h"
+#include "../common/hsc_lib.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <string>
 #include <vector>
 
 namespace {
@@ -398,71 +396,25 @@ __global__ __launch_bounds__(kThreads) void nmf_dupdate_kernel(const T* __restri
     for (int c = threadIdx.x; c < NW; c += kThreads) d[c] = nrm > T(0) ? sum[c] / nrm : sum[c];
 }
 
-thread_local std::string g_err;
-
 }  // namespace
 
-struct hscnmf_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    std::string err;
+static_assert(HSCNMF_OK == hsc::OK && HSCNMF_ERR_INVALID == hsc::ERR_INVALID && HSCNMF_ERR_NO_DEVICE == hsc::ERR_NO_DEVICE &&
+              HSCNMF_ERR_HIP == hsc::ERR_HIP && HSCNMF_ERR_UNSUPPORTED == hsc::ERR_UNSUPPORTED && HSCNMF_ERR_ALLOC == hsc::ERR_ALLOC,
+              "include/hscnmf.h and common/hsc_lib.h disagree on a status");
+
+struct HSC_HIDDEN hscnmf_ctx : hsc::CtxBase {
+    hipEvent_t ev[4] = {};
 };
 
-static int fail(hscnmf_ctx* ctx, int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    (ctx ? ctx->err : g_err) = buf;
-    return code;
-}
-
-#define NMF_TRY(expr)                                                                                        \
-    do {                                                                                                     \
-        hipError_t e_ = (expr);                                                                              \
-        if (e_ != hipSuccess) { rc = fail(ctx, HSCNMF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); goto done; } \
-    } while (0)
+using hsc::fail;
 
 extern "C" int hscnmf_version(void) { return 2; }
 
-extern "C" const char* hscnmf_last_error(hscnmf_ctx* ctx) { return ctx ? ctx->err.c_str() : g_err.c_str(); }
+extern "C" const char* hscnmf_last_error(hscnmf_ctx* ctx) { return hsc::last_error(ctx); }
 
-extern "C" int hscnmf_create(hscnmf_ctx** out, int device_id)
-{
-    if (!out) return fail(nullptr, HSCNMF_ERR_INVALID, "hscnmf_create: out is NULL");
-    *out = nullptr;
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0)
-        return fail(nullptr, HSCNMF_ERR_NO_DEVICE, "hscnmf_create: no HIP device visible (%s)", hipGetErrorString(e));
-    if (device_id < 0 || device_id >= n)
-        return fail(nullptr, HSCNMF_ERR_INVALID, "hscnmf_create: device %d out of range (%d devices)", device_id, n);
-    hscnmf_ctx* ctx = new hscnmf_ctx();
-    ctx->device = device_id;
-    e = hipSetDevice(device_id);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&ctx->ev[i]);
-    if (e != hipSuccess) {
-        int rc = fail(nullptr, HSCNMF_ERR_HIP, "hscnmf_create: %s", hipGetErrorString(e));
-        hscnmf_destroy(ctx);
-        return rc;
-    }
-    *out = ctx;
-    return HSCNMF_OK;
-}
+extern "C" int hscnmf_create(hscnmf_ctx** out, int device_id) { return hsc::create(out, device_id, "hscnmf_create"); }
 
-extern "C" void hscnmf_destroy(hscnmf_ctx* ctx)
-{
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (hipEvent_t ev : ctx->ev) if (ev) (void)hipEventDestroy(ev);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
-}
+extern "C" void hscnmf_destroy(hscnmf_ctx* ctx) { hsc::destroy(ctx); }
 
 // LDS layout of one workgroup: reconstruction tile [kRows][F], then the P slab [PR][slab * CB] (also the
 // residual kernel's reduction scratch, 2 * kThreads doubles)
@@ -479,107 +431,173 @@ static bool lds_plan(int W, int F, int& PR, int& slab, size_t& bytes)
     return bytes <= (size_t)kLdsBytes;
 }
 
+namespace {
+
+// What hscnmf_compute and hscnmf_learn share: the chunk of Bc signals the memory budget allows, its device buffers
+// (allocated per call; the destructor frees them after a stream sync), the per-chunk upload and download around the
+// iterations, and the timings summed over chunks (timing_ms of include/hscnmf.h).
+template <typename T>
+struct Chunks {
+    hscnmf_ctx* ctx;
+    int Tn, F, K, W, L, ntt;
+    size_t dsz;                       // D values per signal when every signal has a D of its own (learn), else 0
+    int Bc = 0;
+    T *dA[2] = {nullptr, nullptr}, *dX = nullptr, *dR = nullptr, *dD = nullptr, *dPD = nullptr;
+    double *dPart = nullptr, *dEn = nullptr, *dSnr = nullptr, *dRs = nullptr;
+    int *dDone = nullptr, *dIt = nullptr, *dStop = nullptr;
+    std::vector<int> hdone;
+    double tm[5] = {0, 0, 0, 0, 0};
+
+    Chunks(hscnmf_ctx* c, int Tn_, int F_, int K_, int W_, size_t dsz_)
+        : ctx(c), Tn(Tn_), F(F_), K(K_), W(W_), L(Tn_ - W_ + 1), ntt((Tn_ + kRows - 1) / kRows), dsz(dsz_) {}
+
+    ~Chunks()
+    {
+        (void)hipStreamSynchronize(ctx->stream);
+        void* ptrs[] = {dA[0], dA[1], dX, dR, dD, dPD, dPart, dEn, dSnr, dRs, dDone, dIt, dStop};
+        for (void* q : ptrs) if (q) (void)hipFree(q);
+    }
+
+    // chunk size and buffers: per signal the A pair, X, R, the stop state and (learn) its D and psz partial values
+    int alloc(const hscnmf_params& p, int B, size_t psz)
+    {
+        HSC_TRY(hipSetDevice(ctx->device));
+        size_t freeb = 0, totalb = 0;
+        HSC_TRY(hipMemGetInfo(&freeb, &totalb));
+        const size_t per = (2 * (size_t)L * K + 2 * (size_t)Tn * F + dsz + psz) * sizeof(T) + (size_t)ntt * 2 * sizeof(double) +
+                           3 * sizeof(double) + 3 * sizeof(int);
+        const size_t budget = p.memory_budget ? (size_t)p.memory_budget : freeb / 10 * 6;
+        Bc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)B, budget / per, (size_t)65535}));
+        HSC_TRY(hipMalloc(&dA[0], (size_t)Bc * L * K * sizeof(T)));
+        HSC_TRY(hipMalloc(&dA[1], (size_t)Bc * L * K * sizeof(T)));
+        HSC_TRY(hipMalloc(&dX, (size_t)Bc * Tn * F * sizeof(T)));
+        HSC_TRY(hipMalloc(&dR, (size_t)Bc * Tn * F * sizeof(T)));
+        HSC_TRY(hipMalloc(&dD, (dsz ? (size_t)Bc * dsz : (size_t)K * W * F) * sizeof(T)));
+        if (psz) HSC_TRY(hipMalloc(&dPD, (size_t)Bc * psz * sizeof(T)));
+        HSC_TRY(hipMalloc(&dPart, (size_t)Bc * ntt * 2 * sizeof(double)));
+        HSC_TRY(hipMalloc(&dEn, (size_t)Bc * sizeof(double)));
+        HSC_TRY(hipMalloc(&dSnr, (size_t)Bc * sizeof(double)));
+        HSC_TRY(hipMalloc(&dRs, (size_t)Bc * sizeof(double)));
+        HSC_TRY(hipMalloc(&dDone, (size_t)Bc * sizeof(int)));
+        HSC_TRY(hipMalloc(&dIt, (size_t)Bc * sizeof(int)));
+        HSC_TRY(hipMalloc(&dStop, (size_t)Bc * sizeof(int)));
+        hdone.resize(Bc);
+        return hsc::OK;
+    }
+
+    // signals c0 .. c0 + nb - 1 between events 0 and 1: X, rows 0 .. L-1 of the initial coefficients, (learn) the
+    // initial dictionaries D_init, the energies; done, iterations and stop zeroed
+    int upload(int c0, int nb, const T* x, const T* a_init, const T* D_init, const double* energy)
+    {
+        hipStream_t st = ctx->stream;
+        HSC_TRY(hipEventRecord(ctx->ev[0], st));
+        HSC_TRY(hipMemcpyAsync(dX, x + (size_t)c0 * Tn * F, (size_t)nb * Tn * F * sizeof(T), hipMemcpyHostToDevice, st));
+        HSC_TRY(hipMemcpy2DAsync(dA[0], (size_t)L * K * sizeof(T), a_init + (size_t)c0 * Tn * K, (size_t)Tn * K * sizeof(T),
+                                 (size_t)L * K * sizeof(T), nb, hipMemcpyHostToDevice, st));
+        if (dsz) HSC_TRY(hipMemcpyAsync(dD, D_init + (size_t)c0 * dsz, (size_t)nb * dsz * sizeof(T), hipMemcpyHostToDevice, st));
+        HSC_TRY(hipMemcpyAsync(dEn, energy + c0, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, st));
+        HSC_TRY(hipMemsetAsync(dDone, 0, (size_t)nb * sizeof(int), st));
+        HSC_TRY(hipMemsetAsync(dIt, 0, (size_t)nb * sizeof(int), st));
+        HSC_TRY(hipMemsetAsync(dStop, 0, (size_t)nb * sizeof(int), st));
+        HSC_TRY(hipEventRecord(ctx->ev[1], st));
+        return hsc::OK;
+    }
+
+    // after iteration `it`: 1 when every signal of the chunk has stopped, else 0 (or a negative status).  The flags are
+    // read once per iteration, only with a tolerance and another iteration to go.
+    int all_stopped(const hscnmf_params& p, int it, int nb)
+    {
+        if (!(p.has_residual_scale || p.has_snr) || it + 1 >= p.max_iterations) return 0;
+        HSC_TRY(hipMemcpyAsync(hdone.data(), dDone, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HSC_TRY(hipStreamSynchronize(ctx->stream));
+        return std::all_of(hdone.begin(), hdone.begin() + nb, [](int v) { return v != 0; }) ? 1 : 0;
+    }
+
+    // event 2 (the iterations end), then the chunk's iterations, stop reasons, SNR and residual scales
+    int download_stats(int c0, int nb, int32_t* iters, int32_t* stop, double* snr, double* rscale)
+    {
+        hipStream_t st = ctx->stream;
+        HSC_TRY(hipEventRecord(ctx->ev[2], st));
+        HSC_TRY(hipMemcpyAsync(iters + c0, dIt, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
+        HSC_TRY(hipMemcpyAsync(stop + c0, dStop, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
+        HSC_TRY(hipMemcpyAsync(snr + c0, dSnr, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st));
+        HSC_TRY(hipMemcpyAsync(rscale + c0, dRs, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st));
+        return hsc::OK;
+    }
+
+    // once event 3 has completed: the chunk's upload, iteration and download times and the `it` iterations it ran
+    int add_times(int it)
+    {
+        if (int rc = hsc::add_times(ctx, 3, tm)) return rc;
+        tm[3] += 1;
+        tm[4] += it;
+        return hsc::OK;
+    }
+};
+
+// the first signal of c0 .. c0 + nb - 1 without a result (its iteration count outside [1, it]), or -1
+int no_result(const int32_t* iters, int c0, int nb, int it)
+{
+    for (int b = c0; b < c0 + nb; ++b)
+        if (iters[b] < 1 || iters[b] > it) return b;
+    return -1;
+}
+
+}  // namespace
+
 template <typename T>
 static int compute_t(hscnmf_ctx* ctx, const T* x, int B, int Tn, int F, const T* D, int K, int W, const T* a_init,
                      const double* energy, const hscnmf_params& p, T* coef, T* resid, int32_t* iters, int32_t* stop,
                      double* snr, double* rscale, double* timing)
 {
-    int rc = HSCNMF_OK;
     const int L = Tn - W + 1, ntl = (L + kRows - 1) / kRows, ntt = (Tn + kRows - 1) / kRows, off = (W - 1) / 2;
-    const bool need_flags = p.has_residual_scale || p.has_snr;
     int PR = 0, slab = 0;
     size_t lds = 0;
-    T *dA[2] = {nullptr, nullptr}, *dX = nullptr, *dR = nullptr, *dD = nullptr;
-    double *dPart = nullptr, *dEn = nullptr, *dSnr = nullptr, *dRs = nullptr;
-    int *dDone = nullptr, *dIt = nullptr, *dStop = nullptr;
-    size_t freeb = 0, totalb = 0, per = 0, budget = 0;
-    int Bc = 0;
-    std::vector<int> hdone;
-    double tm[5] = {0, 0, 0, 0, 0};
     if (!lds_plan<T>(W, F, PR, slab, lds))
         return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_compute: W = %d, F = %d needs more than %d bytes of LDS per workgroup",
                     W, F, kLdsBytes);
-    NMF_TRY(hipSetDevice(ctx->device));
-    NMF_TRY(hipMemGetInfo(&freeb, &totalb));
-    per = (2 * (size_t)L * K + 2 * (size_t)Tn * F) * sizeof(T) + (size_t)ntt * 2 * sizeof(double) + 3 * sizeof(double) + 3 * sizeof(int);
-    budget = p.memory_budget ? (size_t)p.memory_budget : freeb / 10 * 6;
-    Bc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)B, budget / per, (size_t)65535}));
-    NMF_TRY(hipMalloc(&dA[0], (size_t)Bc * L * K * sizeof(T)));
-    NMF_TRY(hipMalloc(&dA[1], (size_t)Bc * L * K * sizeof(T)));
-    NMF_TRY(hipMalloc(&dX, (size_t)Bc * Tn * F * sizeof(T)));
-    NMF_TRY(hipMalloc(&dR, (size_t)Bc * Tn * F * sizeof(T)));
-    NMF_TRY(hipMalloc(&dD, (size_t)K * W * F * sizeof(T)));
-    NMF_TRY(hipMalloc(&dPart, (size_t)Bc * ntt * 2 * sizeof(double)));
-    NMF_TRY(hipMalloc(&dEn, (size_t)Bc * sizeof(double)));
-    NMF_TRY(hipMalloc(&dSnr, (size_t)Bc * sizeof(double)));
-    NMF_TRY(hipMalloc(&dRs, (size_t)Bc * sizeof(double)));
-    NMF_TRY(hipMalloc(&dDone, (size_t)Bc * sizeof(int)));
-    NMF_TRY(hipMalloc(&dIt, (size_t)Bc * sizeof(int)));
-    NMF_TRY(hipMalloc(&dStop, (size_t)Bc * sizeof(int)));
-    NMF_TRY(hipMemcpyAsync(dD, D, (size_t)K * W * F * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    hdone.resize(Bc);
-    for (int c0 = 0; c0 < B; c0 += Bc) {
-        const int nb = std::min(Bc, B - c0);
-        NMF_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
-        NMF_TRY(hipMemcpyAsync(dX, x + (size_t)c0 * Tn * F, (size_t)nb * Tn * F * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-        NMF_TRY(hipMemcpy2DAsync(dA[0], (size_t)L * K * sizeof(T), a_init + (size_t)c0 * Tn * K, (size_t)Tn * K * sizeof(T),
-                                 (size_t)L * K * sizeof(T), nb, hipMemcpyHostToDevice, ctx->stream));
-        NMF_TRY(hipMemcpyAsync(dEn, energy + c0, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        NMF_TRY(hipMemsetAsync(dDone, 0, (size_t)nb * sizeof(int), ctx->stream));
-        NMF_TRY(hipMemsetAsync(dIt, 0, (size_t)nb * sizeof(int), ctx->stream));
-        NMF_TRY(hipMemsetAsync(dStop, 0, (size_t)nb * sizeof(int), ctx->stream));
-        NMF_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+    Chunks<T> c(ctx, Tn, F, K, W, 0);
+    if (int rc = c.alloc(p, B, 0)) return rc;
+    HSC_TRY(hipMemcpyAsync(c.dD, D, (size_t)K * W * F * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    for (int c0 = 0; c0 < B; c0 += c.Bc) {
+        const int nb = std::min(c.Bc, B - c0);
+        if (int rc = c.upload(c0, nb, x, a_init, nullptr, energy)) return rc;
         int it = 0;
         for (; it < p.max_iterations; ++it) {
             for (int t = 0; t < W; ++t) {
                 const int g = it * W + t;
-                hipLaunchKernelGGL(nmf_step_kernel<T>, dim3(ntl, nb), dim3(kThreads), lds, ctx->stream, dA[g & 1],
-                                   dA[(g + 1) & 1], dX, dD, (size_t)0, dDone, L, Tn, K, W, F, t, PR, slab);
+                hipLaunchKernelGGL(nmf_step_kernel<T>, dim3(ntl, nb), dim3(kThreads), lds, ctx->stream, c.dA[g & 1],
+                                   c.dA[(g + 1) & 1], c.dX, c.dD, (size_t)0, c.dDone, L, Tn, K, W, F, t, PR, slab);
             }
             hipLaunchKernelGGL(nmf_residual_kernel<T>, dim3(ntt, nb), dim3(kThreads), lds, ctx->stream,
-                               dA[((it + 1) * W) & 1], dX, dD, (size_t)0, dDone, dR, dPart, L, Tn, K, W, F, PR, slab);
-            hipLaunchKernelGGL(nmf_decide_kernel, dim3(nb), dim3(64), 0, ctx->stream, dPart, ntt, dEn, dDone, dIt, dStop, dSnr,
-                               dRs, it + 1, p);
-            NMF_TRY(hipGetLastError());
-            if (need_flags && it + 1 < p.max_iterations) {       // one read of the flags per iteration, only with tolerances
-                NMF_TRY(hipMemcpyAsync(hdone.data(), dDone, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-                NMF_TRY(hipStreamSynchronize(ctx->stream));
-                if (std::all_of(hdone.begin(), hdone.begin() + nb, [](int v) { return v != 0; })) { ++it; break; }
-            }
+                               c.dA[((it + 1) * W) & 1], c.dX, c.dD, (size_t)0, c.dDone, c.dR, c.dPart, L, Tn, K, W, F, PR, slab);
+            hipLaunchKernelGGL(nmf_decide_kernel, dim3(nb), dim3(64), 0, ctx->stream, c.dPart, ntt, c.dEn, c.dDone, c.dIt,
+                               c.dStop, c.dSnr, c.dRs, it + 1, p);
+            HSC_TRY(hipGetLastError());
+            const int stopped = c.all_stopped(p, it, nb);
+            if (stopped < 0) return stopped;
+            if (stopped) { ++it; break; }
         }
-        NMF_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
-        NMF_TRY(hipMemcpyAsync(iters + c0, dIt, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        NMF_TRY(hipMemcpyAsync(stop + c0, dStop, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        NMF_TRY(hipMemcpyAsync(snr + c0, dSnr, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        NMF_TRY(hipMemcpyAsync(rscale + c0, dRs, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        NMF_TRY(hipMemcpyAsync(resid + (size_t)c0 * Tn * F, dR, (size_t)nb * Tn * F * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        NMF_TRY(hipStreamSynchronize(ctx->stream));
+        if (int rc = c.download_stats(c0, nb, iters, stop, snr, rscale)) return rc;
+        HSC_TRY(hipMemcpyAsync(resid + (size_t)c0 * Tn * F, c.dR, (size_t)nb * Tn * F * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+        HSC_TRY(hipStreamSynchronize(ctx->stream));
+        const int bad = no_result(iters, c0, nb, it);
+        if (bad >= 0) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_compute: signal %d has no result", bad);
         for (int b = 0; b < nb; ++b) {
             // a signal that stopped after n iterations holds its coefficients in buffer (n * W) mod 2
             const int n = iters[c0 + b];
-            if (n < 1 || n > it) { rc = fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_compute: signal %d has no result", c0 + b); goto done; }
             T* dst = coef + (size_t)(c0 + b) * Tn * K;
             std::memset(dst, 0, (size_t)off * K * sizeof(T));
             std::memset(dst + (size_t)(off + L) * K, 0, (size_t)(Tn - off - L) * K * sizeof(T));
-            NMF_TRY(hipMemcpyAsync(dst + (size_t)off * K, dA[((size_t)n * W) & 1] + (size_t)b * L * K, (size_t)L * K * sizeof(T),
+            HSC_TRY(hipMemcpyAsync(dst + (size_t)off * K, c.dA[((size_t)n * W) & 1] + (size_t)b * L * K, (size_t)L * K * sizeof(T),
                                    hipMemcpyDeviceToHost, ctx->stream));
         }
-        NMF_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-        NMF_TRY(hipStreamSynchronize(ctx->stream));
-        float ms[3] = {0, 0, 0};
-        for (int i = 0; i < 3; ++i) NMF_TRY(hipEventElapsedTime(&ms[i], ctx->ev[i], ctx->ev[i + 1]));
-        tm[0] += ms[0];
-        tm[1] += ms[1];
-        tm[2] += ms[2];
-        tm[3] += 1;
-        tm[4] += it;
+        HSC_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
+        HSC_TRY(hipStreamSynchronize(ctx->stream));
+        if (int rc = c.add_times(it)) return rc;
     }
-    if (timing) std::memcpy(timing, tm, sizeof(tm));
-done:
-    (void)hipStreamSynchronize(ctx->stream);
-    void* ptrs[] = {dA[0], dA[1], dX, dR, dD, dPart, dEn, dSnr, dRs, dDone, dIt, dStop};
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    return rc;
+    if (timing) std::memcpy(timing, c.tm, sizeof(c.tm));
+    return HSCNMF_OK;
 }
 
 extern "C" int hscnmf_compute(hscnmf_ctx* ctx, int dtype, const void* x, int B, int T, int F, const void* D, int K, int W,
@@ -612,107 +630,52 @@ static int learn_t(hscnmf_ctx* ctx, const T* x, int B, int Tn, int F, const T* D
                    const double* energy, const hscnmf_params& p, T* D_out, int32_t* iters, int32_t* stop, double* snr,
                    double* rscale, double* timing)
 {
-    int rc = HSCNMF_OK;
     const int L = Tn - W + 1, ntl = (L + kRows - 1) / kRows, ntt = (Tn + kRows - 1) / kRows, NW = W * F;
     const size_t dsz = (size_t)K * NW, psz = (size_t)ntl * K * (NW + 1);
-    const bool need_flags = p.has_residual_scale || p.has_snr;
     const size_t lds_part = (size_t)(kRows + W - 1) * F * sizeof(T), lds_upd = (size_t)(kThreads + NW + 1) * sizeof(T);
     int PR = 0, slab = 0;
     size_t lds = 0;
-    T *dA[2] = {nullptr, nullptr}, *dX = nullptr, *dR = nullptr, *dD = nullptr, *dPD = nullptr;
-    double *dPart = nullptr, *dEn = nullptr, *dSnr = nullptr, *dRs = nullptr;
-    int *dDone = nullptr, *dIt = nullptr, *dStop = nullptr;
-    size_t freeb = 0, totalb = 0, per = 0, budget = 0;
-    int Bc = 0;
-    std::vector<int> hdone;
-    double tm[5] = {0, 0, 0, 0, 0};
     if (!lds_plan<T>(W, F, PR, slab, lds) || lds_part > (size_t)kLdsBytes || lds_upd > (size_t)kLdsBytes)
         return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_learn: W = %d, F = %d needs more than %d bytes of LDS per workgroup",
                     W, F, kLdsBytes);
-    NMF_TRY(hipSetDevice(ctx->device));
-    NMF_TRY(hipMemGetInfo(&freeb, &totalb));
-    per = (2 * (size_t)L * K + 2 * (size_t)Tn * F + dsz + psz) * sizeof(T) + (size_t)ntt * 2 * sizeof(double) +
-          3 * sizeof(double) + 3 * sizeof(int);
-    budget = p.memory_budget ? (size_t)p.memory_budget : freeb / 10 * 6;
-    Bc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)B, budget / per, (size_t)65535}));
-    NMF_TRY(hipMalloc(&dA[0], (size_t)Bc * L * K * sizeof(T)));
-    NMF_TRY(hipMalloc(&dA[1], (size_t)Bc * L * K * sizeof(T)));
-    NMF_TRY(hipMalloc(&dX, (size_t)Bc * Tn * F * sizeof(T)));
-    NMF_TRY(hipMalloc(&dR, (size_t)Bc * Tn * F * sizeof(T)));
-    NMF_TRY(hipMalloc(&dD, (size_t)Bc * dsz * sizeof(T)));
-    NMF_TRY(hipMalloc(&dPD, (size_t)Bc * psz * sizeof(T)));
-    NMF_TRY(hipMalloc(&dPart, (size_t)Bc * ntt * 2 * sizeof(double)));
-    NMF_TRY(hipMalloc(&dEn, (size_t)Bc * sizeof(double)));
-    NMF_TRY(hipMalloc(&dSnr, (size_t)Bc * sizeof(double)));
-    NMF_TRY(hipMalloc(&dRs, (size_t)Bc * sizeof(double)));
-    NMF_TRY(hipMalloc(&dDone, (size_t)Bc * sizeof(int)));
-    NMF_TRY(hipMalloc(&dIt, (size_t)Bc * sizeof(int)));
-    NMF_TRY(hipMalloc(&dStop, (size_t)Bc * sizeof(int)));
-    hdone.resize(Bc);
-    for (int c0 = 0; c0 < B; c0 += Bc) {
-        const int nb = std::min(Bc, B - c0);
-        NMF_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
-        NMF_TRY(hipMemcpyAsync(dX, x + (size_t)c0 * Tn * F, (size_t)nb * Tn * F * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-        NMF_TRY(hipMemcpy2DAsync(dA[0], (size_t)L * K * sizeof(T), a_init + (size_t)c0 * Tn * K, (size_t)Tn * K * sizeof(T),
-                                 (size_t)L * K * sizeof(T), nb, hipMemcpyHostToDevice, ctx->stream));
-        NMF_TRY(hipMemcpyAsync(dD, D_init + (size_t)c0 * dsz, (size_t)nb * dsz * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-        NMF_TRY(hipMemcpyAsync(dEn, energy + c0, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        NMF_TRY(hipMemsetAsync(dDone, 0, (size_t)nb * sizeof(int), ctx->stream));
-        NMF_TRY(hipMemsetAsync(dIt, 0, (size_t)nb * sizeof(int), ctx->stream));
-        NMF_TRY(hipMemsetAsync(dStop, 0, (size_t)nb * sizeof(int), ctx->stream));
-        NMF_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+    Chunks<T> c(ctx, Tn, F, K, W, dsz);
+    if (int rc = c.alloc(p, B, psz)) return rc;
+    for (int c0 = 0; c0 < B; c0 += c.Bc) {
+        const int nb = std::min(c.Bc, B - c0);
+        if (int rc = c.upload(c0, nb, x, a_init, D_init, energy)) return rc;
         int it = 0;
         for (; it < p.max_iterations; ++it) {
             for (int t = 0; t < W; ++t) {
                 const int g = it * W + t;
-                hipLaunchKernelGGL(nmf_step_kernel<T>, dim3(ntl, nb), dim3(kThreads), lds, ctx->stream, dA[g & 1],
-                                   dA[(g + 1) & 1], dX, dD, dsz, dDone, L, Tn, K, W, F, t, PR, slab);
+                hipLaunchKernelGGL(nmf_step_kernel<T>, dim3(ntl, nb), dim3(kThreads), lds, ctx->stream, c.dA[g & 1],
+                                   c.dA[(g + 1) & 1], c.dX, c.dD, dsz, c.dDone, L, Tn, K, W, F, t, PR, slab);
             }
-            const T* dAn = dA[((it + 1) * W) & 1];
-            hipLaunchKernelGGL(nmf_ratio_kernel<T>, dim3(ntt, nb), dim3(kThreads), lds, ctx->stream, dAn, dX, dD, dsz, dDone,
-                               dR, L, Tn, K, W, F, PR, slab);
-            hipLaunchKernelGGL(nmf_dpart_kernel<T>, dim3(ntl, nb), dim3(kThreads), lds_part, ctx->stream, dAn, dR, dDone,
-                               dPD, L, Tn, K, W, F);
-            hipLaunchKernelGGL(nmf_dupdate_kernel<T>, dim3(K, nb), dim3(kThreads), lds_upd, ctx->stream, dPD, ntl, dDone, dD,
-                               K, NW);
-            hipLaunchKernelGGL(nmf_residual_kernel<T>, dim3(ntt, nb), dim3(kThreads), lds, ctx->stream, dAn, dX, dD, dsz,
-                               dDone, dR, dPart, L, Tn, K, W, F, PR, slab);
-            hipLaunchKernelGGL(nmf_decide_kernel, dim3(nb), dim3(64), 0, ctx->stream, dPart, ntt, dEn, dDone, dIt, dStop, dSnr,
-                               dRs, it + 1, p);
-            NMF_TRY(hipGetLastError());
-            if (need_flags && it + 1 < p.max_iterations) {       // one read of the flags per iteration, only with tolerances
-                NMF_TRY(hipMemcpyAsync(hdone.data(), dDone, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-                NMF_TRY(hipStreamSynchronize(ctx->stream));
-                if (std::all_of(hdone.begin(), hdone.begin() + nb, [](int v) { return v != 0; })) { ++it; break; }
-            }
+            const T* dAn = c.dA[((it + 1) * W) & 1];
+            hipLaunchKernelGGL(nmf_ratio_kernel<T>, dim3(ntt, nb), dim3(kThreads), lds, ctx->stream, dAn, c.dX, c.dD, dsz,
+                               c.dDone, c.dR, L, Tn, K, W, F, PR, slab);
+            hipLaunchKernelGGL(nmf_dpart_kernel<T>, dim3(ntl, nb), dim3(kThreads), lds_part, ctx->stream, dAn, c.dR, c.dDone,
+                               c.dPD, L, Tn, K, W, F);
+            hipLaunchKernelGGL(nmf_dupdate_kernel<T>, dim3(K, nb), dim3(kThreads), lds_upd, ctx->stream, c.dPD, ntl, c.dDone,
+                               c.dD, K, NW);
+            hipLaunchKernelGGL(nmf_residual_kernel<T>, dim3(ntt, nb), dim3(kThreads), lds, ctx->stream, dAn, c.dX, c.dD, dsz,
+                               c.dDone, c.dR, c.dPart, L, Tn, K, W, F, PR, slab);
+            hipLaunchKernelGGL(nmf_decide_kernel, dim3(nb), dim3(64), 0, ctx->stream, c.dPart, ntt, c.dEn, c.dDone, c.dIt,
+                               c.dStop, c.dSnr, c.dRs, it + 1, p);
+            HSC_TRY(hipGetLastError());
+            const int stopped = c.all_stopped(p, it, nb);
+            if (stopped < 0) return stopped;
+            if (stopped) { ++it; break; }
         }
-        NMF_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
-        NMF_TRY(hipMemcpyAsync(iters + c0, dIt, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        NMF_TRY(hipMemcpyAsync(stop + c0, dStop, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        NMF_TRY(hipMemcpyAsync(snr + c0, dSnr, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        NMF_TRY(hipMemcpyAsync(rscale + c0, dRs, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        NMF_TRY(hipMemcpyAsync(D_out + (size_t)c0 * dsz, dD, (size_t)nb * dsz * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        NMF_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-        NMF_TRY(hipStreamSynchronize(ctx->stream));
-        for (int b = 0; b < nb; ++b)
-            if (iters[c0 + b] < 1 || iters[c0 + b] > it) {
-                rc = fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: learner %d has no result", c0 + b);
-                goto done;
-            }
-        float ms[3] = {0, 0, 0};
-        for (int i = 0; i < 3; ++i) NMF_TRY(hipEventElapsedTime(&ms[i], ctx->ev[i], ctx->ev[i + 1]));
-        tm[0] += ms[0];
-        tm[1] += ms[1];
-        tm[2] += ms[2];
-        tm[3] += 1;
-        tm[4] += it;
+        if (int rc = c.download_stats(c0, nb, iters, stop, snr, rscale)) return rc;
+        HSC_TRY(hipMemcpyAsync(D_out + (size_t)c0 * dsz, c.dD, (size_t)nb * dsz * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+        HSC_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
+        HSC_TRY(hipStreamSynchronize(ctx->stream));
+        const int bad = no_result(iters, c0, nb, it);
+        if (bad >= 0) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: learner %d has no result", bad);
+        if (int rc = c.add_times(it)) return rc;
     }
-    if (timing) std::memcpy(timing, tm, sizeof(tm));
-done:
-    (void)hipStreamSynchronize(ctx->stream);
-    void* ptrs[] = {dA[0], dA[1], dX, dR, dD, dPD, dPart, dEn, dSnr, dRs, dDone, dIt, dStop};
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    return rc;
+    if (timing) std::memcpy(timing, c.tm, sizeof(c.tm));
+    return HSCNMF_OK;
 }
 
 extern "C" int hscnmf_learn(hscnmf_ctx* ctx, int dtype, const void* x, int B, int T, int F, const void* D_init, int K, int W,

@@ -42,52 +42,23 @@ _lib = None
 def load_library():
     """Load libhsckmeans.so; raises (never falls back) when it is missing."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.isfile(LIB_PATH):
-        raise _native.HscmpError('libhsckmeans.so is not built (%s). Run `python __graft_entry__.py build` '
-                                 '(hipcc --offload-arch=gfx950). There is no CPU fallback.' % LIB_PATH)
-    lib = ctypes.CDLL(LIB_PATH)
-    vp, ci = ctypes.c_void_p, ctypes.c_int
-    lib.hsckmeans_version.restype = ci
-    lib.hsckmeans_create.argtypes = [ctypes.POINTER(vp), ci]
-    lib.hsckmeans_create.restype = ci
-    lib.hsckmeans_destroy.argtypes = [vp]
-    lib.hsckmeans_destroy.restype = None
-    lib.hsckmeans_last_error.argtypes = [vp]
-    lib.hsckmeans_last_error.restype = ctypes.c_char_p
-    lib.hsckmeans_set_data.argtypes = [vp, vp, ci, ci, ci, ci, vp, ci, ci]
-    lib.hsckmeans_set_data.restype = ci
-    lib.hsckmeans_step.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
-    lib.hsckmeans_step.restype = ci
-    _lib = lib
-    return lib
+    if _lib is None:
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        _lib = _native.load_satellite(LIB_PATH, 'hsckmeans', {'hsckmeans_set_data': [vp, vp, ci, ci, ci, ci, vp, ci, ci],
+                                                              'hsckmeans_step': [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]})
+    return _lib
 
 
-class _Context(object):
+class _Context(_native.LibraryContext):
     def __init__(self, device):
-        self._lib = load_library()
-        h = ctypes.c_void_p()
-        rc = self._lib.hsckmeans_create(ctypes.byref(h), int(device))
-        if rc != 0:
-            ex = _native.HscmpError('hsckmeans_create failed (%d): %s' % (rc, self._lib.hsckmeans_last_error(None).decode()))
-            ex.code = int(rc)
-            raise ex
-        self._h = h
-
-    def _check(self, rc, what):
-        if rc != 0:
-            ex = _native.HscmpError('%s failed (%d): %s' % (what, rc, self._lib.hsckmeans_last_error(self._h).decode()))
-            ex.code = int(rc)
-            raise ex
+        super(_Context, self).__init__(load_library(), 'hsckmeans', device)
 
     def set_data(self, x, starts, W):
         """x [B,T,F] float32/float64 C order, starts [B,N] int64."""
         B, T, F = x.shape
         N = starts.shape[1]
         self.B, self.N, self.W, self.F, self.dtype = B, N, W, F, x.dtype
-        self._check(self._lib.hsckmeans_set_data(self._h, _native._ptr(x), F32 if x.dtype == np.float32 else F64, B, T, F,
-                                                 _native._ptr(starts), N, W), 'hsckmeans_set_data')
+        self.call('set_data', _native._ptr(x), F32 if x.dtype == np.float32 else F64, B, T, F, _native._ptr(starts), N, W)
 
     def step(self, D, mode):
         """D [B,K,W,F] float64, mode [B] int32.  Returns t, k [B,N], count, nonzero [B,K], sums [B,K,W*F], timing [4]."""
@@ -99,14 +70,8 @@ class _Context(object):
         sums = np.zeros((B, K, self.W * self.F), dtype=self.dtype)
         timing = np.zeros((TIMES,), dtype=np.float64)
         p = _native._ptr
-        self._check(self._lib.hsckmeans_step(self._h, p(D), K, p(mode), p(t), p(k), p(count), p(nonzero), p(sums), p(timing)),
-                    'hsckmeans_step')
+        self.call('step', p(D), K, p(mode), p(t), p(k), p(count), p(nonzero), p(sums), p(timing))
         return t, k, count, nonzero, sums, timing
-
-    def __del__(self):
-        if getattr(self, '_h', None):
-            self._lib.hsckmeans_destroy(self._h)
-            self._h = None
 
 
 _contexts = {}

@@ -42,41 +42,10 @@ _lib = None
 def load_library():
     """Load libhscksvd.so; raises (never falls back) when it is missing."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.isfile(LIB_PATH):
-        raise _native.HscmpError('libhscksvd.so is not built (%s). Run `python __graft_entry__.py build` '
-                                 '(hipcc --offload-arch=gfx950). There is no CPU fallback.' % LIB_PATH)
-    lib = ctypes.CDLL(LIB_PATH)
-    vp, ci = ctypes.c_void_p, ctypes.c_int
-    lib.hscksvd_version.restype = ci
-    lib.hscksvd_create.argtypes = [ctypes.POINTER(vp), ci]
-    lib.hscksvd_create.restype = ci
-    lib.hscksvd_destroy.argtypes = [vp]
-    lib.hscksvd_destroy.restype = None
-    lib.hscksvd_last_error.argtypes = [vp]
-    lib.hscksvd_last_error.restype = ctypes.c_char_p
-    lib.hscksvd_update.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp]
-    lib.hscksvd_update.restype = ci
-    _lib = lib
-    return lib
-
-
-class _Context(object):
-    def __init__(self, device):
-        self._lib = load_library()
-        h = ctypes.c_void_p()
-        rc = self._lib.hscksvd_create(ctypes.byref(h), int(device))
-        if rc != 0:
-            ex = _native.HscmpError('hscksvd_create failed (%d): %s' % (rc, self._lib.hscksvd_last_error(None).decode()))
-            ex.code = int(rc)
-            raise ex
-        self._h = h
-
-    def __del__(self):
-        if getattr(self, '_h', None):
-            self._lib.hscksvd_destroy(self._h)
-            self._h = None
+    if _lib is None:
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        _lib = _native.load_satellite(LIB_PATH, 'hscksvd', {'hscksvd_update': [vp, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp]})
+    return _lib
 
 
 _contexts = {}
@@ -84,7 +53,7 @@ _contexts = {}
 
 def _context(device):
     if device not in _contexts:
-        _contexts[device] = _Context(device)
+        _contexts[device] = _native.LibraryContext(load_library(), 'hscksvd', device)
     return _contexts[device]
 
 
@@ -123,12 +92,7 @@ def update(D, coefficients, usePCA=False, device=0):
     timing = np.zeros((3,), dtype=np.float64)
     ctx = _context(device)
     p = _native._ptr
-    rc = ctx._lib.hscksvd_update(ctx._h, T, K, W, F, p(D3), p(indptr), p(indices), p(data), 1 if usePCA else 0,
-                                 p(stats), p(timing))
-    if rc != 0:
-        ex = _native.HscmpError('hscksvd_update failed (%d): %s' % (rc, ctx._lib.hscksvd_last_error(ctx._h).decode()))
-        ex.code = int(rc)
-        raise ex
+    ctx.call('update', T, K, W, F, p(D3), p(indptr), p(indices), p(data), 1 if usePCA else 0, p(stats), p(timing))
     out = scipy.sparse.csc_matrix((data, indices, indptr), shape=csc.shape)
     return D3.reshape(D.shape), out, stats, timing
 

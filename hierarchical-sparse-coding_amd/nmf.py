@@ -42,45 +42,11 @@ _lib = None
 def load_library():
     """Load libhscnmf.so; raises (never falls back) when it is missing."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.isfile(LIB_PATH):
-        raise _native.HscmpError('libhscnmf.so is not built (%s). Run `python __graft_entry__.py build` '
-                                 '(hipcc --offload-arch=gfx950). There is no CPU fallback.' % LIB_PATH)
-    lib = ctypes.CDLL(LIB_PATH)
-    vp, ci = ctypes.c_void_p, ctypes.c_int
-    lib.hscnmf_version.restype = ci
-    lib.hscnmf_create.argtypes = [ctypes.POINTER(vp), ci]
-    lib.hscnmf_create.restype = ci
-    lib.hscnmf_destroy.argtypes = [vp]
-    lib.hscnmf_destroy.restype = None
-    lib.hscnmf_last_error.argtypes = [vp]
-    lib.hscnmf_last_error.restype = ctypes.c_char_p
-    lib.hscnmf_compute.argtypes = [vp, ci, vp, ci, ci, ci, vp, ci, ci, vp, vp, ctypes.POINTER(HscnmfParams),
-                                   vp, vp, vp, vp, vp, vp, vp]
-    lib.hscnmf_compute.restype = ci
-    lib.hscnmf_learn.argtypes = [vp, ci, vp, ci, ci, ci, vp, ci, ci, vp, vp, ctypes.POINTER(HscnmfParams),
-                                 vp, vp, vp, vp, vp, vp]
-    lib.hscnmf_learn.restype = ci
-    _lib = lib
-    return lib
-
-
-class _Context(object):
-    def __init__(self, device):
-        self._lib = load_library()
-        h = ctypes.c_void_p()
-        rc = self._lib.hscnmf_create(ctypes.byref(h), int(device))
-        if rc != 0:
-            ex = _native.HscmpError('hscnmf_create failed (%d): %s' % (rc, self._lib.hscnmf_last_error(None).decode()))
-            ex.code = int(rc)
-            raise ex
-        self._h = h
-
-    def __del__(self):
-        if getattr(self, '_h', None):
-            self._lib.hscnmf_destroy(self._h)
-            self._h = None
+    if _lib is None:
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        head = [vp, ci, vp, ci, ci, ci, vp, ci, ci, vp, vp, ctypes.POINTER(HscnmfParams)]
+        _lib = _native.load_satellite(LIB_PATH, 'hscnmf', {'hscnmf_compute': head + [vp] * 7, 'hscnmf_learn': head + [vp] * 6})
+    return _lib
 
 
 _contexts = {}
@@ -88,7 +54,7 @@ _contexts = {}
 
 def _context(device):
     if device not in _contexts:
-        _contexts[device] = _Context(device)
+        _contexts[device] = _native.LibraryContext(load_library(), 'hscnmf', device)
     return _contexts[device]
 
 
@@ -175,12 +141,8 @@ class ConvolutionalNMF(SparseApproximator):
         rscale = np.zeros((B,), dtype=np.float64)
         timing = np.zeros((5,), dtype=np.float64)
         p = _native._ptr
-        rc = ctx._lib.hscnmf_compute(ctx._h, _native.dtype_code(dt), p(x), B, T, F, p(D3), K, W, p(a0), p(energy),
-                                     ctypes.byref(params), p(coef), p(resid), p(iters), p(stop), p(snr), p(rscale), p(timing))
-        if rc != 0:
-            ex = _native.HscmpError('hscnmf_compute failed (%d): %s' % (rc, ctx._lib.hscnmf_last_error(ctx._h).decode()))
-            ex.code = int(rc)
-            raise ex
+        ctx.call('compute', _native.dtype_code(dt), p(x), B, T, F, p(D3), K, W, p(a0), p(energy), ctypes.byref(params), p(coef),
+                 p(resid), p(iters), p(stop), p(snr), p(rscale), p(timing))
         if sequences.ndim == 2 or D.ndim == 2:
             resid = np.squeeze(resid, axis=2)                                                  # modeling.py:744-745
         if np.issubdtype(sequences.dtype, np.floating) and resid.dtype != sequences.dtype:
@@ -214,12 +176,8 @@ def _call_learn(device, dt, x, D0, a0, energy, params):
     rscale = np.zeros((B,), dtype=np.float64)
     timing = np.zeros((5,), dtype=np.float64)
     p = _native._ptr
-    rc = ctx._lib.hscnmf_learn(ctx._h, _native.dtype_code(dt), p(x), B, T, F, p(D0), K, W, p(a0), p(energy),
-                               ctypes.byref(params), p(D), p(iters), p(stop), p(snr), p(rscale), p(timing))
-    if rc != 0:
-        ex = _native.HscmpError('hscnmf_learn failed (%d): %s' % (rc, ctx._lib.hscnmf_last_error(ctx._h).decode()))
-        ex.code = int(rc)
-        raise ex
+    ctx.call('learn', _native.dtype_code(dt), p(x), B, T, F, p(D0), K, W, p(a0), p(energy), ctypes.byref(params), p(D),
+             p(iters), p(stop), p(snr), p(rscale), p(timing))
     return D, NMFStats(iters, stop, snr, rscale, timing)
 
 
