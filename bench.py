@@ -17,14 +17,19 @@ results (hsc_amd.parallel.gather_results: fixed-shape tensors through all_gather
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with:
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step and the configuration with the output
+check of the timed workload.  A plain run does only that: set up, warm up, time the steps, dump the outputs if asked, print.
+With --full it also measures what follows (a plain line has these keys as null, `secondary` not at all):
   roofline      dominant kernel: algorithmic FLOP / its HIP-event duration vs the fp32 MFMA peak; plus the HBM side of
                 SURVEY 8(d): hbm_fraction (PMC bytes/s / 8 TB/s) and table_scan_equiv (what the reference's formulation --
                 re-scan the [T,K] table for every selection -- would need in HBM bandwidth at the measured rate)
   value_incl_transfers   the same encode fed from pinned host memory (H2D of step i+1 under the kernels of step i) with the
                 per-signal results (events, stats, energies) copied back every step
+  gather        N > 1: the gather of the per-signal results over the ranks
   cpu_baseline  the NumPy port of the reference's CPU path (oracle/numpy_port.py) timed AFTER the GPU section in a fresh
                 child process (one worker per host core) on a bounded sample (rank 0, N=1 only)
+  secondary     config 2, N=1: a few steps each of config 2 in float64 and of the hierarchical configurations 4 / 5
+and, in either run,
   dump_outputs  with --dump-outputs DIR: where the arrays of the last timed step went (dump_cmp, bench_hsc.dump_outputs).  The
                 inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
@@ -197,14 +202,17 @@ def main():
                     'nearest shape whose hierarchy is self-consistent; 16 = the literal BASELINE shape, see hsc_amd.synth.make_hierarchy)')
     ap.add_argument('--method', default='cmp', choices=['cmp', 'locomp'], help="configs 4 / 5: method of the hierarchical encoder ('locomp' is the "
                     "reference's default, modeling.py:1429; BASELINE's metric is quoted on the greedy loop, 'cmp')")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-transfers', action='store_true', help='skip the PCIe-inclusive leg')
-    ap.add_argument('--no-secondary', action='store_true', help='config 2 only: skip the bounded runs of the hierarchical configurations (configs 4 / 5)')
+    ap.add_argument('--full', action='store_true', help='after the headline figure, also measure what else the line reports: per-kernel '
+                    'timing and roofline, the PCIe-inclusive leg, the gather over the ranks, the CPU baseline and (config 2) the secondary '
+                    'runs; the --no-* options below trim it')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-transfers', action='store_true', help='--full: skip the PCIe-inclusive leg')
+    ap.add_argument('--no-secondary', action='store_true', help='--full, config 2 only: skip the bounded runs of the float64 and hierarchical configurations')
     ap.add_argument('--secondary-budget-s', type=int, default=150, help='wall-clock budget of that section')
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend: 'nccl' (= RCCL over xGMI) or 'gloo' (rehearsal)")
     ap.add_argument('--cpu-procs', type=int, default=0, help='processes of the CPU baseline (0 = one per usable core, at most 16: the CPU share of one GPU; the port is memory-bound and slows down beyond that)')
     ap.add_argument('--cpu-signals-per-proc', type=int, default=2, help='signals each CPU process encodes (~3-6 s each)')
-    ap.add_argument('--profile-steps', type=int, default=5, help='extra untimed steps used for per-kernel HIP-event timing')
+    ap.add_argument('--profile-steps', type=int, default=5, help='--full: extra untimed steps used for per-kernel HIP-event timing')
     ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write what the last one computed (rank 0\'s '
                     'signals) as DIR/<name>.npy, at most 64 MB in all (larger outputs: a fixed, seeded sample of the signals)')
     ap.add_argument('--cpu-baseline-only', default=None, help=argparse.SUPPRESS)
@@ -320,20 +328,22 @@ def bench_cmp(args, ctx):
     dumped = dump_cmp(args.dump_outputs, eng, stats, energies, r) if args.dump_outputs and rank == 0 else None
     del r
 
-    # ---- per-kernel durations (HIP events on the engine's stream), untimed extra steps
+    # ---- (--full) per-kernel durations (HIP events on the engine's stream), untimed extra steps
     #      in the regime of the timed loop: three encodes queued back to back, the events of the last one read, repeated
-    kms = np.zeros(4, dtype=np.float64)
-    for _ in range(max(1, args.profile_steps)):
-        for _ in range(3):
-            step()
-        stream.synchronize()
-        kms += eng.last_kernel_ms().astype(np.float64)
-    kms /= max(1, args.profile_steps)
+    kms = None
+    if args.full:
+        kms = np.zeros(4, dtype=np.float64)
+        for _ in range(max(1, args.profile_steps)):
+            for _ in range(3):
+                step()
+            stream.synchronize()
+            kms += eng.last_kernel_ms().astype(np.float64)
+        kms /= max(1, args.profile_steps)
 
-    # ---- the same encode fed over PCIe: pinned host buffers, H2D of step i+1 under the kernels of step i, the
+    # ---- (--full) the same encode fed over PCIe: pinned host buffers, H2D of step i+1 under the kernels of step i, the
     #      per-signal results (events in selection order, stats, energies) back to pinned memory every step
     incl = None
-    if not args.no_transfers:
+    if args.full and not args.no_transfers:
         nt = max(4, min(steps, 40))
         x_pin = torch.from_numpy(x_host).pin_memory()
         xd = [torch.empty_like(x), torch.empty_like(x)]
@@ -379,9 +389,9 @@ def bench_cmp(args, ctx):
                 'note': 'pinned host buffers; input H2D of step i+1 overlaps the kernels of step i; events / stats / energies D2H every step; residuals stay on the device'}
     del x_host
 
-    # ---- gather of the per-signal results over the ranks (north_star: "scatter/gather of per-signal results only")
+    # ---- (--full) gather of the per-signal results over the ranks (north_star: "scatter/gather of per-signal results only")
     gather = None
-    if world > 1:
+    if args.full and world > 1:
         t2 = time.perf_counter()
         try:                              # (reported beside the metric, never part of it: a failure here must not cost the line)
             g = parallel.gather_results(eng, device=dev if args.backend == 'nccl' else None)
@@ -395,6 +405,49 @@ def bench_cmp(args, ctx):
     if rank != 0:
         return None
 
+    rate = nsel_total * steps / elapsed_max
+    out = {
+        'metric': 'atom-selections/sec (+ residual-energy match) on 1-D CSC',
+        'value': rate,
+        'unit': 'atom-selections/s',
+        'n_gpus': world, 'steps': steps, 'warmup': warmup,
+        'ms_per_step': 1e3 * elapsed_max / steps,
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': args.dtype, 'data': 'synthetic',
+        'config': {'workload': 'BASELINE configs[1]: single-level CSC, %d signals/GPU x len %d, %d-atom x %d-tap dict, '
+                               'L0=%d, nbBlocks=1, %s signals' % (cfg['B'], cfg['T'], cfg['K'], cfg['W'], cfg['L0'], cfg['kind']),
+                   'signals_per_gpu': cfg['B'], 'T': cfg['T'], 'K': cfg['K'], 'W': cfg['W'], 'L0': cfg['L0'],
+                   'selections_per_step': nsel_total, 'variant': variant,
+                   'stop_reasons': {_native.STOP_NAMES[i]: int(n) for i, n in enumerate(stops) if n},
+                   'output_check': check},
+        'value_incl_transfers': (nsel_total * 1e3 / incl['ms_per_step']) if incl else None,
+        'transfers': incl,
+        'roofline': cmp_roofline(args, cfg, kms, variant, nsel_local, rate, elapsed_max / steps, world) if kms is not None else None,
+        'gather': gather,
+        'cpu_baseline': None,
+    }
+    if check and not all(check.values()):
+        out['config']['output_check']['FAILED'] = True
+    if dumped:
+        out['dump_outputs'] = dumped
+    if world == 1:
+        eng.close()
+        del x
+        torch.cuda.empty_cache()
+    if not args.full:
+        return out
+    # ---- the hierarchical configurations of BASELINE.json at their own sizes, a few steps each (bounded: it must never
+    #      cost the headline line): configs[3] with 17 and with the literal 16 level-1 taps, configs[4] at its per-GPU share
+    if world == 1 and not args.no_secondary:
+        out['secondary'] = run_secondary(args, ctx)
+    if world == 1 and not args.no_cpu_baseline:
+        nproc = args.cpu_procs or min(16, host_cores())
+        out['cpu_baseline'] = run_cpu_baseline(cfg, nproc, args.cpu_signals_per_proc)
+    return out
+
+
+def cmp_roofline(args, cfg, kms, variant, nsel_local, rate, step_s, world):
+    """--full, config 2: the roofline of the dominant kernel from the per-kernel durations `kms` (prepare, corr_init, iterate)."""
     F = 1
     flop_init = 2.0 * cfg['T'] * cfg['K'] * cfg['W'] * F * cfg['B']                       # per launch (SURVEY 8d)
     flop_loop = 2.0 * (2 * cfg['W'] - 1) * cfg['K'] * cfg['W'] * F * nsel_local           # per launch
@@ -414,62 +467,26 @@ def bench_cmp(args, ctx):
         if pmc is not None and not pmc_stale and cfg['B'] == 1024 and cfg['T'] == 65536 and variant.startswith('mfma') and args.dtype == 'f32':
             traffic = pmc[dom[3]]['hbm_bytes_per_launch']
             step_bytes = sum(pmc[k]['hbm_bytes_per_launch'] for k in ('prepare_kernel', 'corr_init_mfma_kernel', 'iterate_kernel') if k in pmc)
-            hbm_fraction = step_bytes / (elapsed_max / steps) / PEAK_HBM_BYTES
+            hbm_fraction = step_bytes / step_s / PEAK_HBM_BYTES
             pmc_src = pmc.get('_source')
     except Exception:
         traffic = None
-    rate = nsel_total * steps / elapsed_max
     esz = 8 if args.dtype == 'f64' else 4
     table_bytes = cfg['T'] * cfg['K'] * esz                                                # one scan of the [T,K] table per selection (:967)
-    out = {
-        'metric': 'atom-selections/sec (+ residual-energy match) on 1-D CSC',
-        'value': rate,
-        'unit': 'atom-selections/s',
-        'n_gpus': world, 'steps': steps, 'warmup': warmup,
-        'ms_per_step': 1e3 * elapsed_max / steps,
-        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-        'dtype': args.dtype, 'data': 'synthetic',
-        'config': {'workload': 'BASELINE configs[1]: single-level CSC, %d signals/GPU x len %d, %d-atom x %d-tap dict, '
-                               'L0=%d, nbBlocks=1, %s signals' % (cfg['B'], cfg['T'], cfg['K'], cfg['W'], cfg['L0'], cfg['kind']),
-                   'signals_per_gpu': cfg['B'], 'T': cfg['T'], 'K': cfg['K'], 'W': cfg['W'], 'L0': cfg['L0'],
-                   'selections_per_step': nsel_total, 'variant': variant,
-                   'stop_reasons': {_native.STOP_NAMES[i]: int(n) for i, n in enumerate(stops) if n},
-                   'output_check': check},
-        'value_incl_transfers': (nsel_total * 1e3 / incl['ms_per_step']) if incl else None,
-        'transfers': incl,
-        'roofline': {'bound': 'mfma', 'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s',
-                     'frac': achieved / peak, 'traffic': traffic, 'traffic_unit': 'HBM bytes/launch (PMC)', 'kernel': dom[0],
-                     'kernel_ms': float(dom[2]),
-                     'all_kernels': [{'kernel': k[0], 'algorithmic_tflop': k[1] / 1e12, 'ms': float(k[2]),
-                                      'tflops': (k[1] / (k[2] * 1e-3) / 1e12) if k[2] > 0 else None,
-                                      'frac': (k[1] / (k[2] * 1e-3) / 1e12 / peak) if k[2] > 0 else None} for k in kern],
-                     'prepare_ms': float(kms[0]),
-                     'whole_job_tflops': (flop_init + flop_loop) * steps * world / elapsed_max / 1e12,
-                     'whole_job_frac': (flop_init + flop_loop) * steps * world / elapsed_max / 1e12 / peak / world,
-                     # the HBM side: measured bytes/s of the table-free formulation against 8 TB/s, and the
-                     # bandwidth the reference's formulation (one scan of the [T,K] table per selection) would need at this rate
-                     'hbm_fraction': hbm_fraction, 'pmc_source': pmc_src, 'pmc_stale': pmc_stale,
-                     'table_scan_equiv': {'bytes_per_selection': table_bytes, 'tb_per_s_needed': rate / world * table_bytes / 1e12,
-                                          'x_hbm_peak': rate / world * table_bytes / PEAK_HBM_BYTES}},
-        'gather': gather,
-        'cpu_baseline': None,
-    }
-    if check and not all(check.values()):
-        out['config']['output_check']['FAILED'] = True
-    if dumped:
-        out['dump_outputs'] = dumped
-    # ---- the hierarchical configurations of BASELINE.json at their own sizes, a few steps each (bounded: it must never
-    #      cost the headline line): configs[3] with 17 and with the literal 16 level-1 taps, configs[4] at its per-GPU share
-    if world == 1:
-        eng.close()
-        del x
-        torch.cuda.empty_cache()
-    if world == 1 and not args.no_secondary:
-        out['secondary'] = run_secondary(args, ctx)
-    if world == 1 and not args.no_cpu_baseline:
-        nproc = args.cpu_procs or min(16, host_cores())
-        out['cpu_baseline'] = run_cpu_baseline(cfg, nproc, args.cpu_signals_per_proc)
-    return out
+    return {'bound': 'mfma', 'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s',
+            'frac': achieved / peak, 'traffic': traffic, 'traffic_unit': 'HBM bytes/launch (PMC)', 'kernel': dom[0],
+            'kernel_ms': float(dom[2]),
+            'all_kernels': [{'kernel': k[0], 'algorithmic_tflop': k[1] / 1e12, 'ms': float(k[2]),
+                             'tflops': (k[1] / (k[2] * 1e-3) / 1e12) if k[2] > 0 else None,
+                             'frac': (k[1] / (k[2] * 1e-3) / 1e12 / peak) if k[2] > 0 else None} for k in kern],
+            'prepare_ms': float(kms[0]),
+            'whole_job_tflops': (flop_init + flop_loop) * world / step_s / 1e12,
+            'whole_job_frac': (flop_init + flop_loop) * world / step_s / 1e12 / peak / world,
+            # the HBM side: measured bytes/s of the table-free formulation against 8 TB/s, and the
+            # bandwidth the reference's formulation (one scan of the [T,K] table per selection) would need at this rate
+            'hbm_fraction': hbm_fraction, 'pmc_source': pmc_src, 'pmc_stale': pmc_stale,
+            'table_scan_equiv': {'bytes_per_selection': table_bytes, 'tb_per_s_needed': rate / world * table_bytes / 1e12,
+                                 'x_hbm_peak': rate / world * table_bytes / PEAK_HBM_BYTES}}
 
 
 def run_secondary(args, ctx):

@@ -15,7 +15,9 @@ scripts/learn_mlcsc_dataset.py:108-133) on BASELINE.json's multilevel configurat
 One step = one multilevel encode of the rank's batch, signals resident in HBM when it starts: level 0 (f32 MFMA kernels,
 blocked selection), every further level on the previous level's coefficient slots scattered on the device (float64 sparse
 x sparse kernels), then the device epilogue (redistribution, CSC, residual) and the fetch of the per-signal results.
-`value` = atom selections of all levels per second of that whole step.
+`value` = atom selections of all levels per second of that whole step.  The per-level figures come from the timed steps
+themselves; bench.py --full adds the runs of their own: the step with the residual samples fetched, the step fed from the host,
+the gather over the ranks and the CPU baseline.
 """
 import json
 import os
@@ -219,23 +221,26 @@ def run(args, ctx):
         dist.barrier()
     nsel_local = int(sum(tm['selections'] for tm in timings))
     dumped = dump_outputs(args.dump_outputs, coefs, energies) if getattr(args, 'dump_outputs', None) and rank == 0 else None
-    # the same step with the residual samples fetched (never `value`)
-    nres = max(1, min(3, steps))
-    t1 = time.perf_counter()
-    for _ in range(nres):
-        _, residuals, _ = step('samples')
-    torch.cuda.synchronize(dev)
-    elapsed_res = (time.perf_counter() - t1) / nres
-    energies_match = bool(np.allclose(energies, np.sum(np.square(residuals.reshape((B, -1))), axis=1), rtol=1e-10, atol=0.0))
-    del residuals
-    # SURVEY 8(d)'s wall clock: the signals cross PCIe into the encoder every step (host array in, no device pointer) and the
-    # per-signal results (coefficient matrices, residual energies) come back -- never `value`
-    nin = max(1, min(3, steps))
-    t2 = time.perf_counter()
-    for _ in range(nin):
-        hcmp.computeCoefficientsBatch(xs, mlds, residuals='energy', **kw)
-    torch.cuda.synchronize(dev)
-    elapsed_in = (time.perf_counter() - t2) / nin
+    full = getattr(args, 'full', False)
+    elapsed_res = elapsed_in = energies_match = None
+    if full:
+        # the same step with the residual samples fetched (never `value`)
+        nres = max(1, min(3, steps))
+        t1 = time.perf_counter()
+        for _ in range(nres):
+            _, residuals, _ = step('samples')
+        torch.cuda.synchronize(dev)
+        elapsed_res = (time.perf_counter() - t1) / nres
+        energies_match = bool(np.allclose(energies, np.sum(np.square(residuals.reshape((B, -1))), axis=1), rtol=1e-10, atol=0.0))
+        del residuals
+        # SURVEY 8(d)'s wall clock: the signals cross PCIe into the encoder every step (host array in, no device pointer) and the
+        # per-signal results (coefficient matrices, residual energies) come back -- never `value`
+        nin = max(1, min(3, steps))
+        t2 = time.perf_counter()
+        for _ in range(nin):
+            hcmp.computeCoefficientsBatch(xs, mlds, residuals='energy', **kw)
+        torch.cuda.synchronize(dev)
+        elapsed_in = (time.perf_counter() - t2) / nin
 
     # output check of the timed workload: the multilevel code reconstructs the signals
     snr = 10 * np.log10(np.sum(xs.astype(np.float64) ** 2, axis=1) / np.maximum(energies, 1e-300))
@@ -245,10 +250,11 @@ def run(args, ctx):
     consistent = not (config == 4 and args.level1_taps == 16)
     check = {'snr_db_min': float(snr.min()), 'snr_db_median': float(np.median(snr)), 'snr_floor_db': floor,
              'reconstructs': bool(snr.min() >= floor) if consistent else None,
-             'device_energies_match_fetched_residuals': energies_match,
              'nnz_per_level_mean': [float(np.mean([c[l].nnz for c in coefs])) for l in range(nlev)]}
+    if full:                                # (the residual samples behind this one are fetched by --full only)
+        check['device_energies_match_fetched_residuals'] = energies_match
     # (a failed check is reported in the line, after the collectives below: a rank that left here would hang the others)
-    if (consistent and snr.min() < floor) or not energies_match:
+    if (consistent and snr.min() < floor) or energies_match is False:
         check['FAILED'] = True
 
     import bench as _b
@@ -256,7 +262,7 @@ def run(args, ctx):
     #      "batch sharded 8 GPU"): event records (hsc/dataset.py:798-811) + float64 values + counts + residual energies, rebuilt
     #      into per-level matrices on every rank.  After the timed region, reported beside the metric.
     gather = None
-    if world > 1:
+    if full and world > 1:
         try:
             from hsc_amd import parallel
             coefs_g, energies_g, _, events_g = hcmp.computeCoefficientsBatch(xs, mlds, deviceInput=x_dev.data_ptr(), residuals='energy',
@@ -277,7 +283,7 @@ def run(args, ctx):
         except Exception as ex:            # (reported beside the metric, never part of it)
             gather = {'error': '%s: %s' % (type(ex).__name__, ex)}
     elapsed_max, nsel_total = _b.reduce_over_ranks(ctx, args, elapsed, nsel_local)
-    elapsed_in_max, _ = _b.reduce_over_ranks(ctx, args, elapsed_in, 0)
+    elapsed_in_max = _b.reduce_over_ranks(ctx, args, elapsed_in, 0)[0] if full else None
     if rank != 0:
         return None
     kernel_ms = float(sum(sum(tm['kernel_ms'][:3]) for tm in timings))
@@ -315,18 +321,18 @@ def run(args, ctx):
                      'peak': PEAK_FP32_MFMA_TFLOPS, 'unit': 'TFLOP/s', 'frac': l0['loop_frac'], 'kernel_ms': l0['loop_ms'],
                      'traffic': (pmc or {}).get('level0_loop_hbm_bytes_per_launch'), 'dominant_level': dom['level'],
                      'levels': levels, 'pmc': pmc, 'pmc_stale': pmc_stale},
-        'value_incl_transfers': nsel_total / elapsed_in_max,
+        'value_incl_transfers': nsel_total / elapsed_in_max if full else None,
         'transfers': {'ms_per_step': 1e3 * elapsed_in_max, 'h2d_bytes_per_step': int(xs.nbytes),
-                      'note': 'the same step fed from a (pageable) host array: H2D of the signals, the encode, D2H of the coefficient matrices and residual energies'},
+                      'note': 'the same step fed from a (pageable) host array: H2D of the signals, the encode, D2H of the coefficient matrices and residual energies'} if full else None,
         'gather': gather,
-        'value_incl_residual_transfer': nsel_local * world / elapsed_res,
+        'value_incl_residual_transfer': nsel_local * world / elapsed_res if full else None,
         'residual_transfer': {'ms_per_step': 1e3 * elapsed_res, 'd2h_bytes_per_step': int(B * T * 8),
-                              'note': 'the same step with the float64 residual samples of every signal fetched to the host (this rank)'},
+                              'note': 'the same step with the float64 residual samples of every signal fetched to the host (this rank)'} if full else None,
         'cpu_baseline': None,
     }
     if dumped:
         out['dump_outputs'] = dumped
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         nproc = args.cpu_procs or min(16, _b.host_cores())
         payload = json.dumps(dict(config=config, nproc=nproc, T=T, level1_taps=args.level1_taps))
         env = dict(os.environ, OMP_NUM_THREADS='1', OPENBLAS_NUM_THREADS='1', HIP_VISIBLE_DEVICES='', ROCR_VISIBLE_DEVICES='')
@@ -344,7 +350,7 @@ def run(args, ctx):
 
 
 def compact(out):
-    """The figures of a hierarchical bench line that bench.py's default run carries in its `secondary` object."""
+    """The figures of a hierarchical bench line that bench.py --full carries in its `secondary` object."""
     if out is None:
         return None
     keep = {k: out[k] for k in ('value', 'unit', 'ms_per_step', 'steps', 'warmup', 'dtype', 'value_incl_transfers', 'value_incl_residual_transfer')}

@@ -54,7 +54,7 @@ def test_config2_line_reports_what_section_8d_defines():
 
 
 def test_default_line_carries_the_hierarchical_configurations():
-    """The default invocation (what the driver records) appends a bounded `secondary` object: BASELINE configs[3] with 17 and
+    """The full invocation (`bench.py --full`; the default one when this line was recorded) appends a bounded `secondary` object: BASELINE configs[3] with 17 and
     with the literal 16 level-1 taps, configs[4] at its per-GPU share -- per-level rooflines, the rate with the residual
     samples fetched, the reconstruction check."""
     d = _load('r03_bench_default.json')

@@ -8,7 +8,7 @@ tag=$1
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 for cfg in 2 4 5 4locomp 5locomp; do
-    n=${cfg%locomp}; extra=""; [ "$n" != "$cfg" ] && extra="--method locomp"
+    n=${cfg%locomp}; extra="--full"; [ "$n" != "$cfg" ] && extra="--full --method locomp"
     steps=20; [ $n = 4 ] && steps=4; [ $n = 5 ] && steps=3; [ $cfg = 5locomp ] && steps=2
     name=c$n; [ "$n" != "$cfg" ] && name=c${n}_locomp
     rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/${tag}_stats_$name -- python3 $R/bench.py --config $n $extra --steps $steps --warmup 2 --no-cpu-baseline --no-secondary \
