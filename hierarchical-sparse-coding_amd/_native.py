@@ -27,7 +27,7 @@ METHOD_CMP, METHOD_LOCOMP = 0, 1
 EXPORTS = ['hscmp_version', 'hscmp_create', 'hscmp_destroy', 'hscmp_last_error', 'hscmp_set_stream', 'hscmp_set_method',
            'hscmp_synchronize', 'hscmp_set_dictionary', 'hscmp_convolve1d', 'hscmp_select_best_atoms',
            'hscmp_update_inner_products', 'hscmp_table_open', 'hscmp_table_select', 'hscmp_table_update', 'hscmp_table_read', 'hscmp_assign_windows', 'hscmp_host_overlap_add', 'hscmp_host_slots_to_csc', 'hscmp_hierarchy_epilogue', 'hscmp_encode_batch',
-           'hscmp_encode_batch_device', 'hscmp_encode_batch_from_level', 'hscmp_continue', 'hscmp_grow_events', 'hscmp_mem_info', 'hscmp_copy_from_device', 'hscmp_stop_signal', 'hscmp_fetch_events',
+           'hscmp_encode_batch_device', 'hscmp_encode_batch_ragged', 'hscmp_encode_batch_ragged_device', 'hscmp_encode_batch_from_level', 'hscmp_continue', 'hscmp_grow_events', 'hscmp_mem_info', 'hscmp_copy_from_device', 'hscmp_stop_signal', 'hscmp_fetch_events',
            'hscmp_fetch_stats', 'hscmp_fetch_residual', 'hscmp_fetch_energies', 'hscmp_fetch_slots',
            'hscmp_get_device_view', 'hscmp_last_kernel_ms', 'hscmp_last_variant']
 
@@ -105,6 +105,8 @@ def load_library():
     lib.hscmp_hierarchy_epilogue.argtypes = [vp, vp, ci, ctypes.POINTER(HscmpEpilogueLevel), ci, ctypes.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.hscmp_encode_batch.argtypes = [vp, vp, ci, ci, ctypes.POINTER(HscmpParams)]
     lib.hscmp_encode_batch_device.argtypes = [vp, vp, ci, ci, ctypes.POINTER(HscmpParams)]
+    lib.hscmp_encode_batch_ragged.argtypes = [vp, vp, ci, ci, vp, ctypes.POINTER(HscmpParams)]
+    lib.hscmp_encode_batch_ragged_device.argtypes = [vp, vp, ci, ci, vp, ctypes.POINTER(HscmpParams)]
     lib.hscmp_encode_batch_from_level.argtypes = [vp, vp, ci, ci, ctypes.c_double, ctypes.POINTER(HscmpParams)]
     lib.hscmp_continue.argtypes = [vp, ci]
     lib.hscmp_grow_events.argtypes = [vp, ci]
@@ -442,6 +444,25 @@ class Engine(object):
         """x_dev_ptr: device address of [B,T,F] in the dictionary dtype; asynchronous."""
         self._check(self._lib.hscmp_encode_batch_device(self._h, ctypes.c_void_p(x_dev_ptr), int(B), int(T),
                                                         ctypes.byref(params)), 'hscmp_encode_batch_device')
+        self._batch = (int(B), int(T), int(params.max_events))
+
+    def encode_batch_ragged(self, x, lengths, params):
+        """x [B,T,F] host array of the dictionary dtype, T the longest length; lengths int [B] with W <= lengths[b] <= T.
+        Rows t >= lengths[b] of x are never read.  Fetched arrays keep the [B,T] strides."""
+        x3 = np.ascontiguousarray(x, dtype=self.dtype)
+        assert x3.ndim == 3 and x3.shape[2] == self.F
+        B, T = x3.shape[0], x3.shape[1]
+        lens = np.ascontiguousarray(lengths, dtype=np.int32)
+        assert lens.shape == (B,)
+        self._check(self._lib.hscmp_encode_batch_ragged(self._h, _ptr(x3), B, T, _ptr(lens), ctypes.byref(params)), 'hscmp_encode_batch_ragged')
+        self._batch = (B, T, int(params.max_events))
+
+    def encode_batch_ragged_device(self, x_dev_ptr, B, T, lengths, params):
+        """x_dev_ptr: device address of [B,T,F] in the dictionary dtype; lengths host int [B]; asynchronous."""
+        lens = np.ascontiguousarray(lengths, dtype=np.int32)
+        assert lens.shape == (int(B),)
+        self._check(self._lib.hscmp_encode_batch_ragged_device(self._h, ctypes.c_void_p(x_dev_ptr), int(B), int(T), _ptr(lens),
+                                                               ctypes.byref(params)), 'hscmp_encode_batch_ragged_device')
         self._batch = (int(B), int(T), int(params.max_events))
 
     def encode_batch_from_level(self, prev, first, count, minCoefficients, params):

@@ -78,6 +78,7 @@ struct EncodePlan {
     bool kept_lists = false;  // ... and the loop keeps them current: it enters every cell it writes
     bool init_only = false;   // HSCMP_INIT_ONLY (tests): stop behind the initial correlation
     bool bound_loop = false;  // the four-signal loop re-correlates as upper bounds (MfmaRecorr BOUND)
+    bool ragged = false;      // signals of different lengths: the RAGGED instances of the loops read each signal's geometry
     Knobs knobs{};            // the encode's snapshot: the launches read pairing, row bitmaps and LDS pad from it
 };
 
@@ -131,6 +132,12 @@ struct hscmp_ctx {
     int* d_sel_t = nullptr; int* d_sel_k = nullptr; void* d_sel_c = nullptr;
     int* d_stats = nullptr; void* d_energy = nullptr; unsigned long long* d_edge = nullptr;
     DevParams P{};
+    // ragged batch (hscmp_encode_batch_ragged): per signal {length, block size, block count} on the host and the device, until the
+    // next encode of any kind; the batch's P.T is the longest length and every per-signal array keeps that stride
+    bool ragged = false;
+    std::vector<int> geom;
+    int* d_geom = nullptr;
+    size_t cap_geom = 0;
     hscmp_params last{};
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool timed = false;
@@ -225,7 +232,7 @@ static void free_all(hscmp_ctx* c)
 {
     for (void* p : c->d_epi) if (p) (void)hipFree(p);
     void* ptrs[] = {c->d_D, c->d_w, c->d_Dfrag, c->d_Bimg, c->d_Dt, c->d_Dc, c->d_nzptr, c->d_nzwf, c->d_nzval, c->d_fptr, c->d_fkw, c->d_fval, c->d_rl_cnt, c->d_rl_f, c->d_scratch, c->d_rowflag, c->d_x, c->d_resid, c->d_best_c, c->d_best_k, c->d_ev_t, c->d_ev_k, c->d_ev_c,
-                    c->d_slot_t, c->d_slot_k, c->d_slot_a, c->d_hkey, c->d_hval, c->d_head, c->d_lgram, c->d_sel_t, c->d_sel_k, c->d_sel_c, c->d_stats, c->d_energy, c->d_edge};
+                    c->d_slot_t, c->d_slot_k, c->d_slot_a, c->d_hkey, c->d_hval, c->d_head, c->d_lgram, c->d_sel_t, c->d_sel_k, c->d_sel_c, c->d_stats, c->d_energy, c->d_edge, c->d_geom};
     for (void* p : ptrs) if (p) (void)hipFree(p);
 }
 
@@ -304,6 +311,7 @@ extern "C" int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W,
     }
     ctx->K = K; ctx->W = W; ctx->F = F; ctx->dtype = dtype;
     ctx->have_batch = false;
+    ctx->ragged = false;
     if (F > 1) {
         // Dt[w][f][k] = D[k][w][f]: atom index contiguous, for the gathered-window kernels
         std::vector<char> dt(nD);
@@ -523,6 +531,7 @@ template <typename R> static State<R> make_state(hscmp_ctx* c)
     S.hkey = c->d_hkey; S.hval = c->d_hval; S.head = c->d_head; S.lgram = c->d_lgram;
     S.sel_t = c->d_sel_t; S.sel_k = c->d_sel_k; S.sel_c = (R*)c->d_sel_c;
     S.stats = c->d_stats; S.energy = (R*)c->d_energy; S.edge = c->d_edge;
+    S.geom = c->ragged ? c->d_geom : nullptr;
     return S;
 }
 
@@ -549,14 +558,14 @@ template <typename Pol> static size_t policy_lds_bytes(const DevParams& P0, cons
 
 // The loop of policy Pol (iterate_kernel), `signals_per_wg` signals per workgroup.  dry: only tell whether its LDS fits (158 KB:
 // the kernel's own static bytes count too), queue nothing.  0: launched (or fits); -1: it cannot run this shape.
-template <typename R, typename Pol>
+template <typename R, typename Pol, bool RAGGED = false>
 static int launch_policy(hscmp_ctx* ctx, const DevParams& P0, const typename Pol::Args& A, int signals_per_wg, bool dry)
 {
     DevParams P = P0;
     set_segments(P, Pol::kMaxSegments);
     const size_t lds = Pol::total_lds_bytes(P, A);
     if (dry) return lds <= (size_t)158 * 1024 ? 0 : -1;
-    auto kern = iterate_kernel<R, Pol>;
+    auto kern = iterate_kernel<R, Pol, RAGGED>;
     if (set_dyn_lds((const void*)kern, lds) != hipSuccess) return -1;
     hipLaunchKernelGGL(kern, dim3((P.B + signals_per_wg - 1) / signals_per_wg), dim3(signals_per_wg * kThreads), lds, ctx->stream, P,
                        make_state<R>(ctx), A);
@@ -588,10 +597,12 @@ static int launch_locomp_mfma(hscmp_ctx* ctx, const DevParams& P, int group, boo
 
 // The one place that chooses the kernels of an encode: every knob that selects a kernel is looked at here, and every LDS-fit
 // check runs here.  row_lists: the encode keeps per-row feature lists where its kernels can use them (use_row_lists).
-template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const Knobs& kn, const DevParams& P, bool row_lists)
+// min_T: the shortest signal (a ragged batch; P.T otherwise).
+template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const Knobs& kn, const DevParams& P, bool row_lists, int min_T)
 {
     EncodePlan plan;
     plan.knobs = kn;
+    plan.ragged = ctx->ragged;
     plan.f64 = sizeof(R) == 8;
     plan.dict_lists = ctx->d_nzptr != nullptr;
     const State<R> S = make_state<R>(ctx);
@@ -614,10 +625,10 @@ template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const Knobs&
 
     // The matrix-core kernels come as a pair: the score-only state the initial correlation leaves is what the MFMA loop reads (the
     // generic / sparse kernels keep coefficient + atom instead).  The score-only path assumes single-bounce reflection at the
-    // edges (T >= 3W-2).  Four signals per workgroup pay off once a CU would otherwise hold more than two signals in turn
+    // edges (T >= 3W-2; in a ragged batch every signal's: the shortest one decides).  Four signals per workgroup pay off once a CU would otherwise hold more than two signals in turn
     // (B > 2 x CUs); HSCMP_MFMA_QUAD=0/1 forces the choice (tests run both; the results are bit-identical).
     bool mf = false;
-    if (!locomp && !kn.force_generic && dimg && P.T >= 3 * ctx->W - 2 && mfma_launch_corr_init<R>(ctx->stream, P, S, dimg, true) == 0) {
+    if (!locomp && !kn.force_generic && dimg && min_T >= 3 * ctx->W - 2 && mfma_launch_corr_init<R>(ctx->stream, P, S, dimg, true) == 0) {
         const bool quad = kn.mfma_quad >= 0 ? kn.mfma_quad != 0 : sizeof(R) == 4 && P.B > 2 * cus;
         if (quad && mfma_launch_iterate<R>(ctx->stream, P, S, dimg, 4, kn.lds_pad, true) == 0) plan.group = 4;
         mf = plan.group == 4 || mfma_launch_iterate<R>(ctx->stream, P, S, dimg, 1, kn.lds_pad, true) == 0;
@@ -687,6 +698,7 @@ static std::string variant_of(const EncodePlan& plan)
     std::string v = std::string(init) + "_init+" + loop + "_loop_" + (plan.f64 ? "f64" : "f32") + (bound ? "_bound" : "");
     if (plan.rp) v += "_rp";
     else if (plan.loop == EncodePlan::kLoopMfma && plan.group > 1) v += "_x" + std::to_string(plan.group);
+    if (plan.ragged) v += "_ragged";
     return v;
 }
 
@@ -745,7 +757,9 @@ template <typename R> static int launch_loop(hscmp_ctx* ctx, const EncodePlan& p
         rc = plan.packed ? launch_policy<R, SparseRecorr<R, true>>(ctx, P, sparse_args<R>(ctx, plan, P.T, true), 1, false)
                          : launch_policy<R, SparseRecorr<R, false>>(ctx, P, sparse_args<R>(ctx, plan, P.T), 1, false);
         break;
-    case EncodePlan::kLoopGeneric: rc = launch_policy<R, GenericRecorr<R>>(ctx, P, {}, 1, false); break;
+    case EncodePlan::kLoopGeneric:
+        rc = plan.ragged ? launch_policy<R, GenericRecorr<R>, true>(ctx, P, {}, 1, false) : launch_policy<R, GenericRecorr<R>>(ctx, P, {}, 1, false);
+        break;
     case EncodePlan::kLoopLocomp: rc = launch_policy<R, LocompRecorr<R>>(ctx, P, {}, 1, false); break;
     case EncodePlan::kLoopLocompSparse: rc = launch_policy<R, LocompSparse<R>>(ctx, P, sparse_args<R>(ctx, plan, P.T), 1, false); break;
     case EncodePlan::kLoopLocompMfma:
@@ -801,19 +815,69 @@ static int run_encode(hscmp_ctx* ctx, const EncodePlan& plan, const DevParams& P
     return HSCMP_OK;
 }
 
-static int encode_common(hscmp_ctx* ctx, const void* x, bool host, int B, int T, const hscmp_params* params)
+// Per-signal geometry of a ragged batch, checked before anything is queued: {T_b, bs_b, nbk_b} per signal with the block size
+// of modeling.py:908-918 on the signal's own length; P.maxsel grows to the largest block count.  *min_T: the shortest length.
+static int ragged_geometry(hscmp_ctx* ctx, const char* who, int B, int T, const int32_t* lengths, const hscmp_params* p, DevParams& P,
+                           std::vector<int>& geom, int* min_T)
 {
-    if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_encode_batch: ctx is NULL");
-    if (ctx->dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_encode_batch: no dictionary set");
-    if (!x || !params || B <= 0 || T <= 0) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch: bad arguments (B=%d T=%d)", B, T);
+    geom.assign((size_t)B * kGeomWords, 0);
+    *min_T = T;
+    for (int b = 0; b < B; ++b) {
+        const int Tb = lengths[b];
+        if (Tb < ctx->W || Tb > T)
+            return fail(ctx, HSCMP_ERR_INVALID, "%s: signal %d has length %d outside [W=%d, T=%d]", who, b, Tb, ctx->W, T);
+        int bs = 0, nbk = 0;
+        if (P.blocked) {
+            bs = p->nb_blocks < 0 ? 4 * ctx->W : (int)std::floor((double)Tb / (double)p->nb_blocks);
+            if (bs % 2 == 1) bs += 1;
+            if (bs <= 0) return fail(ctx, HSCMP_ERR_INVALID, "%s: signal %d: nbBlocks=%d gives an empty block for its length %d", who, b, p->nb_blocks, Tb);
+            nbk = (int)std::ceil((double)Tb / (double)bs);
+            P.maxsel = std::max(P.maxsel, nbk + 1);
+        }
+        geom[(size_t)b * kGeomWords + 0] = Tb;
+        geom[(size_t)b * kGeomWords + 1] = bs;
+        geom[(size_t)b * kGeomWords + 2] = nbk;
+        *min_T = std::min(*min_T, Tb);
+    }
+    return HSCMP_OK;
+}
+
+// lengths: NULL for a uniform batch, else host int32 [B] (hscmp_encode_batch_ragged*)
+static int encode_common(hscmp_ctx* ctx, const void* x, bool host, int B, int T, const hscmp_params* params, const int32_t* lengths = nullptr,
+                         const char* who = "hscmp_encode_batch")
+{
+    if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "%s: ctx is NULL", who);
+    if (ctx->dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "%s: no dictionary set", who);
+    if (!x || !params || B <= 0 || T <= 0) return fail(ctx, HSCMP_ERR_INVALID, "%s: bad arguments (B=%d T=%d)", who, B, T);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const Knobs kn = read_knobs();
     DevParams P;
     int rc = make_params(ctx, kn, B, T, params, &P);
     if (rc) return rc;
+    int min_T = T;
+    std::vector<int> geom;
+    if (lengths && (rc = ragged_geometry(ctx, who, B, T, lengths, params, P, geom, &min_T))) return rc;
     const bool row_lists = use_row_lists(ctx, kn);
     if ((rc = ensure_workspace(ctx, P, host, row_lists))) return rc;
-    const EncodePlan plan = ctx->dtype == HSCMP_F32 ? plan_encode<float>(ctx, kn, P, row_lists) : plan_encode<double>(ctx, kn, P, row_lists);
+    if (lengths) {
+        const size_t bytes = geom.size() * sizeof(int);
+        if (!ctx->d_geom || ctx->cap_geom < bytes) {
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (ctx->d_geom) { (void)hipFree(ctx->d_geom); ctx->d_geom = nullptr; ctx->cap_geom = 0; }
+            HIP_TRY(ctx, hipMalloc((void**)&ctx->d_geom, bytes));
+            ctx->cap_geom = bytes;
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the previous batch's kernels may still read the old geometry)
+        ctx->geom.swap(geom);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_geom, ctx->geom.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    ctx->ragged = lengths != nullptr;           // (a plain encode clears the lengths of an earlier ragged one)
+    if (!lengths) ctx->geom.clear();
+    const EncodePlan plan = ctx->dtype == HSCMP_F32 ? plan_encode<float>(ctx, kn, P, row_lists, min_T) : plan_encode<double>(ctx, kn, P, row_lists, min_T);
+    if (plan.ragged && ((plan.loop != EncodePlan::kLoopMfma && plan.loop != EncodePlan::kLoopGeneric) || plan.init == EncodePlan::kInitSparse)) {
+        ctx->ragged = false; ctx->have_batch = false;
+        return fail(ctx, HSCMP_ERR_UNSUPPORTED, "%s: %s has no ragged form (dense level-0 kernels only)", who, variant_of(plan).c_str());
+    }
     const void* xd = x;
     if (host) {
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_x, x, (size_t)B * T * ctx->F * esize(ctx->dtype), hipMemcpyHostToDevice, ctx->stream));
@@ -839,6 +903,25 @@ extern "C" int hscmp_encode_batch_device(hscmp_ctx* ctx, const void* x_dev, int 
     return encode_common(ctx, x_dev, false, B, T, params);
 }
 
+static int encode_ragged(hscmp_ctx* ctx, const void* x, bool host, int B, int T, const int32_t* lengths, const hscmp_params* params, const char* who)
+{
+    if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "%s: ctx is NULL", who);
+    if (B < 1) return fail(ctx, HSCMP_ERR_INVALID, "%s: B=%d, at least one signal is needed", who, B);
+    if (!lengths) return fail(ctx, HSCMP_ERR_INVALID, "%s: lengths is NULL", who);
+    if (ctx->method == HSCMP_METHOD_LOCOMP) return fail(ctx, HSCMP_ERR_UNSUPPORTED, "%s: the LoCOMP loop has no ragged form", who);
+    return encode_common(ctx, x, host, B, T, params, lengths, who);
+}
+
+extern "C" int hscmp_encode_batch_ragged(hscmp_ctx* ctx, const void* x, int B, int T, const int32_t* lengths, const hscmp_params* params)
+{
+    return encode_ragged(ctx, x, true, B, T, lengths, params, "hscmp_encode_batch_ragged");
+}
+
+extern "C" int hscmp_encode_batch_ragged_device(hscmp_ctx* ctx, const void* x_dev, int B, int T, const int32_t* lengths, const hscmp_params* params)
+{
+    return encode_ragged(ctx, x_dev, false, B, T, lengths, params, "hscmp_encode_batch_ragged_device");
+}
+
 extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, int first, int count, double min_coefficients,
                                              const hscmp_params* params)
 {
@@ -848,7 +931,9 @@ extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, in
     if (ctx->device != prev->device) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: contexts on different GPUs");
     if (ctx->F != prev->K) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: F=%d of this level != K=%d of the previous one", ctx->F, prev->K);
     if (!params || first < 0 || count <= 0 || first + count > prev->B) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: bad signal range");
+    if (prev->ragged) return fail(ctx, HSCMP_ERR_UNSUPPORTED, "hscmp_encode_batch_from_level: the previous level holds a ragged batch (level chaining has no ragged form)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->ragged = false;
     HIP_TRY(ctx, hipStreamSynchronize(prev->stream));           // the previous level's results are final
     const int T = prev->T;
     const Knobs kn = read_knobs();
@@ -857,7 +942,7 @@ extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, in
     if (rc) return rc;
     const bool row_lists = use_row_lists(ctx, kn);
     if ((rc = ensure_workspace(ctx, P, false, row_lists))) return rc;        // no input buffer: the slots are scattered straight into the residual
-    const EncodePlan plan = plan_encode<double>(ctx, kn, P, row_lists);
+    const EncodePlan plan = plan_encode<double>(ctx, kn, P, row_lists, P.T);
     const bool lists = plan.row_lists;          // (the scatter writes them)
     const size_t bytes = (size_t)count * T * ctx->F * sizeof(double);
     if (ctx->listed_rows > 0 && ctx->listed_F == ctx->F && !kn.no_lazy_clear) {
@@ -1251,6 +1336,7 @@ extern "C" int hscmp_hierarchy_epilogue(hscmp_ctx* last, hscmp_ctx* level0, int 
 {
     if (!last || !level0) return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: NULL context");
     if (!last->have_batch || !level0->have_batch) return fail(last, HSCMP_ERR_STATE, "hscmp_hierarchy_epilogue: no batch encoded");
+    if (last->ragged || level0->ragged) return fail(last, HSCMP_ERR_UNSUPPORTED, "hscmp_hierarchy_epilogue: a ragged batch has no hierarchical epilogue");
     if (last->device != level0->device) return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: contexts on different GPUs");
     if (!levels || nlevels < 1 || nlevels > kEpiMaxLevels || !offsets || !out_n || !out_colptr || !out_indices || !out_data)
         return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: bad arguments");
@@ -1376,6 +1462,7 @@ static int select_on_device(hscmp_ctx* ctx, const Knobs& kn, const R* d_ip, cons
     if (rc == HSCMP_OK) rc = ensure_workspace_g(ctx, P, false, sizeof(R), false, false);
     if (rc != HSCMP_OK) return rc;
     ctx->have_batch = false;
+    ctx->ragged = false;
     ctx->listed_rows = 0;
     State<R> S = make_state<R>(ctx);
     S.D = nullptr; S.Dc = nullptr; S.weights = d_w;

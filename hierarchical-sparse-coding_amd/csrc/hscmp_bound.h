@@ -206,7 +206,8 @@ __global__ __launch_bounds__(kThreads) void corr_bound_kernel(DevParams P, State
         const int next = item + gridDim.x;
         if (next < nitems) fetch(next);                 // in flight while this chunk is computed
         const int b = item / cps, c0 = (item % cps) * kMfmaChunk;
-        const int npos = min(kMfmaChunk, T - c0);
+        const int Tb = signal_length(P, S, b);          // (ragged batches: rows from Tb on are dead and not computed)
+        const int npos = min(kMfmaChunk, Tb - c0);
         const int ntiles = (npos + 31) / 32;
         for (int q = wv; q < ntiles; q += kWaves) {
             float sc;
@@ -217,7 +218,7 @@ __global__ __launch_bounds__(kThreads) void corr_bound_kernel(DevParams P, State
                 grp = sc == 0.0f ? 0 : -1;              // an exact 0 is a score (hint 0, as the exact tile); else a bound
             }
             const int t = c0 + 32 * q + lane;
-            if (lane < 32 && t < T) {
+            if (lane < 32 && t < Tb) {
                 S.best_c[(int64_t)b * T + t] = sc;
                 S.best_k[(int64_t)b * T + t] = grp;
             }

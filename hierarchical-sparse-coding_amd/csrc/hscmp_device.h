@@ -282,7 +282,33 @@ template <typename R> struct State {
     unsigned long long* edge;   // [B][kEdgeWords]: edge rows re-correlated at least once + the stale-sample record (score-only policies)
     int* head;          // [B][T] round-parallel loop: most recent coefficient slot at position t (-1: none), chained through hval
     double* lgram;      // [B][lgram_doubles(lg_cap)] LoCOMP: what a group keeps beyond its LDS copy (nullptr: other methods)
+    const int* geom;    // [B][kGeomWords] ragged batches: the signal's own length and block geometry; nullptr: uniform
 };
+
+// Ragged batches: every per-signal array keeps the stride of the longest length P.T, and a signal's rows t >= T_b are dead --
+// zero in the residual, never read as a candidate or a segment maximum, never written by the loop.  The kernels that work on one
+// signal take its own geometry (length, segment count, block size and count) in place of the batch's, through signal_params:
+// RAGGED = false returns P itself (the copy folds away), so the loops of a uniform batch compile to the code they were before.
+constexpr int kGeomWords = 3;   // T_b, bs_b, nbk_b
+template <bool RAGGED, typename R> __device__ __forceinline__ DevParams signal_params(const DevParams& P, const State<R>& S, int b)
+{
+    if constexpr (!RAGGED) {
+        return P;
+    } else {
+        DevParams Q = P;
+        const int* g = S.geom + kGeomWords * b;
+        Q.T = __builtin_amdgcn_readfirstlane(g[0]);
+        Q.bs = __builtin_amdgcn_readfirstlane(g[1]);
+        Q.nbk = __builtin_amdgcn_readfirstlane(g[2]);
+        Q.nseg = (Q.T + P.seg - 1) >> P.seg_shift;
+        return Q;
+    }
+}
+// the length of signal b (uniform batches: P.T)
+template <typename R> __device__ __forceinline__ int signal_length(const DevParams& P, const State<R>& S, int b)
+{
+    return S.geom ? S.geom[kGeomWords * b] : P.T;
+}
 
 __device__ __forceinline__ float rabs(float v) { return fabsf(v); }
 __device__ __forceinline__ double rabs(double v) { return fabs(v); }

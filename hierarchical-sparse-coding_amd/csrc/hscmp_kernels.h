@@ -29,15 +29,17 @@ __global__ __launch_bounds__(kThreads) void prepare_kernel(DevParams P, State<R>
     __shared__ R red[2 * kWaves];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int64_t n = (int64_t)P.T * P.F;
+    const int64_t nb = (int64_t)signal_length(P, S, b) * P.F;     // (ragged batches: the signal's own rows; == n otherwise)
     const R* xs = x + (int64_t)b * n;
     R* r = S.residual + (int64_t)b * n;
     R p = (R)0, q = (R)0;
-    for (int64_t i = tid; i < n; i += kThreads) {   // strided partials, sequential in i (pinned order)
+    for (int64_t i = tid; i < nb; i += kThreads) {  // strided partials, sequential in i (pinned order)
         const R v = xs[i];
         r[i] = v;
         const R sq = v * v;
         p = p + sq;
     }
+    for (int64_t i = nb + tid; i < n; i += kThreads) r[i] = (R)0;  // dead rows: the zero padding of 'same' (never read from x)
     pinned_tree2(p, q, red);
     if (tid == 0) {
         S.energy[2 * b + 0] = p;
@@ -274,6 +276,7 @@ __global__ __launch_bounds__(kThreads) void corr_init_generic_kernel(DevParams P
     const int b = blockIdx.y;
     const int t = blockIdx.x * kThreads + threadIdx.x;
     if (t >= Tout) return;
+    if (!TABLE && t >= signal_length(P, S, b)) return;      // (a dead row of a ragged batch: left as it is)
     const int T = P.T, K = P.K, W = P.W, F = P.F;
     const R* x = src + (int64_t)b * T * F;
     const R* __restrict__ D = S.D;
@@ -1014,8 +1017,8 @@ __device__ __forceinline__ void locomp_precompute(const DevParams& P, const Stat
                                                   const int* ord_t, const int* ord_k, const R* ord_c, int first, int count, LocompPre<R>& pre,
                                                   LocompRows& rows, SY& sy);
 
-template <typename R, typename Recorr>
-__global__ __launch_bounds__(kThreads * Recorr::kGroup, Recorr::kMinWavesPerSimd) void iterate_kernel(DevParams P, State<R> S, typename Recorr::Args A)
+template <typename R, typename Recorr, bool RAGGED = false>
+__global__ __launch_bounds__(kThreads * Recorr::kGroup, Recorr::kMinWavesPerSimd) void iterate_kernel(DevParams PB, State<R> S, typename Recorr::Args A)
 {
     // all LDS comes from ONE dynamic array (16-byte aligned base): per signal the control block first, then the
     // policy's region (dictionary image, residual window); a policy with kGroup > 1 keeps what the signals share
@@ -1023,11 +1026,13 @@ __global__ __launch_bounds__(kThreads * Recorr::kGroup, Recorr::kMinWavesPerSimd
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using SH = typename Recorr::Shared;
     constexpr int GS = Recorr::kGroup;
-    Recorr::prologue_shared(P, S, A, smem);              // (kGroup > 1: the shared image, behind a hardware barrier)
+    Recorr::prologue_shared(PB, S, A, smem);             // (kGroup > 1: the shared image, behind a hardware barrier)
     // (wave-uniform by construction; readfirstlane tells the compiler, so the per-signal pointers live in SGPRs)
     const int b = GS == 1 ? (int)blockIdx.x : (int)blockIdx.x * GS + gsig();
-    if (GS > 1 && b >= P.B) return;                      // (a ragged last workgroup; no hardware barrier from here on)
-    char* sbase = smem + Recorr::signal_lds_offset(P, A);
+    if (GS > 1 && b >= PB.B) return;                     // (a ragged last workgroup; no hardware barrier from here on)
+    // PB: the batch (strides, LDS layout); P: this signal (its own length and blocks in a ragged batch)
+    const DevParams P = signal_params<RAGGED>(PB, S, b);
+    char* sbase = smem + Recorr::signal_lds_offset(PB, A);
     SH& sh = *reinterpret_cast<SH*>(sbase);
     char* plds = sbase + ((sizeof(SH) + 15) / 16) * 16;
     int tid = ltid(), lane = tid & 63, wv = tid >> 6;     // (re-derived at the top of every round: see laundered_tid)
@@ -1037,14 +1042,14 @@ __global__ __launch_bounds__(kThreads * Recorr::kGroup, Recorr::kMinWavesPerSimd
 
     const int T = P.T, W = P.W, F = P.F;
     Sig<R> G;
-    G.r = S.residual + (int64_t)b * T * F;
-    G.bc = S.best_c + (int64_t)b * T;
-    G.bk = S.best_k + (int64_t)b * T;
+    G.r = S.residual + (int64_t)b * PB.T * F;
+    G.bc = S.best_c + (int64_t)b * PB.T;
+    G.bk = S.best_k + (int64_t)b * PB.T;
     G.ev_t = S.ev_t + (int64_t)b * P.cap; G.ev_k = S.ev_k + (int64_t)b * P.cap; G.ev_c = S.ev_c + (int64_t)b * P.cap;
     G.slot_t = S.slot_t + (int64_t)b * P.cap; G.slot_k = S.slot_k + (int64_t)b * P.cap; G.slot_a = S.slot_a + (int64_t)b * P.cap;
     G.hkey = S.hkey + (int64_t)b * ((int64_t)P.hmask + 1); G.hval = S.hval + (int64_t)b * ((int64_t)P.hmask + 1);
     G.sel_t = S.sel_t + (int64_t)b * 2 * P.maxsel; G.sel_k = S.sel_k + (int64_t)b * 2 * P.maxsel; G.sel_c = S.sel_c + (int64_t)b * 2 * P.maxsel;
-    G.head = (Recorr::kLocomp && S.head) ? S.head + (int64_t)b * T : S.head;
+    G.head = (Recorr::kLocomp && S.head) ? S.head + (int64_t)b * PB.T : S.head;
     G.lgram = S.lgram ? S.lgram + (int64_t)b * (int64_t)lgram_doubles(P.lg_cap) : nullptr;
 #ifdef HSCMP_DBG_STAMPS
     if (tid == 0 && b < 4096) {

@@ -602,13 +602,14 @@ __global__ __launch_bounds__(kThreads) void corr_init_mfma_kernel(DevParams P, S
         const int next = item + gridDim.x;
         if (next < nitems) fetch(next);                 // in flight while this chunk is computed
         const int b = item / cps, c0 = (item % cps) * kMfmaChunk;
-        const int npos = min(kMfmaChunk, T - c0);
+        const int Tb = signal_length(P, S, b);          // (ragged batches: rows from Tb on are dead and not computed)
+        const int npos = min(kMfmaChunk, Tb - c0);
         const int ntiles = (npos + TP - 1) / TP;
         for (int q = wv; q < ntiles; q += kWaves) {
             int grp;
             const R sc = Tile::template tile_score<S4C, HAS_W>(dimg, xs + TP * q, wts, G, S4, lane, grp);
             const int t = c0 + TP * q + lane;
-            if (lane < TP && t < T) {                                       // score-only state (see mfma_tile_score)
+            if (lane < TP && t < Tb) {                                      // score-only state (see mfma_tile_score)
                 S.best_c[(int64_t)b * T + t] = sc;
                 S.best_k[(int64_t)b * T + t] = grp;                         // the group hint, not an atom
             }
@@ -1660,7 +1661,7 @@ static int mfma_launch_iterate_g(hipStream_t stream, const DevParams& P0, const 
     size_t lds = Pol::total_lds_bytes(P, A);
     if (GS > 1 && lds > (size_t)160 * 1024) return -1;
     lds += (size_t)lds_pad;
-    auto kern = iterate_kernel<typename Tile::R, Pol>;
+    auto kern = S.geom ? iterate_kernel<typename Tile::R, Pol, true> : iterate_kernel<typename Tile::R, Pol, false>;     // (ragged batch)
     if (set_dyn_lds((const void*)kern, lds) != hipSuccess) return -1;
     if (dry) return 0;
     hipLaunchKernelGGL(kern, dim3((P.B + GS - 1) / GS), dim3(GS * kThreads), lds, stream, P, S, A);

@@ -406,8 +406,8 @@ __device__ __forceinline__ void rp_wave_prefix(const DevParams& P, SH& sh, const
 // the round-parallel loop          grid = B, block = kRpThreads
 //   Pol supplies the per-wave pieces: candidate (resolve + energies), energies, subtract, recorrelate.
 // ------------------------------------------------------------------------------------------------
-template <typename R, typename Pol>
-__global__ __launch_bounds__(kRpThreads) void iterate_rp_kernel(DevParams P, State<R> S, typename Pol::Args A)
+template <typename R, typename Pol, bool RAGGED = false>
+__global__ __launch_bounds__(kRpThreads) void iterate_rp_kernel(DevParams PB, State<R> S, typename Pol::Args A)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using SH = typename Pol::Shared;
@@ -418,15 +418,17 @@ __global__ __launch_bounds__(kRpThreads) void iterate_rp_kernel(DevParams P, Sta
     int* stats = S.stats + (int64_t)b * ST_COUNT;
     if (stats[ST_STOP] != STOP_RUNNING) return;          // converged in an earlier launch (uniform)
 
+    // PB: the batch (strides); P: this signal (its own length and blocks in a ragged batch)
+    const DevParams P = signal_params<RAGGED>(PB, S, b);
     const int T = P.T, W = P.W, F = P.F;
     Sig<R> G;
-    G.r = S.residual + (int64_t)b * T * F;
-    G.bc = S.best_c + (int64_t)b * T;
-    G.bk = S.best_k + (int64_t)b * T;
+    G.r = S.residual + (int64_t)b * PB.T * F;
+    G.bc = S.best_c + (int64_t)b * PB.T;
+    G.bk = S.best_k + (int64_t)b * PB.T;
     G.ev_t = S.ev_t + (int64_t)b * P.cap; G.ev_k = S.ev_k + (int64_t)b * P.cap; G.ev_c = S.ev_c + (int64_t)b * P.cap;
     G.slot_t = S.slot_t + (int64_t)b * P.cap; G.slot_k = S.slot_k + (int64_t)b * P.cap; G.slot_a = S.slot_a + (int64_t)b * P.cap;
     G.hkey = S.hkey + (int64_t)b * ((int64_t)P.hmask + 1); G.hval = S.hval + (int64_t)b * ((int64_t)P.hmask + 1);
-    G.head = S.head + (int64_t)b * T;
+    G.head = S.head + (int64_t)b * PB.T;
     G.sel_t = nullptr; G.sel_k = nullptr; G.sel_c = nullptr;
 
     Pol::prologue(P, S, G, A, plds, b);                  // (ends with a workgroup barrier)
@@ -843,7 +845,7 @@ static int rp_mfma_launch_t(hipStream_t stream, const DevParams& P0, const State
     set_segments(P, Pol::kMaxSegments);
     const size_t lds = Pol::total_lds_bytes(A);
     if (lds > (size_t)160 * 1024) return -1;
-    auto kern = iterate_rp_kernel<float, Pol>;
+    auto kern = S.geom ? iterate_rp_kernel<float, Pol, true> : iterate_rp_kernel<float, Pol, false>;     // (ragged batch)
     if (set_dyn_lds((const void*)kern, lds) != hipSuccess) return -1;
     if (dry) return 0;
     hipLaunchKernelGGL(kern, dim3(P.B), dim3(kRpThreads), lds, stream, P, S, A);

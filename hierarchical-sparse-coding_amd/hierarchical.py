@@ -16,7 +16,7 @@ import os
 import numpy as np
 import scipy.sparse
 
-from .modeling import ConvolutionalMatchingPursuit, ConvolutionalSparseCoder, SparseApproximator, reconstructSignal
+from .modeling import ConvolutionalMatchingPursuit, ConvolutionalSparseCoder, SparseApproximator, reconstructSignal, reject_ragged
 
 
 def _is_multilevel_dict(obj):
@@ -144,7 +144,7 @@ class HierarchicalConvolutionalMatchingPursuit(SparseApproximator):
 
     def computeCoefficientsBatch(self, sequences, multilevelDict, toleranceSnr=None, nbBlocks=1, singletonWeight=0.5,
                                  returnDistributed=True, chained=True, memoryBudget=None, epilogue='device', returnEvents=False,
-                                 deviceInput=None, residuals='samples'):
+                                 deviceInput=None, residuals='samples', lengths=None):
         """Batch form (the reference has no batch axis): `sequences` [B,T] (or [B,T,F]); every level encodes
         many signals per GPU call.  chained=True keeps the level hand-off on the device
         (hscmp_encode_batch_from_level): the dense [T, K_prev] float64 input of a level (modeling.py:1489)
@@ -165,6 +165,7 @@ class HierarchicalConvolutionalMatchingPursuit(SparseApproximator):
         per-level kernel timings); with returnEvents=True a fourth item: per-signal event record arrays.
         The steps live in _LevelPipeline (below): level set-up, one level over one chunk with event-list regrowth, chunk sizing,
         the two epilogues, the per-signal fallback."""
+        reject_ragged(sequences, lengths, 'HierarchicalConvolutionalMatchingPursuit.computeCoefficientsBatch (levels >= 1, level chaining, epilogue)')
         assert residuals in ('samples', 'energy')
         assert _is_multilevel_dict(multilevelDict)
         if self.method not in ('cmp', 'locomp'):

@@ -22,7 +22,7 @@ import numpy as np
 import scipy.sparse
 
 from . import _native
-from .modeling import Atom, ConvolutionalMatchingPursuit, _compute_dtype
+from .modeling import Atom, ConvolutionalMatchingPursuit, _compute_dtype, reject_ragged
 from .utils import overlapAdd, peek
 
 logger = logging.getLogger(__name__)
@@ -101,12 +101,13 @@ class LoCOMP(ConvolutionalMatchingPursuit):
     _method = _native.METHOD_LOCOMP      # computeCoefficientsBatch of the base class then runs the device loop of hscmp_locomp.h
 
     def computeCoefficientsBatch(self, sequences, D, nbNonzeroCoefs=None, toleranceResidualScale=None, toleranceSnr=None, nbBlocks=1,
-                                 minCoefficients=1e-16, weights=None, stopCondition=None, maxEvents=None):
+                                 minCoefficients=1e-16, weights=None, stopCondition=None, maxEvents=None, lengths=None):
         """The B signals of `sequences` side by side, one workgroup each, through the LoCOMP atom body of the greedy-loop kernel
         (csrc/hscmp_locomp.h: neighbourhood from the device slot list, normal equations of the group in LDS, group update and
         re-correlation in the kernel).  A signal with a neighbourhood beyond the kernel's capacity (stop reason 'group') is
         taken again by the host loop below; so is every call with a stopCondition (its argument there is the coefficient matrix,
         :1397) or with verbose plots.  Returns a BatchResult like the base class."""
+        reject_ragged(sequences, lengths, 'LoCOMP.computeCoefficientsBatch (the LoCOMP device loop)')
         if stopCondition is not None or self.verbose or self.refit == 'host' or os.environ.get('HSCMP_LOCOMP_HOST') == '1':
             return self._batch_on_host(sequences, D, nbNonzeroCoefs, toleranceResidualScale, toleranceSnr, nbBlocks, minCoefficients, weights,
                                        stopCondition)

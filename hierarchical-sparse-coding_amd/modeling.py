@@ -177,18 +177,73 @@ def _slots_to_csc(slot_t, slot_k, slot_a, n, shape, minCoefficients):
     return m
 
 
+def is_ragged(sequences, lengths=None):
+    """True for the ragged forms of a batch: a list / tuple of signals, or a padded array with `lengths`."""
+    return isinstance(sequences, (list, tuple)) or lengths is not None
+
+
+def reject_ragged(sequences, lengths, what):
+    """The entry points without a ragged form say so before any device work."""
+    if is_ragged(sequences, lengths):
+        raise NotImplementedError('%s has no ragged form (signals of different lengths): pass one length per call, or use '
+                                  'ConvolutionalMatchingPursuit.computeCoefficientsBatch' % what)
+
+
+def ragged_batch(sequences, lengths, dtype, W, F):
+    """The padded form of a ragged batch, checked on the host: (x [B,T,F] of `dtype` with T the longest length, lengths int32 [B],
+    per-signal views [T_b] / [T_b,F] of the caller's data).  `sequences`: a list / tuple of arrays [T_b] or [T_b,F], or an array
+    [B,T(,F)] with lengths [B].  Rows of the padding are zero here; the engine never reads them."""
+    if isinstance(sequences, (list, tuple)):
+        if lengths is not None:
+            raise ValueError('lengths= goes with a padded array, not with a list of signals')
+        seqs = [np.asarray(q) for q in sequences]
+        if len(seqs) == 0:
+            raise ValueError('a ragged batch needs at least one signal')
+        nd = seqs[0].ndim
+        if nd not in (1, 2) or any(q.ndim != nd for q in seqs):
+            raise ValueError('the signals of a ragged batch must all be [T_b] or all be [T_b,F]')
+        for b, q in enumerate(seqs):
+            fb = 1 if nd == 1 else q.shape[1]
+            if fb != F:
+                raise ValueError('signal %d has %d features, the dictionary %d' % (b, fb, F))
+        lens = np.array([q.shape[0] for q in seqs], dtype=np.int64)
+    else:
+        seq = np.asarray(sequences)
+        if seq.ndim not in (2, 3):
+            raise ValueError('a padded ragged batch is [B,T] or [B,T,F]')
+        fb = 1 if seq.ndim == 2 else seq.shape[2]
+        if fb != F:
+            raise ValueError('the signals have %d features, the dictionary %d' % (fb, F))
+        lens = np.asarray(lengths).astype(np.int64).reshape(-1)
+        if lens.shape[0] != seq.shape[0]:
+            raise ValueError('lengths has %d entries for %d signals' % (lens.shape[0], seq.shape[0]))
+        seqs = [seq[b, :max(0, int(lens[b]))] for b in range(seq.shape[0])]
+        if np.any(lens > seq.shape[1]):
+            b = int(np.argmax(lens > seq.shape[1]))
+            raise ValueError('signal %d: length %d beyond the padded length %d' % (b, lens[b], seq.shape[1]))
+    if np.any(lens < W):
+        b = int(np.argmax(lens < W))
+        raise ValueError('signal %d: length %d is shorter than the filters (W=%d)' % (b, lens[b], W))
+    B, T = len(seqs), int(lens.max())
+    x = np.zeros((B, T, F), dtype=dtype)
+    for b, q in enumerate(seqs):
+        x[b, :q.shape[0]] = q.reshape((q.shape[0], F))
+    return x, lens.astype(np.int32), seqs
+
+
 class BatchResult(object):
     """Per-signal outputs of computeCoefficientsBatch (everything the reference returns, plus the
     ordered selection trace the reference only logs)."""
 
-    def __init__(self, coefficients, residuals, events, stats, energies, variant, kernel_ms):
-        self.coefficients = coefficients      # list of csc_matrix float64 [T,K]
-        self.residuals = residuals            # [B,T] or [B,T,F]
+    def __init__(self, coefficients, residuals, events, stats, energies, variant, kernel_ms, lengths=None):
+        self.coefficients = coefficients      # list of csc_matrix float64 [T,K] ([T_b,K] in a ragged batch)
+        self.residuals = residuals            # [B,T] or [B,T,F]; a ragged batch: list of [T_b] or [T_b,F]
         self.events = events                  # list of (t int32[n], k int32[n], c dtype[n]) in selection order
         self.stats = stats                    # int32 [B,8], hscmp.h HSCMP_STAT_*
         self.energies = energies              # float64 [B,2]: signal, tracked residual
         self.variant = variant
         self.kernel_ms = kernel_ms
+        self.lengths = lengths                # int32 [B] of a ragged batch, else None
 
     def stop_reasons(self):
         if self.stats is None:                # (a result of LoCOMP's host loop, which keeps no per-signal counters)
@@ -274,19 +329,37 @@ class ConvolutionalMatchingPursuit(SparseApproximator):
     # ---------------------------------------------------------------------------------------
     def computeCoefficientsBatch(self, sequences, D, nbNonzeroCoefs=None, toleranceResidualScale=None,
                                  toleranceSnr=None, nbBlocks=1, minCoefficients=1e-16, weights=None,
-                                 stopCondition=None, maxEvents=None):
+                                 stopCondition=None, maxEvents=None, lengths=None):
         """Batch form of computeCoefficients: `sequences` is [B,T] (D [K,W]) or [B,T,F] (D [K,W,F]).
         The B signals are independent (no cross-signal term in modeling.py:1053-1186) and are
-        encoded concurrently, one persistent workgroup each.  Returns a BatchResult."""
-        assert sequences.ndim == 2 or sequences.ndim == 3
+        encoded concurrently, one persistent workgroup each.  Returns a BatchResult.
+        Signals of different lengths (a ragged batch): `sequences` a list / tuple of arrays [T_b] or [T_b,F], or a padded array
+        [B,T(,F)] with `lengths` [B]; every signal gets exactly what computeCoefficients gives it alone, the result holds
+        per-signal residuals [T_b(,F)] and coefficients [T_b,K]."""
         assert D.ndim == 2 or D.ndim == 3
+        ragged = is_ragged(sequences, lengths)
+        method = getattr(self, '_method', _native.METHOD_CMP)       # (hsc_amd.locomp.LoCOMP: the loop with the group re-fit)
+        if ragged and method != _native.METHOD_CMP:
+            raise NotImplementedError('the LoCOMP loop has no ragged form (signals of different lengths)')
         eps = float(np.finfo(D.dtype).eps) if np.issubdtype(D.dtype, np.floating) else float(np.finfo(np.float64).eps)
-        dt = _compute_dtype(sequences.dtype, D.dtype)
-        B, T = sequences.shape[0], sequences.shape[1]
-        x = np.ascontiguousarray(sequences.reshape((B, T, -1)), dtype=dt)
-        D3 = np.ascontiguousarray(D.reshape((D.shape[0], D.shape[1], -1)), dtype=dt)
-        K, W, F = D3.shape
-        assert F == x.shape[2]
+        if ragged:
+            src_dtype = np.result_type(*[np.asarray(q).dtype for q in sequences]) if isinstance(sequences, (list, tuple)) else np.asarray(sequences).dtype
+            dt = _compute_dtype(src_dtype, D.dtype)
+            D3 = np.ascontiguousarray(D.reshape((D.shape[0], D.shape[1], -1)), dtype=dt)
+            K, W, F = D3.shape
+            x, lens, seqs = ragged_batch(sequences, lengths, dt, W, F)
+            B, T = x.shape[0], x.shape[1]
+            out_ndim = 1 if (seqs[0].ndim == 1 or D.ndim == 2) else 2
+        else:
+            assert sequences.ndim == 2 or sequences.ndim == 3
+            src_dtype = sequences.dtype
+            dt = _compute_dtype(sequences.dtype, D.dtype)
+            B, T = sequences.shape[0], sequences.shape[1]
+            x = np.ascontiguousarray(sequences.reshape((B, T, -1)), dtype=dt)
+            D3 = np.ascontiguousarray(D.reshape((D.shape[0], D.shape[1], -1)), dtype=dt)
+            K, W, F = D3.shape
+            assert F == x.shape[2]
+            lens, seqs = None, None
         if weights is not None:
             assert len(weights) == K
         eng = _native.engine_for(self.device, D3, None if weights is None else np.asarray(weights, dtype=dt))
@@ -296,18 +369,20 @@ class ConvolutionalMatchingPursuit(SparseApproximator):
         per_round = stopCondition is not None
         params = _native.make_params(nbNonzeroCoefs, toleranceResidualScale, toleranceSnr, nbBlocks,
                                      minCoefficients, eps, maxEvents, 1 if per_round else 0)
-        method = getattr(self, '_method', _native.METHOD_CMP)       # (hsc_amd.locomp.LoCOMP: the loop with the group re-fit)
         if method != _native.METHOD_CMP:
             eng.set_method(method)
         try:
-            eng.encode_batch(x, params)
+            if ragged:
+                eng.encode_batch_ragged(x, lens, params)
+            else:
+                eng.encode_batch(x, params)
         finally:
             if method != _native.METHOD_CMP:
                 eng.set_method(_native.METHOD_CMP)                   # (engines are shared; a resumed batch keeps its own loop)
         kernel_ms = list(eng.last_kernel_ms())
         while True:
             if per_round:
-                self._run_with_callback(eng, sequences, D, K, T, minCoefficients, stopCondition)
+                self._run_with_callback(eng, seqs if ragged else sequences, D, K, T, minCoefficients, stopCondition, lens)
             stats = eng.fetch_stats()
             if not np.any(stats[:, _native.STAT_STOP] == _native.STOP_CAPACITY):
                 break
@@ -329,13 +404,20 @@ class ConvolutionalMatchingPursuit(SparseApproximator):
         coefficients, events = [], []
         for b in range(B):
             ne, ns = int(stats[b, _native.STAT_EVENTS]), int(stats[b, _native.STAT_SLOTS])
-            coefficients.append(_slots_to_csc(st[b], sk[b], sa[b], ns, (T, K), minCoefficients))
+            coefficients.append(_slots_to_csc(st[b], sk[b], sa[b], ns, (T if lens is None else int(lens[b]), K), minCoefficients))
             events.append((ev_t[b, :ne].copy(), ev_k[b, :ne].copy(), ev_c[b, :ne].copy()))
-        if sequences.ndim == 2 or D.ndim == 2:
-            residuals = np.squeeze(residuals, axis=2)                      # modeling.py:1183-1184
-        if residuals.dtype != sequences.dtype and np.issubdtype(sequences.dtype, np.floating):
-            residuals = residuals.astype(sequences.dtype)
-        res = BatchResult(coefficients, residuals, events, stats, energies, eng.last_variant(), kernel_ms)
+        cast = residuals.dtype != src_dtype and np.issubdtype(src_dtype, np.floating)
+        if ragged:
+            # per-signal residuals of the signal's own length, shaped like computeCoefficients' (modeling.py:1183-1186)
+            residuals = [residuals[b, :int(lens[b])] for b in range(B)]
+            residuals = [r[:, 0] if out_ndim == 1 else r for r in residuals]
+            residuals = [r.astype(src_dtype) if cast else r.copy() for r in residuals]
+        else:
+            if sequences.ndim == 2 or D.ndim == 2:
+                residuals = np.squeeze(residuals, axis=2)                  # modeling.py:1183-1184
+            if cast:
+                residuals = residuals.astype(sequences.dtype)
+        res = BatchResult(coefficients, residuals, events, stats, energies, eng.last_variant(), kernel_ms, lens)
         self.lastResult = res
         if self.verbose:
             for b in range(B):
@@ -347,9 +429,10 @@ class ConvolutionalMatchingPursuit(SparseApproximator):
                 stats[b, _native.STAT_DUPLICATES], _native.STOP_NAMES.get(int(stats[b, _native.STAT_STOP]))))
         return res
 
-    def _run_with_callback(self, eng, sequences, D, K, T, minCoefficients, stopCondition):
+    def _run_with_callback(self, eng, sequences, D, K, T, minCoefficients, stopCondition, lengths=None):
         """modeling.py:1155-1158: stopCondition(sequence, residual, coefficients) after every
-        selection round.  One GPU launch per round; the callback sees host copies."""
+        selection round.  One GPU launch per round; the callback sees host copies (a ragged batch: `sequences` the per-signal
+        arrays, and the signal's own [T_b(,F)] views and [T_b,K] matrix)."""
         while True:
             stats = eng.fetch_stats()
             running = np.where(stats[:, _native.STAT_STOP] == _native.STOP_RUNNING)[0]
@@ -359,11 +442,12 @@ class ConvolutionalMatchingPursuit(SparseApproximator):
             residuals = eng.fetch_residual()
             for b in running:
                 ns = int(stats[b, _native.STAT_SLOTS])
-                coef = scipy.sparse.lil_matrix((T, K))
+                Tb = T if lengths is None else int(lengths[b])
+                coef = scipy.sparse.lil_matrix((Tb, K))
                 if ns > 0:
                     coef[st[b, :ns], sk[b, :ns]] = sa[b, :ns]
-                seq = sequences[b].reshape((T, -1))                        # the reference passes [T,F] views
-                if stopCondition(seq, residuals[b], coef):
+                seq = np.asarray(sequences[b]).reshape((Tb, -1))           # the reference passes [T,F] views
+                if stopCondition(seq, residuals[b, :Tb], coef):
                     logger.warning('Custom stop condition reached: considering convergence is achieved')
                     eng.stop_signal(int(b))
             eng.continue_rounds(1)
@@ -394,6 +478,7 @@ class ConvolutionalSparseCoder(object):
         return self.approximator.computeCoefficients(X, self.D, *args, **kwargs)
 
     def encodeBatch(self, X, *args, **kwargs):
+        """X [B,T(,F)], or a ragged batch: a list / tuple of [T_b(,F)] arrays, or a padded array with lengths=."""
         return self.approximator.computeCoefficientsBatch(X, self.D, *args, **kwargs)
 
     def reconstruct(self, coefficients):

@@ -208,6 +208,8 @@ def encode_sharded(sequences_shard, D, encode_fn=None, gather=True, residuals=Fa
       'energies' float64 [B_total, 2]     'coefficients' list of csc_matrix (rebuilt from the events)
       'residuals' [B_total, T(,F)] or None     'bytes_per_signal' gathered payload per signal
     """
+    from .modeling import reject_ragged
+    reject_ragged(sequences_shard, kwargs.get('lengths'), 'parallel.encode_sharded (the multi-GPU gather)')
     dist = _dist()
     if encode_fn is None:
         import os

@@ -158,6 +158,17 @@ int hscmp_encode_batch(hscmp_ctx* ctx, const void* x, int B, int T, const hscmp_
  * context's stream. */
 int hscmp_encode_batch_device(hscmp_ctx* ctx, const void* x_dev, int B, int T, const hscmp_params* params);
 
+/* A batch of signals of different lengths in one call: x [B][T][F] with T the longest length, lengths host int32 [B] with
+ * W <= lengths[b] <= T.  Signal b is encoded exactly as hscmp_encode_batch would encode x[b][0:lengths[b]] alone (its
+ * zero padding, reflection, blocks and stop rules at its own end); rows t >= lengths[b] of x are never read and may hold
+ * anything.  The context keeps the lengths for hscmp_continue, hscmp_grow_events, hscmp_stop_signal and the fetches until
+ * the next encode; fetched arrays keep the [B][T] strides, and hscmp_fetch_residual returns zeros in rows >= lengths[b].
+ * HSCMP_ERR_INVALID for B < 1, lengths == NULL or a length out of range (hscmp_last_error names the signal);
+ * HSCMP_ERR_UNSUPPORTED under HSCMP_METHOD_LOCOMP and for inputs that take the sparse (multi-feature) kernels.
+ * hscmp_last_variant ends in "_ragged".  The _device form takes x in GPU memory and is asynchronous on the context's stream. */
+int hscmp_encode_batch_ragged(hscmp_ctx* ctx, const void* x, int B, int T, const int32_t* lengths, const hscmp_params* params);
+int hscmp_encode_batch_ragged_device(hscmp_ctx* ctx, const void* x_dev, int B, int T, const int32_t* lengths, const hscmp_params* params);
+
 /* Level chaining of the hierarchical encoder (modeling.py:1489, `input = levelCoefficients.todense()`),
  * entirely on the device: the accumulated coefficients of signals [first, first+count) of `prev`
  * (its distinct (t,k) slots, clipped like the CSC epilogue modeling.py:1171-1181 with
