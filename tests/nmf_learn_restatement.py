@@ -16,16 +16,17 @@ import numpy as np
 from tests.nmf_restatement import STOP_MAX_ITERATIONS, STOP_RESIDUAL_SCALE, STOP_SNR, reconstruct
 
 
-def learn(sequence, D_init, A0, nbMaxIterations=None, toleranceResidualScale=None, toleranceSnr=None):
+def learn(sequence, D_init, A0, nbMaxIterations=None, toleranceResidualScale=None, toleranceSnr=None, dtype=np.float64):
     """sequence [T] or [T,F], D_init [K,W] or [K,W,F], A0 [T,K] the initial coefficients.
-    Returns (D [K,W,F], iterations, stop code, snr, residualScale), float64."""
-    X = np.asarray(sequence, dtype=np.float64).reshape((sequence.shape[0], -1))
-    D3 = np.array(D_init, dtype=np.float64).reshape((D_init.shape[0], D_init.shape[1], -1))
+    Returns (D [K,W,F], iterations, stop code, snr, residualScale), D in `dtype` (float32: the same sums in numpy's
+    float32 arithmetic, for the round-off spread of a float32 run)."""
+    X = np.asarray(sequence, dtype=dtype).reshape((sequence.shape[0], -1))
+    D3 = np.array(D_init, dtype=dtype).reshape((D_init.shape[0], D_init.shape[1], -1))
     T, (K, W, F) = X.shape[0], D3.shape
     if W < 2 or T < W:
         raise Exception('bad shape: T = %d, W = %d' % (T, W))
     L = T - W + 1
-    A = np.array(A0[:L], dtype=np.float64)
+    A = np.array(A0[:L], dtype=dtype)
     energySignal = np.sum(np.square(X))
     maxIt = 1 if nbMaxIterations is None else nbMaxIterations
     it = 0

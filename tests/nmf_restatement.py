@@ -13,25 +13,28 @@ STOP_MAX_ITERATIONS, STOP_RESIDUAL_SCALE, STOP_SNR = 1, 2, 3
 
 
 def reconstruct(A, D3, T):
-    """A [L,K] (L = T-W+1), D3 [K,W,F] -> [T,F]: each P[s, j] = sum_k A[s,k] D[k,j,:] lands on sample s+j."""
+    """A [L,K] (L = T-W+1), D3 [K,W,F] -> [T,F] in A's dtype: each P[s, j] = sum_k A[s,k] D[k,j,:] lands on sample
+    s+j, the W products of a sample summed in ascending j."""
     K, W, F = D3.shape
     L = A.shape[0]
-    out = np.zeros((T, F), dtype=np.float64)
+    P = A.dot(D3.reshape((K, W * F))).reshape((L, W, F))
+    out = np.zeros((T, F), dtype=A.dtype)
     for j in range(W):
-        out[j:j + L] += np.einsum('sk,kf->sf', A, D3[:, j, :])
+        out[j:j + L] += P[:, j, :]
     return out
 
 
-def nmf(sequence, D, A0, nbMaxIterations=None, toleranceResidualScale=None, toleranceSnr=None):
+def nmf(sequence, D, A0, nbMaxIterations=None, toleranceResidualScale=None, toleranceSnr=None, dtype=np.float64):
     """sequence [T] or [T,F], D [K,W] or [K,W,F], A0 [T,K] the initial coefficients.
-    Returns (coefficientsCentered [T,K], residual [T,F], iterations, stop code, snr, residualScale), float64."""
-    X = np.asarray(sequence, dtype=np.float64).reshape((sequence.shape[0], -1))
-    D3 = np.asarray(D, dtype=np.float64).reshape((D.shape[0], D.shape[1], -1))
+    Returns (coefficientsCentered [T,K], residual [T,F], iterations, stop code, snr, residualScale), every array in
+    `dtype` (float32: the same sums in numpy's float32 arithmetic, for the round-off spread of a float32 run)."""
+    X = np.asarray(sequence, dtype=dtype).reshape((sequence.shape[0], -1))
+    D3 = np.asarray(D, dtype=dtype).reshape((D.shape[0], D.shape[1], -1))
     T, (K, W, F) = X.shape[0], D3.shape
     if W < 2 or T < W:
         raise Exception('bad shape: T = %d, W = %d' % (T, W))
     L = T - W + 1
-    A = np.array(A0[:L], dtype=np.float64)
+    A = np.array(A0[:L], dtype=dtype)
     energySignal = np.sum(np.square(X))
     maxIt = 1 if nbMaxIterations is None else nbMaxIterations
     it = 0
@@ -54,7 +57,7 @@ def nmf(sequence, D, A0, nbMaxIterations=None, toleranceResidualScale=None, tole
         else:
             continue
         break
-    coef = np.zeros((T, K), dtype=np.float64)
+    coef = np.zeros((T, K), dtype=dtype)
     off = (W - 1) // 2
     coef[off:off + L] = A
     return coef, residual, it, stop, snr, rs
