@@ -32,11 +32,15 @@ __device__ unsigned long long g_cnt[16];         // free-form event counters of 
 // tools/read_stamps.py / tools/hsc_stamps.py through hscmp_debug_stamps(); never compiled into the product library
 #define HSCMP_STAMP(i) do { if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { const unsigned long long now_ = clock64(); g_stamps[i] += now_ - stamp_last_; stamp_last_ = now_; } } while (0)
 #define HSCMP_STAMP_BEGIN() unsigned long long stamp_last_ = clock64()
+#define HSCMP_STAMP_PARAM , unsigned long long& stamp_last_     // a callee that stamps on its caller's clock
+#define HSCMP_STAMP_ARG , stamp_last_
 #define HSCMP_COUNT(i) (g_stamps[i] += 1)
 #define HSCMP_TALLY(i, v) do { if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) g_cnt[i] += (unsigned long long)(v); } while (0)
 #else
 #define HSCMP_STAMP(i) do {} while (0)
 #define HSCMP_STAMP_BEGIN() do {} while (0)
+#define HSCMP_STAMP_PARAM
+#define HSCMP_STAMP_ARG
 #define HSCMP_COUNT(i) ((void)0)
 #define HSCMP_TALLY(i, v) do {} while (0)
 #endif

@@ -604,14 +604,19 @@ template <typename SH> __device__ __forceinline__ FusedCtl fused_ctl_fetch(const
 
 // Positions whose bound (hscmp_bound.h) the select step of the current selection replaced by the exact score
 // (MfmaRecorr::refine), and the segment maxima that changed with them.  Every wave of the signal builds the same list
-// (wave-uniform, computed redundantly: no barrier).  It reaches memory only behind the atom's first barrier
+// (wave-uniform; the exact loops compute it redundantly, without a barrier, and the waves of the bound loop all merge
+// the same four records of the refine's exchange).  It reaches memory only behind the atom's first barrier
 // (MfmaRecorr::apply_atom): until every wave has finished its selection, no wave may see another wave's refines, or
 // their views of the state -- and with them their selections -- could part.
 constexpr int kRefineCap = 4;
 template <typename R> struct RefineList {
     int n;
+    unsigned nx;                                                 // bound loop: exchanges of this launch so far; the low bit names the slot set of the next
     int t[kRefineCap]; R s[kRefineCap]; int g[kRefineCap];       // refined position, exact score, group hint
     int sg[kRefineCap]; R ms[kRefineCap]; int mt[kRefineCap];    // its segment and that segment's maximum after the refine
+    // bound loop: the entry with the largest score, lowest position among equals -- if the selection's winner is in the list, it is
+    // that entry, by the selection's own rule -- with the lowest atom attaining its score and that atom's pinned chain (hk = -1: not kept)
+    int ht, hk; R hs, hc;
     // exact score / hint of t if the list holds it (a later entry never repeats a position)
     __device__ __forceinline__ bool find(int tq, R& so, int& go) const
     {
@@ -620,6 +625,18 @@ template <typename R> struct RefineList {
         for (int i = 0; i < kRefineCap; ++i)
             if (i < n && t[i] == tq) { so = s[i]; go = g[i]; f = true; }
         return f;
+    }
+    // entry (tq, so) joins the list with atom ko and chain co: does it lead?  (exact scores are >= 0 and finite, see refine)
+    __device__ __forceinline__ void lead(int tq, R so, int ko, R co)
+    {
+        if (n == 0 || so > hs || (so == hs && tq < ht)) { ht = tq; hs = so; hk = ko; hc = co; }
+    }
+    // (k, c) of the selection's winner tq if this selection refined it and the refine kept them
+    __device__ __forceinline__ bool find_atom(int tq, int& ko, R& co) const
+    {
+        if (n == 0 || ht != tq || hk < 0) return false;
+        ko = hk; co = hc;
+        return true;
     }
 };
 
@@ -1109,7 +1126,7 @@ __global__ __launch_bounds__(kThreads * Recorr::kGroup, Recorr::kMinWavesPerSimd
 
     FusedCtl fc = fused_ctl_fetch(sh);                   // (behind the barrier above; only the fused bodies keep it current)
     RefineList<R> rl;                                    // (fused bodies: refines of the current selection, see RefineList)
-    rl.n = 0;
+    rl.n = 0; rl.nx = 0u;
     HSCMP_STAMP_BEGIN();
     for (int round = 0; P.max_rounds <= 0 || round < P.max_rounds; ++round) {
         if constexpr (Recorr::kMinWavesPerSimd >= 4) asm volatile("" : "+v"(tid));     // (register-constrained builds only)
@@ -1166,13 +1183,23 @@ __global__ __launch_bounds__(kThreads * Recorr::kGroup, Recorr::kMinWavesPerSimd
                         R s_ex; int g_ex;
                         if (rl.find(p_sel, s_ex, g_ex)) break;                 // refined by this selection: exact
                         if (__builtin_amdgcn_readfirstlane(G.bk[p_sel]) != -1) break;   // an exact score
+                        // Every wave of the signal comes here or none does: bound_init is a launch parameter, and the winner, its
+                        // best_k and the list derive from state (segment maxima, scores, hints) that nobody writes between the
+                        // previous atom's last barrier and this atom's B1 -- refines stay in the list until then, or go to memory
+                        // between the full list's two barriers, which all four waves pass -- so the four waves decide alike.  The
+                        // barriers below (the full list's two, the one of the bound loop's refine) rest on that: no refine result may
+                        // reach memory earlier than it does.
                         if (rl.n == kRefineCap) {                              // (rare) the list is full: commit it, behind
                             sy.full();                                         // every wave's reads of the state ...
                             if (tid == 0) Recorr::refine_commit(G, sh, rl, INT_MAX, INT_MIN, INT_MAX, INT_MIN);
                             sy.full();                                         // ... and before anybody's next read
                             rl.n = 0;
                         }
-                        Recorr::refine_position(P, G, A, plds, rl, p_sel, lane);
+                        HSCMP_STAMP(48);                                       // segment-maxima scan(s) in front of a refine
+                        HSCMP_MARK("refine");
+                        Recorr::refine_position(P, G, A, plds, rl, p_sel, lane, sy);
+                        HSCMP_MARK("select");
+                        HSCMP_STAMP(52);                                       // the refine (49 + 50 + 51, stamped inside)
                     } else {
                         break;
                     }

@@ -906,6 +906,11 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
 #ifndef HSCMP_QUAD_LOCKSTEP
 #define HSCMP_QUAD_LOCKSTEP 0
 #endif
+    // -DHSCMP_REFINE_HANDOVER=0 (measurement only): the bound loop's atom body resolves (k, c) again instead of taking them from
+    // the refine of its selection (DESIGN.md section 11 times the two steps apart).
+#ifndef HSCMP_REFINE_HANDOVER
+#define HSCMP_REFINE_HANDOVER 1
+#endif
     static constexpr bool kLockstep = GS > 1 && HSCMP_QUAD_LOCKSTEP != 0;
     static constexpr int kMinWavesPerSimd = GS;         // (launch bounds: 4 signals x 4 waves = 4 waves per SIMD)
     using Sync = typename std::conditional<GS == 1, HwSync, SoftSync>::type;
@@ -916,6 +921,8 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     static constexpr int kBook = 192;           // bookkeeping thread: lane 0 of wave 3, idle while waves 0.. rescan segments
     using R = typename Tile::R;
     static constexpr int TP = Tile::TP;
+    // (BOUND) the refine's exchange: two sets of one 16-byte record {score bits, k, c bits, -} per wave of the signal
+    static constexpr int kRefineSlotBytes = 2 * kWaves * 16;
     static __device__ __forceinline__ const R* weights(const DevParams&, const State<R>& S, const MfmaArgsT<R>&, char*) { return S.weights; }
     static __device__ __forceinline__ void on_atom(const DevParams&, const State<R>&, const MfmaArgsT<R>&, char*, int, int) {}
     static __device__ __forceinline__ bool update_residual(const DevParams&, const State<R>&, const Sig<R>&, const MfmaArgsT<R>&, char*, int, int, R,
@@ -936,6 +943,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
         R* dimg; R* wts; R* win; R* esq; R* sbs; unsigned* bloom;
         R* rwin; R* rwin_w; unsigned long long* edge;
         unsigned short* bimg; unsigned short* xh; unsigned short* xl;      // (BOUND) the planes; the window's bf16 hi / lo
+        int* rx;                                                           // (BOUND) the refine's exchange slots (see refine)
         int nwin, wp, nsbmax, nplane;
     };
 
@@ -958,7 +966,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     {
         const size_t relems = (size_t)window_floats(P.W, A.S4) + 2 * 8 * A.S4 + (size_t)segbuf_len_p(P) + 8 * A.S4 + kWaves * 8 * A.S4;
         return relems * sizeof(R) + kBloomWords * sizeof(unsigned) + kEdgeWords * sizeof(unsigned long long) +
-               (BOUND ? (size_t)2 * window_floats(P.W, A.S4) * sizeof(unsigned short) : 0);
+               (BOUND ? (size_t)2 * window_floats(P.W, A.S4) * sizeof(unsigned short) + kRefineSlotBytes : 0);
     }
     static __host__ __device__ size_t per_signal_lds_bytes(const DevParams& P, const Args& A)
     {
@@ -997,6 +1005,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
         L.edge = reinterpret_cast<unsigned long long*>(L.rwin_w + kWaves * L.wp);
         L.xh = reinterpret_cast<unsigned short*>(L.edge + kEdgeWords);
         L.xl = L.xh + L.nwin;
+        L.rx = reinterpret_cast<int*>(L.xl + L.nwin);        // (16-byte aligned: every region in front is a multiple of 16 bytes)
         return L;
     }
 
@@ -1123,7 +1132,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     }
 
     // ---- refining a bound --------------------------------------------------------------
-    // Position t holds an upper bound (best_k[t] == -1): its exact score and group hint, by every wave for itself.
+    // Position t holds an upper bound (best_k[t] == -1): its exact score and group hint.
     // Two passes write bounds: the initial correlation (over the zero-padded signal) and, in the bound loop, the
     // re-correlation of an applied atom (over the reflect-padded window of the moment).  Exactness: the window of a row
     // that holds a bound has not changed since the bound was written.  Every later atom whose support overlaps the
@@ -1135,27 +1144,74 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     // kind of row, exactly the window the pass that wrote the bound saw, and the pinned chain of every atom over it
     // (bit for bit the MFMA chain) reproduces the score and the hint the exact tile would have written there.
     // The residual is the engine's own buffer: a caller's input that changes between resumed rounds does not matter.
+    //
+    // Who computes it.  The exact loops: every wave for itself, all K chains, no barrier (k_out = -1: nothing to hand on).
+    // The bound loop (its vector ALU is the full unit, and a chain over the planes is ~400 vector instructions): the
+    // signal's four waves share the K chains.  Every wave still loads the window into its own strip (no exchange in
+    // front of the chains); wave q takes the atoms 64 q + lane + 256 j and reduces them to one record -- the largest
+    // |c w_k| as bits, the lowest k attaining it, the c of that k; a wave or lane without atoms carries score -1, k =
+    // INT_MAX, as in the one-wave reduction.  Lane 0 writes the record to the wave's slot, the waves meet at ONE barrier,
+    // and every wave reads the four slots and merges them in wave order by the tie rule of the reduction (larger score,
+    // compared as bits; then lower k).  All four waves merge the same four records, so they hold the same (s, g = k >> 5,
+    // k, c): their selections cannot part.  And the result is what one wave would have found over all K atoms: a maximum
+    // and the lowest index attaining it do not depend on how the atoms are split.
+    // Slots: two sets, taken in turn by the count of exchanges (nx, wave-uniform and equal in the four waves, which
+    // refine alike -- see the call in iterate_kernel).  A wave that has left barrier n may write set (n + 1) & 1 for the
+    // next refine while a slow wave still reads set n & 1; it cannot write set n & 1 again before it has left barrier
+    // n + 1, which waits for the slow wave's arrival, behind that wave's reads of exchange n (the LDS executes a wave's
+    // operations in issue order).  Barriers of the atom body in between only add to that.
     static __device__ __forceinline__ void refine(const DevParams& P, const Sig<R>& Gs, const Args& A, char* lds, int t, int lane,
-                                                  R& s_out, int& g_out)
+                                                  Sync& sy, unsigned nx, R& s_out, int& g_out, int& k_out, R& c_out HSCMP_STAMP_PARAM)
     {
         const Layout L = layout(P, A, lds);
         const int S4 = S4C > 0 ? S4C : A.S4;
-        R* rw = L.rwin_w + (ltid() >> 6) * L.wp;            // this wave's strip (taps past W stay zero)
+        const int wv = __builtin_amdgcn_readfirstlane(ltid() >> 6);
+        R* rw = L.rwin_w + wv * L.wp;                       // this wave's strip (taps past W stay zero)
         __builtin_amdgcn_wave_barrier();
         for (int w = lane; w < P.W; w += 64) rw[w] = edge_window_value(Gs.r, P.T, t - P.off + w, t, L.edge);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
-        // lane l: atoms l, l + 64, ...; the score of the tile (|c * w_k|, max over atoms) and the lowest atom attaining it,
-        // whose group is the tile's hint (mfma_tile_score: the lowest group that holds an atom attaining the maximum)
-        R best = (R)-1;
+        HSCMP_MARK("refine_chains");
+        // lane l: atoms l, l + 64, ... (bound loop: of this wave's share); the score of the tile (|c * w_k|, max over atoms) and
+        // the lowest atom attaining it, whose group is the tile's hint (mfma_tile_score: the lowest group that holds an atom
+        // attaining the maximum)
+        R best = (R)-1, bc = (R)0;
         int bk = INT_MAX;
-        for (int k = lane; k < P.K; k += 64) {
+        for (int k = (BOUND ? 64 * wv : 0) + lane; k < P.K; k += (BOUND ? 64 * kWaves : 64)) {
             const R c = dchain(L, rw, k, S4);
             const R v = HAS_W ? rabs(c * L.wts[k]) : rabs(c);
-            if (v > best) { best = v; bk = k; }
+            if (v > best) { best = v; bk = k; bc = c; }
         }
-        const int mb = wave_max_i32(__float_as_int(best));   // scores are >= 0 and finite here: bit order is value order
-        const int kmin = wave_min_i32(__float_as_int(best) == mb ? bk : INT_MAX);
+        int mb = wave_max_i32(__float_as_int(best));   // scores are >= 0 and finite here: bit order is value order
+        int kmin = wave_min_i32(__float_as_int(best) == mb ? bk : INT_MAX);
+        k_out = -1; c_out = (R)0;
+        if constexpr (BOUND) {
+            HSCMP_MARK("refine_exchange");
+            HSCMP_STAMP(49);                                // window + this wave's chains
+            int cb = __float_as_int(wave_bcast(bc, kmin & 63));             // (lane of atom k: k & 63)
+            int4* slot = reinterpret_cast<int4*>(L.rx) + (nx & 1u) * kWaves;
+            if (lane == 0) slot[wv] = make_int4(mb, kmin, cb, 0);
+            sy.lds();
+            const int4 rec = slot[lane & (kWaves - 1)];     // one read; record q in lanes q, q + 4, ...
+            mb = __builtin_amdgcn_readlane(rec.x, 0); kmin = __builtin_amdgcn_readlane(rec.y, 0); cb = __builtin_amdgcn_readlane(rec.z, 0);
+#pragma unroll
+            for (int q = 1; q < kWaves; ++q) {
+                const int sq = __builtin_amdgcn_readlane(rec.x, q), kq = __builtin_amdgcn_readlane(rec.y, q), cq = __builtin_amdgcn_readlane(rec.z, q);
+                if (sq > mb || (sq == mb && kq < kmin)) { mb = sq; kmin = kq; cb = cq; }
+            }
+            k_out = kmin; c_out = __int_as_float(cb);
+#ifdef HSCMP_DBG_CHECKSEG
+            // diagnostic build: wave 0 publishes what it merged, the others compare (two more barriers: every wave has read the
+            // records before wave 0 overwrites one, and has compared before the set is written again)
+            sy.lds();
+            if (wv == 0 && lane == 0) slot[0] = make_int4(mb, kmin, cb, 0);
+            sy.lds();
+            const int4 pub = slot[0];
+            if (lane == 0 && (pub.x != mb || pub.y != kmin || pub.z != cb)) atomicAdd(&g_cnt[2], 1ull);
+            if (wv == 0 && lane == 0) atomicAdd(&g_cnt[3], 1ull);           // exchanges checked
+            sy.lds();
+#endif
+        }
         s_out = __int_as_float(mb);
         g_out = kmin >> 5;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1165,11 +1221,14 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     // refine t and append it to the list, with the new maximum of its segment (the stored scores of the segment, this
     // selection's refined ones in place of their bounds)
     static __device__ __forceinline__ void refine_position(const DevParams& P, const Sig<R>& Gs, const Args& A, char* lds,
-                                                           RefineList<R>& rl, int t, int lane)
+                                                           RefineList<R>& rl, int t, int lane, Sync& sy)
     {
-        R s_ex;
-        int g_ex;
-        refine(P, Gs, A, lds, t, lane, s_ex, g_ex);
+        R s_ex, c_ex;
+        int g_ex, k_ex;
+        HSCMP_STAMP_BEGIN();
+        refine(P, Gs, A, lds, t, lane, sy, rl.nx, s_ex, g_ex, k_ex, c_ex HSCMP_STAMP_ARG);
+        HSCMP_STAMP(BOUND ? 50 : 49);                       // the exchange: slot, barrier, merge (exact loops: window + all chains)
+        HSCMP_MARK("refine_rescan");
 #ifdef HSCMP_DBG_STAMPS
         if (blockIdx.x == 0 && threadIdx.x == 0) g_stamps[13] += 1;       // refines of signal 0 (g_stamps[15]: its atoms)
 #endif
@@ -1178,6 +1237,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
         // (constant indices only: the list stays in registers)
 #pragma unroll
         for (int j = 0; j < kRefineCap; ++j) if (j == i) { rl.t[j] = t; rl.s[j] = s_ex; rl.g[j] = g_ex; }
+        if constexpr (BOUND) { rl.lead(t, s_ex, k_ex, c_ex); rl.nx += 1u; }
         rl.n = i + 1;
         const int t0 = sg << P.seg_shift, t1 = min(P.T, t0 + P.seg);
         const int per = P.seg >> 6;                         // consecutive positions per lane (wave_argmax_first)
@@ -1195,6 +1255,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
         const int bt = __builtin_amdgcn_readfirstlane(best.i);
 #pragma unroll
         for (int j = 0; j < kRefineCap; ++j) if (j == i) { rl.sg[j] = sg; rl.ms[j] = best.s; rl.mt[j] = bt; }
+        HSCMP_STAMP(51);                                    // rescan of the refined position's segment
     }
 
     // the list to memory (one thread): scores outside the rows [rlo, rhi] (those the atom re-correlates and stores itself),
@@ -1253,7 +1314,15 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
         const int segbase = (sg0 << P.seg_shift);
         const int nsb = min(T, ((sg1 + 1) << P.seg_shift)) - segbase;    // positions of the touched segments
 
-        if (resolved) { k = __builtin_amdgcn_readfirstlane(k); c = wave_bcast(c, 0); }
+        // (bound loop) the position was refined by this selection -- in the bound loop every row holds a bound, so every
+        // winner is: the refine's record is the first atom attaining the maximum and its pinned chain over the same window,
+        // exactly what resolve_group returns from the hinted group.  No window load, no strip write, no second pass over
+        // the group's chains; the null test and the duplicate check run as for a resolved-here (k, c).  A winner that holds
+        // an exact score from memory (the exact fallback tile, HSCMP_EXACT_RECORR=1) was not refined and resolves below.
+        bool handed = false;
+        if constexpr (BOUND && HSCMP_REFINE_HANDOVER != 0) { if (!resolved) handed = rl.find_atom(p, k, c); }
+        const bool known = resolved || handed;              // (uniform)
+        if (known) { k = __builtin_amdgcn_readfirstlane(k); c = wave_bcast(c, 0); }
         HSCMP_MARK("A_loads");
         // ---- phase A: every global load of this atom, issued together -------------------------
         // first what the longest chain of the atom waits for: the position's window and its group hint.  EVERY wave
@@ -1267,7 +1336,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
         R wres[2] = {(R)0, (R)0};                               // W <= 128: two taps per lane
         R rv[2] = {(R)0, (R)0}; int rm[2] = {-1, -1};
         if (interior) {
-            if (!resolved) {
+            if (!known) {
                 gh = Gs.bk[p];
 #pragma unroll
                 for (int u = 0; u < kUW; ++u) if (lane + 64 * u < W) wres[u] = Gs.r[p - P.off + lane + 64 * u];
@@ -1278,7 +1347,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
                 if (i < span) { rm[u] = tstart + i; rv[u] = Gs.r[rm[u]]; }
             }
         } else {
-            if (!resolved) {
+            if (!known) {
                 gh = Gs.bk[p];
 #pragma unroll
                 for (int u = 0; u < kUW; ++u) if (lane + 64 * u < W) wres[u] = edge_window_value(Gs.r, T, p - P.off + lane + 64 * u, p, L.edge);
@@ -1305,7 +1374,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
                 R so; int go;
 #pragma unroll
                 for (int u = 0; u < 2; ++u) if (rl.find(segbase + tid + u * kThreads, so, go)) os[u] = so;
-                if (!resolved && rl.find(p, so, go)) gh = go;
+                if (!known && rl.find(p, so, go)) gh = go;
             }
         }
 #pragma unroll
@@ -1324,14 +1393,16 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
         HSCMP_MARK("resolve");
         // ---- resolve (k, c) of the selected position (:970) ------------------------------------
         if (!resolved) {
-            R* rw = L.rwin_w + wv * L.wp;                   // this wave's strip
+            if (!handed) {
+                R* rw = L.rwin_w + wv * L.wp;               // this wave's strip
 #pragma unroll
-            for (int u = 0; u < kUW; ++u) if (lane + 64 * u < W) rw[lane + 64 * u] = wres[u];
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            resolve_group(P, L, rw, gh, lane, S4, k, c);
-            k = __builtin_amdgcn_readfirstlane(k);
-            c = wave_bcast(c, 0);
+                for (int u = 0; u < kUW; ++u) if (lane + 64 * u < W) rw[lane + 64 * u] = wres[u];
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_wave_barrier();
+                resolve_group(P, L, rw, gh, lane, S4, k, c);
+                k = __builtin_amdgcn_readfirstlane(k);
+                c = wave_bcast(c, 0);
+            }
             if (P.has_thres && !(fabs((double)c) > P.thres)) {  // :974 null coefficient: empty selection
                 // (with a residual-scale rule the reference tests that rule first, :1145-1153: the slow rules name the reason)
                 if (tid == 0) {

@@ -23,6 +23,9 @@ for i, nm in enumerate(names):
     print('  %-18s %8.0f cycles/atom' % (nm, v[i] / n))
 for i, nm in ((8, 'phase A issue'), (9, 'resolve (Bx..By)'), (10, '[return -> next round]'), (11, '[selection + round checks]'), (12, '[atom body incl. entry]')):
     print('  %-18s %8.0f cycles/atom' % (nm, v[i] / n))
+# the selection in front of the atom body, split (float32 loops that refine bounds; 11 above is what the pieces leave: the last scan and the round's checks)
+for i, nm in ((48, '  scan(s) before a refine'), (49, '  refine: window + chains'), (50, '  refine: exchange'), (51, '  refine: segment rescan'), (52, '  [refine, whole]')):
+    print('  %-26s %8.0f cycles/atom' % (nm, v[i] / n))
 print('  %-18s %8.0f cycles/atom (sum; the select between atoms is not stamped)' % ('total', (v[:8].sum() + v[8] + v[9]) / n))
 print('  refines per selection %.3f (%d; bound pass of the initial correlation and bound loop)' % (v[13] / n, v[13]))
 
