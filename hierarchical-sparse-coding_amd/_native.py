@@ -334,11 +334,12 @@ class Engine(object):
         key = _dictionary_key(D3, w)
         if key == getattr(self, '_dict_key', None):
             return
+        # (a failed call leaves the context without a dictionary and without a batch: say the same here first)
         self._dict_key = None
+        self.dtype = self.K = self.W = self.F = self._batch = None
         self._check(self._lib.hscmp_set_dictionary(self._h, _ptr(D3), K, W, F, code, _ptr(w)), 'hscmp_set_dictionary')
         self._dict_key = key
         self.dtype, self.K, self.W, self.F = D3.dtype, K, W, F
-        self._batch = None
         # (a table opened under the previous dictionary is retired: engine_for recycles its least recently used engine, and a
         #  handle that outlived that must fail loudly instead of reading a table of another dictionary)
         self._table_generation = getattr(self, '_table_generation', 0) + 1

@@ -28,7 +28,8 @@ using namespace hscmp;
 
 // The environment knobs (field x is HSCMP_X): tests and diagnostics force a path with them, every path
 // bit-identical.  read_knobs is the only reader of the environment: each entry point takes one snapshot when it is called and
-// passes it down, and an encode keeps its snapshot in its plan, so hscmp_continue resumes with it.
+// passes it down, and an encode keeps its snapshot in its plan, so hscmp_continue resumes with it.  The snapshot also arms
+// HSCMP_ALLOC_FAIL_AT for the call (DevBuf::alloc counts from it), so every entry point that allocates takes one.
 struct Knobs {
     bool no_dict_lists, no_row_lists, no_rowbits, no_pairing, force_gathered, force_generic;     // set or not
     bool init_only, exact_init, exact_recorr, locomp_no_mfma, no_sorted_prepare, no_lazy_clear;
@@ -37,6 +38,53 @@ struct Knobs {
     int slot_hash_min, locomp_group_cap, locomp_ahead, sorted_prepare_min, lds_pad;     // the value, or the default
     int epi_lds_keys;                     // the value if a power of two in 64..kEpiLdsKeys, else kEpiLdsKeys
     bool epi_lds_keys_set;                // ... set at all, valid or not (the epilogue's LDS floor is then 8 KB instead of 64 KB)
+    int alloc_fail_at;                    // tests: the n-th device allocation of the call fails as on a full card; 0: not set
+};
+
+// One device allocation, owned: freed by the destructor, handed on by move.  Every hipMalloc / hipFree of the engine is in here.
+// A buffer that queued kernels may still read is freed by replace(), grow() and the destructor alike: waiting for the stream
+// first is the caller's part.  Knows nothing of contexts or messages: the callers turn the hipError_t into a status.
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;           // bytes
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); o.release(); return *this; }
+    ~DevBuf() { release(); }
+    template <typename T> T* as() const { return (T*)p; }
+    bool holds(size_t bytes) const { return p && cap >= bytes; }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    // Holds at least `bytes` afterwards, contents lost.  Too small: freed FIRST, then exactly `bytes` allocated (the residual
+    // buffer is gigabytes: old and new together would not fit); a failure leaves the buffer empty.
+    hipError_t replace(size_t bytes)
+    {
+        if (holds(bytes)) return hipSuccess;
+        release();
+        const hipError_t e = alloc(&p, bytes);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    // Holds at least `bytes` afterwards, 1/8 more allocated than asked.  `keep`: the old contents are copied over.  The old
+    // buffer is freed last: a failure leaves it untouched.  *failed_bytes: the size of an allocation that failed.
+    hipError_t grow(size_t bytes, bool keep, size_t* failed_bytes)
+    {
+        if (holds(bytes)) return hipSuccess;
+        DevBuf fresh;
+        const size_t want = bytes + bytes / 8 + 256;
+        hipError_t e = alloc(&fresh.p, want);
+        if (e != hipSuccess) { *failed_bytes = want; return e; }
+        fresh.cap = want;
+        if (keep && p && (e = hipMemcpy(fresh.p, p, cap, hipMemcpyDeviceToDevice)) != hipSuccess) return e;
+        *this = std::move(fresh);
+        return hipSuccess;
+    }
+    // HSCMP_ALLOC_FAIL_AT (tests): read_knobs arms it for the calling thread's entry point; the n-th allocation behind it answers
+    // what hipMalloc answers on a full card, and HIP is not called
+    static inline thread_local int fail_at = 0, count = 0;
+    static hipError_t alloc(void** out, size_t bytes)
+    {
+        return fail_at > 0 && ++count == fail_at ? hipErrorOutOfMemory : hipMalloc(out, bytes);
+    }
 };
 
 static Knobs read_knobs()
@@ -59,6 +107,8 @@ static Knobs read_knobs()
     k.epi_lds_keys_set = (v = getenv("HSCMP_EPI_LDS_KEYS"));
     const int n = v ? atoi(v) : 0;
     k.epi_lds_keys = n >= 64 && n <= kEpiLdsKeys && (n & (n - 1)) == 0 ? n : kEpiLdsKeys;
+    k.alloc_fail_at = (v = getenv("HSCMP_ALLOC_FAIL_AT")) ? atoi(v) : 0;
+    DevBuf::fail_at = k.alloc_fail_at; DevBuf::count = 0;
     return k;
 }
 
@@ -82,62 +132,69 @@ struct EncodePlan {
     Knobs knobs{};            // the encode's snapshot: the launches read pairing, row bitmaps and LDS pad from it
 };
 
+// The dictionary and everything derived from it: replaced as a whole by hscmp_set_dictionary (dtype < 0: none set).
+struct Dictionary {
+    int K = 0, W = 0, F = 0, dtype = -1;
+    DevBuf D;
+    DevBuf w;                 // empty when no weights
+    DevBuf Dfrag;             // MFMA fragment-ordered copy (F == 1)
+    DevBuf Bimg;              // bf16 hi / lo (/ rem) planes of the bound passes (f32, F == 1, dictionary inside its model: hscmp_bound.h)
+    float bound_cmax = 0.0f;            // >= max_k ||d_k|| |w_k|
+    bool bound_loop_image = false;      // Bimg also holds the rem plane: hi, lo, rem rebuild every element (the bound loop's image)
+    DevBuf Dt;                // [W][F][K] transposed copy for the sparsity-aware kernels (F > 1)
+    DevBuf Dc;                // [K][F][W] chain-ordered copy for the dense chains (F > 1)
+    DevBuf nzptr, nzwf, nzval;          // CSR of the dictionary's non-zeros per atom, chain order (sparse level dictionaries)
+    int dict_nnz = 0;
+    DevBuf fptr, fkw, fval;             // the same non-zeros grouped by feature
+};
+
+// The buffers of a batch, each grown on its own by ensure_workspace_g (replace: freed, then allocated), hscmp_grow_events aside.
+struct Workspace {
+    DevBuf x;                 // staging for host inputs
+    DevBuf resid, best_c, best_k, ev_t, ev_k, ev_c, slot_t, slot_k, slot_a, sel_t, sel_k, sel_c, stats, energy, edge, scratch;
+    DevBuf rowflag;           // [B][T] non-zero input rows handed over by the level chaining
+    DevBuf rl_cnt, rl_f;      // per-row feature lists of the residual's possibly non-zero cells (sparse dictionaries)
+    DevBuf hkey, hval;        // slot hash table [B][hmask+1]
+    DevBuf head;              // [B][T] slot chains by position (round-parallel loop)
+    DevBuf lgram;             // [B][kLgramDoubles] LoCOMP: Gram matrices beyond the LDS copy
+    DevBuf geom;              // [B][kGeomWords] of a ragged batch
+};
+
+// Workspace arena of the entry points outside the batch encode (grow-only, lives as long as the context): the hierarchical
+// epilogue's buffers, then those of the row-level entry points and the device-resident table
+enum { kArenaEpiRep, kArenaEpiOffsets, kArenaEpiN, kArenaEpiColptr, kArenaEpiIndices, kArenaEpiData, kArenaEpiOut, kArenaEpiKeys,
+       kArenaRowA, kArenaRowB, kArenaRowC, kArenaRowD, kArenaTable, kArenaTabRes, kArenaTabW, kArenaEpiEnergy, kArenaSlots };
+
+// The batch state and what it rests on (include/hscmp.h, "What a failed call leaves behind"):
+//  - a call that may replace the dictionary or a workspace buffer first drops what depends on it (drop_batch), in front of its
+//    first allocation; a failed hscmp_set_dictionary leaves no dictionary, a failed encode no batch, and every entry point
+//    answers either with HSCMP_ERR_STATE before it queues anything;
+//  - have_batch, ragged, geom, P, plan, B / T / cap / maxsel, last and last_x_dev are written together (commit_batch), after the
+//    last launch of the encode has been queued without error;
+//  - listed_rows, rowflag_valid and rl_filled describe buffer contents, not the batch: they follow the writes to those buffers.
 struct hscmp_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     std::string err;
     std::string variant = "none";
-    // dictionary
-    int K = 0, W = 0, F = 0, dtype = -1;
-    void* d_D = nullptr;
-    void* d_w = nullptr;      // nullptr when no weights
-    void* d_Dfrag = nullptr;  // MFMA fragment-ordered copy (f32, F == 1)
-    unsigned short* d_Bimg = nullptr;   // bf16 hi / lo (/ rem) planes of the bound passes (f32, F == 1, dictionary inside its model: hscmp_bound.h)
-    float bound_cmax = 0.0f;            // >= max_k ||d_k|| |w_k|
-    bool bound_loop_image = false;      // d_Bimg also holds the rem plane: hi, lo, rem rebuild every element (the bound loop's image)
-    void* d_Dt = nullptr;     // [W][F][K] transposed copy for the sparsity-aware kernels (F > 1)
-    void* d_Dc = nullptr;     // [K][F][W] chain-ordered copy for the dense chains (F > 1)
-    void* d_scratch = nullptr;
-    int* d_nzptr = nullptr;   // CSR of the dictionary's non-zeros per atom, chain order (sparse level dictionaries)
-    int* d_nzwf = nullptr;
-    void* d_nzval = nullptr;
-    int dict_nnz = 0;
-    int* d_fptr = nullptr;    // the same non-zeros grouped by feature
-    int* d_fkw = nullptr;
-    void* d_fval = nullptr;
-    int* d_rl_cnt = nullptr;  // per-row feature lists of the residual's possibly non-zero cells (sparse dictionaries)
-    int* d_rl_f = nullptr;
+    Dictionary dict;
+    Workspace ws;
+    DevBuf arena[kArenaSlots];
     bool rl_filled = false;   // the lists of the current input were written by the level chaining
-    // rows of d_resid (x F float64) that a chained encode left behind with every possibly non-zero cell named by
-    // d_rl_cnt / d_rl_f: the next chained encode clears those cells instead of the whole buffer (0: clear everything)
+    // rows of ws.resid (x F float64) that a chained encode left behind with every possibly non-zero cell named by
+    // ws.rl_cnt / ws.rl_f: the next chained encode clears those cells instead of the whole buffer (0: clear everything)
     int64_t listed_rows = 0;
     int listed_F = 0;
-    unsigned char* d_rowflag = nullptr;  // [B][T] non-zero input rows handed over by the level chaining
     bool rowflag_valid = false;
-    size_t Dfrag_bytes = 0;
-    // batch workspace
+    // the batch
     int B = 0, T = 0, cap = 0, maxsel = 0;
     bool have_batch = false;
-    size_t caps[16] = {0};
-    size_t cap_scratch = 0, cap_rowflag = 0, cap_rl_cnt = 0, cap_rl_f = 0;
-    void* d_x = nullptr;      // staging for host inputs
-    void* d_resid = nullptr; void* d_best_c = nullptr; int* d_best_k = nullptr;
-    int* d_ev_t = nullptr; int* d_ev_k = nullptr; void* d_ev_c = nullptr;
-    int* d_slot_t = nullptr; int* d_slot_k = nullptr; double* d_slot_a = nullptr;
-    unsigned long long* d_hkey = nullptr; int* d_hval = nullptr;   // slot hash table [B][hmask+1]
-    int* d_head = nullptr;     // [B][T] slot chains by position (round-parallel loop)
-    double* d_lgram = nullptr; // [B][kLgramDoubles] LoCOMP: Gram matrices beyond the LDS copy
-    size_t cap_hkey = 0, cap_hval = 0, cap_head = 0, cap_lgram = 0;
-    int* d_sel_t = nullptr; int* d_sel_k = nullptr; void* d_sel_c = nullptr;
-    int* d_stats = nullptr; void* d_energy = nullptr; unsigned long long* d_edge = nullptr;
     DevParams P{};
-    // ragged batch (hscmp_encode_batch_ragged): per signal {length, block size, block count} on the host and the device, until the
+    // ragged batch (hscmp_encode_batch_ragged): per signal {length, block size, block count} on the host and in ws.geom, until the
     // next encode of any kind; the batch's P.T is the longest length and every per-signal array keeps that stride
     bool ragged = false;
     std::vector<int> geom;
-    int* d_geom = nullptr;
-    size_t cap_geom = 0;
     hscmp_params last{};
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool timed = false;
@@ -145,14 +202,17 @@ struct hscmp_ctx {
     int method = 0;                 // hscmp_set_method: 0 = greedy pursuit (modeling.py:1053), 1 = LoCOMP (:1267)
     EncodePlan plan;                // the kernels of the last encode (hscmp_continue resumes its loop)
     const void* last_x_dev = nullptr;   // device address of the signals of the last encode (hscmp_hierarchy_epilogue reads them)
-    // workspace arena of the entry points outside the batch encode (grow-only, lives as long as the context): slots
-    // 0-7 the hierarchical epilogue, 8-15 the row-level entry points and the device-resident table
-    void* d_epi[16] = {nullptr};
-    size_t cap_epi[16] = {0};
     // device-resident inner-product table of LoCOMP (hscmp_table_*): [T][K] in slot kArenaTable, its residual in kArenaTabRes
     int tab_T = 0;
 };
-enum { kArenaRowA = 8, kArenaRowB = 9, kArenaRowC = 10, kArenaRowD = 11, kArenaTable = 12, kArenaTabRes = 13, kArenaTabW = 14, kArenaEpiEnergy = 15 };
+
+// In front of the first allocation of a call that replaces workspace buffers (dictionary: or the dictionary, which a resident
+// table and the listed rows belong to as well).
+static void drop_batch(hscmp_ctx* ctx, bool dictionary = false)
+{
+    ctx->have_batch = false; ctx->ragged = false; ctx->geom.clear();
+    if (dictionary) { ctx->tab_T = 0; ctx->listed_rows = 0; }
+}
 
 static thread_local std::string g_err;
 
@@ -176,27 +236,22 @@ static int fail(hscmp_ctx* ctx, int code, const char* fmt, ...)
 
 static size_t esize(int dtype) { return dtype == HSCMP_F64 ? 8 : 4; }
 
+static int alloc_failed(hscmp_ctx* ctx, size_t bytes, hipError_t e)
+{
+    return fail(ctx, HSCMP_ERR_ALLOC, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+}
+
 // Arena slot i holds at least `bytes` afterwards.  Grow-only: a call that fits reuses the buffer (no hipMalloc in the
 // steady state of any entry point); a call that does not fit waits for the stream (kernels may still read the old
-// buffer), frees and allocates 1/8 more than asked.  `keep`: the old contents are copied over.
+// buffer) and grows the slot (DevBuf::grow).  `keep`: the old contents are copied over.
 static int epi_buffer(hscmp_ctx* ctx, int i, size_t bytes, bool keep = false)
 {
-    if (ctx->d_epi[i] && ctx->cap_epi[i] >= bytes) return HSCMP_OK;
+    if (ctx->arena[i].holds(bytes)) return HSCMP_OK;
     hipError_t e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return fail(ctx, HSCMP_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
-    const size_t want = bytes + bytes / 8 + 256;
-    void* fresh = nullptr;
-    e = hipMalloc(&fresh, want);
-    if (e != hipSuccess) return fail(ctx, HSCMP_ERR_ALLOC, "hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
-    if (ctx->d_epi[i]) {
-        if (keep && (e = hipMemcpy(fresh, ctx->d_epi[i], ctx->cap_epi[i], hipMemcpyDeviceToDevice)) != hipSuccess) {
-            (void)hipFree(fresh);
-            return fail(ctx, HSCMP_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
-        }
-        (void)hipFree(ctx->d_epi[i]);
-    }
-    ctx->d_epi[i] = fresh; ctx->cap_epi[i] = want;
-    return HSCMP_OK;
+    size_t failed_bytes = 0;
+    if ((e = ctx->arena[i].grow(bytes, keep, &failed_bytes)) == hipSuccess) return HSCMP_OK;
+    return failed_bytes ? alloc_failed(ctx, failed_bytes, e) : fail(ctx, HSCMP_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
 }
 
 extern "C" int hscmp_version(void) { return HSCMP_VERSION; }
@@ -228,23 +283,14 @@ extern "C" int hscmp_create(hscmp_ctx** out, int device_id)
     return HSCMP_OK;
 }
 
-static void free_all(hscmp_ctx* c)
-{
-    for (void* p : c->d_epi) if (p) (void)hipFree(p);
-    void* ptrs[] = {c->d_D, c->d_w, c->d_Dfrag, c->d_Bimg, c->d_Dt, c->d_Dc, c->d_nzptr, c->d_nzwf, c->d_nzval, c->d_fptr, c->d_fkw, c->d_fval, c->d_rl_cnt, c->d_rl_f, c->d_scratch, c->d_rowflag, c->d_x, c->d_resid, c->d_best_c, c->d_best_k, c->d_ev_t, c->d_ev_k, c->d_ev_c,
-                    c->d_slot_t, c->d_slot_k, c->d_slot_a, c->d_hkey, c->d_hval, c->d_head, c->d_lgram, c->d_sel_t, c->d_sel_k, c->d_sel_c, c->d_stats, c->d_energy, c->d_edge, c->d_geom};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-}
-
 extern "C" void hscmp_destroy(hscmp_ctx* ctx)
 {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    free_all(ctx);
     for (int i = 0; i < 4; ++i) if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx;               // (the buffers free themselves)
 }
 
 extern "C" int hscmp_set_method(hscmp_ctx* ctx, int method)
@@ -272,31 +318,34 @@ extern "C" int hscmp_synchronize(hscmp_ctx* ctx)
     return HSCMP_OK;
 }
 
+// A dictionary buffer of its own: `bytes` from the host, in a fresh allocation of at least `room` bytes (lists may be empty).
+static int upload(hscmp_ctx* ctx, DevBuf& buf, const void* src, size_t bytes, size_t room = 0)
+{
+    const hipError_t e = buf.replace(std::max(bytes, room));
+    if (e != hipSuccess) return alloc_failed(ctx, std::max(bytes, room), e);
+    HIP_TRY(ctx, hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice));
+    return HSCMP_OK;
+}
+
 extern "C" int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W, int F, hscmp_dtype dtype, const void* weights)
 {
-    if (ctx) { ctx->tab_T = 0; ctx->listed_rows = 0; }     // a resident table belongs to the dictionary it was built with
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_set_dictionary: ctx is NULL");
     if (!D || K <= 0 || W <= 0 || F <= 0) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_set_dictionary: bad shape K=%d W=%d F=%d", K, W, F);
     if (dtype != HSCMP_F32 && dtype != HSCMP_F64) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_set_dictionary: bad dtype %d", (int)dtype);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const Knobs kn = read_knobs();
+    // the old dictionary goes before the new one is allocated (the two need not fit side by side), and with it the batch and
+    // the resident table that were computed with it; the new one is built aside and moved in whole, so a failure on the way
+    // leaves "no dictionary set"
+    drop_batch(ctx, true);
+    ctx->dict = Dictionary{};
+    Dictionary d;
+    d.K = K; d.W = W; d.F = F; d.dtype = dtype;
     const size_t es = esize(dtype);
     const size_t nD = (size_t)K * W * F * es;
-    if (ctx->d_D) { (void)hipFree(ctx->d_D); ctx->d_D = nullptr; }
-    if (ctx->d_w) { (void)hipFree(ctx->d_w); ctx->d_w = nullptr; }
-    if (ctx->d_Dfrag) { (void)hipFree(ctx->d_Dfrag); ctx->d_Dfrag = nullptr; ctx->Dfrag_bytes = 0; }
-    if (ctx->d_Bimg) { (void)hipFree(ctx->d_Bimg); ctx->d_Bimg = nullptr; }
-    ctx->bound_loop_image = false;
-    if (ctx->d_Dt) { (void)hipFree(ctx->d_Dt); ctx->d_Dt = nullptr; }
-    if (ctx->d_Dc) { (void)hipFree(ctx->d_Dc); ctx->d_Dc = nullptr; }
-    if (ctx->d_nzptr) { (void)hipFree(ctx->d_nzptr); ctx->d_nzptr = nullptr; }
-    if (ctx->d_nzwf) { (void)hipFree(ctx->d_nzwf); ctx->d_nzwf = nullptr; }
-    if (ctx->d_nzval) { (void)hipFree(ctx->d_nzval); ctx->d_nzval = nullptr; }
-    if (ctx->d_fptr) { (void)hipFree(ctx->d_fptr); ctx->d_fptr = nullptr; }
-    if (ctx->d_fkw) { (void)hipFree(ctx->d_fkw); ctx->d_fkw = nullptr; }
-    if (ctx->d_fval) { (void)hipFree(ctx->d_fval); ctx->d_fval = nullptr; }
-    HIP_TRY(ctx, hipMalloc(&ctx->d_D, nD));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_D, D, nD, hipMemcpyHostToDevice));
+    int rc;
+    if ((rc = upload(ctx, d.D, D, nD))) return rc;
     // weights that are all exactly 1 select like no weights at all (|c * 1| == |c| bit for bit; the level-0 weights of the
     // hierarchical encoder, modeling.py:1448-1450 with no singletons): the unweighted kernels are the cheaper instances
     if (weights) {
@@ -305,13 +354,7 @@ extern "C" int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W,
             all_one = dtype == HSCMP_F32 ? ((const float*)weights)[k] == 1.0f : ((const double*)weights)[k] == 1.0;
         if (all_one) weights = nullptr;
     }
-    if (weights) {
-        HIP_TRY(ctx, hipMalloc(&ctx->d_w, (size_t)K * es));
-        HIP_TRY(ctx, hipMemcpy(ctx->d_w, weights, (size_t)K * es, hipMemcpyHostToDevice));
-    }
-    ctx->K = K; ctx->W = W; ctx->F = F; ctx->dtype = dtype;
-    ctx->have_batch = false;
-    ctx->ragged = false;
+    if (weights && (rc = upload(ctx, d.w, weights, (size_t)K * es))) return rc;
     if (F > 1) {
         // Dt[w][f][k] = D[k][w][f]: atom index contiguous, for the gathered-window kernels
         std::vector<char> dt(nD);
@@ -319,18 +362,16 @@ extern "C" int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W,
             for (int w = 0; w < W; ++w)
                 for (int f = 0; f < F; ++f)
                     memcpy(&dt[(((size_t)w * F + f) * K + k) * es], (const char*)D + (((size_t)k * W + w) * F + f) * es, es);
-        HIP_TRY(ctx, hipMalloc(&ctx->d_Dt, nD));
-        HIP_TRY(ctx, hipMemcpy(ctx->d_Dt, dt.data(), nD, hipMemcpyHostToDevice));
+        if ((rc = upload(ctx, d.Dt, dt.data(), nD))) return rc;
         // Dc[k][f][w] = D[k][w][f]: consecutive addresses along the pinned chain (f outer, w inner)
         for (int k = 0; k < K; ++k)
             for (int w = 0; w < W; ++w)
                 for (int f = 0; f < F; ++f)
                     memcpy(&dt[(((size_t)k * F + f) * W + w) * es], (const char*)D + (((size_t)k * W + w) * F + f) * es, es);
-        HIP_TRY(ctx, hipMalloc(&ctx->d_Dc, nD));
-        HIP_TRY(ctx, hipMemcpy(ctx->d_Dc, dt.data(), nD, hipMemcpyHostToDevice));
+        if ((rc = upload(ctx, d.Dc, dt.data(), nD))) return rc;
         // per-atom list of non-zeros in chain order (f outer, w inner), kept when the dictionary is sparse
         // (level dictionaries built from decompositions + singletons, hsc/dataset.py:137-194, 826-860)
-        if (W <= 32767 && F <= 65535 && !read_knobs().no_dict_lists) {
+        if (W <= 32767 && F <= 65535 && !kn.no_dict_lists) {
             std::vector<int> ptr(K + 1, 0), wf;
             std::vector<char> val;
             const size_t limit = (size_t)kDictListMaxPerAtom * K;
@@ -348,16 +389,13 @@ extern "C" int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W,
                 ptr[k + 1] = (int)wf.size();
             }
             if (sparse) {
-                HIP_TRY(ctx, hipMalloc((void**)&ctx->d_nzptr, (K + 1) * sizeof(int)));
-                HIP_TRY(ctx, hipMemcpy(ctx->d_nzptr, ptr.data(), (K + 1) * sizeof(int), hipMemcpyHostToDevice));
-                HIP_TRY(ctx, hipMalloc((void**)&ctx->d_nzwf, std::max<size_t>(1, wf.size()) * sizeof(int)));
-                HIP_TRY(ctx, hipMemcpy(ctx->d_nzwf, wf.data(), wf.size() * sizeof(int), hipMemcpyHostToDevice));
-                HIP_TRY(ctx, hipMalloc(&ctx->d_nzval, std::max<size_t>(es, val.size())));
-                HIP_TRY(ctx, hipMemcpy(ctx->d_nzval, val.data(), val.size(), hipMemcpyHostToDevice));
+                if ((rc = upload(ctx, d.nzptr, ptr.data(), (K + 1) * sizeof(int)))) return rc;
+                if ((rc = upload(ctx, d.nzwf, wf.data(), wf.size() * sizeof(int), sizeof(int)))) return rc;
+                if ((rc = upload(ctx, d.nzval, val.data(), val.size(), es))) return rc;
                 // grouped by feature: counting sort of the per-atom lists
                 if (K <= 65535) {
                     const size_t nnz = wf.size();
-                    ctx->dict_nnz = (int)nnz;
+                    d.dict_nnz = (int)nnz;
                     std::vector<int> fp(F + 1, 0), kw(nnz);
                     std::vector<char> fv(std::max<size_t>(es, nnz * es));
                     for (size_t e = 0; e < nnz; ++e) fp[(wf[e] & 0xffff) + 1] += 1;
@@ -369,12 +407,9 @@ extern "C" int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W,
                             kw[o] = (int)(((unsigned)k << 16) | (unsigned)(wf[e] >> 16));
                             memcpy(&fv[(size_t)o * es], &val[(size_t)e * es], es);
                         }
-                    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_fptr, (F + 1) * sizeof(int)));
-                    HIP_TRY(ctx, hipMemcpy(ctx->d_fptr, fp.data(), (F + 1) * sizeof(int), hipMemcpyHostToDevice));
-                    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_fkw, std::max<size_t>(1, nnz) * sizeof(int)));
-                    HIP_TRY(ctx, hipMemcpy(ctx->d_fkw, kw.data(), nnz * sizeof(int), hipMemcpyHostToDevice));
-                    HIP_TRY(ctx, hipMalloc(&ctx->d_fval, fv.size()));
-                    HIP_TRY(ctx, hipMemcpy(ctx->d_fval, fv.data(), fv.size(), hipMemcpyHostToDevice));
+                    if ((rc = upload(ctx, d.fptr, fp.data(), (F + 1) * sizeof(int)))) return rc;
+                    if ((rc = upload(ctx, d.fkw, kw.data(), nnz * sizeof(int), sizeof(int)))) return rc;
+                    if ((rc = upload(ctx, d.fval, fv.data(), fv.size()))) return rc;
                 }
             }
         }
@@ -383,9 +418,7 @@ extern "C" int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W,
     if (dtype == HSCMP_F32 && mfma_supported<float>(K, W, F)) {
         std::vector<float> frag;
         mfma_build_dict_image((const float*)D, K, W, F, frag);
-        ctx->Dfrag_bytes = frag.size() * sizeof(float);
-        HIP_TRY(ctx, hipMalloc(&ctx->d_Dfrag, ctx->Dfrag_bytes));
-        HIP_TRY(ctx, hipMemcpy(ctx->d_Dfrag, frag.data(), ctx->Dfrag_bytes, hipMemcpyHostToDevice));
+        if ((rc = upload(ctx, d.Dfrag, frag.data(), frag.size() * sizeof(float)))) return rc;
         // the bound pass of the initial correlation (hscmp_bound.h): bf16 images no larger than the float32 one, and a
         // dictionary and weights inside the error model; otherwise every encode runs the exact initial correlation
         // (the third plane, rem, is for the four-signal loop's own bound tile: only if it rebuilds every element exactly)
@@ -394,18 +427,16 @@ extern "C" int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W,
         bool rem_exact = false;
         if ((size_t)2 * mfma_groups(K) * bound_steps(W) * 1024 <= TileF32::kMaxImageBytes &&
             bound_build_dict_image((const float*)D, (const float*)weights, K, W, bimg, cmax, rem_exact)) {
-            HIP_TRY(ctx, hipMalloc((void**)&ctx->d_Bimg, bimg.size() * sizeof(unsigned short)));
-            HIP_TRY(ctx, hipMemcpy(ctx->d_Bimg, bimg.data(), bimg.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-            ctx->bound_cmax = cmax;
-            ctx->bound_loop_image = rem_exact;
+            if ((rc = upload(ctx, d.Bimg, bimg.data(), bimg.size() * sizeof(unsigned short)))) return rc;
+            d.bound_cmax = cmax;
+            d.bound_loop_image = rem_exact;
         }
     } else if (dtype == HSCMP_F64 && mfma_supported<double>(K, W, F)) {
         std::vector<double> frag;
         mfma_build_dict_image_f64((const double*)D, K, W, frag);
-        ctx->Dfrag_bytes = frag.size() * sizeof(double);
-        HIP_TRY(ctx, hipMalloc(&ctx->d_Dfrag, ctx->Dfrag_bytes));
-        HIP_TRY(ctx, hipMemcpy(ctx->d_Dfrag, frag.data(), ctx->Dfrag_bytes, hipMemcpyHostToDevice));
+        if ((rc = upload(ctx, d.Dfrag, frag.data(), frag.size() * sizeof(double)))) return rc;
     }
+    ctx->dict = std::move(d);
     return HSCMP_OK;
 }
 
@@ -451,18 +482,15 @@ static int make_params_g(hscmp_ctx* ctx, const Knobs& kn, int K, int W, int F, i
 
 static int make_params(hscmp_ctx* ctx, const Knobs& kn, int B, int T, const hscmp_params* p, DevParams* out)
 {
-    return make_params_g(ctx, kn, ctx->K, ctx->W, ctx->F, B, T, p, out);
+    return make_params_g(ctx, kn, ctx->dict.K, ctx->dict.W, ctx->dict.F, B, T, p, out);
 }
-
-// every buffer tracks its own capacity in bytes (element size changes with the dictionary dtype)
-struct BufCap { void** p; size_t* cap; size_t bytes; };
 
 // Per-row feature lists: multi-feature inputs with a sparse dictionary (the per-atom lists tell which cells an
 // atom touches).
 constexpr int kRowListCap = 8;
 static bool use_row_lists(const hscmp_ctx* ctx, const Knobs& kn)
 {
-    return ctx->F > 1 && ctx->d_nzptr != nullptr && !kn.no_row_lists;
+    return ctx->dict.F > 1 && ctx->dict.nzptr.p != nullptr && !kn.no_row_lists;
 }
 
 // Workgroups per signal of the sparse initial correlation: enough to fill the chip at small batches.
@@ -472,80 +500,71 @@ static int sparse_init_split(int B, int T, int W)
     return std::max(1, std::min(nblocks, (2048 + B - 1) / B));
 }
 
-static int ensure_workspace_g(hscmp_ctx* ctx, const DevParams& P, bool need_x, size_t es, bool multi_feature, bool row_lists);
-static int ensure_workspace(hscmp_ctx* ctx, const DevParams& P, bool need_x, bool row_lists)
-{
-    return ensure_workspace_g(ctx, P, need_x, esize(ctx->dtype), ctx->F > 1, row_lists);
-}
+// Every workspace buffer holds what a batch of shape P needs afterwards (0 bytes: not needed, left as it is).  A buffer that is too
+// small is replaced, after one wait for the stream (the previous batch's kernels may still read it): on HSCMP_ERR_ALLOC some
+// buffers are gone, which is why the callers drop the batch first.  geom_bytes: the per-signal geometry of a ragged batch.
 // (element size and feature layout given explicitly: see make_params_g)
-static int ensure_workspace_g(hscmp_ctx* ctx, const DevParams& P, bool need_x, size_t es, bool multi_feature, bool row_lists)
+static int ensure_workspace_g(hscmp_ctx* ctx, const DevParams& P, bool need_x, size_t es, bool multi_feature, bool row_lists, size_t geom_bytes = 0)
 {
     const size_t B = P.B, TF = (size_t)P.T * P.F, T = P.T, cap = P.cap, ms = P.maxsel;
-    BufCap bufs[] = {
-        {(void**)&ctx->d_x, &ctx->caps[0], need_x ? B * TF * es : 0},
-        {(void**)&ctx->d_resid, &ctx->caps[1], B * TF * es},
-        {(void**)&ctx->d_best_c, &ctx->caps[2], B * T * es},
-        {(void**)&ctx->d_best_k, &ctx->caps[3], B * T * sizeof(int)},
-        {(void**)&ctx->d_ev_t, &ctx->caps[4], B * cap * 4},
-        {(void**)&ctx->d_ev_k, &ctx->caps[5], B * cap * 4},
-        {(void**)&ctx->d_ev_c, &ctx->caps[6], B * cap * es},
-        {(void**)&ctx->d_slot_t, &ctx->caps[7], B * cap * 4},
-        {(void**)&ctx->d_slot_k, &ctx->caps[8], B * cap * 4},
-        {(void**)&ctx->d_slot_a, &ctx->caps[9], B * cap * 8},
-        {(void**)&ctx->d_sel_t, &ctx->caps[10], B * 2 * ms * 4},
-        {(void**)&ctx->d_sel_k, &ctx->caps[11], B * 2 * ms * 4},
-        {(void**)&ctx->d_sel_c, &ctx->caps[12], B * 2 * ms * es},
-        {(void**)&ctx->d_stats, &ctx->caps[13], B * ST_COUNT * sizeof(int)},
-        {(void**)&ctx->d_energy, &ctx->caps[14], B * 2 * es},
-        {(void**)&ctx->d_edge, &ctx->caps[15], B * kEdgeWords * sizeof(unsigned long long)},
-        {(void**)&ctx->d_scratch, &ctx->cap_scratch, multi_feature ? B * (size_t)sparse_init_split(P.B, P.T, P.W) * (2 * P.W - 1) * P.K * es : 0},
-        {(void**)&ctx->d_rowflag, &ctx->cap_rowflag, multi_feature ? B * T : 0},
-        {(void**)&ctx->d_rl_cnt, &ctx->cap_rl_cnt, row_lists ? B * T * sizeof(int) : 0},
-        {(void**)&ctx->d_rl_f, &ctx->cap_rl_f, row_lists ? B * T * kRowListCap * sizeof(int) : 0},
-        {(void**)&ctx->d_hkey, &ctx->cap_hkey, B * ((size_t)P.hmask + 1) * sizeof(unsigned long long)},
-        {(void**)&ctx->d_hval, &ctx->cap_hval, B * ((size_t)P.hmask + 1) * sizeof(int)},
-        {(void**)&ctx->d_head, &ctx->cap_head, (P.blocked || ctx->method == HSCMP_METHOD_LOCOMP) ? B * T * sizeof(int) : 0},
-        {(void**)&ctx->d_lgram, &ctx->cap_lgram, ctx->method == HSCMP_METHOD_LOCOMP ? B * lgram_doubles(P.lg_cap) * sizeof(double) : 0},
+    const bool locomp = ctx->method == HSCMP_METHOD_LOCOMP;
+    Workspace& w = ctx->ws;
+    const struct { DevBuf& buf; size_t bytes; } want[] = {
+        {w.x, need_x ? B * TF * es : 0}, {w.resid, B * TF * es}, {w.best_c, B * T * es}, {w.best_k, B * T * sizeof(int)},
+        {w.ev_t, B * cap * 4}, {w.ev_k, B * cap * 4}, {w.ev_c, B * cap * es},
+        {w.slot_t, B * cap * 4}, {w.slot_k, B * cap * 4}, {w.slot_a, B * cap * 8},
+        {w.sel_t, B * 2 * ms * 4}, {w.sel_k, B * 2 * ms * 4}, {w.sel_c, B * 2 * ms * es},
+        {w.stats, B * ST_COUNT * sizeof(int)}, {w.energy, B * 2 * es}, {w.edge, B * kEdgeWords * sizeof(unsigned long long)},
+        {w.scratch, multi_feature ? B * (size_t)sparse_init_split(P.B, P.T, P.W) * (2 * P.W - 1) * P.K * es : 0},
+        {w.rowflag, multi_feature ? B * T : 0},
+        {w.rl_cnt, row_lists ? B * T * sizeof(int) : 0}, {w.rl_f, row_lists ? B * T * kRowListCap * sizeof(int) : 0},
+        {w.hkey, B * ((size_t)P.hmask + 1) * sizeof(unsigned long long)}, {w.hval, B * ((size_t)P.hmask + 1) * sizeof(int)},
+        {w.head, (P.blocked || locomp) ? B * T * sizeof(int) : 0},
+        {w.lgram, locomp ? B * lgram_doubles(P.lg_cap) * sizeof(double) : 0},
+        {w.geom, geom_bytes},
     };
     bool stream_idle = false;
-    for (const BufCap& b : bufs) {
-        if (b.bytes == 0 || (*b.p && *b.cap >= b.bytes)) continue;
+    for (const auto& b : want) {
+        if (b.bytes == 0 || b.buf.holds(b.bytes)) continue;
         if (!stream_idle) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); stream_idle = true; }
-        if (*b.p) { (void)hipFree(*b.p); *b.p = nullptr; *b.cap = 0; }
         ctx->listed_rows = 0;                   // (a fresh buffer knows nothing of the previous batch)
-        hipError_t e = hipMalloc(b.p, b.bytes);
-        if (e != hipSuccess) return fail(ctx, HSCMP_ERR_ALLOC, "hipMalloc(%zu bytes) failed: %s", b.bytes, hipGetErrorString(e));
-        *b.cap = b.bytes;
+        const hipError_t e = b.buf.replace(b.bytes);
+        if (e != hipSuccess) return alloc_failed(ctx, b.bytes, e);
     }
     return HSCMP_OK;
 }
+static int ensure_workspace(hscmp_ctx* ctx, const DevParams& P, bool need_x, bool row_lists, size_t geom_bytes = 0)
+{
+    return ensure_workspace_g(ctx, P, need_x, esize(ctx->dict.dtype), ctx->dict.F > 1, row_lists, geom_bytes);
+}
 
-template <typename R> static State<R> make_state(hscmp_ctx* c)
+// ragged: of the batch being encoded or resumed (its plan says so), not of the one the context may still hold
+template <typename R> static State<R> make_state(hscmp_ctx* c, bool ragged)
 {
     State<R> S;
-    S.D = (const R*)c->d_D; S.weights = (const R*)c->d_w;
-    S.Dc = c->d_Dc ? (const R*)c->d_Dc : (const R*)c->d_D;
-    S.residual = (R*)c->d_resid; S.best_c = (R*)c->d_best_c; S.best_k = c->d_best_k;
-    S.ev_t = c->d_ev_t; S.ev_k = c->d_ev_k; S.ev_c = (R*)c->d_ev_c;
-    S.slot_t = c->d_slot_t; S.slot_k = c->d_slot_k; S.slot_a = c->d_slot_a;
-    S.hkey = c->d_hkey; S.hval = c->d_hval; S.head = c->d_head; S.lgram = c->d_lgram;
-    S.sel_t = c->d_sel_t; S.sel_k = c->d_sel_k; S.sel_c = (R*)c->d_sel_c;
-    S.stats = c->d_stats; S.energy = (R*)c->d_energy; S.edge = c->d_edge;
-    S.geom = c->ragged ? c->d_geom : nullptr;
+    S.D = c->dict.D.as<const R>(); S.weights = c->dict.w.as<const R>();
+    S.Dc = c->dict.Dc.p ? c->dict.Dc.as<const R>() : c->dict.D.as<const R>();
+    S.residual = c->ws.resid.as<R>(); S.best_c = c->ws.best_c.as<R>(); S.best_k = c->ws.best_k.as<int>();
+    S.ev_t = c->ws.ev_t.as<int>(); S.ev_k = c->ws.ev_k.as<int>(); S.ev_c = c->ws.ev_c.as<R>();
+    S.slot_t = c->ws.slot_t.as<int>(); S.slot_k = c->ws.slot_k.as<int>(); S.slot_a = c->ws.slot_a.as<double>();
+    S.hkey = c->ws.hkey.as<unsigned long long>(); S.hval = c->ws.hval.as<int>(); S.head = c->ws.head.as<int>(); S.lgram = c->ws.lgram.as<double>();
+    S.sel_t = c->ws.sel_t.as<int>(); S.sel_k = c->ws.sel_k.as<int>(); S.sel_c = c->ws.sel_c.as<R>();
+    S.stats = c->ws.stats.as<int>(); S.energy = c->ws.energy.as<R>(); S.edge = c->ws.edge.as<unsigned long long>();
+    S.geom = ragged ? c->ws.geom.as<int>() : nullptr;
     return S;
 }
 
 template <typename R> static SparseArgs<R> sparse_args(hscmp_ctx* ctx, const EncodePlan& plan, int T, bool packed = false)
 {
     SparseArgs<R> A;
-    A.Dt = (const R*)ctx->d_Dt; A.scratch = (R*)ctx->d_scratch;
-    A.rowflag = (T <= kRowBitsMaxT && !plan.knobs.no_rowbits) ? ctx->d_rowflag : nullptr;
+    A.Dt = ctx->dict.Dt.as<const R>(); A.scratch = ctx->ws.scratch.as<R>();
+    A.rowflag = (T <= kRowBitsMaxT && !plan.knobs.no_rowbits) ? ctx->ws.rowflag.as<unsigned char>() : nullptr;
     A.rowflag_filled = ctx->rowflag_valid ? 1 : 0;
-    A.nzptr = ctx->d_nzptr; A.nzwf = ctx->d_nzwf; A.nzval = (const R*)ctx->d_nzval;
-    A.fptr = plan.knobs.no_pairing ? nullptr : ctx->d_fptr; A.fkw = ctx->d_fkw; A.fval = (const R*)ctx->d_fval;
-    A.nnz = ctx->dict_nnz; A.wts = (const R*)ctx->d_w;
-    A.caps = sparse_caps(ctx->W, packed);
-    A.rl_cnt = plan.row_lists ? ctx->d_rl_cnt : nullptr; A.rl_f = ctx->d_rl_f; A.rl_cap = kRowListCap; A.rl_filled = ctx->rl_filled ? 1 : 0;
+    A.nzptr = ctx->dict.nzptr.as<int>(); A.nzwf = ctx->dict.nzwf.as<int>(); A.nzval = ctx->dict.nzval.as<const R>();
+    A.fptr = plan.knobs.no_pairing ? nullptr : ctx->dict.fptr.as<int>(); A.fkw = ctx->dict.fkw.as<int>(); A.fval = ctx->dict.fval.as<const R>();
+    A.nnz = ctx->dict.dict_nnz; A.wts = ctx->dict.w.as<const R>();
+    A.caps = sparse_caps(ctx->dict.W, packed);
+    A.rl_cnt = plan.row_lists ? ctx->ws.rl_cnt.as<int>() : nullptr; A.rl_f = ctx->ws.rl_f.as<int>(); A.rl_cap = kRowListCap; A.rl_filled = ctx->rl_filled ? 1 : 0;
     return A;
 }
 
@@ -568,7 +587,7 @@ static int launch_policy(hscmp_ctx* ctx, const DevParams& P0, const typename Pol
     auto kern = iterate_kernel<R, Pol, RAGGED>;
     if (set_dyn_lds((const void*)kern, lds) != hipSuccess) return -1;
     hipLaunchKernelGGL(kern, dim3((P.B + signals_per_wg - 1) / signals_per_wg), dim3(signals_per_wg * kThreads), lds, ctx->stream, P,
-                       make_state<R>(ctx), A);
+                       make_state<R>(ctx, RAGGED), A);
     return 0;
 }
 
@@ -585,7 +604,7 @@ template <int S4C, bool HAS_W> static int launch_locomp_mfma_t(hscmp_ctx* ctx, c
 static int launch_locomp_mfma(hscmp_ctx* ctx, const DevParams& P, int group, bool dry)
 {
     MfmaArgs A;
-    A.dimg = (const float*)ctx->d_Dfrag; A.G = mfma_groups(P.K); A.S4 = mfma_chunks(P.W); A.has_w = ctx->d_w != nullptr ? 1 : 0;
+    A.dimg = ctx->dict.Dfrag.as<const float>(); A.G = mfma_groups(P.K); A.S4 = mfma_chunks(P.W); A.has_w = ctx->dict.w.p != nullptr ? 1 : 0;
     const bool w = A.has_w != 0;
     switch (A.S4) {
     case 8: return w ? launch_locomp_mfma_t<8, true>(ctx, P, A, group, dry) : launch_locomp_mfma_t<8, false>(ctx, P, A, group, dry);
@@ -597,16 +616,16 @@ static int launch_locomp_mfma(hscmp_ctx* ctx, const DevParams& P, int group, boo
 
 // The one place that chooses the kernels of an encode: every knob that selects a kernel is looked at here, and every LDS-fit
 // check runs here.  row_lists: the encode keeps per-row feature lists where its kernels can use them (use_row_lists).
-// min_T: the shortest signal (a ragged batch; P.T otherwise).
-template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const Knobs& kn, const DevParams& P, bool row_lists, int min_T)
+// min_T: the shortest signal (a ragged batch, `ragged`; P.T otherwise).
+template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const Knobs& kn, const DevParams& P, bool row_lists, int min_T, bool ragged = false)
 {
     EncodePlan plan;
     plan.knobs = kn;
-    plan.ragged = ctx->ragged;
+    plan.ragged = ragged;
     plan.f64 = sizeof(R) == 8;
-    plan.dict_lists = ctx->d_nzptr != nullptr;
-    const State<R> S = make_state<R>(ctx);
-    const R* dimg = (const R*)ctx->d_Dfrag;
+    plan.dict_lists = ctx->dict.nzptr.p != nullptr;
+    const State<R> S = make_state<R>(ctx, ragged);
+    const R* dimg = ctx->dict.Dfrag.as<const R>();
     const int cus = mfma_device_cus();
     const bool locomp = ctx->method == HSCMP_METHOD_LOCOMP;      // (its loop keeps coefficient + atom per position: no score-only state)
     // Round-parallel loops for blocked rounds (HSCMP_RP=0/1 forces the choice; tests run both, the results are bit-identical).
@@ -619,8 +638,8 @@ template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const Knobs&
     // (measured: for dense single-feature windows the dense chain is 3x faster; subtracting dense atoms fills the residual, the
     // windows then overflow the gathered lists and the dense LDS-staged chain of GenericRecorr is several times faster -- a k-means
     // dictionary with ~150 of 528 non-zeros per atom: 1.3 ms vs 0.37 ms per atom).  ((f << 16) | row keys: W <= 16384, F <= 32767)
-    const bool sparse_shape = ctx->F > 1 && ctx->d_Dt != nullptr && ctx->W <= 16384 && ctx->F <= 32767;
-    const bool sparse_loop = sparse_shape && (ctx->d_nzptr != nullptr || kn.force_gathered);
+    const bool sparse_shape = ctx->dict.F > 1 && ctx->dict.Dt.p != nullptr && ctx->dict.W <= 16384 && ctx->dict.F <= 32767;
+    const bool sparse_loop = sparse_shape && (ctx->dict.nzptr.p != nullptr || kn.force_gathered);
     plan.row_lists = row_lists && sparse_loop;
 
     // The matrix-core kernels come as a pair: the score-only state the initial correlation leaves is what the MFMA loop reads (the
@@ -628,7 +647,7 @@ template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const Knobs&
     // edges (T >= 3W-2; in a ragged batch every signal's: the shortest one decides).  Four signals per workgroup pay off once a CU would otherwise hold more than two signals in turn
     // (B > 2 x CUs); HSCMP_MFMA_QUAD=0/1 forces the choice (tests run both; the results are bit-identical).
     bool mf = false;
-    if (!locomp && !kn.force_generic && dimg && min_T >= 3 * ctx->W - 2 && mfma_launch_corr_init<R>(ctx->stream, P, S, dimg, true) == 0) {
+    if (!locomp && !kn.force_generic && dimg && min_T >= 3 * ctx->dict.W - 2 && mfma_launch_corr_init<R>(ctx->stream, P, S, dimg, true) == 0) {
         const bool quad = kn.mfma_quad >= 0 ? kn.mfma_quad != 0 : sizeof(R) == 4 && P.B > 2 * cus;
         if (quad && mfma_launch_iterate<R>(ctx->stream, P, S, dimg, 4, kn.lds_pad, true) == 0) plan.group = 4;
         mf = plan.group == 4 || mfma_launch_iterate<R>(ctx->stream, P, S, dimg, 1, kn.lds_pad, true) == 0;
@@ -640,13 +659,13 @@ template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const Knobs&
         if constexpr (sizeof(R) == 4) {
             // float32 single-arg-max encodes: the initial correlation as upper bounds on the bf16 matrix cores, refined by the loop
             // where a selection needs it (hscmp_bound.h).  HSCMP_EXACT_INIT=1: the exact pass everywhere.
-            if (!P.blocked && !P.select_only && ctx->d_Bimg && !kn.exact_init &&
-                bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->d_Bimg, ctx->bound_cmax, true) == 0)
+            if (!P.blocked && !P.select_only && ctx->dict.Bimg.p && !kn.exact_init &&
+                bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->dict.Bimg.as<unsigned short>(), ctx->dict.bound_cmax, true) == 0)
                 plan.init = EncodePlan::kInitBound;
             // ... and the four-signal loop re-correlates as upper bounds too, on the bf16 planes (HSCMP_EXACT_RECORR=1: the
             // exact re-correlation behind the bound pass; HSCMP_EXACT_INIT=1 keeps both exact)
-            if (plan.init == EncodePlan::kInitBound && plan.group == 4 && ctx->bound_loop_image && !kn.exact_recorr &&
-                mfma_launch_iterate<R>(ctx->stream, P, S, dimg, 4, kn.lds_pad, true, ctx->d_Bimg, ctx->bound_cmax) == 0)
+            if (plan.init == EncodePlan::kInitBound && plan.group == 4 && ctx->dict.bound_loop_image && !kn.exact_recorr &&
+                mfma_launch_iterate<R>(ctx->stream, P, S, dimg, 4, kn.lds_pad, true, ctx->dict.Bimg.as<unsigned short>(), ctx->dict.bound_cmax) == 0)
                 plan.bound_loop = true;
             plan.rp = rp_mfma && rp_mfma_launch(ctx->stream, P, S, dimg, true) == 0;
         }
@@ -663,7 +682,7 @@ template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const Knobs&
         if (sparse_loop && launch_policy<R, LocompSparse<R>>(ctx, P, sparse_args<R>(ctx, plan, P.T), 1, true) == 0) {
             plan.loop = EncodePlan::kLoopLocompSparse;
             plan.kept_lists = plan.row_lists;
-        } else if (sizeof(R) == 4 && ctx->F == 1 && dimg && !kn.locomp_no_mfma) {
+        } else if (sizeof(R) == 4 && ctx->dict.F == 1 && dimg && !kn.locomp_no_mfma) {
             for (int g : {4, 2, 1})
                 if ((pack >= g || g == 1) && launch_locomp_mfma(ctx, P, g, true) == 0) {
                     plan.init = EncodePlan::kInitOwn; plan.loop = EncodePlan::kLoopLocompMfma; plan.group = g;
@@ -706,20 +725,20 @@ static std::string variant_of(const EncodePlan& plan)
 // where the loop uses them and the level chaining has not written them while it scattered.
 template <typename R> static int launch_init(hscmp_ctx* ctx, const EncodePlan& plan, const DevParams& P, const void* x_dev)
 {
-    const State<R> S = make_state<R>(ctx);
-    const R* dimg = (const R*)ctx->d_Dfrag;
+    const State<R> S = make_state<R>(ctx, plan.ragged);
+    const R* dimg = ctx->dict.Dfrag.as<const R>();
     if (plan.row_lists && !ctx->rl_filled) {
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_rl_cnt, 0, (size_t)P.B * P.T * sizeof(int), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_rl_f, 0xff, (size_t)P.B * P.T * kRowListCap * sizeof(int), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->ws.rl_cnt.as<int>(), 0, (size_t)P.B * P.T * sizeof(int), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->ws.rl_f.as<int>(), 0xff, (size_t)P.B * P.T * kRowListCap * sizeof(int), ctx->stream));
         const int split = std::max(1, std::min(256, 4096 / P.B));
         hipLaunchKernelGGL((build_row_lists_kernel<R>), dim3(P.B, split), dim3(kThreads), 0, ctx->stream, (const R*)x_dev, P.T, P.F,
-                           ctx->d_rl_cnt, ctx->d_rl_f, kRowListCap);
+                           ctx->ws.rl_cnt.as<int>(), ctx->ws.rl_f.as<int>(), kRowListCap);
     }
     int rc = 0;
     switch (plan.init) {
     case EncodePlan::kInitMfma: rc = mfma_launch_corr_init<R>(ctx->stream, P, S, dimg); break;
     case EncodePlan::kInitBound:
-        if constexpr (sizeof(R) == 4) rc = bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->d_Bimg, ctx->bound_cmax);
+        if constexpr (sizeof(R) == 4) rc = bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->dict.Bimg.as<unsigned short>(), ctx->dict.bound_cmax);
         break;
     case EncodePlan::kInitSparse: {
         const SparseArgs<R> A = sparse_args<R>(ctx, plan, P.T);
@@ -732,7 +751,7 @@ template <typename R> static int launch_init(hscmp_ctx* ctx, const EncodePlan& p
     case EncodePlan::kInitOwn: break;
     case EncodePlan::kInitGeneric:
         hipLaunchKernelGGL((corr_init_generic_kernel<R, false>), dim3((P.T + kThreads - 1) / kThreads, P.B), dim3(kThreads), 0, ctx->stream,
-                           P, S, (const R*)ctx->d_resid, P.off, P.T, (R*)nullptr);
+                           P, S, ctx->ws.resid.as<const R>(), P.off, P.T, (R*)nullptr);
         break;
     }
     if (rc != 0) return fail(ctx, HSCMP_ERR_HIP, "the initial correlation of %s could not be launched", variant_of(plan).c_str());
@@ -742,18 +761,18 @@ template <typename R> static int launch_init(hscmp_ctx* ctx, const EncodePlan& p
 // Queue the loop of the plan: run_encode behind the initial correlation, hscmp_continue on the state an earlier launch left.
 template <typename R> static int launch_loop(hscmp_ctx* ctx, const EncodePlan& plan, const DevParams& P)
 {
-    const R* dimg = (const R*)ctx->d_Dfrag;
+    const R* dimg = ctx->dict.Dfrag.as<const R>();
     int rc = -1;
     switch (plan.loop) {
     case EncodePlan::kLoopMfma:
         if constexpr (sizeof(R) == 4)
-            if (plan.rp) { rc = rp_mfma_launch(ctx->stream, P, make_state<float>(ctx), dimg); break; }
-        rc = mfma_launch_iterate<R>(ctx->stream, P, make_state<R>(ctx), dimg, plan.group, plan.knobs.lds_pad, false,
-                                    plan.bound_loop ? ctx->d_Bimg : nullptr, ctx->bound_cmax);
+            if (plan.rp) { rc = rp_mfma_launch(ctx->stream, P, make_state<float>(ctx, plan.ragged), dimg); break; }
+        rc = mfma_launch_iterate<R>(ctx->stream, P, make_state<R>(ctx, plan.ragged), dimg, plan.group, plan.knobs.lds_pad, false,
+                                    plan.bound_loop ? ctx->dict.Bimg.as<unsigned short>() : nullptr, ctx->dict.bound_cmax);
         break;
     case EncodePlan::kLoopSparse:
         if constexpr (sizeof(R) == 8)
-            if (plan.rp) { rc = rp_sparse_launch<R>(ctx->stream, P, make_state<R>(ctx), sparse_args<R>(ctx, plan, P.T), false); break; }
+            if (plan.rp) { rc = rp_sparse_launch<R>(ctx->stream, P, make_state<R>(ctx, plan.ragged), sparse_args<R>(ctx, plan, P.T), false); break; }
         rc = plan.packed ? launch_policy<R, SparseRecorr<R, true>>(ctx, P, sparse_args<R>(ctx, plan, P.T, true), 1, false)
                          : launch_policy<R, SparseRecorr<R, false>>(ctx, P, sparse_args<R>(ctx, plan, P.T), 1, false);
         break;
@@ -774,10 +793,20 @@ template <typename R> static int launch_loop(hscmp_ctx* ctx, const EncodePlan& p
 // residual buffer and prepare only needs the energy.
 struct ChainSource { const int* slot_t; const int* slot_k; const double* slot_a; const int* stats; int cap, first, has_min; double minc; bool lists; int max_slots; };
 
+// The batch an encode has just queued becomes the context's: everything hscmp_continue, the fetches and the epilogue go by, at once.
+static void commit_batch(hscmp_ctx* ctx, const EncodePlan& plan, const DevParams& P, const hscmp_params& params, const void* x_dev, std::vector<int>&& geom)
+{
+    ctx->P = P; ctx->P.bound_init = plan.init == EncodePlan::kInitBound ? 1 : 0;     // (the loop read it: hscmp_continue resumes on the same state)
+    ctx->plan = plan; ctx->last = params; ctx->B = P.B; ctx->T = P.T; ctx->cap = P.cap; ctx->maxsel = P.maxsel;
+    ctx->last_x_dev = x_dev;
+    ctx->ragged = plan.ragged; ctx->geom = std::move(geom);
+    ctx->have_batch = true;
+}
+
 template <typename R>
 static int run_encode(hscmp_ctx* ctx, const EncodePlan& plan, const DevParams& P, const void* x_dev, const ChainSource* chain = nullptr)
 {
-    State<R> S = make_state<R>(ctx);
+    State<R> S = make_state<R>(ctx, plan.ragged);
     HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     if (chain) {
         // long slot lists: counting sort in LDS when a word per slot fits (cell index / 256 and slot number in 32 bits)
@@ -794,18 +823,16 @@ static int run_encode(hscmp_ctx* ctx, const EncodePlan& plan, const DevParams& P
         else
             hipLaunchKernelGGL((prepare_from_slots_kernel<R>), dim3(P.B), dim3(kThreads), 0, ctx->stream, P, S, chain->slot_t, chain->slot_k,
                                chain->slot_a, chain->stats, chain->cap, chain->first, chain->has_min, chain->minc,
-                               chain->lists ? ctx->d_rl_cnt : nullptr, ctx->d_rl_f, kRowListCap);
+                               chain->lists ? ctx->ws.rl_cnt.as<int>() : nullptr, ctx->ws.rl_f.as<int>(), kRowListCap);
     } else
         hipLaunchKernelGGL((prepare_kernel<R>), dim3(P.B), dim3(kThreads), 0, ctx->stream, P, S, (const R*)x_dev);
     HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    ctx->plan = plan;
-    ctx->P.bound_init = plan.init == EncodePlan::kInitBound ? 1 : 0;     // (the loop reads it; hscmp_continue resumes on the same state)
     int rc = launch_init<R>(ctx, plan, P, x_dev);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
     if (!plan.init_only) {          // (HSCMP_INIT_ONLY: best_c / best_k of the initial correlation through hscmp_get_device_view)
         DevParams PL = P;
-        PL.bound_init = ctx->P.bound_init;
+        PL.bound_init = plan.init == EncodePlan::kInitBound ? 1 : 0;
         if ((rc = launch_loop<R>(ctx, plan, PL))) return rc;
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
@@ -824,11 +851,11 @@ static int ragged_geometry(hscmp_ctx* ctx, const char* who, int B, int T, const 
     *min_T = T;
     for (int b = 0; b < B; ++b) {
         const int Tb = lengths[b];
-        if (Tb < ctx->W || Tb > T)
-            return fail(ctx, HSCMP_ERR_INVALID, "%s: signal %d has length %d outside [W=%d, T=%d]", who, b, Tb, ctx->W, T);
+        if (Tb < ctx->dict.W || Tb > T)
+            return fail(ctx, HSCMP_ERR_INVALID, "%s: signal %d has length %d outside [W=%d, T=%d]", who, b, Tb, ctx->dict.W, T);
         int bs = 0, nbk = 0;
         if (P.blocked) {
-            bs = p->nb_blocks < 0 ? 4 * ctx->W : (int)std::floor((double)Tb / (double)p->nb_blocks);
+            bs = p->nb_blocks < 0 ? 4 * ctx->dict.W : (int)std::floor((double)Tb / (double)p->nb_blocks);
             if (bs % 2 == 1) bs += 1;
             if (bs <= 0) return fail(ctx, HSCMP_ERR_INVALID, "%s: signal %d: nbBlocks=%d gives an empty block for its length %d", who, b, p->nb_blocks, Tb);
             nbk = (int)std::ceil((double)Tb / (double)bs);
@@ -847,7 +874,7 @@ static int encode_common(hscmp_ctx* ctx, const void* x, bool host, int B, int T,
                          const char* who = "hscmp_encode_batch")
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "%s: ctx is NULL", who);
-    if (ctx->dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "%s: no dictionary set", who);
+    if (ctx->dict.dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "%s: no dictionary set", who);
     if (!x || !params || B <= 0 || T <= 0) return fail(ctx, HSCMP_ERR_INVALID, "%s: bad arguments (B=%d T=%d)", who, B, T);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const Knobs kn = read_knobs();
@@ -858,37 +885,25 @@ static int encode_common(hscmp_ctx* ctx, const void* x, bool host, int B, int T,
     std::vector<int> geom;
     if (lengths && (rc = ragged_geometry(ctx, who, B, T, lengths, params, P, geom, &min_T))) return rc;
     const bool row_lists = use_row_lists(ctx, kn);
-    if ((rc = ensure_workspace(ctx, P, host, row_lists))) return rc;
-    if (lengths) {
-        const size_t bytes = geom.size() * sizeof(int);
-        if (!ctx->d_geom || ctx->cap_geom < bytes) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->d_geom) { (void)hipFree(ctx->d_geom); ctx->d_geom = nullptr; ctx->cap_geom = 0; }
-            HIP_TRY(ctx, hipMalloc((void**)&ctx->d_geom, bytes));
-            ctx->cap_geom = bytes;
-        }
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the previous batch's kernels may still read the old geometry)
-        ctx->geom.swap(geom);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_geom, ctx->geom.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    ctx->ragged = lengths != nullptr;           // (a plain encode clears the lengths of an earlier ragged one)
-    if (!lengths) ctx->geom.clear();
-    const EncodePlan plan = ctx->dtype == HSCMP_F32 ? plan_encode<float>(ctx, kn, P, row_lists, min_T) : plan_encode<double>(ctx, kn, P, row_lists, min_T);
-    if (plan.ragged && ((plan.loop != EncodePlan::kLoopMfma && plan.loop != EncodePlan::kLoopGeneric) || plan.init == EncodePlan::kInitSparse)) {
-        ctx->ragged = false; ctx->have_batch = false;
+    drop_batch(ctx);
+    if ((rc = ensure_workspace(ctx, P, host, row_lists, geom.size() * sizeof(int)))) return rc;
+    const EncodePlan plan = ctx->dict.dtype == HSCMP_F32 ? plan_encode<float>(ctx, kn, P, row_lists, min_T, lengths != nullptr)
+                                                         : plan_encode<double>(ctx, kn, P, row_lists, min_T, lengths != nullptr);
+    if (plan.ragged && ((plan.loop != EncodePlan::kLoopMfma && plan.loop != EncodePlan::kLoopGeneric) || plan.init == EncodePlan::kInitSparse))
         return fail(ctx, HSCMP_ERR_UNSUPPORTED, "%s: %s has no ragged form (dense level-0 kernels only)", who, variant_of(plan).c_str());
+    if (lengths) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the previous batch's kernels may still read the old geometry)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ws.geom.p, geom.data(), geom.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     }
     const void* xd = x;
     if (host) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_x, x, (size_t)B * T * ctx->F * esize(ctx->dtype), hipMemcpyHostToDevice, ctx->stream));
-        xd = ctx->d_x;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ws.x.p, x, (size_t)B * T * ctx->dict.F * esize(ctx->dict.dtype), hipMemcpyHostToDevice, ctx->stream));
+        xd = ctx->ws.x.p;
     }
-    ctx->P = P; ctx->last = *params; ctx->B = B; ctx->T = T; ctx->cap = P.cap; ctx->maxsel = P.maxsel;
     ctx->listed_rows = 0;                       // the residual buffer is overwritten with a dense input
-    ctx->last_x_dev = xd;
-    rc = ctx->dtype == HSCMP_F32 ? run_encode<float>(ctx, plan, P, xd) : run_encode<double>(ctx, plan, P, xd);
+    rc = ctx->dict.dtype == HSCMP_F32 ? run_encode<float>(ctx, plan, P, xd) : run_encode<double>(ctx, plan, P, xd);
     if (rc) return rc;
-    ctx->have_batch = true;
+    commit_batch(ctx, plan, P, *params, xd, std::move(geom));      // (geom keeps its storage: the upload above may still read it)
     if (host) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return HSCMP_OK;
 }
@@ -926,14 +941,13 @@ extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, in
                                              const hscmp_params* params)
 {
     if (!ctx || !prev) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: NULL context");
-    if (ctx->dtype != HSCMP_F64) return fail(ctx, HSCMP_ERR_STATE, "hscmp_encode_batch_from_level: the level dictionary must be float64");
+    if (ctx->dict.dtype != HSCMP_F64) return fail(ctx, HSCMP_ERR_STATE, "hscmp_encode_batch_from_level: the level dictionary must be float64");
     if (!prev->have_batch) return fail(ctx, HSCMP_ERR_STATE, "hscmp_encode_batch_from_level: the previous level has no results");
     if (ctx->device != prev->device) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: contexts on different GPUs");
-    if (ctx->F != prev->K) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: F=%d of this level != K=%d of the previous one", ctx->F, prev->K);
+    if (ctx->dict.F != prev->dict.K) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: F=%d of this level != K=%d of the previous one", ctx->dict.F, prev->dict.K);
     if (!params || first < 0 || count <= 0 || first + count > prev->B) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: bad signal range");
     if (prev->ragged) return fail(ctx, HSCMP_ERR_UNSUPPORTED, "hscmp_encode_batch_from_level: the previous level holds a ragged batch (level chaining has no ragged form)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->ragged = false;
     HIP_TRY(ctx, hipStreamSynchronize(prev->stream));           // the previous level's results are final
     const int T = prev->T;
     const Knobs kn = read_knobs();
@@ -941,48 +955,48 @@ extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, in
     int rc = make_params(ctx, kn, count, T, params, &P);
     if (rc) return rc;
     const bool row_lists = use_row_lists(ctx, kn);
+    drop_batch(ctx);                            // (this level's batch; prev is only read)
     if ((rc = ensure_workspace(ctx, P, false, row_lists))) return rc;        // no input buffer: the slots are scattered straight into the residual
     const EncodePlan plan = plan_encode<double>(ctx, kn, P, row_lists, P.T);
     const bool lists = plan.row_lists;          // (the scatter writes them)
-    const size_t bytes = (size_t)count * T * ctx->F * sizeof(double);
-    if (ctx->listed_rows > 0 && ctx->listed_F == ctx->F && !kn.no_lazy_clear) {
+    const size_t bytes = (size_t)count * T * ctx->dict.F * sizeof(double);
+    if (ctx->listed_rows > 0 && ctx->listed_F == ctx->dict.F && !kn.no_lazy_clear) {
         // the buffer still holds the previous chained batch; its lists say where
         hipLaunchKernelGGL((clear_listed_cells_kernel<double>), dim3((unsigned)((ctx->listed_rows + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream,
-                           (double*)ctx->d_resid, ctx->listed_rows, ctx->F, ctx->d_rl_cnt, ctx->d_rl_f, kRowListCap);
-        const size_t covered = (size_t)ctx->listed_rows * ctx->F * sizeof(double);
-        if (bytes > covered) HIP_TRY(ctx, hipMemsetAsync((char*)ctx->d_resid + covered, 0, bytes - covered, ctx->stream));
+                           ctx->ws.resid.as<double>(), ctx->listed_rows, ctx->dict.F, ctx->ws.rl_cnt.as<int>(), ctx->ws.rl_f.as<int>(), kRowListCap);
+        const size_t covered = (size_t)ctx->listed_rows * ctx->dict.F * sizeof(double);
+        if (bytes > covered) HIP_TRY(ctx, hipMemsetAsync(ctx->ws.resid.as<char>() + covered, 0, bytes - covered, ctx->stream));
     } else {
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_resid, 0, bytes, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->ws.resid.p, 0, bytes, ctx->stream));
     }
     ctx->listed_rows = 0;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_rowflag, 0, (size_t)count * T, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ws.rowflag.as<unsigned char>(), 0, (size_t)count * T, ctx->stream));
     if (lists) {
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_rl_cnt, 0, (size_t)count * T * sizeof(int), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_rl_f, 0xff, (size_t)count * T * kRowListCap * sizeof(int), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->ws.rl_cnt.as<int>(), 0, (size_t)count * T * sizeof(int), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->ws.rl_f.as<int>(), 0xff, (size_t)count * T * kRowListCap * sizeof(int), ctx->stream));
     }
     const int has_min = !std::isnan(min_coefficients);
-    hipLaunchKernelGGL((scatter_slots_kernel<double>), dim3(count), dim3(kThreads), 0, ctx->stream, (double*)ctx->d_resid, T, ctx->F,
-                       prev->d_slot_t, prev->d_slot_k, prev->d_slot_a, prev->d_stats, prev->cap, first, has_min,
-                       has_min ? min_coefficients : 0.0, ctx->d_rowflag, lists ? ctx->d_rl_cnt : nullptr, ctx->d_rl_f, kRowListCap);
-    ctx->P = P; ctx->last = *params; ctx->B = count; ctx->T = T; ctx->cap = P.cap; ctx->maxsel = P.maxsel;
+    hipLaunchKernelGGL((scatter_slots_kernel<double>), dim3(count), dim3(kThreads), 0, ctx->stream, ctx->ws.resid.as<double>(), T, ctx->dict.F,
+                       prev->ws.slot_t.as<int>(), prev->ws.slot_k.as<int>(), prev->ws.slot_a.as<double>(), prev->ws.stats.as<int>(), prev->cap, first, has_min,
+                       has_min ? min_coefficients : 0.0, ctx->ws.rowflag.as<unsigned char>(), lists ? ctx->ws.rl_cnt.as<int>() : nullptr, ctx->ws.rl_f.as<int>(), kRowListCap);
     ctx->rowflag_valid = true;                  // the sparse initial correlation skips its scan of the dense input
     ctx->rl_filled = lists;
     // (the longest slot list of the range sizes the LDS of the energy kernel: the previous level's counters are final)
     int max_slots = 0;
     {
         std::vector<int> pst((size_t)count * ST_COUNT);
-        HIP_TRY(ctx, hipMemcpy(pst.data(), prev->d_stats + (size_t)first * ST_COUNT, pst.size() * sizeof(int), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(pst.data(), prev->ws.stats.as<int>() + (size_t)first * ST_COUNT, pst.size() * sizeof(int), hipMemcpyDeviceToHost));
         for (int i = 0; i < count; ++i) max_slots = std::max(max_slots, pst[(size_t)i * ST_COUNT + ST_SLOTS]);
     }
-    const ChainSource chain{prev->d_slot_t, prev->d_slot_k, prev->d_slot_a, prev->d_stats, prev->cap, first, has_min,
+    const ChainSource chain{prev->ws.slot_t.as<int>(), prev->ws.slot_k.as<int>(), prev->ws.slot_a.as<double>(), prev->ws.stats.as<int>(), prev->cap, first, has_min,
                             has_min ? min_coefficients : 0.0, lists, max_slots};
-    rc = run_encode<double>(ctx, plan, P, ctx->d_resid, &chain);
+    rc = run_encode<double>(ctx, plan, P, ctx->ws.resid.p, &chain);
     ctx->rowflag_valid = false; ctx->rl_filled = false;
     if (rc) return rc;
-    ctx->have_batch = true;
+    commit_batch(ctx, plan, P, *params, nullptr, {});      // (no input of its own on the device: the slots were scattered)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // (only now: a failed launch leaves the buffer in an unknown state, and so does any other writer -- see the resets)
-    if (plan.kept_lists) { ctx->listed_rows = (int64_t)count * T; ctx->listed_F = ctx->F; }
+    if (plan.kept_lists) { ctx->listed_rows = (int64_t)count * T; ctx->listed_F = ctx->dict.F; }
     return HSCMP_OK;
 }
 
@@ -1011,43 +1025,33 @@ extern "C" int hscmp_grow_events(hscmp_ctx* ctx, int new_max_events)
     if (new_max_events <= ctx->cap) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_grow_events: %d is not above the current capacity %d", new_max_events, ctx->cap);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t es = esize(ctx->dtype), B = (size_t)ctx->B, oc = (size_t)ctx->cap, nc = (size_t)new_max_events;
-    struct Row { void** p; size_t* cap; size_t elem; void* fresh; };
-    Row rows[] = {{(void**)&ctx->d_ev_t, &ctx->caps[4], 4, nullptr}, {(void**)&ctx->d_ev_k, &ctx->caps[5], 4, nullptr}, {(void**)&ctx->d_ev_c, &ctx->caps[6], es, nullptr},
-                  {(void**)&ctx->d_slot_t, &ctx->caps[7], 4, nullptr}, {(void**)&ctx->d_slot_k, &ctx->caps[8], 4, nullptr}, {(void**)&ctx->d_slot_a, &ctx->caps[9], 8, nullptr}};
+    (void)read_knobs();
+    const size_t es = esize(ctx->dict.dtype), B = (size_t)ctx->B, oc = (size_t)ctx->cap, nc = (size_t)new_max_events;
     // the slot hash table follows the capacity; the loop rebuilds its contents from the slot list on the next launch
     const unsigned hmask = slot_hash_mask(new_max_events);
-    struct Tab { void** p; size_t* cap; size_t elem; void* fresh; };
-    Tab tabs[] = {{(void**)&ctx->d_hkey, &ctx->cap_hkey, sizeof(unsigned long long), nullptr}, {(void**)&ctx->d_hval, &ctx->cap_hval, sizeof(int), nullptr}};
+    Workspace& w = ctx->ws;
+    DevBuf* const bufs[8] = {&w.ev_t, &w.ev_k, &w.ev_c, &w.slot_t, &w.slot_k, &w.slot_a, &w.hkey, &w.hval};     // six lists, then the table
+    const size_t elem[6] = {4, 4, es, 4, 4, 8}, H = (size_t)hmask + 1;
+    const size_t bytes[8] = {B * nc * elem[0], B * nc * elem[1], B * nc * elem[2], B * nc * elem[3], B * nc * elem[4], B * nc * elem[5],
+                             B * H * sizeof(unsigned long long), B * H * sizeof(int)};
     // every new buffer first; the context changes only when all of them exist (a failed call leaves the batch as it was)
+    DevBuf fresh[8];
     hipError_t e = hipSuccess;
     size_t failed_bytes = 0;
-    for (Row& r : rows) {
-        if ((e = hipMalloc(&r.fresh, B * nc * r.elem)) != hipSuccess) { failed_bytes = B * nc * r.elem; break; }
-    }
-    if (e == hipSuccess)
-        for (Tab& t : tabs) {
-            const size_t bytes = B * ((size_t)hmask + 1) * t.elem;
-            if (*t.p && *t.cap >= bytes) continue;
-            if ((e = hipMalloc(&t.fresh, bytes)) != hipSuccess) { failed_bytes = bytes; break; }
-        }
-    if (e == hipSuccess)
-        for (Row& r : rows)
-            if ((e = hipMemcpy2D(r.fresh, nc * r.elem, *r.p, oc * r.elem, oc * r.elem, B, hipMemcpyDeviceToDevice)) != hipSuccess) break;
+    for (int i = 0; i < 8 && e == hipSuccess; ++i)
+        if ((i < 6 || !bufs[i]->holds(bytes[i])) && (e = fresh[i].replace(bytes[i])) != hipSuccess) failed_bytes = bytes[i];
+    for (int i = 0; i < 6 && e == hipSuccess; ++i)
+        e = hipMemcpy2D(fresh[i].p, nc * elem[i], bufs[i]->p, oc * elem[i], oc * elem[i], B, hipMemcpyDeviceToDevice);
     std::vector<int> stats(B * ST_COUNT);
-    if (e == hipSuccess) e = hipMemcpy(stats.data(), ctx->d_stats, stats.size() * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(stats.data(), w.stats.p, stats.size() * sizeof(int), hipMemcpyDeviceToHost);
     if (e == hipSuccess) {
         for (size_t b = 0; b < B; ++b)
             if (stats[b * ST_COUNT + ST_STOP] == STOP_CAPACITY) stats[b * ST_COUNT + ST_STOP] = STOP_RUNNING;
-        e = hipMemcpy(ctx->d_stats, stats.data(), stats.size() * sizeof(int), hipMemcpyHostToDevice);
+        e = hipMemcpy(w.stats.p, stats.data(), stats.size() * sizeof(int), hipMemcpyHostToDevice);
     }
-    if (e != hipSuccess) {
-        for (Row& r : rows) if (r.fresh) (void)hipFree(r.fresh);
-        for (Tab& t : tabs) if (t.fresh) (void)hipFree(t.fresh);
+    if (e != hipSuccess)        // (the fresh buffers free themselves)
         return fail(ctx, failed_bytes ? HSCMP_ERR_ALLOC : HSCMP_ERR_HIP, "hscmp_grow_events: %s (%zu bytes)", hipGetErrorString(e), failed_bytes);
-    }
-    for (Row& r : rows) { (void)hipFree(*r.p); *r.p = r.fresh; *r.cap = B * nc * r.elem; }
-    for (Tab& t : tabs) if (t.fresh) { if (*t.p) (void)hipFree(*t.p); *t.p = t.fresh; *t.cap = B * ((size_t)hmask + 1) * t.elem; }
+    for (int i = 0; i < 8; ++i) if (fresh[i].p) *bufs[i] = std::move(fresh[i]);
     ctx->cap = new_max_events; ctx->P.cap = new_max_events; ctx->P.hmask = hmask; ctx->last.max_events = new_max_events;
     return HSCMP_OK;
 }
@@ -1060,9 +1064,9 @@ extern "C" int hscmp_stop_signal(hscmp_ctx* ctx, int b)
     int v = STOP_CALLBACK;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     int cur = 0;
-    HIP_TRY(ctx, hipMemcpy(&cur, ctx->d_stats + (size_t)b * ST_COUNT + ST_STOP, sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(&cur, ctx->ws.stats.as<int>() + (size_t)b * ST_COUNT + ST_STOP, sizeof(int), hipMemcpyDeviceToHost));
     if (cur == STOP_RUNNING)
-        HIP_TRY(ctx, hipMemcpy(ctx->d_stats + (size_t)b * ST_COUNT + ST_STOP, &v, sizeof(int), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(ctx->ws.stats.as<int>() + (size_t)b * ST_COUNT + ST_STOP, &v, sizeof(int), hipMemcpyHostToDevice));
     return HSCMP_OK;
 }
 
@@ -1083,9 +1087,9 @@ extern "C" int hscmp_fetch_events(hscmp_ctx* ctx, int32_t* ev_t, int32_t* ev_k, 
     NEED_BATCH(ctx, "hscmp_fetch_events");
     const size_t n = (size_t)ctx->B * ctx->cap;
     int rc;
-    if ((rc = fetch(ctx, ev_t, ctx->d_ev_t, n * 4))) return rc;
-    if ((rc = fetch(ctx, ev_k, ctx->d_ev_k, n * 4))) return rc;
-    if ((rc = fetch(ctx, ev_c, ctx->d_ev_c, n * esize(ctx->dtype)))) return rc;
+    if ((rc = fetch(ctx, ev_t, ctx->ws.ev_t.as<int>(), n * 4))) return rc;
+    if ((rc = fetch(ctx, ev_k, ctx->ws.ev_k.as<int>(), n * 4))) return rc;
+    if ((rc = fetch(ctx, ev_c, ctx->ws.ev_c.p, n * esize(ctx->dict.dtype)))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return HSCMP_OK;
 }
@@ -1095,9 +1099,9 @@ extern "C" int hscmp_fetch_slots(hscmp_ctx* ctx, int32_t* slot_t, int32_t* slot_
     NEED_BATCH(ctx, "hscmp_fetch_slots");
     const size_t n = (size_t)ctx->B * ctx->cap;
     int rc;
-    if ((rc = fetch(ctx, slot_t, ctx->d_slot_t, n * 4))) return rc;
-    if ((rc = fetch(ctx, slot_k, ctx->d_slot_k, n * 4))) return rc;
-    if ((rc = fetch(ctx, slot_acc, ctx->d_slot_a, n * 8))) return rc;
+    if ((rc = fetch(ctx, slot_t, ctx->ws.slot_t.as<int>(), n * 4))) return rc;
+    if ((rc = fetch(ctx, slot_k, ctx->ws.slot_k.as<int>(), n * 4))) return rc;
+    if ((rc = fetch(ctx, slot_acc, ctx->ws.slot_a.as<double>(), n * 8))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return HSCMP_OK;
 }
@@ -1105,7 +1109,7 @@ extern "C" int hscmp_fetch_slots(hscmp_ctx* ctx, int32_t* slot_t, int32_t* slot_
 extern "C" int hscmp_fetch_stats(hscmp_ctx* ctx, int32_t* stats)
 {
     NEED_BATCH(ctx, "hscmp_fetch_stats");
-    int rc = fetch(ctx, stats, ctx->d_stats, (size_t)ctx->B * ST_COUNT * sizeof(int));
+    int rc = fetch(ctx, stats, ctx->ws.stats.as<int>(), (size_t)ctx->B * ST_COUNT * sizeof(int));
     if (rc) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return HSCMP_OK;
@@ -1114,7 +1118,7 @@ extern "C" int hscmp_fetch_stats(hscmp_ctx* ctx, int32_t* stats)
 extern "C" int hscmp_fetch_residual(hscmp_ctx* ctx, void* residual)
 {
     NEED_BATCH(ctx, "hscmp_fetch_residual");
-    int rc = fetch(ctx, residual, ctx->d_resid, (size_t)ctx->B * ctx->T * ctx->F * esize(ctx->dtype));
+    int rc = fetch(ctx, residual, ctx->ws.resid.p, (size_t)ctx->B * ctx->T * ctx->dict.F * esize(ctx->dict.dtype));
     if (rc) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return HSCMP_OK;
@@ -1125,13 +1129,13 @@ extern "C" int hscmp_fetch_energies(hscmp_ctx* ctx, double* energies)
     NEED_BATCH(ctx, "hscmp_fetch_energies");
     if (!energies) return HSCMP_OK;
     const size_t n = (size_t)ctx->B * 2;
-    if (ctx->dtype == HSCMP_F64) {
-        int rc = fetch(ctx, energies, ctx->d_energy, n * 8);
+    if (ctx->dict.dtype == HSCMP_F64) {
+        int rc = fetch(ctx, energies, ctx->ws.energy.p, n * 8);
         if (rc) return rc;
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     } else {
         std::vector<float> tmp(n);
-        int rc = fetch(ctx, tmp.data(), ctx->d_energy, n * 4);
+        int rc = fetch(ctx, tmp.data(), ctx->ws.energy.p, n * 4);
         if (rc) return rc;
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         for (size_t i = 0; i < n; ++i) energies[i] = (double)tmp[i];
@@ -1143,10 +1147,10 @@ extern "C" int hscmp_get_device_view(hscmp_ctx* ctx, hscmp_device_view* v)
 {
     NEED_BATCH(ctx, "hscmp_get_device_view");
     if (!v) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_get_device_view: view is NULL");
-    v->B = ctx->B; v->T = ctx->T; v->F = ctx->F; v->K = ctx->K; v->W = ctx->W; v->max_events = ctx->cap;
-    v->dtype = ctx->dtype; v->reserved = 0;
-    v->ev_t = ctx->d_ev_t; v->ev_k = ctx->d_ev_k; v->ev_c = ctx->d_ev_c; v->stats = ctx->d_stats;
-    v->residual = ctx->d_resid; v->energies = ctx->d_energy; v->best_c = ctx->d_best_c; v->best_k = ctx->d_best_k;
+    v->B = ctx->B; v->T = ctx->T; v->F = ctx->dict.F; v->K = ctx->dict.K; v->W = ctx->dict.W; v->max_events = ctx->cap;
+    v->dtype = ctx->dict.dtype; v->reserved = 0;
+    v->ev_t = ctx->ws.ev_t.as<int>(); v->ev_k = ctx->ws.ev_k.as<int>(); v->ev_c = ctx->ws.ev_c.p; v->stats = ctx->ws.stats.as<int>();
+    v->residual = ctx->ws.resid.p; v->energies = ctx->ws.energy.p; v->best_c = ctx->ws.best_c.p; v->best_k = ctx->ws.best_k.as<int>();
     return HSCMP_OK;
 }
 
@@ -1188,23 +1192,23 @@ extern "C" int hscmp_copy_from_device(hscmp_ctx* ctx, const void* src_dev, uint6
 template <typename R> static void launch_convolve(hscmp_ctx* ctx, const R* dx, int T, int same, int Tout, R* dout)
 {
     DevParams P{};
-    P.B = 1; P.T = T; P.K = ctx->K; P.W = ctx->W; P.F = ctx->F; P.off = (ctx->W - 1) / 2;
+    P.B = 1; P.T = T; P.K = ctx->dict.K; P.W = ctx->dict.W; P.F = ctx->dict.F; P.off = (ctx->dict.W - 1) / 2;
     State<R> S{};
-    S.D = (const R*)ctx->d_D; S.weights = nullptr;
-    S.Dc = ctx->d_Dc ? (const R*)ctx->d_Dc : (const R*)ctx->d_D;
+    S.D = ctx->dict.D.as<const R>(); S.weights = nullptr;
+    S.Dc = ctx->dict.Dc.p ? ctx->dict.Dc.as<const R>() : ctx->dict.D.as<const R>();
     dim3 grid((Tout + kThreads - 1) / kThreads, 1);
     hipLaunchKernelGGL((corr_init_generic_kernel<R, true>), grid, dim3(kThreads), 0, ctx->stream, P, S, dx, same ? P.off : 0, Tout, dout);
 }
 
 template <typename R> static int run_convolve(hscmp_ctx* ctx, const void* x, int T, int same, void* out)
 {
-    const int K = ctx->K, W = ctx->W, F = ctx->F;
+    const int K = ctx->dict.K, W = ctx->dict.W, F = ctx->dict.F;
     const int Tout = same ? T : T - W + 1;
     if (Tout <= 0) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_convolve1d: T=%d shorter than the filters (W=%d)", T, W);
     int rc;
     if ((rc = epi_buffer(ctx, kArenaRowA, (size_t)T * F * sizeof(R))) != HSCMP_OK) return rc;
     if ((rc = epi_buffer(ctx, kArenaRowB, (size_t)Tout * K * sizeof(R))) != HSCMP_OK) return rc;
-    R* dx = (R*)ctx->d_epi[kArenaRowA]; R* dout = (R*)ctx->d_epi[kArenaRowB];
+    R* dx = ctx->arena[kArenaRowA].as<R>(); R* dout = ctx->arena[kArenaRowB].as<R>();
     HIP_TRY(ctx, hipMemcpyAsync(dx, x, (size_t)T * F * sizeof(R), hipMemcpyHostToDevice, ctx->stream));
     launch_convolve<R>(ctx, dx, T, same, Tout, dout);
     HIP_TRY(ctx, hipGetLastError());
@@ -1216,28 +1220,29 @@ template <typename R> static int run_convolve(hscmp_ctx* ctx, const void* x, int
 extern "C" int hscmp_convolve1d(hscmp_ctx* ctx, const void* x, int T, int same, void* out)
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_convolve1d: ctx is NULL");
-    if (ctx->dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_convolve1d: no dictionary set");
+    if (ctx->dict.dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_convolve1d: no dictionary set");
     if (!x || !out || T <= 0) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_convolve1d: bad arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return ctx->dtype == HSCMP_F32 ? run_convolve<float>(ctx, x, T, same, out) : run_convolve<double>(ctx, x, T, same, out);
+    (void)read_knobs();
+    return ctx->dict.dtype == HSCMP_F32 ? run_convolve<float>(ctx, x, T, same, out) : run_convolve<double>(ctx, x, T, same, out);
 }
 
 // modeling.py:454-460: per-window best (position, atom, coefficient) of the k-means learner
 template <typename R>
 static int run_assign(hscmp_ctx* ctx, const void* windows, int N, int L, int32_t* out_t, int32_t* out_k, void* out_c)
 {
-    const int K = ctx->K, W = ctx->W, F = ctx->F;
+    const int K = ctx->dict.K, W = ctx->dict.W, F = ctx->dict.F;
     const size_t wbytes = (size_t)N * L * F * sizeof(R);
     int rc;
     if ((rc = epi_buffer(ctx, kArenaRowA, wbytes)) != HSCMP_OK) return rc;
     if ((rc = epi_buffer(ctx, kArenaRowB, (size_t)N * sizeof(int))) != HSCMP_OK) return rc;
     if ((rc = epi_buffer(ctx, kArenaRowC, (size_t)N * sizeof(int))) != HSCMP_OK) return rc;
     if ((rc = epi_buffer(ctx, kArenaRowD, (size_t)N * sizeof(R))) != HSCMP_OK) return rc;
-    R* dwin = (R*)ctx->d_epi[kArenaRowA]; int* dt = (int*)ctx->d_epi[kArenaRowB]; int* dk = (int*)ctx->d_epi[kArenaRowC]; R* dc = (R*)ctx->d_epi[kArenaRowD];
+    R* dwin = ctx->arena[kArenaRowA].as<R>(); int* dt = ctx->arena[kArenaRowB].as<int>(); int* dk = ctx->arena[kArenaRowC].as<int>(); R* dc = ctx->arena[kArenaRowD].as<R>();
     HIP_TRY(ctx, hipMemcpyAsync(dwin, windows, wbytes, hipMemcpyHostToDevice, ctx->stream));
     const int lds_elems = (size_t)L * F * sizeof(R) <= 32768 ? L * F : 0;
     hipLaunchKernelGGL((assign_windows_kernel<R>), dim3(N), dim3(kThreads), (size_t)lds_elems * sizeof(R), ctx->stream,
-                       (const R*)dwin, L, K, W, F, (const R*)ctx->d_D, lds_elems, dt, dk, dc);
+                       (const R*)dwin, L, K, W, F, ctx->dict.D.as<const R>(), lds_elems, dt, dk, dc);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(out_t, dt, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out_k, dk, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -1249,11 +1254,12 @@ static int run_assign(hscmp_ctx* ctx, const void* windows, int N, int L, int32_t
 extern "C" int hscmp_assign_windows(hscmp_ctx* ctx, const void* windows, int N, int L, int32_t* out_t, int32_t* out_k, void* out_c)
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_assign_windows: ctx is NULL");
-    if (ctx->dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_assign_windows: no dictionary set");
+    if (ctx->dict.dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_assign_windows: no dictionary set");
     if (!windows || !out_t || !out_k || N <= 0) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_assign_windows: bad arguments");
-    if (L < ctx->W) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_assign_windows: windows of %d samples are shorter than the filters (W=%d)", L, ctx->W);
+    if (L < ctx->dict.W) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_assign_windows: windows of %d samples are shorter than the filters (W=%d)", L, ctx->dict.W);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return ctx->dtype == HSCMP_F32 ? run_assign<float>(ctx, windows, N, L, out_t, out_k, out_c)
+    (void)read_knobs();
+    return ctx->dict.dtype == HSCMP_F32 ? run_assign<float>(ctx, windows, N, L, out_t, out_k, out_c)
                                    : run_assign<double>(ctx, windows, N, L, out_t, out_k, out_c);
 }
 
@@ -1340,7 +1346,7 @@ extern "C" int hscmp_hierarchy_epilogue(hscmp_ctx* last, hscmp_ctx* level0, int 
     if (last->device != level0->device) return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: contexts on different GPUs");
     if (!levels || nlevels < 1 || nlevels > kEpiMaxLevels || !offsets || !out_n || !out_colptr || !out_indices || !out_data)
         return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: bad arguments");
-    const int count = last->B, T = last->T, Fd = level0->F, Ktot = last->K;
+    const int count = last->B, T = last->T, Fd = level0->dict.F, Ktot = last->dict.K;
     if (first < 0 || first + count > level0->B || level0->T != T) return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: signal range / length mismatch");
     if (!level0->last_x_dev) return fail(last, HSCMP_ERR_STATE, "hscmp_hierarchy_epilogue: the level-0 input is not on the device any more");
     if (Ktot >= (1 << kEpiColBits) || T >= (1 << kEpiTBits) || last->cap >= (1 << kEpiIdxBits))
@@ -1348,6 +1354,7 @@ extern "C" int hscmp_hierarchy_epilogue(hscmp_ctx* last, hscmp_ctx* level0, int 
     HIP_TRY(last, hipSetDevice(last->device));
     HIP_TRY(last, hipStreamSynchronize(level0->stream));
     HIP_TRY(last, hipStreamSynchronize(last->stream));
+    const Knobs kn = read_knobs();
     const long long total = offsets[count];
     EpiArgs A{};
     A.nlevels = nlevels; A.Ktot = Ktot; A.T = T; A.Fd = Fd;
@@ -1360,7 +1367,7 @@ extern "C" int hscmp_hierarchy_epilogue(hscmp_ctx* last, hscmp_ctx* level0, int 
         rep_bytes += ((size_t)std::max(0, d.col1) * std::max(0, d.scale) * Fd * (d.rep_is_f32 ? 4 : 8) + 15) / 16 * 16;
     }
     int rc;
-    if ((rc = epi_buffer(last, 0, std::max<size_t>(16, rep_bytes)))) return rc;
+    if ((rc = epi_buffer(last, kArenaEpiRep, std::max<size_t>(16, rep_bytes)))) return rc;
     size_t ro = 0;
     for (int l = 0; l < nlevels; ++l) {
         const hscmp_epilogue_level& d = levels[l];
@@ -1368,42 +1375,39 @@ extern "C" int hscmp_hierarchy_epilogue(hscmp_ctx* last, hscmp_ctx* level0, int 
         L.col0 = d.col0; L.col1 = d.col1; L.scale = d.scale; L.lead = (d.scale - 1) / 2; L.rep_f32 = d.rep_is_f32; L.rep = nullptr;
         if (d.col1 <= d.col0) continue;
         const size_t nb = (size_t)d.col1 * d.scale * Fd * (d.rep_is_f32 ? 4 : 8);       // rows [0, col1): indexed by the column number
-        L.rep = (char*)last->d_epi[0] + ro;
-        HIP_TRY(last, hipMemcpyAsync((char*)last->d_epi[0] + ro, d.rep, nb, hipMemcpyHostToDevice, last->stream));
+        L.rep = last->arena[kArenaEpiRep].as<char>() + ro;
+        HIP_TRY(last, hipMemcpyAsync(last->arena[kArenaEpiRep].as<char>() + ro, d.rep, nb, hipMemcpyHostToDevice, last->stream));
         ro += (nb + 15) / 16 * 16;
         A.max_back = std::max(A.max_back, d.scale - 1 - L.lead);
         A.max_fwd = std::max(A.max_fwd, L.lead);
     }
     int nmax = 2;
     while (nmax < last->cap) nmax <<= 1;
-    const Knobs kn = read_knobs();
     const int lds_keys = kn.epi_lds_keys;                        // (HSCMP_EPI_LDS_KEYS: tests force the chunked sort at small sizes)
-    const bool need_scratch = true;                              // (the t-sorted keys move there while the LDS holds residual tiles)
     const size_t nres = out_residual ? (size_t)count * T * Fd * sizeof(double) : 0;
+    const size_t nev = out_events ? (size_t)total * 16 : 0;      // (a multiple of 16: the residual behind the events stays aligned)
+    // by arena slot, kArenaEpiOffsets .. kArenaEpiKeys (kArenaEpiOut: the events, then the residual)
     const size_t sizes[8] = {0, (size_t)(count + 1) * sizeof(long long), (size_t)count * sizeof(int), (size_t)count * (Ktot + 1) * sizeof(int),
                              std::max<size_t>(16, (size_t)total * sizeof(int)), std::max<size_t>(16, (size_t)total * sizeof(double)),
-                             std::max<size_t>(16, (out_events ? (size_t)total * 16 : 0) + nres),
-                             need_scratch ? (size_t)count * nmax * sizeof(unsigned long long) : 0};
-    for (int i = 1; i < 8; ++i) if (sizes[i] && (rc = epi_buffer(last, i, sizes[i]))) return rc;
-    HIP_TRY(last, hipMemcpyAsync(last->d_epi[1], offsets, sizes[1], hipMemcpyHostToDevice, last->stream));
-    A.slot_t = last->d_slot_t; A.slot_k = last->d_slot_k; A.slot_a = last->d_slot_a; A.stats = last->d_stats; A.cap = last->cap;
-    A.offsets = (const long long*)last->d_epi[1]; A.out_n = (int*)last->d_epi[2]; A.out_colptr = (int*)last->d_epi[3];
-    A.out_indices = (int*)last->d_epi[4]; A.out_data = (double*)last->d_epi[5];
-    A.out_events = out_events ? (int*)last->d_epi[6] : nullptr;
-    A.out_residual = out_residual ? (double*)((char*)last->d_epi[6] + (out_events ? ((size_t)total * 16 + 15) / 16 * 16 : 0)) : nullptr;
-    if (out_events && out_residual && (rc = epi_buffer(last, 6, ((size_t)total * 16 + 15) / 16 * 16 + nres))) return rc;
-    A.out_events = out_events ? (int*)last->d_epi[6] : nullptr;
-    A.out_residual = out_residual ? (double*)((char*)last->d_epi[6] + (out_events ? ((size_t)total * 16 + 15) / 16 * 16 : 0)) : nullptr;
-    A.scratch = (unsigned long long*)last->d_epi[7]; A.scratch_n = nmax;
-    A.out_energy = nullptr;
+                             std::max<size_t>(16, nev + nres),
+                             (size_t)count * nmax * sizeof(unsigned long long)};       // (the t-sorted keys move there while the LDS holds residual tiles)
+    for (int i = kArenaEpiOffsets; i <= kArenaEpiKeys; ++i) if (sizes[i] && (rc = epi_buffer(last, i, sizes[i]))) return rc;
+    DevBuf* const arena = last->arena;
+    HIP_TRY(last, hipMemcpyAsync(arena[kArenaEpiOffsets].p, offsets, sizes[kArenaEpiOffsets], hipMemcpyHostToDevice, last->stream));
+    A.slot_t = last->ws.slot_t.as<int>(); A.slot_k = last->ws.slot_k.as<int>(); A.slot_a = last->ws.slot_a.as<double>(); A.stats = last->ws.stats.as<int>(); A.cap = last->cap;
+    A.offsets = arena[kArenaEpiOffsets].as<const long long>(); A.out_n = arena[kArenaEpiN].as<int>(); A.out_colptr = arena[kArenaEpiColptr].as<int>();
+    A.out_indices = arena[kArenaEpiIndices].as<int>(); A.out_data = arena[kArenaEpiData].as<double>();
+    A.out_events = out_events ? arena[kArenaEpiOut].as<int>() : nullptr;
+    A.out_residual = out_residual ? (double*)(arena[kArenaEpiOut].as<char>() + nev) : nullptr;
+    A.scratch = arena[kArenaEpiKeys].as<unsigned long long>(); A.scratch_n = nmax;
     if (out_residual_energy) {
         if ((rc = epi_buffer(last, kArenaEpiEnergy, (size_t)count * sizeof(double)))) return rc;
-        A.out_energy = (double*)last->d_epi[kArenaEpiEnergy];
+        A.out_energy = last->arena[kArenaEpiEnergy].as<double>();
     }
     const size_t lds = std::max<size_t>((size_t)std::min(nmax, lds_keys) * sizeof(unsigned long long), kn.epi_lds_keys_set ? 8192 : 65536);
     A.lds_keys = std::min(nmax, lds_keys); A.lds_bytes = (int)lds;
-    const size_t xoff = (size_t)first * T * Fd * esize(level0->dtype);
-    if (level0->dtype == HSCMP_F32) {
+    const size_t xoff = (size_t)first * T * Fd * esize(level0->dict.dtype);
+    if (level0->dict.dtype == HSCMP_F32) {
         auto kern = hier_epilogue_kernel<float>;
         HIP_TRY(last, set_dyn_lds((const void*)kern, lds));
         hipLaunchKernelGGL(kern, dim3(count), dim3(kEpiThreads), lds, last->stream, A, (const float*)((const char*)level0->last_x_dev + xoff));
@@ -1413,8 +1417,8 @@ extern "C" int hscmp_hierarchy_epilogue(hscmp_ctx* last, hscmp_ctx* level0, int 
         hipLaunchKernelGGL(kern, dim3(count), dim3(kEpiThreads), lds, last->stream, A, (const double*)((const char*)level0->last_x_dev + xoff));
     }
     HIP_TRY(last, hipGetLastError());
-    HIP_TRY(last, hipMemcpyAsync(out_n, A.out_n, sizes[2], hipMemcpyDeviceToHost, last->stream));
-    HIP_TRY(last, hipMemcpyAsync(out_colptr, A.out_colptr, sizes[3], hipMemcpyDeviceToHost, last->stream));
+    HIP_TRY(last, hipMemcpyAsync(out_n, A.out_n, sizes[kArenaEpiN], hipMemcpyDeviceToHost, last->stream));
+    HIP_TRY(last, hipMemcpyAsync(out_colptr, A.out_colptr, sizes[kArenaEpiColptr], hipMemcpyDeviceToHost, last->stream));
     if (total > 0) {
         HIP_TRY(last, hipMemcpyAsync(out_indices, A.out_indices, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, last->stream));
         HIP_TRY(last, hipMemcpyAsync(out_data, A.out_data, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, last->stream));
@@ -1459,18 +1463,17 @@ static int select_on_device(hscmp_ctx* ctx, const Knobs& kn, const R* d_ip, cons
     hp.null_coeff_thres = thres; hp.eps = 0.0; hp.max_events = 1; hp.max_rounds = 1;
     DevParams P;
     int rc = make_params_g(ctx, kn, K, W, 1, 1, T, &hp, &P);               // only T, K, W matter for the selection
-    if (rc == HSCMP_OK) rc = ensure_workspace_g(ctx, P, false, sizeof(R), false, false);
     if (rc != HSCMP_OK) return rc;
-    ctx->have_batch = false;
-    ctx->ragged = false;
+    drop_batch(ctx);
+    if ((rc = ensure_workspace_g(ctx, P, false, sizeof(R), false, false)) != HSCMP_OK) return rc;
     ctx->listed_rows = 0;
-    State<R> S = make_state<R>(ctx);
+    State<R> S = make_state<R>(ctx, false);
     S.D = nullptr; S.Dc = nullptr; S.weights = d_w;
     hipLaunchKernelGGL((table_to_best_kernel<R>), dim3((T + kThreads - 1) / kThreads), dim3(kThreads), 0, ctx->stream,
                        d_ip, T, K, d_w, S.best_c, S.best_k);
     int st[ST_COUNT] = {0};
     st[ST_OFFSET] = offset ? 1 : 0;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_stats, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ws.stats.as<int>(), st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
     P.select_only = 1; P.has_snr = 0; P.has_scale = 0;
     set_segments(P, GenericRecorr<R>::kMaxSegments);
     const size_t lds = ((sizeof(typename GenericRecorr<R>::Shared) + 15) / 16) * 16 + GenericRecorr<R>::extra_lds_bytes(P);
@@ -1478,15 +1481,15 @@ static int select_on_device(hscmp_ctx* ctx, const Knobs& kn, const R* d_ip, cons
     HIP_TRY(ctx, set_dyn_lds((const void*)kern, lds));
     hipLaunchKernelGGL(kern, dim3(1), dim3(kThreads), lds, ctx->stream, P, S, typename GenericRecorr<R>::Args{});
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(st, ctx->d_stats, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(st, ctx->ws.stats.as<int>(), sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const int n = st[ST_EVENTS];
     *n_out = n;
     if (n > max_out) return fail(ctx, HSCMP_ERR_INVALID, "%s: %d atoms selected, room for %d", who, n, max_out);
     if (n > 0) {                                                        // the ordered list lives in the second half of the selection scratch
-        HIP_TRY(ctx, hipMemcpyAsync(out_t, ctx->d_sel_t + P.maxsel, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(out_k, ctx->d_sel_k + P.maxsel, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(out_c, (R*)ctx->d_sel_c + P.maxsel, (size_t)n * sizeof(R), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(out_t, ctx->ws.sel_t.as<int>() + P.maxsel, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(out_k, ctx->ws.sel_k.as<int>() + P.maxsel, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(out_c, ctx->ws.sel_c.as<R>() + P.maxsel, (size_t)n * sizeof(R), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     return HSCMP_OK;
@@ -1498,8 +1501,8 @@ template <typename R> static int upload_weights(hscmp_ctx* ctx, const void* weig
     if (!weights) return HSCMP_OK;
     int rc = epi_buffer(ctx, kArenaTabW, (size_t)K * sizeof(R));
     if (rc != HSCMP_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_epi[kArenaTabW], weights, (size_t)K * sizeof(R), hipMemcpyHostToDevice, ctx->stream));
-    *d_w = (const R*)ctx->d_epi[kArenaTabW];
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->arena[kArenaTabW].p, weights, (size_t)K * sizeof(R), hipMemcpyHostToDevice, ctx->stream));
+    *d_w = ctx->arena[kArenaTabW].as<const R>();
     return HSCMP_OK;
 }
 
@@ -1509,10 +1512,10 @@ static int run_select(hscmp_ctx* ctx, const Knobs& kn, const void* ip, int T, in
 {
     int rc = epi_buffer(ctx, kArenaRowA, (size_t)T * K * sizeof(R));
     if (rc != HSCMP_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_epi[kArenaRowA], ip, (size_t)T * K * sizeof(R), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->arena[kArenaRowA].p, ip, (size_t)T * K * sizeof(R), hipMemcpyHostToDevice, ctx->stream));
     const R* d_w;
     if ((rc = upload_weights<R>(ctx, weights, K, &d_w)) != HSCMP_OK) return rc;
-    return select_on_device<R>(ctx, kn, (const R*)ctx->d_epi[kArenaRowA], d_w, T, K, W, nb_blocks, offset, thres, out_t, out_k, out_c, max_out, n_out,
+    return select_on_device<R>(ctx, kn, ctx->arena[kArenaRowA].as<const R>(), d_w, T, K, W, nb_blocks, offset, thres, out_t, out_k, out_c, max_out, n_out,
                                "hscmp_select_best_atoms");
 }
 
@@ -1533,20 +1536,20 @@ extern "C" int hscmp_select_best_atoms(hscmp_ctx* ctx, const void* ip, int T, in
 
 template <typename R> static void launch_update_rows(hscmp_ctx* ctx, const R* d_r, int T, int p, R* d_rows, R* d_table)
 {
-    const int K = ctx->K, W = ctx->W, nrows = 2 * W - 1;
+    const int K = ctx->dict.K, W = ctx->dict.W, nrows = 2 * W - 1;
     DevParams P{};
-    P.B = 1; P.T = T; P.K = K; P.W = W; P.F = ctx->F; P.off = (W - 1) / 2;
+    P.B = 1; P.T = T; P.K = K; P.W = W; P.F = ctx->dict.F; P.off = (W - 1) / 2;
     const int grid = (nrows * K + kThreads - 1) / kThreads;
-    hipLaunchKernelGGL((update_rows_kernel<R>), dim3(grid), dim3(kThreads), 0, ctx->stream, P, d_r, (const R*)ctx->d_D, p, d_rows, d_table);
+    hipLaunchKernelGGL((update_rows_kernel<R>), dim3(grid), dim3(kThreads), 0, ctx->stream, P, d_r, ctx->dict.D.as<const R>(), p, d_rows, d_table);
 }
 
 template <typename R> static int run_update_rows(hscmp_ctx* ctx, void* ip, const void* residual, int T, int p)
 {
-    const int K = ctx->K, W = ctx->W, F = ctx->F, nrows = 2 * W - 1;
+    const int K = ctx->dict.K, W = ctx->dict.W, F = ctx->dict.F, nrows = 2 * W - 1;
     int rc;
     if ((rc = epi_buffer(ctx, kArenaRowA, (size_t)T * F * sizeof(R))) != HSCMP_OK) return rc;
     if ((rc = epi_buffer(ctx, kArenaRowB, (size_t)nrows * K * sizeof(R))) != HSCMP_OK) return rc;
-    R* d_r = (R*)ctx->d_epi[kArenaRowA]; R* d_out = (R*)ctx->d_epi[kArenaRowB];
+    R* d_r = ctx->arena[kArenaRowA].as<R>(); R* d_out = ctx->arena[kArenaRowB].as<R>();
     std::vector<R> rows((size_t)nrows * K);
     HIP_TRY(ctx, hipMemcpyAsync(d_r, residual, (size_t)T * F * sizeof(R), hipMemcpyHostToDevice, ctx->stream));
     launch_update_rows<R>(ctx, d_r, T, p, d_out, nullptr);
@@ -1564,11 +1567,12 @@ template <typename R> static int run_update_rows(hscmp_ctx* ctx, void* ip, const
 extern "C" int hscmp_update_inner_products(hscmp_ctx* ctx, void* ip, const void* residual, int T, int p)
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_update_inner_products: ctx is NULL");
-    if (ctx->dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_update_inner_products: no dictionary set");
+    if (ctx->dict.dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_update_inner_products: no dictionary set");
     if (!ip || !residual || T <= 0) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_update_inner_products: bad arguments");
     if (p < 0 || p >= T) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_update_inner_products: atom centre %d outside the signal [0, %d)", p, T);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return ctx->dtype == HSCMP_F32 ? run_update_rows<float>(ctx, ip, residual, T, p) : run_update_rows<double>(ctx, ip, residual, T, p);
+    (void)read_knobs();
+    return ctx->dict.dtype == HSCMP_F32 ? run_update_rows<float>(ctx, ip, residual, T, p) : run_update_rows<double>(ctx, ip, residual, T, p);
 }
 
 // ---- LoCOMP's table on the device (hsc/modeling.py:1267-1425) -----------------------------------------------------------
@@ -1578,28 +1582,28 @@ extern "C" int hscmp_update_inner_products(hscmp_ctx* ctx, void* ip, const void*
 // (:1018-1051) for every atom of the re-fitted group, in place.  Per iteration the host moves O(W) samples, not T*K.
 // Multi-feature tables (hierarchical levels >= 1) are built row by row from the non-zero cells of each row's window
 // (table_rows_sparse_kernel); single-feature inputs are dense and keep the dense kernels.
-static bool table_rows_are_sparse(const hscmp_ctx* ctx) { return ctx->F > 1 && ctx->W <= 32767 && ctx->F <= 65535; }
+static bool table_rows_are_sparse(const hscmp_ctx* ctx) { return ctx->dict.F > 1 && ctx->dict.W <= 32767 && ctx->dict.F <= 65535; }
 constexpr int kTableRowCap = 1024;             // listed non-zeros per row window (12 KB of LDS in float64); more: dense chain
 template <typename R> static void launch_table_rows_sparse(hscmp_ctx* ctx, const R* d_r, int T, int row0, int nrows, int p, R* d_table)
 {
     DevParams P{};
-    P.B = 1; P.T = T; P.K = ctx->K; P.W = ctx->W; P.F = ctx->F; P.off = (ctx->W - 1) / 2;
+    P.B = 1; P.T = T; P.K = ctx->dict.K; P.W = ctx->dict.W; P.F = ctx->dict.F; P.off = (ctx->dict.W - 1) / 2;
     hipLaunchKernelGGL((table_rows_sparse_kernel<R>), dim3(nrows), dim3(kThreads), (size_t)kTableRowCap * (sizeof(R) + 4), ctx->stream,
-                       P, d_r, (const R*)ctx->d_D, row0, p, d_table, kTableRowCap);
+                       P, d_r, ctx->dict.D.as<const R>(), row0, p, d_table, kTableRowCap);
 }
 
 template <typename R> static int run_table_open(hscmp_ctx* ctx, const void* x, int T)
 {
-    const int K = ctx->K, F = ctx->F;
+    const int K = ctx->dict.K, F = ctx->dict.F;
     int rc;
     if ((rc = epi_buffer(ctx, kArenaTabRes, (size_t)T * F * sizeof(R))) != HSCMP_OK) return rc;
     if ((rc = epi_buffer(ctx, kArenaTable, (size_t)T * K * sizeof(R))) != HSCMP_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_epi[kArenaTabRes], x, (size_t)T * F * sizeof(R), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->arena[kArenaTabRes].p, x, (size_t)T * F * sizeof(R), hipMemcpyHostToDevice, ctx->stream));
     // the caller's buffer may be reused as soon as this returns (as hscmp_table_update promises): wait for the upload (not through
     // ev[]: those are the batch-timing events hscmp_last_kernel_ms reads)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (table_rows_are_sparse(ctx)) launch_table_rows_sparse<R>(ctx, (const R*)ctx->d_epi[kArenaTabRes], T, 0, T, -1, (R*)ctx->d_epi[kArenaTable]);
-    else launch_convolve<R>(ctx, (const R*)ctx->d_epi[kArenaTabRes], T, 1, T, (R*)ctx->d_epi[kArenaTable]);
+    if (table_rows_are_sparse(ctx)) launch_table_rows_sparse<R>(ctx, ctx->arena[kArenaTabRes].as<const R>(), T, 0, T, -1, ctx->arena[kArenaTable].as<R>());
+    else launch_convolve<R>(ctx, ctx->arena[kArenaTabRes].as<const R>(), T, 1, T, ctx->arena[kArenaTable].as<R>());
     HIP_TRY(ctx, hipGetLastError());
     ctx->tab_T = T;
     return HSCMP_OK;
@@ -1608,11 +1612,12 @@ template <typename R> static int run_table_open(hscmp_ctx* ctx, const void* x, i
 extern "C" int hscmp_table_open(hscmp_ctx* ctx, const void* x, int T)
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_table_open: ctx is NULL");
-    if (ctx->dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_table_open: no dictionary set");
+    if (ctx->dict.dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_table_open: no dictionary set");
     if (!x || T <= 0) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_table_open: bad arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    (void)read_knobs();
     ctx->tab_T = 0;
-    return ctx->dtype == HSCMP_F32 ? run_table_open<float>(ctx, x, T) : run_table_open<double>(ctx, x, T);
+    return ctx->dict.dtype == HSCMP_F32 ? run_table_open<float>(ctx, x, T) : run_table_open<double>(ctx, x, T);
 }
 
 extern "C" int hscmp_table_select(hscmp_ctx* ctx, int nb_blocks, int offset, double null_coeff_thres, const void* weights,
@@ -1624,15 +1629,15 @@ extern "C" int hscmp_table_select(hscmp_ctx* ctx, int nb_blocks, int offset, dou
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const Knobs kn = read_knobs();
     int rc;
-    if (ctx->dtype == HSCMP_F32) {
+    if (ctx->dict.dtype == HSCMP_F32) {
         const float* d_w;
-        if ((rc = upload_weights<float>(ctx, weights, ctx->K, &d_w)) != HSCMP_OK) return rc;
-        return select_on_device<float>(ctx, kn, (const float*)ctx->d_epi[kArenaTable], d_w, ctx->tab_T, ctx->K, ctx->W, nb_blocks, offset, null_coeff_thres,
+        if ((rc = upload_weights<float>(ctx, weights, ctx->dict.K, &d_w)) != HSCMP_OK) return rc;
+        return select_on_device<float>(ctx, kn, ctx->arena[kArenaTable].as<const float>(), d_w, ctx->tab_T, ctx->dict.K, ctx->dict.W, nb_blocks, offset, null_coeff_thres,
                                        out_t, out_k, out_c, max_out, n_out, "hscmp_table_select");
     }
     const double* d_w;
-    if ((rc = upload_weights<double>(ctx, weights, ctx->K, &d_w)) != HSCMP_OK) return rc;
-    return select_on_device<double>(ctx, kn, (const double*)ctx->d_epi[kArenaTable], d_w, ctx->tab_T, ctx->K, ctx->W, nb_blocks, offset, null_coeff_thres,
+    if ((rc = upload_weights<double>(ctx, weights, ctx->dict.K, &d_w)) != HSCMP_OK) return rc;
+    return select_on_device<double>(ctx, kn, ctx->arena[kArenaTable].as<const double>(), d_w, ctx->tab_T, ctx->dict.K, ctx->dict.W, nb_blocks, offset, null_coeff_thres,
                                     out_t, out_k, out_c, max_out, n_out, "hscmp_table_select");
 }
 
@@ -1646,16 +1651,16 @@ extern "C" int hscmp_table_update(hscmp_ctx* ctx, const void* residual_samples, 
     for (int i = 0; i < ncentres; ++i)
         if (centres[i] < 0 || centres[i] >= T) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_table_update: atom centre %d outside the signal [0, %d)", centres[i], T);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t es = esize(ctx->dtype), row = (size_t)ctx->F * es;
+    const size_t es = esize(ctx->dict.dtype), row = (size_t)ctx->dict.F * es;
     if (count > 0)
-        HIP_TRY(ctx, hipMemcpyAsync((char*)ctx->d_epi[kArenaTabRes] + (size_t)start * row, residual_samples, (size_t)count * row, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->arena[kArenaTabRes].as<char>() + (size_t)start * row, residual_samples, (size_t)count * row, hipMemcpyHostToDevice, ctx->stream));
     const bool sparse_rows_form = table_rows_are_sparse(ctx);
     for (int i = 0; i < ncentres; ++i) {
         if (sparse_rows_form) {
-            if (ctx->dtype == HSCMP_F32) launch_table_rows_sparse<float>(ctx, (const float*)ctx->d_epi[kArenaTabRes], T, 0, 2 * ctx->W - 1, centres[i], (float*)ctx->d_epi[kArenaTable]);
-            else launch_table_rows_sparse<double>(ctx, (const double*)ctx->d_epi[kArenaTabRes], T, 0, 2 * ctx->W - 1, centres[i], (double*)ctx->d_epi[kArenaTable]);
-        } else if (ctx->dtype == HSCMP_F32) launch_update_rows<float>(ctx, (const float*)ctx->d_epi[kArenaTabRes], T, centres[i], nullptr, (float*)ctx->d_epi[kArenaTable]);
-        else launch_update_rows<double>(ctx, (const double*)ctx->d_epi[kArenaTabRes], T, centres[i], nullptr, (double*)ctx->d_epi[kArenaTable]);
+            if (ctx->dict.dtype == HSCMP_F32) launch_table_rows_sparse<float>(ctx, ctx->arena[kArenaTabRes].as<const float>(), T, 0, 2 * ctx->dict.W - 1, centres[i], ctx->arena[kArenaTable].as<float>());
+            else launch_table_rows_sparse<double>(ctx, ctx->arena[kArenaTabRes].as<const double>(), T, 0, 2 * ctx->dict.W - 1, centres[i], ctx->arena[kArenaTable].as<double>());
+        } else if (ctx->dict.dtype == HSCMP_F32) launch_update_rows<float>(ctx, ctx->arena[kArenaTabRes].as<const float>(), T, centres[i], nullptr, ctx->arena[kArenaTable].as<float>());
+        else launch_update_rows<double>(ctx, ctx->arena[kArenaTabRes].as<const double>(), T, centres[i], nullptr, ctx->arena[kArenaTable].as<double>());
     }
     HIP_TRY(ctx, hipGetLastError());
     // the host buffer may be reused as soon as this returns
@@ -1668,9 +1673,9 @@ extern "C" int hscmp_table_read(hscmp_ctx* ctx, void* out_table, void* out_resid
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_table_read: ctx is NULL");
     if (ctx->tab_T <= 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_table_read: no table open (hscmp_table_open)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t es = esize(ctx->dtype);
-    if (out_table) HIP_TRY(ctx, hipMemcpyAsync(out_table, ctx->d_epi[kArenaTable], (size_t)ctx->tab_T * ctx->K * es, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_residual) HIP_TRY(ctx, hipMemcpyAsync(out_residual, ctx->d_epi[kArenaTabRes], (size_t)ctx->tab_T * ctx->F * es, hipMemcpyDeviceToHost, ctx->stream));
+    const size_t es = esize(ctx->dict.dtype);
+    if (out_table) HIP_TRY(ctx, hipMemcpyAsync(out_table, ctx->arena[kArenaTable].p, (size_t)ctx->tab_T * ctx->dict.K * es, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_residual) HIP_TRY(ctx, hipMemcpyAsync(out_residual, ctx->arena[kArenaTabRes].p, (size_t)ctx->tab_T * ctx->dict.F * es, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return HSCMP_OK;
 }

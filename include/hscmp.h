@@ -39,8 +39,19 @@ typedef enum hscmp_status {
     HSCMP_ERR_NO_DEVICE = -3,    /* no gfx950 device / extension cannot run here */
     HSCMP_ERR_STATE = -4,        /* call sequence error (no dictionary, no batch, ...) */
     HSCMP_ERR_UNSUPPORTED = -5,  /* shape outside what the kernels are built for */
-    HSCMP_ERR_ALLOC = -6
+    HSCMP_ERR_ALLOC = -6         /* the GPU has no room for a buffer (message has the size): retry with a smaller batch */
 } hscmp_status;
+
+/* What a failed call leaves behind.  A call that may replace the dictionary or a buffer of the batch first drops what
+ * depends on it, so the context is never half-updated:
+ *  - hscmp_set_dictionary that fails behind its argument checks leaves NO dictionary (and no batch, no open table): every
+ *    call that needs one answers HSCMP_ERR_STATE until a hscmp_set_dictionary succeeds.
+ *  - an encode (hscmp_encode_batch*, hscmp_select_best_atoms, hscmp_table_select) that fails behind its argument checks
+ *    leaves NO batch: hscmp_continue, the fetches, hscmp_get_device_view, hscmp_grow_events, hscmp_stop_signal and
+ *    hscmp_hierarchy_epilogue answer HSCMP_ERR_STATE, and the next encode works.  The dictionary stays, and so does the
+ *    batch of the previous level of a failed hscmp_encode_batch_from_level.
+ *  - a failed hscmp_grow_events, hscmp_hierarchy_epilogue or hscmp_table_open leaves the batch (or batches) as they were;
+ *    after a failed hscmp_table_open no table is open. */
 
 typedef enum hscmp_dtype { HSCMP_F32 = 0, HSCMP_F64 = 1 } hscmp_dtype;
 
