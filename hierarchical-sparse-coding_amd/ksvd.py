@@ -15,6 +15,10 @@ The one intended deviation: an updated atom's sign is chosen so that it points t
 update (LAPACK's sign cannot be reproduced).  The K-SVD trajectory is sign-equivariant (the coders select by |c|, and
 c * D does not change), so only alpha differs from the reference's: alpha is the sign-aligned distance.
 
+A corpus (B signals, one dictionary): update_corpus / ConvolutionalKSVDLearner.trainCorpus encode the whole batch in one
+computeCoefficientsBatch call per iteration (ragged batches included) and update the dictionary from every signal's
+occurrences with hscksvd_update_corpus; no atom reaches into a neighbouring signal.  DESIGN.md section 16.
+
 There is no CPU path: without libhscksvd.so or a visible GPU the calls raise hsc_amd._native.HscmpError.
 ConvolutionalDictionaryLearner(algorithm='ksvd') keeps its host sweep and is not routed here.
 """
@@ -31,8 +35,11 @@ from . import _native
 logger = logging.getLogger(__name__)
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'ksvd', 'libhscksvd.so')
-EXPORTS = ['hscksvd_version', 'hscksvd_create', 'hscksvd_destroy', 'hscksvd_last_error', 'hscksvd_update']
+EXPORTS = ['hscksvd_version', 'hscksvd_create', 'hscksvd_destroy', 'hscksvd_last_error', 'hscksvd_update',
+           'hscksvd_update_corpus']
 MAX_ATOM_SIZE = 64                       # W * F, include/hscksvd.h HSCKSVD_MAX_ATOM_SIZE
+WIDE_FROM_OCCURRENCES = 64               # include/hscksvd.h HSCKSVD_WIDE_FROM_OCCURRENCES: what plan 'auto' decides on
+PLANS = {'auto': 0, 'one': 1, 'wide': 2}
 ATOM_STATS = 4                           # n_k, lambda1, lambda2, Jacobi sweeps
 METHODS = ('locomp', 'cmp')
 
@@ -44,7 +51,9 @@ def load_library():
     global _lib
     if _lib is None:
         vp, ci = ctypes.c_void_p, ctypes.c_int
-        _lib = _native.load_satellite(LIB_PATH, 'hscksvd', {'hscksvd_update': [vp, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp]})
+        _lib = _native.load_satellite(LIB_PATH, 'hscksvd', {
+            'hscksvd_update': [vp, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp],
+            'hscksvd_update_corpus': [vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp, vp]})
     return _lib
 
 
@@ -97,6 +106,84 @@ def update(D, coefficients, usePCA=False, device=0):
     return D3.reshape(D.shape), out, stats, timing
 
 
+def update_corpus(D, coefficients, usePCA=False, device=0, plan='auto'):
+    """One sweep of the K-SVD dictionary update over a corpus (hscksvd_update_corpus): D [K,W] or [K,W,F] and a list of
+    B sparse [T_b,K] coefficient matrices, one per signal.  The patches of an occurrence are built from its own signal's
+    coefficients alone and clipped at that signal's ends.  plan: 'auto', 'one' (one workgroup) or 'wide' (grids per
+    atom); all return the same bits.  Returns (D float64 of D's shape, list of B csc_matrix [T_b,K] float64 with the
+    updated values, stats [K,4] float64: n_k, lambda1, lambda2, Jacobi sweeps, timing_ms [3]: upload, sweep, download).
+    The inputs are not modified."""
+    D = np.asarray(D)
+    assert D.ndim == 2 or D.ndim == 3
+    K, W = D.shape[0], D.shape[1]
+    D3 = np.array(D.reshape((K, W, -1)), dtype=np.float64, order='C')
+    F = D3.shape[2]
+    if plan not in PLANS:
+        raise ValueError("K-SVD: plan must be 'auto', 'one' or 'wide' (got %r)" % (plan,))
+    coefficients = list(coefficients)
+    if len(coefficients) == 0:
+        raise ValueError('K-SVD: a corpus needs at least one signal')
+    for c in coefficients:
+        assert c.shape[1] == K
+        check_update_shapes(c.shape[0], W, F, usePCA)
+    offsets = np.concatenate([[0], np.cumsum([c.shape[0] for c in coefficients], dtype=np.int64)])
+    if offsets[-1] >= 2 ** 31:
+        raise NotImplementedError('K-SVD on the GPU: the corpus has %d samples in all, the limit is 2^31 - 1' % offsets[-1])
+    cscs = []
+    for c in coefficients:
+        c = scipy.sparse.csc_matrix(c, dtype=np.float64, copy=True)
+        if not c.has_sorted_indices:
+            c.sort_indices()
+        cscs.append(c)
+    # the stack in CSC: column, then signal, then time -- a stable sort by column of the signals' entries in signal order
+    cols = np.concatenate([np.repeat(np.arange(K), np.diff(c.indptr)) for c in cscs])
+    order = np.argsort(cols, kind='stable')
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(cols, minlength=K))]).astype(np.int32)
+    indices = np.concatenate([c.indices + off for c, off in zip(cscs, offsets[:-1])])[order].astype(np.int32)
+    data = np.ascontiguousarray(np.concatenate([c.data for c in cscs])[order], dtype=np.float64)
+    row_offsets = offsets.astype(np.int32)
+    stats = np.zeros((K, ATOM_STATS), dtype=np.float64)
+    timing = np.zeros((3,), dtype=np.float64)
+    ctx = _context(device)
+    p = _native._ptr
+    ctx.call('update_corpus', len(cscs), p(row_offsets), K, W, F, p(D3), p(indptr), p(indices), p(data),
+             1 if usePCA else 0, PLANS[plan], p(stats), p(timing))
+    back = np.empty_like(data)
+    back[order] = data
+    first = 0
+    for c in cscs:
+        c.data[:] = back[first:first + c.nnz]
+        first += c.nnz
+    return D3.reshape(D.shape), cscs, stats, timing
+
+
+def _corpus_signals(sequences, lengths):
+    """The signals of a corpus as a list of [T_b] or [T_b,F] views: `sequences` [B,T] / [B,T,F], a list / tuple of
+    arrays, or a padded array with `lengths` [B] (the forms of computeCoefficientsBatch)."""
+    if isinstance(sequences, (list, tuple)):
+        if lengths is not None:
+            raise ValueError('lengths= goes with a padded array, not with a list of signals')
+        seqs = [np.asarray(q) for q in sequences]
+    else:
+        seq = np.asarray(sequences)
+        if seq.ndim != 2 and seq.ndim != 3:
+            raise ValueError('K-SVD: the corpus must be [B,T] or [B,T,F] (got %d dimensions)' % seq.ndim)
+        if lengths is None:
+            seqs = list(seq)
+        else:
+            lens = np.asarray(lengths).astype(np.int64).reshape(-1)
+            if lens.shape[0] != seq.shape[0]:
+                raise ValueError('lengths has %d entries for %d signals' % (lens.shape[0], seq.shape[0]))
+            if np.any(lens > seq.shape[1]) or np.any(lens < 0):
+                raise ValueError('a length is outside the padded length %d' % seq.shape[1])
+            seqs = [seq[b, :int(lens[b])] for b in range(seq.shape[0])]
+    if len(seqs) == 0:
+        raise ValueError('K-SVD: a corpus needs at least one signal')
+    if seqs[0].ndim not in (1, 2) or any(q.ndim != seqs[0].ndim or q.shape[1:] != seqs[0].shape[1:] for q in seqs):
+        raise ValueError('K-SVD: the signals of a corpus must all be [T_b] or all be [T_b,F] with the same F')
+    return seqs
+
+
 class ConvolutionalKSVDLearner(object):
     """The reference's convolutional K-SVD learner (ConvolutionalDictionaryLearner._train_ksvd, hsc/modeling.py:528-641)
     with the dictionary update on the GPU (one hscksvd_update call per iteration).
@@ -120,12 +207,15 @@ class ConvolutionalKSVDLearner(object):
             return ConvolutionalMatchingPursuit()
         raise AssertionError(method)
 
-    def _check(self, data, method, usePCA):
+    def _check_method(self, method):
         if method in ('mptk-mp', 'mptk-cmp'):
             raise NotImplementedError("method='%s' needs the external MPTK toolkit, which this engine does not bind; "
                                       "use method='cmp' or 'locomp'" % method)
         if method not in METHODS:
             raise Exception('Unsupported sparse coding method: %s' % (method))
+
+    def _check(self, data, method, usePCA):
+        self._check_method(method)
         if data.ndim != 1 and data.ndim != 2:
             raise ValueError('K-SVD: the data must be [T] or [T,F] (got %d dimensions)' % data.ndim)
         F = 1 if data.ndim == 1 else data.shape[1]
@@ -157,6 +247,52 @@ class ConvolutionalKSVDLearner(object):
                               eigenvalues=atoms[:, 1:3].copy()))
             logger.debug('K-SVD iteration %d: tolerance = %f, sparsity = %f' % (
                 n, alpha, float(coefficients.nnz) / np.prod(coefficients.shape)))
+            n += 1
+        self.lastStats = stats
+        return D
+
+    def trainCorpus(self, sequences, method='locomp', maxIterations=100, tolerance=0.0, nbNonzeroCoefs=None,
+                    toleranceSnr=40.0, usePCA=False, lengths=None):
+        """`train` for ONE dictionary over a corpus of B signals: `sequences` [B,T] / [B,T,F], or a ragged batch (a list of
+        [T_b(,F)] arrays, or a padded array with `lengths`; method='cmp' only, and within what the engine's ragged encode takes:
+        DESIGN.md section 15), as computeCoefficientsBatch takes them.
+        Each iteration is one encodeBatch of the whole corpus (the stop rules apply per signal) and one update_corpus.
+        D is drawn as `train` draws it, with low / high over the whole corpus; a corpus of one signal gives `train`'s
+        result on that signal, bit for bit.  Returns D float64 [K,W] or [K,W,F].
+        lastStats: `train`'s records (nnz: the stored coefficients of all signals) plus plan (1: one workgroup, 2: wide)
+        and variant (the encode's kernel variant)."""
+        from .learning import ConvolutionalDictionaryLearner
+        from .modeling import ConvolutionalSparseCoder, is_ragged, reject_ragged
+        self._check_method(method)
+        if method == 'locomp':
+            reject_ragged(sequences, lengths, "ConvolutionalKSVDLearner.trainCorpus(method='locomp')")
+        seqs = _corpus_signals(sequences, lengths)
+        for q in seqs:
+            check_update_shapes(q.shape[0], self.windowSize, 1 if q.ndim == 1 else q.shape[1], usePCA)
+        if sum(q.shape[0] for q in seqs) >= 2 ** 31:
+            raise NotImplementedError('K-SVD on the GPU: the corpus has more than 2^31 - 1 samples in all')
+        load_library()                                       # no CPU path: fail before the first encode
+        if not is_ragged(sequences, lengths):
+            sequences = np.asarray(sequences)
+        D = ConvolutionalDictionaryLearner(self.k, self.windowSize, rng=self.rng)._init_D(np.concatenate(seqs), initMethod='noise')
+        D = np.asarray(D, dtype=np.float64)
+        stats = []
+        n, alpha = 0, tolerance + 1.0
+        while n < maxIterations and alpha > tolerance:
+            t0 = time.perf_counter()
+            res = ConvolutionalSparseCoder(D, self._coder(method)).encodeBatch(
+                sequences, nbNonzeroCoefs=nbNonzeroCoefs, toleranceSnr=toleranceSnr, lengths=lengths)
+            t1 = time.perf_counter()
+            oldD = D
+            D, coefficients, atoms, timing = update_corpus(oldD, res.coefficients, usePCA, self.device)
+            t2 = time.perf_counter()
+            alpha = np.sqrt(np.sum(np.square(D - oldD)))
+            nnz = sum(int(c.nnz) for c in coefficients)
+            stats.append(dict(alpha=float(alpha), nnz=nnz, encode_ms=1e3 * (t1 - t0), update_ms=1e3 * (t2 - t1),
+                              sweep_ms=float(timing[1]), n_k=atoms[:, 0].astype(np.int64), eigenvalues=atoms[:, 1:3].copy(),
+                              plan=2 if np.max(atoms[:, 0]) >= WIDE_FROM_OCCURRENCES else 1, variant=res.variant))
+            logger.debug('K-SVD corpus iteration %d: tolerance = %f, sparsity = %f' % (
+                n, alpha, float(nnz) / (sum(q.shape[0] for q in seqs) * self.k)))
             n += 1
         self.lastStats = stats
         return D

@@ -25,6 +25,7 @@ enum {
 };
 
 enum { HSCKSVD_MAX_ATOM_SIZE = 64 };   /* W * F */
+enum { HSCKSVD_WIDE_FROM_OCCURRENCES = 64 };   /* hscksvd_update_corpus, plan 0: wide when some atom occurs this often */
 
 /* per-atom record of hscksvd_update's out_atom_stats */
 enum {
@@ -71,6 +72,30 @@ const char* hscksvd_last_error(hscksvd_ctx* ctx);  /* ctx may be NULL (errors of
  * without atomics, so two calls on the same input return the same bits. */
 int hscksvd_update(hscksvd_ctx* ctx, int T, int K, int W, int F, double* D, const int32_t* indptr,
                    const int32_t* indices, double* data, int use_pca, double* out_atom_stats, double* timing_ms);
+
+/* The same sweep for ONE dictionary over a corpus of B signals of lengths T_0 .. T_{B-1}.  The
+ * coefficient matrix is the vertical stack [sum T_b][K] of the per-signal matrices, in CSC; row g of the stack belongs
+ * to signal b when row_offsets[b] <= g < row_offsets[b+1].
+ *   row_offsets [B+1]  row_offsets[0] = 0, strictly ascending (no empty signal); row_offsets[B] = sum T_b, the row count
+ *                      of the stack (int32: a stack of 2^31 rows or more cannot be passed)
+ *   indices     [nnz]  stacked rows, strictly ascending within each column, in [0, sum T_b)
+ *   plan        0: plan 2 when some atom has HSCKSVD_WIDE_FROM_OCCURRENCES occurrences or more, else plan 1;
+ *               1: one workgroup walks all atoms (hscksvd_update's kernel); 2: wide, per atom a grid over its
+ *               occurrences, a grid over the Gram entries and one workgroup for the eigenvectors, in stream order.
+ *               Every plan returns the same bits.
+ *   D, indptr, data, use_pca, out_atom_stats, timing_ms as in hscksvd_update.
+ * The update is hscksvd_update's, with these differences:
+ *   occurrences: the non-zero entries of column k of the stack in ascending stacked row (signal after signal, time
+ *         ascending within a signal); every sum over the occurrences runs in that order.
+ *   patches: P_i of an occurrence in signal b is the reconstruction of every other atom's non-zero coefficients OF
+ *         SIGNAL b ONLY over [t_i - (W-1)/2, +W), 0 outside [0, T_b) of that signal: an atom's span is clipped at its
+ *         own signal's ends and never contributes to a sample of another signal.  Each sample is summed from 0.0 in
+ *         CSC order of the stack (column, then stacked row), rounded products, no FMA.
+ * Two anchors follow: with B = 1 the result is bit for bit hscksvd_update's; and when every stored entry's span lies
+ * inside its signal ((W-1)/2 <= t <= T_b - W + (W-1)/2) it is bit for bit hscksvd_update's on the plain stack, T = sum T_b. */
+int hscksvd_update_corpus(hscksvd_ctx* ctx, int B, const int32_t* row_offsets, int K, int W, int F, double* D,
+                          const int32_t* indptr, const int32_t* indices, double* data, int use_pca, int plan,
+                          double* out_atom_stats, double* timing_ms);
 
 #ifdef __cplusplus
 }
