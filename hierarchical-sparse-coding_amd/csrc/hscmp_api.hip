@@ -34,6 +34,7 @@ struct Knobs {
     bool no_dict_lists, no_row_lists, no_rowbits, no_pairing, force_gathered, force_generic;     // set or not
     bool init_only, exact_init, exact_recorr, locomp_no_mfma, no_sorted_prepare, no_lazy_clear;
     int rp, mfma_quad, sparse_packed;     // 0 / 1 forces the choice; -1: not set, chosen by the shape
+    int bound_products;                   // bf16 products per tap of the initial bound pass: 3 when set to 3, else 1 (hscmp_bound.h)
     int locomp_pack;                      // at most this many signals per workgroup; 0: not set, by the batch size
     int slot_hash_min, locomp_group_cap, locomp_ahead, sorted_prepare_min, lds_pad;     // the value, or the default
     int epi_lds_keys;                     // the value if a power of two in 64..kEpiLdsKeys, else kEpiLdsKeys
@@ -98,6 +99,7 @@ static Knobs read_knobs()
     k.rp = (v = getenv("HSCMP_RP")) ? atoi(v) != 0 : -1;
     k.mfma_quad = (v = getenv("HSCMP_MFMA_QUAD")) ? atoi(v) != 0 : -1;
     k.sparse_packed = (v = getenv("HSCMP_SPARSE_PACKED")) ? atoi(v) != 0 : -1;
+    k.bound_products = (v = getenv("HSCMP_BOUND_PRODUCTS")) && atoi(v) == 3 ? 3 : 1;
     k.locomp_pack = (v = getenv("HSCMP_LOCOMP_PACK")) ? std::max(1, atoi(v)) : 0;     // (0 and below pack like 1)
     k.slot_hash_min = (v = getenv("HSCMP_SLOT_HASH_MIN")) ? std::max(0, atoi(v)) : kSlotHashMin;
     k.locomp_group_cap = (v = getenv("HSCMP_LOCOMP_GROUP_CAP")) ? std::min(4096, std::max(2, atoi(v))) : kLocompGroupCap;
@@ -660,7 +662,7 @@ template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const Knobs&
             // float32 single-arg-max encodes: the initial correlation as upper bounds on the bf16 matrix cores, refined by the loop
             // where a selection needs it (hscmp_bound.h).  HSCMP_EXACT_INIT=1: the exact pass everywhere.
             if (!P.blocked && !P.select_only && ctx->dict.Bimg.p && !kn.exact_init &&
-                bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->dict.Bimg.as<unsigned short>(), ctx->dict.bound_cmax, true) == 0)
+                bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->dict.Bimg.as<unsigned short>(), ctx->dict.bound_cmax, kn.bound_products, true) == 0)
                 plan.init = EncodePlan::kInitBound;
             // ... and the four-signal loop re-correlates as upper bounds too, on the bf16 planes (HSCMP_EXACT_RECORR=1: the
             // exact re-correlation behind the bound pass; HSCMP_EXACT_INIT=1 keeps both exact)
@@ -738,7 +740,7 @@ template <typename R> static int launch_init(hscmp_ctx* ctx, const EncodePlan& p
     switch (plan.init) {
     case EncodePlan::kInitMfma: rc = mfma_launch_corr_init<R>(ctx->stream, P, S, dimg); break;
     case EncodePlan::kInitBound:
-        if constexpr (sizeof(R) == 4) rc = bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->dict.Bimg.as<unsigned short>(), ctx->dict.bound_cmax);
+        if constexpr (sizeof(R) == 4) rc = bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->dict.Bimg.as<unsigned short>(), ctx->dict.bound_cmax, plan.knobs.bound_products);
         break;
     case EncodePlan::kInitSparse: {
         const SparseArgs<R> A = sparse_args<R>(ctx, plan, P.T);

@@ -8,11 +8,32 @@
 // arg-max over exact scores with the same tie rule.
 //
 // The products: every float32 operand v splits into bf16 hi = rn(v), lo = rn(v - hi) (v - hi is exact in
-// float32), and the tile sums hi.hi + hi.lo + lo.hi on v_mfma_f32_32x32x16_bf16 (3/16 of the cycles of the
-// float32 form: 12 instead of 32 MFMAs per 32 x 32 tile and atom group at W = 64, each 32 cycles instead of 64;
-// measured in DESIGN.md section 11).
+// float32).  The bound pass of the initial correlation sums hi.hi alone on v_mfma_f32_32x32x16_bf16 (NP = 1: 4 MFMAs
+// of 32 cycles per 32 x 32 tile and atom group at W = 64, where the float32 form takes 32 of 64 cycles); the loop's
+// tile, and the initial pass under HSCMP_BOUND_PRODUCTS=3, sum hi.hi + hi.lo + lo.hi (NP = 3: 12 MFMAs).  One product
+// is 64 times looser (2^-7 against 2^-13 of ||x_win|| cmax); what the loop pays for that is a refine of a position that
+// outranks the exact winner by less than the slack, measured in DESIGN.md section 11.
 //
-// ---- derivation of the error constant ------------------------------------------------------------------------
+// ---- derivation of the error constant, one product (NP = 1, kBoundEps1) ----------------------------------------
+// u, u', u'' as below; n = 16 * SB <= 64 products per output, W <= 64 taps.  The tile sees xh and dh only.
+// (1) dropped terms: x d - xh dh = xh (d - dh) + (x - xh) d with |d - dh| <= u|d|, |x - xh| <= u|x|, |xh| <= (1+u)|x|:
+//       |dropped| <= u ((1+u) + 1) |x||d| = u (2 + u) |x||d| = 7.82776e-3 |x||d|  per tap.
+// (2) the matrix core: every product exact in float32 and normal (below), n of them summed in any order with relative
+//       error <= u' per step: gamma_64(u') sum|xh dh| <= 7.6295e-6 (1+u)^2 |x||d| = 7.6892e-6 |x||d|; the flush of a
+//       cancelling partial sum is covered by kBoundAbs as below.
+// (3) the pinned float32 chain against the real sum: 3.8147e-6 |x||d|, as below.
+//   Together  |chain_k - acc_k| <= eps_1 sum_w |x_w||d_kw| <= eps_1 ||x_win|| ||d_k||,
+//       eps_1 = 7.82776e-3 + 7.6892e-6 + 3.8147e-6 = 7.83926e-3  (= 2^-6.995).
+// (4) the bound's own arithmetic is that of NP = 3 with one difference: ss is the float32 sum of xh^2 (the lo halves are
+//     never formed), and |x| <= |xh| / (1-u) tap by tap, so ||x_win|| <= ||xh_win|| / (1-u):
+//       score <= (1+u'')/(1-u'') max_k v_k + (1+u'') eps_1 / (1-u) ||xh_win|| cmax,   (1+u'') eps_1 / (1-u) = 7.87001e-3.
+//     kBoundEps1 = 2^-7 (1 + 2^-6) = 7.93457e-3 is 1.0082 times that.  The margin of 0.82 % is there for the roundings of
+//     rn(rn(kBoundEps1 * rn(sqrt(ss))) * cmax) + 2^-80 and of ss itself (at most 64 fmaf, a sqrt good to 2 ulp, three more
+//     roundings: together below a factor 1 - 2^-17 = 1 - 0.0008 %), a thousand times over; it is not needed for anything
+//     else, and the constant is not tuned on data (tests/test_bound_one_product.py puts it against the pinned chain).
+//     xh = 0 only where x = 0 (|x| >= 2^-60 in the model), so ss == 0 still means an all-zero window: an exact 0.
+//
+// ---- derivation of the error constant, three products (NP = 3, kBoundEps) --------------------------------------
 // u = 2^-8 (bf16 round to nearest), u' = 2^-23 (one accumulation step of the matrix core, ANY order and ANY
 // rounding direction), u'' = 2^-24 (float32 round to nearest), n = 3 * 16 * SB <= 192 products per output,
 // W <= 16 * SB <= 64 taps.  For x (signal) and d (atom) write x = xh + xl + xr (xr the split remainder):
@@ -143,14 +164,16 @@ inline bool bound_build_dict_image(const float* D, const float* wts, int K, int 
 
 // ------------------------------------------------------------------------------------------------
 // The bound pass: the persistent grid of corr_init_mfma_kernel over (signal, 2048-position chunk) items.
-// LDS: [bf16 hi image][bf16 lo image][weights 32*G][chunk: bf16 hi + bf16 lo halves, or the float32 chunk of a chunk
-// outside the model].  A chunk outside the model (see the header) runs mfma_tile_score on the float32 image in global
+// NP = 1 (one product per tap, the default) or 3 (HSCMP_BOUND_PRODUCTS=3): the tile of bound_tile<SB, HAS_W, NP>.
+// LDS: [bf16 hi image][NP = 3: bf16 lo image][weights 32*G][chunk: bf16 hi halves (NP = 3: and the lo halves behind them), or
+// the float32 chunk of a chunk outside the model].  NP = 1 rounds every sample once and never forms a lo half.
+// A chunk outside the model (see the header) runs mfma_tile_score on the float32 image in global
 // memory (L2-resident): the exact score and group hint, bit for bit what corr_init_mfma_kernel writes.
 // A position whose bound came out as an exact 0 (all-zero window) gets the hint 0 like the exact tile: it is exact.
 // ------------------------------------------------------------------------------------------------
 template <int SB> __host__ __device__ constexpr int bound_chunk_samples() { return kMfmaChunk + 16 * SB + 32; }
 
-template <int SB, bool HAS_W>
+template <int SB, bool HAS_W, int NP>
 __global__ __launch_bounds__(kThreads) void corr_bound_kernel(DevParams P, State<float> S, MfmaArgs A,
                                                               const unsigned short* __restrict__ bimg, float cmax)
 {
@@ -160,19 +183,20 @@ __global__ __launch_bounds__(kThreads) void corr_bound_kernel(DevParams P, State
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int G = A.G;
     const int nimg = G * SB * 64;                       // 16-byte fragments per image
+    constexpr int NI = NP == 3 ? 2 : 1;                 // images in LDS: hi (plane 0 of Bimg), and lo (plane 1) behind it
     bf16x8* bh = reinterpret_cast<bf16x8*>(smem);
-    bf16x8* bl = bh + nimg;
-    float* wts = reinterpret_cast<float*>(bl + nimg);
+    bf16x8* bl = bh + nimg;                             // (NP = 1: never read)
+    float* wts = reinterpret_cast<float*>(bh + NI * nimg);
     char* xbuf = reinterpret_cast<char*>(wts + 32 * G);
     unsigned short* xh = reinterpret_cast<unsigned short*>(xbuf);
-    unsigned short* xl = xh + nx;
+    unsigned short* xl = xh + nx;                       // (NP = 1: never written or read)
     float* xs = reinterpret_cast<float*>(xbuf);         // (same bytes: a chunk is staged in one form or the other)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int T = P.T;
     const int cps = (T + kMfmaChunk - 1) / kMfmaChunk;
     const int nitems = cps * P.B;
 
-    lds_copy16(bh, bimg, 2 * nimg * 16);
+    lds_copy16(bh, bimg, NI * nimg * 16);
     if (HAS_W) for (int i = tid; i < 32 * G; i += kThreads) wts[i] = i < P.K ? S.weights[i] : 0.0f;
 
     float xr[kMfmaChunkLoads];
@@ -199,6 +223,7 @@ __global__ __launch_bounds__(kThreads) void corr_bound_kernel(DevParams P, State
             const int i = u * kThreads + tid;
             if (i < nx) {
                 if (exact) xs[i] = xr[u];
+                else if constexpr (NP == 1) xh[i] = (unsigned short)(bf16_rn_bits(__float_as_uint(xr[u])) >> 16);
                 else { unsigned short hi, lo; bf16_split(xr[u], hi, lo); xh[i] = hi; xl[i] = lo; }
             }
         }
@@ -214,7 +239,7 @@ __global__ __launch_bounds__(kThreads) void corr_bound_kernel(DevParams P, State
             int grp;
             if (exact) sc = mfma_tile_score<S4C, HAS_W>(A.dimg, xs + 32 * q, wts, G, S4C, lane, grp);
             else {
-                sc = bound_tile<SB, HAS_W>(bh, bl, xh + 32 * q, xl + 32 * q, wts, G, lane, cmax);
+                sc = bound_tile<SB, HAS_W, NP>(bh, bl, xh + 32 * q, xl + 32 * q, wts, G, lane, cmax);
                 grp = sc == 0.0f ? 0 : -1;              // an exact 0 is a score (hint 0, as the exact tile); else a bound
             }
             const int t = c0 + 32 * q + lane;
@@ -226,15 +251,18 @@ __global__ __launch_bounds__(kThreads) void corr_bound_kernel(DevParams P, State
     }
 }
 
-// LDS bytes of the bound pass
-inline size_t bound_lds_bytes(int G, int SB) { return (size_t)2 * G * SB * 1024 + (size_t)32 * G * 4 + (size_t)(kMfmaChunk + 16 * SB + 32) * 4; }
+// LDS bytes of the bound pass: one image (NP = 1) or two, the weights, the chunk as float32 (the exact tile's form, the larger one)
+inline size_t bound_lds_bytes(int G, int SB, int NP)
+{
+    return (size_t)(NP == 3 ? 2 : 1) * G * SB * 1024 + (size_t)32 * G * 4 + (size_t)(kMfmaChunk + 16 * SB + 32) * 4;
+}
 
-template <int SB, bool HAS_W>
+template <int SB, bool HAS_W, int NP>
 static int bound_launch_t(hipStream_t stream, const DevParams& P, const State<float>& S, const MfmaArgs& A,
                           const unsigned short* bimg, float cmax, bool dry)
 {
-    const size_t lds = bound_lds_bytes(A.G, SB);
-    auto kern = corr_bound_kernel<SB, HAS_W>;
+    const size_t lds = bound_lds_bytes(A.G, SB, NP);
+    auto kern = corr_bound_kernel<SB, HAS_W, NP>;
     if (set_dyn_lds((const void*)kern, lds) != hipSuccess) return -1;
     if (dry) return 0;
     const int cus = mfma_device_cus();
@@ -246,17 +274,26 @@ static int bound_launch_t(hipStream_t stream, const DevParams& P, const State<fl
     return 0;
 }
 
+template <int SB>
+static int bound_launch_sb(hipStream_t stream, const DevParams& P, const State<float>& S, const MfmaArgs& A,
+                           const unsigned short* bimg, float cmax, int products, bool dry)
+{
+    const bool hw = A.has_w != 0;
+    if (products == 3) return hw ? bound_launch_t<SB, true, 3>(stream, P, S, A, bimg, cmax, dry) : bound_launch_t<SB, false, 3>(stream, P, S, A, bimg, cmax, dry);
+    return hw ? bound_launch_t<SB, true, 1>(stream, P, S, A, bimg, cmax, dry) : bound_launch_t<SB, false, 1>(stream, P, S, A, bimg, cmax, dry);
+}
+
 // The bound pass for this shape, or -1 when it does not cover it (the caller then runs the exact corr_init):
 // the float32 chunk counts 2, 4, 8 of the compile-time MFMA kernels (W in 9..16, 25..32, 57..64).
+// products: bf16 products per tap, 1 or 3 (Knobs::bound_products).
 inline int bound_launch_corr_init(hipStream_t stream, const DevParams& P, const State<float>& S, const float* dimg,
-                                  const unsigned short* bimg, float cmax, bool dry = false)
+                                  const unsigned short* bimg, float cmax, int products, bool dry = false)
 {
     const MfmaArgs A = mfma_args<float>(P, S, dimg);
-    const bool hw = A.has_w != 0;
     switch (A.S4) {
-    case 8: return hw ? bound_launch_t<4, true>(stream, P, S, A, bimg, cmax, dry) : bound_launch_t<4, false>(stream, P, S, A, bimg, cmax, dry);
-    case 4: return hw ? bound_launch_t<2, true>(stream, P, S, A, bimg, cmax, dry) : bound_launch_t<2, false>(stream, P, S, A, bimg, cmax, dry);
-    case 2: return hw ? bound_launch_t<1, true>(stream, P, S, A, bimg, cmax, dry) : bound_launch_t<1, false>(stream, P, S, A, bimg, cmax, dry);
+    case 8: return bound_launch_sb<4>(stream, P, S, A, bimg, cmax, products, dry);
+    case 4: return bound_launch_sb<2>(stream, P, S, A, bimg, cmax, products, dry);
+    case 2: return bound_launch_sb<1>(stream, P, S, A, bimg, cmax, products, dry);
     default: return -1;
     }
 }

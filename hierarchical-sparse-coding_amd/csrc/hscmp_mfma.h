@@ -317,14 +317,16 @@ __device__ __forceinline__ float mfma_tile_score_lean(const float* __restrict__ 
 
 // ------------------------------------------------------------------------------------------------
 // The bound tile: certified UPPER BOUNDS of a 32-position tile's scores on the bf16 matrix cores (float32 operands
-// split into bf16 hi + lo; hi.hi + hi.lo + lo.hi on v_mfma_f32_32x32x16_bf16).  One definition for the bound pass of
-// the initial correlation (corr_bound_kernel) and the re-correlation of the four-signal loop (MfmaRecorr, BOUND):
-// hscmp_bound.h derives the constants and states the model the inputs must lie in.
+// split into bf16 hi + lo; NP = 3 products hi.hi + hi.lo + lo.hi, or NP = 1: hi.hi alone, on v_mfma_f32_32x32x16_bf16).
+// One definition for the bound pass of the initial correlation (corr_bound_kernel: NP = 1, or 3 on request) and the
+// re-correlation of the four-signal loop (MfmaRecorr, BOUND: NP = 3): hscmp_bound.h derives the constants and states
+// the model the inputs must lie in.
 // ------------------------------------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr float kBoundEps = 0x1p-13f;        // >= 1.67 eps_0 (hscmp_bound.h)
+constexpr float kBoundEps = 0x1p-13f;        // three products: >= 1.67 eps_0 (hscmp_bound.h)
+constexpr float kBoundEps1 = 0x1p-7f * (1.0f + 0x1p-6f);     // one product: >= 1.008 eps_0 / (1 - 2^-8) (hscmp_bound.h)
 constexpr float kBoundRel = 1.0f + 0x1p-20f;
 constexpr float kBoundAbs = 0x1p-80f;
 constexpr float kBoundXMin = 0x1p-60f, kBoundXMax = 0x1p60f;     // signal samples (per chunk, on the device)
@@ -353,32 +355,37 @@ __device__ __forceinline__ float bf16_hi_f(unsigned w) { return __uint_as_float(
 //   bimg: LDS [hi image][lo image];  xh, xl: the chunk's bf16 halves in LDS, 4-byte aligned, index 0 = the first tap
 //   of the tile's first position.  B operand of k-step s, lane (r, h): samples r + 16s + 8h + j, j = 0..7 -- 8
 //   consecutive bf16 at an odd or even start: five aligned dwords and v_alignbit.
-template <int SB, bool HAS_W>
+// NP = 1: only the hi image and the hi halves are read (bimg_l and xl may be null), one MFMA per k-step, and the window norm
+// comes from the hi halves (||x|| <= ||xh|| / (1 - 2^-8), inside kBoundEps1).
+template <int SB, bool HAS_W, int NP>
 __device__ __forceinline__ float bound_tile(const bf16x8* __restrict__ bimg_h, const bf16x8* __restrict__ bimg_l,
                                             const unsigned short* __restrict__ xh, const unsigned short* __restrict__ xl,
                                             const float* __restrict__ wts, int G, int lane, float cmax)
 {
+    static_assert(NP == 1 || NP == 3, "hi.hi, or hi.hi + hi.lo + lo.hi");
+    constexpr bool LO = NP == 3;
     const int r = lane & 31, h = lane >> 5;
     const unsigned* xh32 = reinterpret_cast<const unsigned*>(xh);
     const unsigned* xl32 = reinterpret_cast<const unsigned*>(xl);
     const unsigned sh = 16u * (unsigned)(r & 1);
-    u32x4 bh[SB], bl[SB];
+    u32x4 bh[SB], bl[LO ? SB : 1];
     float ss = 0.0f;
 #pragma unroll
     for (int s = 0; s < SB; ++s) {
         const int w0 = (r >> 1) + 8 * s + 4 * h;
         unsigned a[5], b[5];
 #pragma unroll
-        for (int i = 0; i < 5; ++i) { a[i] = xh32[w0 + i]; b[i] = xl32[w0 + i]; }
+        for (int i = 0; i < 5; ++i) { a[i] = xh32[w0 + i]; if constexpr (LO) b[i] = xl32[w0 + i]; }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             bh[s][i] = __builtin_amdgcn_alignbit(a[i + 1], a[i], sh);
-            bl[s][i] = __builtin_amdgcn_alignbit(b[i + 1], b[i], sh);
+            if constexpr (LO) bl[s][i] = __builtin_amdgcn_alignbit(b[i + 1], b[i], sh);
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {                           // ||xh + xl||^2 over this half-wave's taps (xh + xl exact)
-            const float y0 = bf16_lo_f(bh[s][i]) + bf16_lo_f(bl[s][i]);
-            const float y1 = bf16_hi_f(bh[s][i]) + bf16_hi_f(bl[s][i]);
+        for (int i = 0; i < 4; ++i) {                           // ||xh + xl||^2 over this half-wave's taps (xh + xl exact); NP = 1: ||xh||^2
+            float y0, y1;
+            if constexpr (LO) { y0 = bf16_lo_f(bh[s][i]) + bf16_lo_f(bl[s][i]); y1 = bf16_hi_f(bh[s][i]) + bf16_hi_f(bl[s][i]); }
+            else { y0 = bf16_lo_f(bh[s][i]); y1 = bf16_hi_f(bh[s][i]); }
             ss = fmaf(y0, y0, ss);
             ss = fmaf(y1, y1, ss);
         }
@@ -393,11 +400,15 @@ __device__ __forceinline__ float bound_tile(const bf16x8* __restrict__ bimg_h, c
         acc = z;
 #pragma unroll
         for (int s = 0; s < SB; ++s) {
-            const bf16x8 ah = bimg_h[(g * SB + s) * 64 + lane], al = bimg_l[(g * SB + s) * 64 + lane];
-            const bf16x8 xbh = __builtin_bit_cast(bf16x8, bh[s]), xbl = __builtin_bit_cast(bf16x8, bl[s]);
+            const bf16x8 ah = bimg_h[(g * SB + s) * 64 + lane];
+            bf16x8 al;
+            if constexpr (LO) al = bimg_l[(g * SB + s) * 64 + lane];
+            const bf16x8 xbh = __builtin_bit_cast(bf16x8, bh[s]);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xbh, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xbl, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xbh, acc, 0, 0, 0);
+            if constexpr (LO) {
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, __builtin_bit_cast(bf16x8, bl[s]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xbh, acc, 0, 0, 0);
+            }
         }
     };
     auto reduce = [&](const f32x16& acc, int g) {
@@ -423,8 +434,8 @@ __device__ __forceinline__ float bound_tile(const bf16x8* __restrict__ bimg_h, c
         reduce(acc0, G - 1);
     }
     bs = fmaxf(bs, swap_halves_f(bs, h));
-    if (ss == 0.0f) return bs;                                  // all-zero window: every product and sum is an exact 0
-    const float e = __fmul_rn(__fmul_rn(kBoundEps, __fsqrt_rn(ss)), cmax) + kBoundAbs;
+    if (ss == 0.0f) return bs;                                  // all-zero window (xh == 0 only where x == 0): every product and sum is an exact 0
+    const float e = __fmul_rn(__fmul_rn(LO ? kBoundEps : kBoundEps1, __fsqrt_rn(ss)), cmax) + kBoundAbs;
     return fmaf(bs, kBoundRel, e);
 }
 
@@ -1547,7 +1558,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
                     sc = planes_tile_score<SB, HAS_W>(L.bimg, L.nplane, L.win + TP * q, L.wts, A.G, lane, grp);
                 } else {
                     const bf16x8* ph = reinterpret_cast<const bf16x8*>(L.bimg);
-                    sc = bound_tile<SB, HAS_W>(ph, ph + L.nplane / 8, L.xh + TP * q, L.xl + TP * q, L.wts, A.G, lane, A.cmax);
+                    sc = bound_tile<SB, HAS_W, 3>(ph, ph + L.nplane / 8, L.xh + TP * q, L.xl + TP * q, L.wts, A.G, lane, A.cmax);
                     grp = sc == 0.0f ? 0 : -1;                  // an exact 0 is a score (hint 0, as the exact tile); else a bound
                 }
             } else if constexpr (GS > 1 && S4C > 0) sc = Tile::template tile_score_lean<S4C, HAS_W>(L.dimg, L.win + TP * q, L.wts, A.G, S4, lane, grp);

@@ -1,13 +1,15 @@
-"""Diagnostic: per-phase cycle shares of the fused greedy loop (libhscmp built with -DHSCMP_DBG_STAMPS)."""
+"""Diagnostic: per-phase cycle shares of the fused greedy loop (libhscmp built with -DHSCMP_DBG_STAMPS).
+    python tools/read_stamps.py <libhscmp.so of that build>      (environment: B = signals, KIND = planted | noise)"""
 import ctypes, os, sys, numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import hsc_amd.synth as synth
 from hsc_amd import _native
 B = int(os.environ.get('B', '1024'))
+KIND = os.environ.get('KIND', 'planted')
 _native.LIB_PATH = os.path.abspath(sys.argv[1])
 D = synth.make_dictionary(256, 64, seed=2)
-x = torch.from_numpy(synth.make_batch(D, 65536, 0, 8, kind='planted', nb_atoms=256, seed=2)).cuda().repeat(B // 8, 1).contiguous()
+x = torch.from_numpy(synth.make_batch(D, 65536, 0, 8, kind=KIND, nb_atoms=256, seed=2)).cuda().repeat(B // 8, 1).contiguous()
 eng = _native.Engine(0); eng.set_dictionary(D)
 params = _native.make_params(nbNonzeroCoefs=256, eps=1.2e-7, maxEvents=576)
 lib = _native.load_library()
@@ -18,7 +20,7 @@ for i in range(3):
     v = np.array(list(out), dtype=np.float64)
     n = max(v[15], 1)
 names = ['dup+update to B1', 'B1', 'energy', 'MFMA tile', 'B4', 'seg+bookkeeping', 'B5', 'deferred stores']
-print('B=%d atoms=%d loop %.3f ms' % (B, n, eng.last_kernel_ms()[2]))
+print('B=%d kind=%s atoms=%d init %.3f ms loop %.3f ms' % (B, KIND, n, eng.last_kernel_ms()[1], eng.last_kernel_ms()[2]))
 for i, nm in enumerate(names):
     print('  %-18s %8.0f cycles/atom' % (nm, v[i] / n))
 for i, nm in ((8, 'phase A issue'), (9, 'resolve (Bx..By)'), (10, '[return -> next round]'), (11, '[selection + round checks]'), (12, '[atom body incl. entry]')):
