@@ -8,11 +8,13 @@
 // arg-max over exact scores with the same tie rule.
 //
 // The products: every float32 operand v splits into bf16 hi = rn(v), lo = rn(v - hi) (v - hi is exact in
-// float32).  The bound pass of the initial correlation sums hi.hi alone on v_mfma_f32_32x32x16_bf16 (NP = 1: 4 MFMAs
-// of 32 cycles per 32 x 32 tile and atom group at W = 64, where the float32 form takes 32 of 64 cycles); the loop's
-// tile, and the initial pass under HSCMP_BOUND_PRODUCTS=3, sum hi.hi + hi.lo + lo.hi (NP = 3: 12 MFMAs).  One product
-// is 64 times looser (2^-7 against 2^-13 of ||x_win|| cmax); what the loop pays for that is a refine of a position that
-// outranks the exact winner by less than the slack, measured in DESIGN.md section 11.
+// float32).  The bound pass of the initial correlation and the loop's tile sum hi.hi alone on v_mfma_f32_32x32x16_bf16
+// (NP = 1: 4 MFMAs of 32 cycles per 32 x 32 tile and atom group at W = 64, where the float32 form takes 32 of 64 cycles);
+// the initial pass under HSCMP_BOUND_PRODUCTS=3, and a library built with -DHSCMP_LOOP_BOUND_PRODUCTS=3 in its loop, sum
+// hi.hi + hi.lo + lo.hi (NP = 3: 12 MFMAs).  One product is 64 times looser (2^-7 against 2^-13 of ||x_win|| cmax); what
+// the loop pays for that is a refine of a position that outranks the exact winner by less than the slack, and a winner
+// that more often holds its exact score from an earlier selection's refine (the cache of committed refines keeps that
+// refine's (k, c) for it), both measured in DESIGN.md section 11.
 //
 // ---- derivation of the error constant, one product (NP = 1, kBoundEps1) ----------------------------------------
 // u, u', u'' as below; n = 16 * SB <= 64 products per output, W <= 64 taps.  The tile sees xh and dh only.
@@ -67,9 +69,22 @@
 // tools/bf16_bound_probe.hip checks assumption (2) on the hardware (profiles/r05_bf16_probe.txt).
 //
 // The four-signal loop (MfmaRecorr with BOUND) re-correlates the rows around an applied atom with the same tile
-// (bound_tile, hscmp_mfma.h) over its reflect-padded window: the derivation above holds unchanged whenever every
-// sample the tile reads is inside the model, and a tile whose window holds one outside it (a wave-wide vote, every atom)
-// runs the exact float32 tile on the planes (planes_tile_score).  Split, epilogue and constants have one definition.
+// (bound_tile<SB, HAS_W, 1>, hscmp_mfma.h) over its reflect-padded window: the derivation above holds unchanged whenever
+// every sample the tile reads is inside the model, and a tile whose window holds one outside it (a wave-wide vote, every
+// atom) runs the exact float32 tile on the planes (planes_tile_score).  Split, epilogue and constants have one definition.
+// The assumptions of the one-product derivation, one by one, for the loop's caller:
+//   * n <= 64 products per output, W <= 64 taps: the tile runs SB <= 4 k-steps of 16 taps; past W the planes hold zeros, whose
+//     products are exact zeros, and the window norm over 16 SB >= W samples is only larger than the one the derivation needs.
+//   * xh = rn(x) of the very samples the pinned chain reads: window_split rounds the float32 value it writes to the window
+//     (the reflected copy near a signal end included, one rounding, bf16_rn_bits), and the refine reads that window again through
+//     edge_window_value -- the invariant that makes the refined score the row's score (MfmaRecorr::refine) whatever the tile.
+//   * dh = rn(d) of the float32 tap the chain uses: plane 0 is rn(d), and the exact chains rebuild d = (hi + lo) + rem bit for
+//     bit (bf16_rem below), so tile and chain speak of the same d.
+//   * every product normal, no sample outside [2^-60, 2^60] or not finite: the vote in front of the tile, over every sample
+//     the tile reads (taps past W included); dictionary and weights were checked on the host (bound_build_dict_image).
+//   * xh = 0 only where x = 0: by the same vote, so the ss == 0 return is an exact 0 and the rule "sc == 0 -> hint 0" stands.
+//   * cmax: the one A.cmax of bound_build_dict_image, as in the bound pass.
+// Nothing in (1)-(4) depends on the padding rule or on who calls the tile, and kBoundEps1 is the slack here too.
 #pragma once
 
 #include "hscmp_mfma.h"

@@ -614,6 +614,10 @@ template <typename R> struct RefineList {
     unsigned nx;                                                 // bound loop: exchanges of this launch so far; the low bit names the slot set of the next
     int t[kRefineCap]; R s[kRefineCap]; int g[kRefineCap];       // refined position, exact score, group hint
     int sg[kRefineCap]; R ms[kRefineCap]; int mt[kRefineCap];    // its segment and that segment's maximum after the refine
+    // bound loop: the lowest atom attaining s and its pinned chain, of every entry (wave-uniform: the refine's merge produces them
+    // for every refined position).  The commit hands those of the entries that did not win on to the signal's cache in LDS
+    // (MfmaRecorr::cache_commit), where the selection that such a position wins later finds them.
+    int k[kRefineCap]; R c[kRefineCap];
     // bound loop: the entry with the largest score, lowest position among equals -- if the selection's winner is in the list, it is
     // that entry, by the selection's own rule -- with the lowest atom attaining its score and that atom's pinned chain (hk = -1: not kept)
     int ht, hk; R hs, hc;
@@ -1192,6 +1196,7 @@ __global__ __launch_bounds__(kThreads * Recorr::kGroup, Recorr::kMinWavesPerSimd
                         if (rl.n == kRefineCap) {                              // (rare) the list is full: commit it, behind
                             sy.full();                                         // every wave's reads of the state ...
                             if (tid == 0) Recorr::refine_commit(G, sh, rl, INT_MAX, INT_MIN, INT_MAX, INT_MIN);
+                            Recorr::cache_commit(P, A, plds, rl, INT_MAX, INT_MIN);   // (bound loop: their (k, c) to the cache)
                             sy.full();                                         // ... and before anybody's next read
                             rl.n = 0;
                         }

@@ -319,8 +319,8 @@ __device__ __forceinline__ float mfma_tile_score_lean(const float* __restrict__ 
 // The bound tile: certified UPPER BOUNDS of a 32-position tile's scores on the bf16 matrix cores (float32 operands
 // split into bf16 hi + lo; NP = 3 products hi.hi + hi.lo + lo.hi, or NP = 1: hi.hi alone, on v_mfma_f32_32x32x16_bf16).
 // One definition for the bound pass of the initial correlation (corr_bound_kernel: NP = 1, or 3 on request) and the
-// re-correlation of the four-signal loop (MfmaRecorr, BOUND: NP = 3): hscmp_bound.h derives the constants and states
-// the model the inputs must lie in.
+// re-correlation of the four-signal loop (MfmaRecorr, BOUND: NP = 1, or 3 in a -DHSCMP_LOOP_BOUND_PRODUCTS=3 build):
+// hscmp_bound.h derives the constants and states the model the inputs must lie in.
 // ------------------------------------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -922,6 +922,20 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
 #ifndef HSCMP_REFINE_HANDOVER
 #define HSCMP_REFINE_HANDOVER 1
 #endif
+    // -DHSCMP_LOOP_BOUND_PRODUCTS=3 (measurement only): the bound loop's tile sums hi.hi + hi.lo + lo.hi and its window is split
+    // into hi and lo halves, as before the one-product tile.  The default, 1, is the tile of the bound pass.
+#ifndef HSCMP_LOOP_BOUND_PRODUCTS
+#define HSCMP_LOOP_BOUND_PRODUCTS 1
+#endif
+    // -DHSCMP_REFINE_CACHE=0 (measurement only): no cache of committed refines; a winner that holds an exact score from memory
+    // resolves (k, c) from its window and hint.
+#ifndef HSCMP_REFINE_CACHE
+#define HSCMP_REFINE_CACHE 1
+#endif
+    static constexpr int kLoopNP = HSCMP_LOOP_BOUND_PRODUCTS;   // (BOUND) bf16 products per tap of the loop's tile
+    static_assert(kLoopNP == 1 || kLoopNP == 3, "HSCMP_LOOP_BOUND_PRODUCTS: 1 or 3");
+    static constexpr bool kCache = BOUND && HSCMP_REFINE_CACHE != 0;
+    static constexpr int kCacheEntries = 64;    // (kCache) one 16-byte entry {t, k, c bits, age} per lane: see cache_commit
     static constexpr bool kLockstep = GS > 1 && HSCMP_QUAD_LOCKSTEP != 0;
     static constexpr int kMinWavesPerSimd = GS;         // (launch bounds: 4 signals x 4 waves = 4 waves per SIMD)
     using Sync = typename std::conditional<GS == 1, HwSync, SoftSync>::type;
@@ -953,8 +967,9 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     struct Layout {
         R* dimg; R* wts; R* win; R* esq; R* sbs; unsigned* bloom;
         R* rwin; R* rwin_w; unsigned long long* edge;
-        unsigned short* bimg; unsigned short* xh; unsigned short* xl;      // (BOUND) the planes; the window's bf16 hi / lo
+        unsigned short* bimg; unsigned short* xh; unsigned short* xl;      // (BOUND) the planes; the window's bf16 hi (kLoopNP = 3: and lo)
         int* rx;                                                           // (BOUND) the refine's exchange slots (see refine)
+        int4* rc;                                                          // (kCache) the cache of committed refines (see cache_commit)
         int nwin, wp, nsbmax, nplane;
     };
 
@@ -977,7 +992,8 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     {
         const size_t relems = (size_t)window_floats(P.W, A.S4) + 2 * 8 * A.S4 + (size_t)segbuf_len_p(P) + 8 * A.S4 + kWaves * 8 * A.S4;
         return relems * sizeof(R) + kBloomWords * sizeof(unsigned) + kEdgeWords * sizeof(unsigned long long) +
-               (BOUND ? (size_t)2 * window_floats(P.W, A.S4) * sizeof(unsigned short) + kRefineSlotBytes : 0);
+               (BOUND ? (size_t)(kLoopNP == 3 ? 2 : 1) * window_floats(P.W, A.S4) * sizeof(unsigned short) + kRefineSlotBytes : 0) +
+               (kCache ? (size_t)kCacheEntries * 16 : 0);
     }
     static __host__ __device__ size_t per_signal_lds_bytes(const DevParams& P, const Args& A)
     {
@@ -1015,8 +1031,10 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
         L.rwin_w = L.rwin + L.wp;
         L.edge = reinterpret_cast<unsigned long long*>(L.rwin_w + kWaves * L.wp);
         L.xh = reinterpret_cast<unsigned short*>(L.edge + kEdgeWords);
-        L.xl = L.xh + L.nwin;
-        L.rx = reinterpret_cast<int*>(L.xl + L.nwin);        // (16-byte aligned: every region in front is a multiple of 16 bytes)
+        L.xl = kLoopNP == 3 ? L.xh + L.nwin : nullptr;
+        // (16-byte aligned: every region in front is a multiple of 16 bytes -- window_floats is a multiple of 8)
+        L.rx = reinterpret_cast<int*>(L.xh + (kLoopNP == 3 ? 2 : 1) * L.nwin);
+        L.rc = reinterpret_cast<int4*>(L.rx) + 2 * kWaves;
         return L;
     }
 
@@ -1049,7 +1067,9 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
             if (HAS_W) for (int i = tid; i < Tile::GA * A.G; i += kThreads) L.wts[i] = i < P.K ? S.weights[i] : (R)0;
         }
         for (int i = tid; i < L.nwin; i += kThreads) L.win[i] = (R)0;   // the tail behind the span stays zero
-        if constexpr (BOUND) for (int i = tid; i < L.nwin; i += kThreads) { L.xh[i] = 0; L.xl[i] = 0; }
+        if constexpr (BOUND) for (int i = tid; i < L.nwin; i += kThreads) { L.xh[i] = 0; if constexpr (kLoopNP == 3) L.xl[i] = 0; }
+        // the cache starts empty on every launch: a resumed encode resolves its first from-memory winners from window and hint
+        if constexpr (kCache) if (tid < kCacheEntries) L.rc[tid] = make_int4(-1, 0, 0, 0);
         for (int i = tid; i < kBloomWords; i += kThreads) L.bloom[i] = 0u;
         for (int i = tid; i < (1 + kWaves) * L.wp; i += kThreads) L.rwin[i] = (R)0;   // padded taps stay zero
         if (tid < kEdgeWords) L.edge[tid] = S.edge[kEdgeWords * b + tid];
@@ -1086,13 +1106,18 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
             return L.dimg[Tile::dindex(k, w, S4)];
         }
     }
-    // (BOUND) sample i of the re-correlation's window as bf16 hi / lo, the bound tile's B operands
+    // (BOUND) sample i of the re-correlation's window as the bound tile's B operand: its bf16 hi half, one rounding (the
+    // one-product tile never reads a lo half); kLoopNP = 3: hi and lo
     static __device__ __forceinline__ void window_split(const Layout& L, int i, R v)
     {
-        unsigned short hi, lo;
-        bf16_split(v, hi, lo);
-        L.xh[i] = hi;
-        L.xl[i] = lo;
+        if constexpr (kLoopNP == 1) {
+            L.xh[i] = (unsigned short)(bf16_rn_bits(__float_as_uint((float)v)) >> 16);
+        } else {
+            unsigned short hi, lo;
+            bf16_split(v, hi, lo);
+            L.xh[i] = hi;
+            L.xl[i] = lo;
+        }
     }
     static __device__ __forceinline__ R dchain(const Layout& L, const R* rw, int k, int S4)
     {
@@ -1247,7 +1272,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
         const int sg = t >> P.seg_shift;
         // (constant indices only: the list stays in registers)
 #pragma unroll
-        for (int j = 0; j < kRefineCap; ++j) if (j == i) { rl.t[j] = t; rl.s[j] = s_ex; rl.g[j] = g_ex; }
+        for (int j = 0; j < kRefineCap; ++j) if (j == i) { rl.t[j] = t; rl.s[j] = s_ex; rl.g[j] = g_ex; if constexpr (kCache) { rl.k[j] = k_ex; rl.c[j] = c_ex; } }
         if constexpr (BOUND) { rl.lead(t, s_ex, k_ex, c_ex); rl.nx += 1u; }
         rl.n = i + 1;
         const int t0 = sg << P.seg_shift, t1 = min(P.T, t0 + P.seg);
@@ -1279,6 +1304,50 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
             if (i >= rl.n) break;
             if (rl.t[i] < rlo || rl.t[i] > rhi) { Gs.bc[rl.t[i]] = rl.s[i]; Gs.bk[rl.t[i]] = rl.g[i]; }
             if (rl.sg[i] < slo || rl.sg[i] > shi) { sh.seg_score[rl.sg[i]] = rl.ms[i]; sh.seg_t[rl.sg[i]] = rl.mt[i]; }
+        }
+    }
+
+    // ---- the cache of committed refines (bound loop) -------------------------------------------
+    // A selection refines the bound that leads, and with loose bounds (one product per tap) that position is often not the
+    // winner: the winner then holds an exact score that an EARLIER selection's refine committed to memory, and that refine
+    // had the position's (k, c) in hand.  The signal keeps them: kCacheEntries entries {t, k, c bits, age} in LDS, entry l
+    // read by lane l; t = -1: empty.
+    // Exactness.  An entry (t, k, c) is the lowest atom attaining the maximum over the window the writing pass of row t saw
+    // and that atom's pinned chain (refine) -- what resolve_group returns from the row's hint for as long as the row has not
+    // been re-correlated, the invariant that keeps the committed score of the row exact.  An atom at p re-correlates the rows
+    // p - (W-1) .. p + (W-1): every entry in that range is dropped at the atom's B1, whatever the tile then writes there.
+    // The stale sample of row T-1 with an even W is recorded in the edge history and read through edge_window_value by the
+    // refine and by resolve_group alike.  A position enters at most once between two drops: once committed, the row holds
+    // an exact score and is not refined again until an atom re-correlates it.
+    // Who writes.  The wave of the thread that commits the list (wave 0), at the two places refine_commit runs: behind B1 of
+    // apply_atom, and between the two barriers of the full list.  Lane l owns entry l, so the drop is one read and one
+    // guarded write; an entry of the list goes to the lowest empty slot, or over the oldest one (age = the count of the
+    // refine that produced it, unique and increasing within a launch).
+    // Who reads, and all-or-none.  apply_atom, when the winner was neither resolved by the selection nor refined by it.
+    // Every wave of the signal reads the cache between the previous atom's B5 (or the full list's second barrier) and this
+    // atom's B1; the writes lie behind B1 and in front of the writing wave's arrival at B4 (or between the full list's two
+    // barriers).  So the four waves see the same entries and take the same path.
+    // rlo..rhi: the rows the atom re-correlates (empty for the full list's commit).
+    static __device__ __forceinline__ void cache_commit(const DevParams& P, const Args& A, char* lds, const RefineList<R>& rl, int rlo, int rhi)
+    {
+        if constexpr (kCache) {
+            const int tid = ltid();
+            if ((tid >> 6) != 0) return;
+            const int lane = tid & 63;
+            int4* rc = layout(P, A, lds).rc;
+            int et = rc[lane].x, ea = rc[lane].w;
+            if (et >= rlo && et <= rhi) { et = -1; rc[lane].x = -1; }          // these rows become bounds again
+#pragma unroll
+            for (int i = 0; i < kRefineCap; ++i) {
+                if (i >= rl.n) break;
+                if (rl.t[i] >= rlo && rl.t[i] <= rhi) continue;               // (uniform) re-correlated by this atom
+                const unsigned long long empty = __builtin_amdgcn_ballot_w64(et < 0);
+                int slot;
+                if (empty != 0ull) slot = __builtin_ctzll(empty);
+                else { const int mn = wave_min_i32(ea); slot = __builtin_ctzll(__builtin_amdgcn_ballot_w64(ea == mn)); }
+                const int age = (int)(rl.nx - (unsigned)rl.n + (unsigned)i);
+                if (lane == slot) { et = rl.t[i]; ea = age; rc[lane] = make_int4(et, rl.k[i], __float_as_int(rl.c[i]), ea); }
+            }
         }
     }
 
@@ -1332,6 +1401,22 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
         // an exact score from memory (the exact fallback tile, HSCMP_EXACT_RECORR=1) was not refined and resolves below.
         bool handed = false;
         if constexpr (BOUND && HSCMP_REFINE_HANDOVER != 0) { if (!resolved) handed = rl.find_atom(p, k, c); }
+        // ... but by an earlier one, whose commit kept its (k, c) in the signal's cache (cache_commit): the same path
+        if constexpr (kCache) {
+            if (!resolved && !handed) {
+                const int4 ce = L.rc[lane];
+                const unsigned long long hit = __builtin_amdgcn_ballot_w64(ce.x == p);
+                if (hit != 0ull) {
+                    const int hl = __builtin_ctzll(hit);
+                    k = __builtin_amdgcn_readlane(ce.y, hl);
+                    c = __int_as_float(__builtin_amdgcn_readlane(ce.z, hl));
+                    handed = true;
+#ifdef HSCMP_DBG_STAMPS
+                    if (blockIdx.x == 0 && threadIdx.x == 0) g_stamps[14] += 1;   // winners of signal 0 taken from the cache
+#endif
+                }
+            }
+        }
         const bool known = resolved || handed;              // (uniform)
         if (known) { k = __builtin_amdgcn_readfirstlane(k); c = wave_bcast(c, 0); }
         HSCMP_MARK("A_loads");
@@ -1519,6 +1604,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
         // this selection's refines to memory: every wave has made its selection and loaded what it reads of the state.
         // The rows this atom re-correlates and the segments it rescans are written below anyway (visible behind B5).
         if constexpr (kRefine) if (rl.n > 0 && tid == 0) refine_commit(Gs, sh, rl, p - (W - 1), p + (W - 1), sg0, sg1);
+        cache_commit(P, A, lds, rl, p - (W - 1), p + (W - 1));  // (bound loop) drop the rows' entries, keep the list's (k, c)
         if (P.has_scale) {                                      // toleranceResidualScale: max|r| of touched segments
             sy.full();                                          // (the stores above are visible to the scan)
             for (int sg = (s >> P.seg_shift) + wv; sg <= ((e - 1) >> P.seg_shift); sg += kWaves) rscan_segment(P, Gs, sh, sg, lane);
@@ -1558,7 +1644,8 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
                     sc = planes_tile_score<SB, HAS_W>(L.bimg, L.nplane, L.win + TP * q, L.wts, A.G, lane, grp);
                 } else {
                     const bf16x8* ph = reinterpret_cast<const bf16x8*>(L.bimg);
-                    sc = bound_tile<SB, HAS_W, 3>(ph, ph + L.nplane / 8, L.xh + TP * q, L.xl + TP * q, L.wts, A.G, lane, A.cmax);
+                    sc = bound_tile<SB, HAS_W, kLoopNP>(ph, ph + L.nplane / 8, L.xh + TP * q, kLoopNP == 3 ? L.xl + TP * q : nullptr, L.wts, A.G,
+                                                        lane, A.cmax);
                     grp = sc == 0.0f ? 0 : -1;                  // an exact 0 is a score (hint 0, as the exact tile); else a bound
                 }
             } else if constexpr (GS > 1 && S4C > 0) sc = Tile::template tile_score_lean<S4C, HAS_W>(L.dimg, L.win + TP * q, L.wts, A.G, S4, lane, grp);

@@ -30,6 +30,7 @@ for i, nm in ((48, '  scan(s) before a refine'), (49, '  refine: window + chains
     print('  %-26s %8.0f cycles/atom' % (nm, v[i] / n))
 print('  %-18s %8.0f cycles/atom (sum; the select between atoms is not stamped)' % ('total', (v[:8].sum() + v[8] + v[9]) / n))
 print('  refines per selection %.3f (%d; bound pass of the initial correlation and bound loop)' % (v[13] / n, v[13]))
+print('  cache hits per selection %.3f (%d; winners whose (k, c) came from the cache of committed refines, bound loop)' % (v[14] / n, v[14]))
 
 # per-workgroup residency (diagnostic build)
 try:
