@@ -13,6 +13,12 @@
 //   2. norm_kernel: ||patch|| of every window's matched patch, numpy's pairwise summation of the squares.
 //   3. member_kernel: one wave per centroid lists its members in ascending window order (ballot + popcount).
 //   4. sum_kernel: one thread per (centroid, element) sums patch / ||patch|| over the members in list order.
+// Steps 3 and 4 are centroid plan 1.  Plan 2 (wide) returns the same bits from a stable partition
+// of the windows by centroid (hist_kernel, scan_kernel, place_kernel: one [N] index array with K + 1 offsets) and
+// wide_sum_kernel: one workgroup per (centroid, tile of 256 elements) that stages its members' rows, divided by their
+// norms, through a double-buffered LDS ring and adds them in list order, one lane per element.
+// hsckmeans_set_corpus stacks signals of different lengths as one learner's data [rows][F]: every kernel reads it as
+// B = 1, T = rows, with window starts that are stacked rows.
 // Compiled with -ffp-contract=off: no product is fused into a sum outside the explicit MFMA chains.
 #include "../../../include/hsckmeans.h"
 #include "../common/hsc_lib.h"
@@ -289,6 +295,229 @@ __global__ __launch_bounds__(256) void sum_kernel(const X* __restrict__ x, int T
     S[(size_t)b * K * Q + e] = acc;
 }
 
+// ---- plan 2: the wide centroid half ----------------------------------------------------------------------------------
+constexpr int kChunk = HSCKMEANS_WIDE_CHUNK_WINDOWS;     // windows per chunk: 4 waves x 4 segments of 64
+constexpr int kRing = HSCKMEANS_WIDE_RING_ROWS;          // kRing * 256 elements per ring half
+constexpr int kSumThreads = 1024;                        // wide_sum_kernel: 16 waves stage, the first tw lanes add
+constexpr int kLoads = kRing * 256 / kSumThreads;        // elements per thread and batch
+constexpr int kWideMaxK = HSCKMEANS_WIDE_MAX_K;
+static_assert(kChunk == 4 * 4 * 64, "place_kernel: 4 waves, 4 segments of 64 windows each");
+
+// an assignment is in [0, K) by construction; clamped so that no LDS or list index can leave its array
+__device__ inline int centroid_of(const int* __restrict__ kb, int n, int K) { return min(max(kb[n], 0), K - 1); }
+
+// grid = (chunks, B), block = 256; dynamic LDS: K ints.  hist[b][c][chunk] = windows of the chunk assigned to c
+__global__ __launch_bounds__(256) void hist_kernel(int N, int K, int C, const int* __restrict__ mode, const int* __restrict__ ak,
+                                                   int* __restrict__ hist)
+{
+    extern __shared__ int s_h[];
+    const int ch = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    if (mode[b] == HSCKMEANS_SKIP) return;
+    for (int c = tid; c < K; c += 256) s_h[c] = 0;
+    __syncthreads();
+    const int* kb = ak + (size_t)b * N;
+    const int n1 = min(N, (ch + 1) * kChunk);
+    for (int n = ch * kChunk + tid; n < n1; n += 256) atomicAdd(&s_h[centroid_of(kb, n, K)], 1);
+    __syncthreads();
+    for (int c = tid; c < K; c += 256) hist[((size_t)b * K + c) * C + ch] = s_h[c];
+}
+
+// grid = B, block = 256: the exclusive scan of hist[b] in (centroid, chunk) order, in place: where in the index array
+// the chunk's members of c begin.  Then offsets [K + 1], count and nonzero.
+__global__ __launch_bounds__(256) void scan_kernel(int N, int K, int C, const int* __restrict__ mode, const int* __restrict__ ak,
+                                                   int* __restrict__ hist, int* __restrict__ offsets, int* __restrict__ count,
+                                                   int* __restrict__ nonzero)
+{
+    __shared__ int s_tot[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (mode[b] == HSCKMEANS_SKIP) return;
+    int* h = hist + (size_t)b * K * C;
+    const int L = K * C, per = (L + 255) / 256, i0 = min(L, tid * per), i1 = min(L, i0 + per);
+    int tot = 0;
+    for (int i = i0; i < i1; ++i) tot += h[i];
+    s_tot[tid] = tot;
+    __syncthreads();
+    int run = 0;
+    for (int j = 0; j < tid; ++j) run += s_tot[j];
+    for (int i = i0; i < i1; ++i) {
+        const int v = h[i];
+        h[i] = run;
+        run += v;
+    }
+    __syncthreads();
+    const int first = centroid_of(ak + (size_t)b * N, 0, K);
+    for (int c = tid; c < K; c += 256) {
+        const int lo = h[(size_t)c * C], hi = c + 1 < K ? h[(size_t)(c + 1) * C] : N;
+        offsets[(size_t)b * (K + 1) + c] = lo;
+        count[(size_t)b * K + c] = hi - lo;
+        nonzero[(size_t)b * K + c] = hi - lo - (first == c ? 1 : 0) > 0 ? 1 : 0;
+    }
+    if (tid == 0) offsets[(size_t)b * (K + 1) + K] = N;
+}
+
+// grid = (chunks, B), block = 256; dynamic LDS: 4 * K ints.  Wave w of the chunk takes its windows [256 w, 256 w + 256)
+// in segments of 64; its cursors start behind the chunk's earlier waves.  A window's place is its centroid's cursor plus
+// its rank among the segment's lanes of the same centroid (ballot + popcount): ascending window order in every list.
+// Writes the window index and, in list order, its patch offset and norm.
+template <typename X>
+__global__ __launch_bounds__(256) void place_kernel(int N, int K, int C, const int* __restrict__ mode, const int* __restrict__ ak,
+                                                    const int* __restrict__ hist, const X* __restrict__ norm, const int* __restrict__ pofs,
+                                                    int* __restrict__ index, int* __restrict__ lpofs, X* __restrict__ lnorm)
+{
+    extern __shared__ int s_cur[];                     // [4][K]
+    const int ch = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (mode[b] == HSCKMEANS_SKIP) return;
+    for (int i = tid; i < 4 * K; i += 256) s_cur[i] = 0;
+    __syncthreads();
+    const int* kb = ak + (size_t)b * N;
+    const int w0 = ch * kChunk + wave * 256;
+    int myk[4];
+#pragma unroll
+    for (int sg = 0; sg < 4; ++sg) {
+        const int n = w0 + sg * 64 + lane;
+        myk[sg] = n < N ? centroid_of(kb, n, K) : -1;
+        if (n < N) atomicAdd(&s_cur[wave * K + myk[sg]], 1);
+    }
+    __syncthreads();
+    for (int c = tid; c < K; c += 256) {               // counts of the waves -> where each wave's members of c begin
+        int run = hist[((size_t)b * K + c) * C + ch];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int v = s_cur[w * K + c];
+            s_cur[w * K + c] = run;
+            run += v;
+        }
+    }
+    __syncthreads();
+    const size_t nb = (size_t)b * N;
+#pragma unroll
+    for (int sg = 0; sg < 4; ++sg) {
+        const int n = w0 + sg * 64 + lane, k = myk[sg];
+        unsigned long long rem = __ballot(k >= 0);
+        int pos = -1;
+        while (rem) {                                  // one round per centroid present in the segment
+            const int src = __ffsll((long long)rem) - 1;
+            const int kk = __shfl(k, src);
+            const bool mine = k == kk;
+            const unsigned long long mask = __ballot(mine);
+            int base = 0;
+            if (lane == src) base = atomicAdd(&s_cur[wave * K + kk], __popcll(mask));
+            base = __shfl(base, src);
+            if (mine) pos = base + __popcll(mask & ((1ull << lane) - 1ull));
+            rem &= ~mask;
+        }
+        if (k >= 0 && pos >= 0 && pos < N) {
+            index[nb + pos] = n;
+            lpofs[nb + pos] = pofs[nb + n];
+            lnorm[nb + pos] = norm[nb + n];
+        }
+    }
+}
+
+// grid = (ceil(Q / 256), K, B), block = kSumThreads: S[b][c][e0 .. e0 + tw) = the members' x[pofs + e] / norm added in list
+// order from the first member's row.  The tile's rows lie in the ring at a pitch tp = tw rounded up to a power of two;
+// a batch is RB = kRing * 256 / tp rows.  All 1024 threads load a batch (thread tid holds column tid % tp of the rows
+// tid / tp + u * 1024 / tp, u < kLoads: coalesced along the elements), divide and store it to one half of the ring
+// while lanes 0 .. tw - 1 add the other half: a member costs its adder lane one LDS read and one add, and the loads and
+// divisions of a row are spread over four times as many lanes as add it.  The rows are loaded two batches ahead of the adds (two register sets, the loop
+// unrolled by two), the patch offsets three.  Every load is issued unconditionally from a clamped (valid) row and
+// column, so a batch's loads are all in flight together; only the store to the ring is predicated.
+template <typename X>
+__global__ __launch_bounds__(kSumThreads) void wide_sum_kernel(const X* __restrict__ x, int T, int F, int N, int Q, int K, const int* __restrict__ mode,
+                                                       const int* __restrict__ offsets, const int* __restrict__ lpofs,
+                                                       const X* __restrict__ lnorm, X* __restrict__ S)
+{
+    __shared__ X ring[2][kRing * 256];
+    const int c = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
+    if (mode[b] == HSCKMEANS_SKIP) return;
+    const int e0 = blockIdx.x * 256, tw = min(256, Q - e0);
+    const int o0 = offsets[(size_t)b * (K + 1) + c], m = offsets[(size_t)b * (K + 1) + c + 1] - o0;
+    X* out = S + ((size_t)b * K + c) * Q + e0;
+    if (m <= 0) {
+        if (tid < tw) out[tid] = (X)0;
+        return;
+    }
+    const int sh = tw > 1 ? 32 - __clz(tw - 1) : 0, tp = 1 << sh;         // tw <= tp <= 256
+    const int RB = (kRing * 256) >> sh, nbatch = (m + RB - 1) / RB;
+    const int r0 = tid >> sh, rstep = kSumThreads >> sh, col = tid & (tp - 1), colc = min(col, tw - 1);
+    const int* lp = lpofs + (size_t)b * N + o0;
+    const X* ln = lnorm + (size_t)b * N + o0;
+    const X* xb = x + (size_t)b * T * F + e0 + colc;
+    int po[kLoads];
+    X va[kLoads], vb[kLoads], nr[kLoads];
+    // the loads of batch jb (clamped to the last batch: valid rows, loaded again, never stored)
+    auto rows_of = [&](int jb) { return min(RB, m - min(jb, nbatch - 1) * RB); };
+    auto row_of = [&](int jb, int u) { return min(jb, nbatch - 1) * RB + min(r0 + u * rstep, rows_of(jb) - 1); };
+    auto load_offsets = [&](int jb) {
+#pragma unroll
+        for (int u = 0; u < kLoads; ++u) po[u] = lp[row_of(jb, u)];
+    };
+    auto load_rows = [&](X (&v)[kLoads]) {
+#pragma unroll
+        for (int u = 0; u < kLoads; ++u) v[u] = xb[po[u]];
+    };
+    auto load_norms = [&](int jb) {
+#pragma unroll
+        for (int u = 0; u < kLoads; ++u) nr[u] = ln[row_of(jb, u)];
+    };
+    auto store_rows = [&](int jb, const X (&v)[kLoads]) {
+        const int rows = rows_of(jb);
+#pragma unroll
+        for (int u = 0; u < kLoads; ++u)
+            if (r0 + u * rstep < rows && col < tw) ring[jb & 1][tid + kSumThreads * u] = v[u] / nr[u];
+    };
+    load_offsets(0);                                   // batch 0 into ring[0]; batch 1 in flight, the offsets of batch 2
+    load_rows(vb);
+    load_norms(0);
+    load_offsets(1);
+    load_rows(va);
+    load_offsets(2);
+    store_rows(0, vb);
+    __syncthreads();
+    X acc = (X)0;
+    // batch j is added from its half of the ring while batch j + 1 (`cur`, loaded an iteration ago) is divided and
+    // stored to the other half and batch j + 2 (`nxt`) is loaded; the offsets run one batch further ahead
+    auto body = [&](int j, const X (&cur)[kLoads], X (&nxt)[kLoads]) {
+        const int rows = rows_of(j);
+        load_rows(nxt);
+        load_norms(j + 1);
+        load_offsets(j + 3);
+        if (tid < tw) {
+            const X* r = ring[j & 1] + tid;
+            int i = 0;
+            if (j == 0) {
+                acc = r[0];
+                i = 1;
+            }
+            if (i + 8 <= rows) {                       // the next eight rows are read while these eight are added
+                X t[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) t[q] = r[(i + q) << sh];
+                for (; i + 16 <= rows; i += 8) {
+                    X nx[8];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) nx[q] = r[(i + 8 + q) << sh];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) acc = acc + t[q];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) t[q] = nx[q];
+                }
+#pragma unroll
+                for (int q = 0; q < 8; ++q) acc = acc + t[q];
+                i += 8;
+            }
+            for (; i < rows; ++i) acc = acc + r[i << sh];
+        }
+        if (j + 1 < nbatch) store_rows(j + 1, cur);
+        __syncthreads();
+    };
+    for (int j = 0; j < nbatch; j += 2) {
+        body(j, va, vb);
+        if (j + 1 < nbatch) body(j + 1, vb, va);
+    }
+    if (tid < tw) out[tid] = acc;
+}
+
 }  // namespace
 
 static_assert(HSCKMEANS_OK == hsc::OK && HSCKMEANS_ERR_INVALID == hsc::ERR_INVALID && HSCKMEANS_ERR_NO_DEVICE == hsc::ERR_NO_DEVICE &&
@@ -298,11 +527,12 @@ static_assert(HSCKMEANS_OK == hsc::OK && HSCKMEANS_ERR_INVALID == hsc::ERR_INVAL
 struct HSC_HIDDEN hsckmeans_ctx : hsc::CtxBase {
     hipEvent_t ev[5] = {};
     // data (set_data)
-    int dtype = -1, B = 0, T = 0, F = 0, N = 0, W = 0;
+    int dtype = -1, B = 0, T = 0, F = 0, N = 0, W = 0;    // a corpus: B = 1 learner, T = the rows of the stack
+    int plan = HSCKMEANS_PLAN_AUTO;
     void* d_x = nullptr;
     int* d_starts = nullptr;
-    // step buffers (grown, never shrunk)
-    enum { kImg32, kImg64, kMode, kT, kK, kNorm, kPofs, kMembers, kCount, kNonzero, kSums, kBufs };
+    // step buffers (grown, never shrunk); kMembers belongs to plan 1, kHist .. kLNorm to plan 2
+    enum { kImg32, kImg64, kMode, kT, kK, kNorm, kPofs, kMembers, kCount, kNonzero, kSums, kHist, kOffsets, kIndex, kLPofs, kLNorm, kBufs };
     hsc::Buffers<kBufs> buf;
     std::vector<float> img32;
     std::vector<double> img64;
@@ -324,6 +554,8 @@ extern "C" int hsckmeans_create(hsckmeans_ctx** out, int device_id) { return hsc
 
 extern "C" void hsckmeans_destroy(hsckmeans_ctx* ctx) { hsc::destroy(ctx); }
 
+static int upload(hsckmeans_ctx* ctx, const void* x, int dtype, int B, int T, int F, const std::vector<int>& s32, int N, int W, const char* fn);
+
 extern "C" int hsckmeans_set_data(hsckmeans_ctx* ctx, const void* x, int dtype, int B, int T, int F, const int64_t* starts,
                                   int N, int W)
 {
@@ -341,6 +573,54 @@ extern "C" int hsckmeans_set_data(hsckmeans_ctx* ctx, const void* x, int dtype, 
             return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_data: start %lld of window %zu is outside [0, %d]", (long long)starts[i], i, T - 2 * W);
         s32[i] = (int)starts[i];
     }
+    return upload(ctx, x, dtype, B, T, F, s32, N, W, "hsckmeans_set_data");
+}
+
+extern "C" int hsckmeans_set_corpus(hsckmeans_ctx* ctx, const void* x, int dtype, int B, const int64_t* row_offsets, int F,
+                                    const int64_t* starts, int N, int W)
+{
+    if (!ctx) return fail(nullptr, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: ctx is NULL");
+    if (!x || !row_offsets || !starts) return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: x, row_offsets or starts is NULL");
+    if (dtype != HSCKMEANS_F32 && dtype != HSCKMEANS_F64) return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: bad dtype %d", dtype);
+    if (B < 1 || F < 1 || N < 1 || W < 1)
+        return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: bad shape B = %d, F = %d, N = %d, W = %d", B, F, N, W);
+    if (W > kMaxW) return fail(ctx, HSCKMEANS_ERR_UNSUPPORTED, "hsckmeans_set_corpus: W = %d exceeds the limit of %d", W, kMaxW);
+    if (row_offsets[0] != 0) return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: row_offsets[0] = %lld, must be 0", (long long)row_offsets[0]);
+    for (int b = 0; b < B; ++b) {
+        const int64_t len = row_offsets[b + 1] - row_offsets[b];
+        if (len < 0) return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: row_offsets descend at signal %d (%lld after %lld)", b,
+                                 (long long)row_offsets[b + 1], (long long)row_offsets[b]);
+        if (len <= 2 * W)
+            return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: signal %d has %lld samples, windows of 2W = %d samples need more than %d", b,
+                        (long long)len, 2 * W, 2 * W);
+    }
+    const int64_t rows = row_offsets[B];
+    if (rows > INT_MAX / F) return fail(ctx, HSCKMEANS_ERR_UNSUPPORTED, "hsckmeans_set_corpus: the stack of %lld x %d elements exceeds 2^31 - 1", (long long)rows, F);
+    std::vector<int> s32((size_t)N);
+    for (int n = 0; n < N; ++n) {
+        const int64_t st = starts[n];
+        if (st < 0 || st >= rows) return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: start %lld of window %d is outside the stack of %lld rows", (long long)st, n, (long long)rows);
+        const int b = (int)(std::upper_bound(row_offsets, row_offsets + B + 1, st) - row_offsets) - 1;     // row_offsets[b] <= st
+        if (st + 2 * W > row_offsets[b + 1])
+            return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: window %d (rows %lld .. %lld) crosses the end of signal %d at row %lld", n,
+                        (long long)st, (long long)(st + 2 * W), b, (long long)row_offsets[b + 1]);
+        s32[n] = (int)st;
+    }
+    return upload(ctx, x, dtype, 1, (int)rows, F, s32, N, W, "hsckmeans_set_corpus");
+}
+
+extern "C" int hsckmeans_set_plan(hsckmeans_ctx* ctx, int plan)
+{
+    if (!ctx) return fail(nullptr, HSCKMEANS_ERR_INVALID, "hsckmeans_set_plan: ctx is NULL");
+    if (plan != HSCKMEANS_PLAN_AUTO && plan != HSCKMEANS_PLAN_LISTS && plan != HSCKMEANS_PLAN_WIDE)
+        return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_plan: plan = %d is not 0 (auto), 1 (lists) or 2 (wide)", plan);
+    ctx->plan = plan;
+    return HSCKMEANS_OK;
+}
+
+// the checked data of set_data / set_corpus to the device; the context holds no data if this fails
+static int upload(hsckmeans_ctx* ctx, const void* x, int dtype, int B, int T, int F, const std::vector<int>& s32, int N, int W, const char* fn)
+{
     HSC_TRY(hipSetDevice(ctx->device));
     HSC_TRY(hipStreamSynchronize(ctx->stream));
     if (ctx->d_x) (void)hipFree(ctx->d_x);
@@ -351,7 +631,7 @@ extern "C" int hsckmeans_set_data(hsckmeans_ctx* ctx, const void* x, int dtype, 
     const size_t bx = (size_t)B * T * F * (dtype == HSCKMEANS_F32 ? 4 : 8), bs = s32.size() * sizeof(int);
     hipError_t e = hipMalloc(&ctx->d_x, bx);
     if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_starts, bs);
-    if (e != hipSuccess) return fail(ctx, HSCKMEANS_ERR_ALLOC, "hsckmeans_set_data: hipMalloc failed (%s)", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, HSCKMEANS_ERR_ALLOC, "%s: hipMalloc failed (%s)", fn, hipGetErrorString(e));
     HSC_TRY(hipMemcpyAsync(ctx->d_x, x, bx, hipMemcpyHostToDevice, ctx->stream));
     HSC_TRY(hipMemcpyAsync(ctx->d_starts, s32.data(), bs, hipMemcpyHostToDevice, ctx->stream));
     HSC_TRY(hipStreamSynchronize(ctx->stream));
@@ -370,7 +650,7 @@ static int launch_assign(hsckmeans_ctx* ctx, const void* img, const AssignArgs& 
 }
 
 template <typename X>
-static int launch_centroids(hsckmeans_ctx* ctx, int K)
+static int launch_centroids(hsckmeans_ctx* ctx, int K, int plan)
 {
     const int B = ctx->B, N = ctx->N, Q = ctx->W * ctx->F;
     const int* mode = (const int*)ctx->buf[hsckmeans_ctx::kMode];
@@ -384,6 +664,25 @@ static int launch_centroids(hsckmeans_ctx* ctx, int K)
     hipLaunchKernelGGL((norm_kernel<X>), dim3((N + 255) / 256, B), dim3(256), 0, ctx->stream, (const X*)ctx->d_x, ctx->T, ctx->F, N,
                        ctx->W, ctx->d_starts, mode, at, norm, pofs);
     HSC_TRY(hipGetLastError());
+    if (plan == HSCKMEANS_PLAN_WIDE) {
+        const int C = (N + kChunk - 1) / kChunk;
+        int* hist = (int*)ctx->buf[hsckmeans_ctx::kHist];
+        int* offsets = (int*)ctx->buf[hsckmeans_ctx::kOffsets];
+        int* index = (int*)ctx->buf[hsckmeans_ctx::kIndex];
+        int* lpofs = (int*)ctx->buf[hsckmeans_ctx::kLPofs];
+        X* lnorm = (X*)ctx->buf[hsckmeans_ctx::kLNorm];
+        hipLaunchKernelGGL(hist_kernel, dim3(C, B), dim3(256), (size_t)K * sizeof(int), ctx->stream, N, K, C, mode, ak, hist);
+        HSC_TRY(hipGetLastError());
+        hipLaunchKernelGGL(scan_kernel, dim3(B), dim3(256), 0, ctx->stream, N, K, C, mode, ak, hist, offsets, count, nonzero);
+        HSC_TRY(hipGetLastError());
+        hipLaunchKernelGGL((place_kernel<X>), dim3(C, B), dim3(256), (size_t)4 * K * sizeof(int), ctx->stream, N, K, C, mode, ak,
+                           (const int*)hist, (const X*)norm, (const int*)pofs, index, lpofs, lnorm);
+        HSC_TRY(hipGetLastError());
+        hipLaunchKernelGGL((wide_sum_kernel<X>), dim3((Q + 255) / 256, K, B), dim3(kSumThreads), 0, ctx->stream, (const X*)ctx->d_x, ctx->T, ctx->F,
+                           N, Q, K, mode, (const int*)offsets, (const int*)lpofs, (const X*)lnorm, (X*)ctx->buf[hsckmeans_ctx::kSums]);
+        HSC_TRY(hipGetLastError());
+        return HSCKMEANS_OK;
+    }
     hipLaunchKernelGGL(member_kernel, dim3(K, B), dim3(64), 0, ctx->stream, N, K, mode, ak, members, count, nonzero);
     HSC_TRY(hipGetLastError());
     hipLaunchKernelGGL((sum_kernel<X>), dim3((unsigned)(((size_t)K * Q + 255) / 256), B), dim3(256), 0, ctx->stream, (const X*)ctx->d_x,
@@ -401,8 +700,15 @@ extern "C" int hsckmeans_step(hsckmeans_ctx* ctx, const double* D, int K, const 
         return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_step: NULL argument");
     const int B = ctx->B, N = ctx->N, W = ctx->W, F = ctx->F, Q = W * F;
     if (K < 1) return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_step: K = %d", K);
-    if ((int64_t)K * Q > INT_MAX / 2 || (int64_t)K * N > INT_MAX / 2)
+    // plan 1's [K][N] table is indexed in int; auto leaves it there, and from HSCKMEANS_WIDE_FROM_WINDOWS windows on
+    const bool lists_fit = (int64_t)K * N <= INT_MAX / 2;
+    int plan = ctx->plan;
+    if (plan == HSCKMEANS_PLAN_AUTO)
+        plan = K <= kWideMaxK && (N >= HSCKMEANS_WIDE_FROM_WINDOWS || !lists_fit) ? HSCKMEANS_PLAN_WIDE : HSCKMEANS_PLAN_LISTS;
+    if ((int64_t)K * Q > INT_MAX / 2 || (plan == HSCKMEANS_PLAN_LISTS && !lists_fit))
         return fail(ctx, HSCKMEANS_ERR_UNSUPPORTED, "hsckmeans_step: K = %d is too large for this shape", K);
+    if (plan == HSCKMEANS_PLAN_WIDE && K > kWideMaxK)
+        return fail(ctx, HSCKMEANS_ERR_UNSUPPORTED, "hsckmeans_step: the wide plan takes K <= %d (K = %d)", kWideMaxK, K);
     bool any32 = false, any64 = false;
     for (int b = 0; b < B; ++b) {
         if (mode[b] < HSCKMEANS_SKIP || mode[b] > HSCKMEANS_ASSIGN_F64)
@@ -438,11 +744,14 @@ extern "C" int hsckmeans_step(hsckmeans_ctx* ctx, const double* D, int K, const 
     }
 
     HSC_TRY(hipSetDevice(ctx->device));
-    const size_t xs = ctx->dtype == HSCKMEANS_F32 ? 4 : 8;
+    const size_t xs = ctx->dtype == HSCKMEANS_F32 ? 4 : 8, chunks = ((size_t)N + kChunk - 1) / kChunk;
+    const bool wide = plan == HSCKMEANS_PLAN_WIDE;
     const size_t bytes[hsckmeans_ctx::kBufs] = {
         any32 ? per * B * 4 : 0, any64 ? per * B * 8 : 0, (size_t)B * sizeof(int), (size_t)B * N * sizeof(int),
-        (size_t)B * N * sizeof(int), (size_t)B * N * xs, (size_t)B * N * sizeof(int), (size_t)B * K * N * sizeof(int),
-        (size_t)B * K * sizeof(int), (size_t)B * K * sizeof(int), (size_t)B * K * Q * xs};
+        (size_t)B * N * sizeof(int), (size_t)B * N * xs, (size_t)B * N * sizeof(int), wide ? 0 : (size_t)B * K * N * sizeof(int),
+        (size_t)B * K * sizeof(int), (size_t)B * K * sizeof(int), (size_t)B * K * Q * xs,
+        wide ? (size_t)B * K * chunks * sizeof(int) : 0, wide ? (size_t)B * (K + 1) * sizeof(int) : 0, wide ? (size_t)B * N * sizeof(int) : 0,
+        wide ? (size_t)B * N * sizeof(int) : 0, wide ? (size_t)B * N * xs : 0};
     if (int rc = ctx->buf.ensure(ctx, bytes, "hsckmeans_step")) return rc;
     hipStream_t st = ctx->stream;
     HSC_TRY(hipEventRecord(ctx->ev[0], st));
@@ -483,7 +792,7 @@ extern "C" int hsckmeans_step(hsckmeans_ctx* ctx, const double* D, int K, const 
         if (rc != HSCKMEANS_OK) return rc;
     }
     HSC_TRY(hipEventRecord(ctx->ev[2], st));
-    rc = ctx->dtype == HSCKMEANS_F32 ? launch_centroids<float>(ctx, K) : launch_centroids<double>(ctx, K);
+    rc = ctx->dtype == HSCKMEANS_F32 ? launch_centroids<float>(ctx, K, plan) : launch_centroids<double>(ctx, K, plan);
     if (rc != HSCKMEANS_OK) return rc;
     HSC_TRY(hipEventRecord(ctx->ev[3], st));
     HSC_TRY(hipMemcpyAsync(out_t, ctx->buf[hsckmeans_ctx::kT], (size_t)B * N * sizeof(int), hipMemcpyDeviceToHost, st));

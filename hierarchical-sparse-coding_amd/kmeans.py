@@ -1,6 +1,6 @@
 """Convolutional k-means dictionary learning on MI355X: the reference's ConvolutionalDictionaryLearner(algorithm='kmean')
 (hsc/modeling.py:420-524) with every iteration's data work on the GPU, through libhsckmeans.so (include/hsckmeans.h).
-DESIGN.md section 14.
+DESIGN.md sections 14 and 17.
 
 The signals and the window starts go to the device once.  Each iteration makes one hsckmeans_step call (one
 synchronise) for every learner still running: the assignment of every window (the arg-max of hscmp_assign_windows,
@@ -10,6 +10,12 @@ the emptiness test (the reference's np.any() of the member indices: a centroid w
 empty), the resets, the +1e-9 of zero-norm centroids, normalize() and alpha.  So the dtype rules are numpy's and the
 random draws are the host learner's, in the same order: the window starts, _init_D, then per iteration the resets
 in centroid order.
+
+trainCorpus learns ONE dictionary from a collection of signals of different lengths: the reference's learner with its
+window draw (extractRandomWindows) taken over the admissible starts of all signals (corpus_windows), so that no window,
+initial atom or reset patch straddles two signals.  The signals go to the device as one stack without padding
+(hsckmeans_set_corpus).  The centroid half of a step has two plans with the same bits (hsckmeans_set_plan): per-centroid
+member tables and one thread per element, or the wide plan for corpus-sized window counts.
 
 There is no CPU path: without libhsckmeans.so or a visible GPU the calls raise hsc_amd._native.HscmpError.
 ConvolutionalDictionaryLearner(algorithm='kmean') keeps its host path and is not routed here.
@@ -28,10 +34,16 @@ logger = logging.getLogger(__name__)
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'kmeans', 'libhsckmeans.so')
 EXPORTS = ['hsckmeans_version', 'hsckmeans_create', 'hsckmeans_destroy', 'hsckmeans_last_error', 'hsckmeans_set_data',
-           'hsckmeans_step']
+           'hsckmeans_set_corpus', 'hsckmeans_set_plan', 'hsckmeans_step']
 INIT_METHODS = ('random_samples', 'noise')
 RESET_METHODS = ('random_samples', 'random_samples_average', 'noise')
 MAX_WINDOW_SIZE = 255                    # include/hsckmeans.h: W + 1 positions per workgroup column set
+PLAN_AUTO, PLAN_LISTS, PLAN_WIDE = 0, 1, 2   # hsckmeans_set_plan
+WIDE_CHUNK_WINDOWS = 1024                # HSCKMEANS_WIDE_CHUNK_WINDOWS: windows per chunk of the wide plan's partition
+WIDE_RING_ROWS = 16                      # HSCKMEANS_WIDE_RING_ROWS: rows of a 256-element tile per half of its LDS ring
+WIDE_MAX_K = 1024                        # HSCKMEANS_WIDE_MAX_K
+WIDE_FROM_WINDOWS = 1000                 # HSCKMEANS_WIDE_FROM_WINDOWS: auto takes the wide plan from this many windows
+MAX_STACK_ELEMENTS = 2 ** 31 - 1         # sum T_b * F of a corpus
 F32, F64 = 0, 1                          # HSCKMEANS_F32 / _F64
 SKIP, ASSIGN_F32, ASSIGN_F64 = 0, 1, 2   # modes of hsckmeans_step
 TIMES = 4                                # upload, assignment, centroids, download
@@ -45,6 +57,8 @@ def load_library():
     if _lib is None:
         vp, ci = ctypes.c_void_p, ctypes.c_int
         _lib = _native.load_satellite(LIB_PATH, 'hsckmeans', {'hsckmeans_set_data': [vp, vp, ci, ci, ci, ci, vp, ci, ci],
+                                                              'hsckmeans_set_corpus': [vp, vp, ci, ci, vp, ci, vp, ci, ci],
+                                                              'hsckmeans_set_plan': [vp, ci],
                                                               'hsckmeans_step': [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]})
     return _lib
 
@@ -59,6 +73,19 @@ class _Context(_native.LibraryContext):
         N = starts.shape[1]
         self.B, self.N, self.W, self.F, self.dtype = B, N, W, F, x.dtype
         self.call('set_data', _native._ptr(x), F32 if x.dtype == np.float32 else F64, B, T, F, _native._ptr(starts), N, W)
+
+    def set_corpus(self, x, row_offsets, starts, W):
+        """x [rows,F] float32/float64 C order: the stacked signals; row_offsets [B+1], starts [N] (stacked rows) int64.
+        Afterwards the context holds one learner (B = 1)."""
+        F = x.shape[1]
+        N = starts.shape[0]
+        self.B, self.N, self.W, self.F, self.dtype = 1, N, W, F, x.dtype
+        self.call('set_corpus', _native._ptr(x), F32 if x.dtype == np.float32 else F64, row_offsets.shape[0] - 1,
+                  _native._ptr(row_offsets), F, _native._ptr(starts), N, W)
+
+    def set_plan(self, plan):
+        """PLAN_AUTO, PLAN_LISTS or PLAN_WIDE for the centroid half of the later steps (the same bits either way)."""
+        self.call('set_plan', int(plan))
 
     def step(self, D, mode):
         """D [B,K,W,F] float64, mode [B] int32.  Returns t, k [B,N], count, nonzero [B,K], sums [B,K,W*F], timing [4]."""
@@ -85,6 +112,63 @@ def _context(device):
 
 def _rng(rng):
     return np.random if rng is None else rng
+
+
+def corpus_signals(sequences, lengths=None):
+    """The signals of a corpus as a list of [T_b] or [T_b,F] views: `sequences` [B,T] / [B,T,F], a list / tuple of
+    arrays, or a padded array with `lengths` [B] (the ragged forms of modeling.is_ragged).  The padding is not read."""
+    if isinstance(sequences, (list, tuple)):
+        if lengths is not None:
+            raise ValueError('lengths= goes with a padded array, not with a list of signals')
+        seqs = [np.asarray(q) for q in sequences]
+    else:
+        seq = np.asarray(sequences)
+        if seq.ndim != 2 and seq.ndim != 3:
+            raise ValueError('k-means: the corpus must be [B,T] or [B,T,F] (got %d dimensions)' % seq.ndim)
+        if lengths is None:
+            seqs = list(seq)
+        else:
+            lens = np.asarray(lengths).astype(np.int64).reshape(-1)
+            if lens.shape[0] != seq.shape[0]:
+                raise ValueError('lengths has %d entries for %d signals' % (lens.shape[0], seq.shape[0]))
+            if np.any(lens > seq.shape[1]) or np.any(lens < 0):
+                raise ValueError('a length is outside the padded length %d' % seq.shape[1])
+            seqs = [seq[b, :int(lens[b])] for b in range(seq.shape[0])]
+    if len(seqs) == 0:
+        raise ValueError('k-means: a corpus needs at least one signal')
+    if seqs[0].ndim not in (1, 2) or any(q.ndim != seqs[0].ndim or q.shape[1:] != seqs[0].shape[1:] for q in seqs):
+        raise ValueError('k-means: the signals of a corpus must all be [T_b] or all be [T_b,F] with the same F')
+    if any(q.dtype != seqs[0].dtype for q in seqs):
+        raise ValueError('k-means: the signals of a corpus must share one dtype')
+    return seqs
+
+
+def corpus_windows(signals, nb, width, rng=None):
+    """extractRandomWindows over a corpus: `nb` windows of `width` samples, drawn uniformly over the admissible starts of
+    all signals in ONE randint call (signal b has A_b = T_b - width of them, 0 .. T_b - width - 1, as the reference's
+    randint(low=0, high=T - width) leaves them).  Returns (signal [nb], start [nb]) int64 in draw order; for one signal
+    the starts are extractRandomWindows' own."""
+    A = np.array([q.shape[0] - width for q in signals], dtype=np.int64)
+    if np.any(A < 1):
+        raise ValueError('signal %d: %d samples leave no window of %d' % (int(np.argmax(A < 1)), signals[int(np.argmax(A < 1))].shape[0], width))
+    C = np.cumsum(A)
+    g = np.asarray(_rng(rng).randint(low=0, high=int(C[-1]), size=(nb,)), dtype=np.int64)
+    b = np.searchsorted(C, g, side='right').astype(np.int64)
+    return b, g - (C[b] - A[b])
+
+
+def check_corpus_arguments(k, W, seqs, nbRandomWindows, initMethod, resetMethod):
+    """The argument checks of trainCorpus (raised before any device call): the rules of check_arguments, the length
+    rule for every signal, and the element limit of the stack."""
+    W = int(W)
+    _, F = check_arguments(k, W, (2 * max(W, 0) + 1,) + seqs[0].shape[1:], seqs[0].dtype, nbRandomWindows, initMethod, resetMethod)
+    for b, q in enumerate(seqs):
+        if 2 * W >= q.shape[0]:
+            raise ValueError('k-means: signal %d has %d samples, windows of 2 * windowSize = %d samples need a longer signal' % (
+                b, q.shape[0], 2 * W))
+    if sum(q.shape[0] for q in seqs) * F > MAX_STACK_ELEMENTS:
+        raise NotImplementedError('k-means on the GPU: the corpus has more than 2^31 - 1 elements in all')
+    return F
 
 
 def check_arguments(k, W, data_shape, dtype, nbRandomWindows, initMethod, resetMethod, batch=False):
@@ -133,6 +217,7 @@ class ConvolutionalKMeansLearner(object):
         self.device = device
         self.rng = rng
         self.lastStats = None
+        self.lastWindows = None                              # after trainCorpus: (signal [N], start [N]) of the drawn windows
 
     def train(self, data, nbRandomWindows, maxIterations=100, tolerance=0.0, initMethod='random_samples',
               resetMethod='noise', nbAveragedPatches=8):
@@ -170,15 +255,49 @@ class ConvolutionalKMeansLearner(object):
         self.lastStats = stats
         return np.stack(Ds), stats
 
+    def trainCorpus(self, sequences, nbRandomWindows, maxIterations=100, tolerance=0.0, initMethod='random_samples',
+                    resetMethod='noise', nbAveragedPatches=8, lengths=None):
+        """`train` for ONE dictionary over a corpus of B signals: `sequences` [B,T] / [B,T,F], a list / tuple of [T_b] or
+        [T_b,F] arrays, or a padded array with `lengths` (its padding is never read and may hold NaN); float32 or float64,
+        one dtype and one F.  The reference's learner with its window draw taken over all signals (corpus_windows): the
+        N windows of 2 * windowSize samples, then _init_D ('random_samples': k windows of windowSize samples by the same
+        rule; 'noise': uniform between the smallest and largest sample of the signals), then per iteration the resets
+        in centroid order, a reset's randint(0, N) naming a drawn window whose matched patch is cut from its own
+        signal.  A corpus of one signal gives `train`'s result on that signal, bit for bit (values and dtype).
+        Returns D [K,W] or [K,W,F]; lastStats as after train, lastWindows = (signal [N], start [N])."""
+        seqs = corpus_signals(sequences, lengths)
+        W, K, N = self.windowSize, self.k, int(nbRandomWindows)
+        F = check_corpus_arguments(K, W, seqs, nbRandomWindows, initMethod, resetMethod)
+        load_library()                                       # no CPU path: fail before the first draw
+        rng = _rng(self.rng)
+        row_offsets = np.zeros((len(seqs) + 1,), dtype=np.int64)
+        row_offsets[1:] = np.cumsum([q.shape[0] for q in seqs])
+        stack = np.concatenate(seqs)                         # [rows] or [rows,F]: the signals' own samples, no padding
+        sig, start = corpus_windows(seqs, N, 2 * W, rng)
+        if initMethod == 'noise':                            # _init_D (modeling.py:308-328) over the corpus
+            D = normalize(rng.uniform(low=np.min(stack), high=np.max(stack), size=(K, W, F)))
+        else:
+            ib, it = corpus_windows(seqs, K, W, rng)
+            rows = (row_offsets[ib] + it)[:, np.newaxis] + np.arange(W)[np.newaxis, :]
+            D = normalize(stack.reshape((-1, F))[rows])
+        if stack.ndim == 1:
+            D = np.squeeze(D, axis=2)
+        starts = (row_offsets[sig] + start)[np.newaxis]      # stacked rows
+        ctx = _context(self.device)
+        ctx.set_corpus(np.ascontiguousarray(stack.reshape((-1, F))), row_offsets, np.ascontiguousarray(starts[0]), W)
+        Ds, stats = self._loop(ctx, [stack], starts, [D], [self.rng], stack.dtype, F, maxIterations, tolerance, resetMethod,
+                               nbAveragedPatches)
+        self.lastStats = stats[0]
+        self.lastWindows = (sig, start)
+        return Ds[0]
+
     # ---- the shared loop ---------------------------------------------------------------------------
     def _run(self, seqs, rngs, N, maxIterations, tolerance, initMethod, resetMethod, nbAveragedPatches):
         from .learning import ConvolutionalDictionaryLearner
-        from .modeling import _compute_dtype
         B, T = seqs.shape[0], seqs.shape[1]
         W, K = self.windowSize, self.k
         x = np.ascontiguousarray(seqs.reshape((B, T, -1)))
         F = x.shape[2]
-        pshape = (W,) if seqs.ndim == 2 else (W, F)
         starts = np.zeros((B, N), dtype=np.int64)
         Ds = []
         for b in range(B):                                   # extractRandomWindows, then _init_D (modeling.py:426-429)
@@ -186,6 +305,14 @@ class ConvolutionalKMeansLearner(object):
             Ds.append(ConvolutionalDictionaryLearner(K, W, rng=rngs[b])._init_D(seqs[b], initMethod))
         ctx = _context(self.device)
         ctx.set_data(x, starts, W)
+        return self._loop(ctx, seqs, starts, Ds, rngs, x.dtype, F, maxIterations, tolerance, resetMethod, nbAveragedPatches)
+
+    def _loop(self, ctx, datas, starts, Ds, rngs, xdtype, F, maxIterations, tolerance, resetMethod, nbAveragedPatches):
+        """The iterations of the B learners whose data the context holds: datas[b] the host's copy ([T] / [T,F]; a corpus:
+        the stack), starts [B,N] its window starts, Ds[b] the initial dictionaries."""
+        from .modeling import _compute_dtype
+        B, W, K = len(Ds), self.windowSize, self.k
+        pshape = (W,) if datas[0].ndim == 1 else (W, F)
         n = [0] * B
         alpha = [tolerance + 1.0] * B
         stats = [[] for _ in range(B)]
@@ -196,13 +323,13 @@ class ConvolutionalKMeansLearner(object):
             mode = np.zeros((B,), dtype=np.int32)
             D64 = np.zeros((B, K, W, F), dtype=np.float64)
             for b in running:
-                mode[b] = ASSIGN_F32 if _compute_dtype(x.dtype, Ds[b].dtype) == np.float32 else ASSIGN_F64
+                mode[b] = ASSIGN_F32 if _compute_dtype(xdtype, Ds[b].dtype) == np.float32 else ASSIGN_F64
                 D64[b] = Ds[b].reshape((K, W, F))
             t0 = time.perf_counter()
             at, ak, count, nonzero, sums, timing = ctx.step(D64, mode)
             step_ms = 1e3 * (time.perf_counter() - t0)
             for b in running:
-                newD, nbResets = self._finish(seqs[b], starts[b], at[b], count[b], nonzero[b], sums[b], Ds[b], pshape,
+                newD, nbResets = self._finish(datas[b], starts[b], at[b], count[b], nonzero[b], sums[b], Ds[b], pshape,
                                               _rng(rngs[b]), resetMethod, nbAveragedPatches)
                 alpha[b] = np.sqrt(np.sum(np.square(Ds[b] - newD)))
                 logger.debug('K-mean iteration %d: tolerance = %f, nb resets = %d' % (n[b], alpha[b], nbResets))

@@ -1,6 +1,7 @@
 /* hsckmeans.h -- C ABI of libhsckmeans.so: one iteration of the convolutional k-means learner
  * (ConvolutionalDictionaryLearner(algorithm='kmean'), hsc/modeling.py:420-524) on MI355X / gfx950, for a batch
- * of independent learners.  DESIGN.md section 14.
+ * of independent learners (hsckmeans_set_data), or for one learner over a corpus of signals of different lengths
+ * (hsckmeans_set_corpus).  DESIGN.md sections 14 and 17.
  *
  * One context per host thread (contexts are not thread safe).  Every entry point returns HSCKMEANS_OK (0) or a
  * negative status; hsckmeans_last_error() describes the last failure.  There is no CPU path: without a visible
@@ -34,9 +35,27 @@ enum { HSCKMEANS_SKIP = 0, HSCKMEANS_ASSIGN_F32 = 1, HSCKMEANS_ASSIGN_F64 = 2 };
 enum {
     HSCKMEANS_TIME_UPLOAD = 0,     /* dictionary images and modes to the device */
     HSCKMEANS_TIME_ASSIGN = 1,     /* the assignment kernels */
-    HSCKMEANS_TIME_CENTROIDS = 2,  /* norms, membership lists and centroid sums */
+    HSCKMEANS_TIME_CENTROIDS = 2,  /* norms, membership and centroid sums */
     HSCKMEANS_TIME_DOWNLOAD = 3,   /* results to the host */
     HSCKMEANS_TIMES = 4
+};
+
+/* The centroid half of a step (membership and sums) has two plans with the same bits in every output:
+ *   1  one wave per centroid lists its members in a [K][N] table; one thread per (centroid, element) sums them;
+ *   2  wide: a stable partition of the windows by centroid into one [N] index array with K + 1 offsets (per-chunk
+ *      histograms, an ordered scan over (centroid, chunk), placement in window order), then one workgroup per
+ *      (centroid, tile of up to 256 elements) that stages its members' normalised rows through a double-buffered LDS
+ *      ring and adds them in list order.  Needs K <= HSCKMEANS_WIDE_MAX_K.
+ *   0  auto (the default): plan 2 from HSCKMEANS_WIDE_FROM_WINDOWS windows on (and wherever plan 1's table would
+ *      exceed its index range), if K allows it; else plan 1. */
+enum { HSCKMEANS_PLAN_AUTO = 0, HSCKMEANS_PLAN_LISTS = 1, HSCKMEANS_PLAN_WIDE = 2 };
+enum {
+    HSCKMEANS_WIDE_CHUNK_WINDOWS = 1024,  /* windows per chunk of the partition (one workgroup of 4 waves, 256 windows each) */
+    HSCKMEANS_WIDE_RING_ROWS = 16,        /* rows of a full 256-element tile per half of the LDS ring; a narrower tile of
+                                             tw elements lies at the pitch tp = tw rounded up to a power of two and
+                                             stages 16 * 256 / tp rows per half */
+    HSCKMEANS_WIDE_MAX_K = 1024,          /* the placement keeps 4 x K cursors in LDS */
+    HSCKMEANS_WIDE_FROM_WINDOWS = 1000    /* auto: measured, DESIGN.md section 17 */
 };
 
 typedef struct hsckmeans_ctx hsckmeans_ctx;
@@ -52,6 +71,22 @@ const char* hsckmeans_last_error(hsckmeans_ctx* ctx);  /* ctx may be NULL (error
  * The windows are read in place on the device in every later step. */
 int hsckmeans_set_data(hsckmeans_ctx* ctx, const void* x, int dtype, int B, int T, int F, const int64_t* starts,
                        int N, int W);
+
+/* Upload a corpus: B signals of different lengths stacked without padding, for ONE learner whose windows each lie
+ * inside one signal.  Replaces the data of an earlier hsckmeans_set_data / _set_corpus (and the other way round).
+ *   x           [row_offsets[B]][F]  the stacked signals, dtype as above
+ *   row_offsets [B + 1]              ascending from 0: signal b is rows row_offsets[b] .. row_offsets[b + 1]
+ *   starts      [N]                  stacked rows: window n is x[starts[n] : +2W]
+ * Checked on the host before any allocation or read of x: every signal is longer than 2W and every window lies inside
+ * one signal (row_offsets[b] <= start, start + 2W <= row_offsets[b + 1]), else HSCKMEANS_ERR_INVALID naming the signal
+ * or window; more than 2^31 - 1 elements in the stack: HSCKMEANS_ERR_UNSUPPORTED.  Afterwards the context holds one
+ * learner: hsckmeans_step takes D [1][K][W][F] and mode [1] and returns [1][N] / [1][K] outputs. */
+int hsckmeans_set_corpus(hsckmeans_ctx* ctx, const void* x, int dtype, int B, const int64_t* row_offsets, int F,
+                         const int64_t* starts, int N, int W);
+
+/* The centroid plan of the later steps: HSCKMEANS_PLAN_AUTO, _LISTS or _WIDE (anything else: HSCKMEANS_ERR_INVALID).
+ * Kept across hsckmeans_set_data / _set_corpus.  A step under plan 2 with K > HSCKMEANS_WIDE_MAX_K is refused. */
+int hsckmeans_set_plan(hsckmeans_ctx* ctx, int plan);
 
 /* One iteration for every learner b with mode[b] != HSCKMEANS_SKIP (their rows of the outputs are undefined).
  *   D       [B][K][W][F] float64, host memory: the current dictionaries.  A learner assigned in float32 must hold
