@@ -34,7 +34,6 @@ struct Knobs {
     bool no_dict_lists, no_row_lists, no_rowbits, no_pairing, force_gathered, force_generic;     // set or not
     bool init_only, exact_init, exact_recorr, locomp_no_mfma, no_sorted_prepare, no_lazy_clear;
     int rp, mfma_quad, sparse_packed;     // 0 / 1 forces the choice; -1: not set, chosen by the shape
-    int bound_products;                   // bf16 products per tap of the initial bound pass: 3 when set to 3, else 1 (hscmp_bound.h)
     int locomp_pack;                      // at most this many signals per workgroup; 0: not set, by the batch size
     int slot_hash_min, locomp_group_cap, locomp_ahead, sorted_prepare_min, lds_pad;     // the value, or the default
     int epi_lds_keys;                     // the value if a power of two in 64..kEpiLdsKeys, else kEpiLdsKeys
@@ -99,7 +98,6 @@ static Knobs read_knobs()
     k.rp = (v = getenv("HSCMP_RP")) ? atoi(v) != 0 : -1;
     k.mfma_quad = (v = getenv("HSCMP_MFMA_QUAD")) ? atoi(v) != 0 : -1;
     k.sparse_packed = (v = getenv("HSCMP_SPARSE_PACKED")) ? atoi(v) != 0 : -1;
-    k.bound_products = (v = getenv("HSCMP_BOUND_PRODUCTS")) && atoi(v) == 3 ? 3 : 1;
     k.locomp_pack = (v = getenv("HSCMP_LOCOMP_PACK")) ? std::max(1, atoi(v)) : 0;     // (0 and below pack like 1)
     k.slot_hash_min = (v = getenv("HSCMP_SLOT_HASH_MIN")) ? std::max(0, atoi(v)) : kSlotHashMin;
     k.locomp_group_cap = (v = getenv("HSCMP_LOCOMP_GROUP_CAP")) ? std::min(4096, std::max(2, atoi(v))) : kLocompGroupCap;
@@ -577,20 +575,15 @@ template <typename Pol> static size_t policy_lds_bytes(const DevParams& P0, cons
     return Pol::total_lds_bytes(P, A);
 }
 
-// The loop of policy Pol (iterate_kernel), `signals_per_wg` signals per workgroup.  dry: only tell whether its LDS fits (158 KB:
-// the kernel's own static bytes count too), queue nothing.  0: launched (or fits); -1: it cannot run this shape.
+// The loop of policy Pol (iterate_kernel), `signals_per_wg` signals per workgroup.  dry: only tell whether its LDS fits (kLdsLoop),
+// queue nothing.  0: launched (or fits); -1: it cannot run this shape.
 template <typename R, typename Pol, bool RAGGED = false>
 static int launch_policy(hscmp_ctx* ctx, const DevParams& P0, const typename Pol::Args& A, int signals_per_wg, bool dry)
 {
     DevParams P = P0;
     set_segments(P, Pol::kMaxSegments);
-    const size_t lds = Pol::total_lds_bytes(P, A);
-    if (dry) return lds <= (size_t)158 * 1024 ? 0 : -1;
-    auto kern = iterate_kernel<R, Pol, RAGGED>;
-    if (set_dyn_lds((const void*)kern, lds) != hipSuccess) return -1;
-    hipLaunchKernelGGL(kern, dim3((P.B + signals_per_wg - 1) / signals_per_wg), dim3(signals_per_wg * kThreads), lds, ctx->stream, P,
-                       make_state<R>(ctx, RAGGED), A);
-    return 0;
+    return launch_tile_kernel(iterate_kernel<R, Pol, RAGGED>, dim3((P.B + signals_per_wg - 1) / signals_per_wg), dim3(signals_per_wg * kThreads),
+                              Pol::total_lds_bytes(P, A), kLdsLoop, 0, dry, ctx->stream, P, make_state<R>(ctx, RAGGED), A);
 }
 
 // LoCOMP with the re-correlations on the matrix cores (LocompMfma: single-feature float32 with a dictionary image), `group`
@@ -607,13 +600,9 @@ static int launch_locomp_mfma(hscmp_ctx* ctx, const DevParams& P, int group, boo
 {
     MfmaArgs A;
     A.dimg = ctx->dict.Dfrag.as<const float>(); A.G = mfma_groups(P.K); A.S4 = mfma_chunks(P.W); A.has_w = ctx->dict.w.p != nullptr ? 1 : 0;
-    const bool w = A.has_w != 0;
-    switch (A.S4) {
-    case 8: return w ? launch_locomp_mfma_t<8, true>(ctx, P, A, group, dry) : launch_locomp_mfma_t<8, false>(ctx, P, A, group, dry);
-    case 4: return w ? launch_locomp_mfma_t<4, true>(ctx, P, A, group, dry) : launch_locomp_mfma_t<4, false>(ctx, P, A, group, dry);
-    case 2: return w ? launch_locomp_mfma_t<2, true>(ctx, P, A, group, dry) : launch_locomp_mfma_t<2, false>(ctx, P, A, group, dry);
-    default: return -1;
-    }
+    return dispatch_chunks<false>(A.S4, A.has_w != 0, [&](auto s4c, auto hw) {
+        return launch_locomp_mfma_t<decltype(s4c)::value, decltype(hw)::value>(ctx, P, A, group, dry);
+    });
 }
 
 // The one place that chooses the kernels of an encode: every knob that selects a kernel is looked at here, and every LDS-fit
@@ -662,7 +651,7 @@ template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const Knobs&
             // float32 single-arg-max encodes: the initial correlation as upper bounds on the bf16 matrix cores, refined by the loop
             // where a selection needs it (hscmp_bound.h).  HSCMP_EXACT_INIT=1: the exact pass everywhere.
             if (!P.blocked && !P.select_only && ctx->dict.Bimg.p && !kn.exact_init &&
-                bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->dict.Bimg.as<unsigned short>(), ctx->dict.bound_cmax, kn.bound_products, true) == 0)
+                bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->dict.Bimg.as<unsigned short>(), ctx->dict.bound_cmax, true) == 0)
                 plan.init = EncodePlan::kInitBound;
             // ... and the four-signal loop re-correlates as upper bounds too, on the bf16 planes (HSCMP_EXACT_RECORR=1: the
             // exact re-correlation behind the bound pass; HSCMP_EXACT_INIT=1 keeps both exact)
@@ -740,7 +729,7 @@ template <typename R> static int launch_init(hscmp_ctx* ctx, const EncodePlan& p
     switch (plan.init) {
     case EncodePlan::kInitMfma: rc = mfma_launch_corr_init<R>(ctx->stream, P, S, dimg); break;
     case EncodePlan::kInitBound:
-        if constexpr (sizeof(R) == 4) rc = bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->dict.Bimg.as<unsigned short>(), ctx->dict.bound_cmax, plan.knobs.bound_products);
+        if constexpr (sizeof(R) == 4) rc = bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->dict.Bimg.as<unsigned short>(), ctx->dict.bound_cmax);
         break;
     case EncodePlan::kInitSparse: {
         const SparseArgs<R> A = sparse_args<R>(ctx, plan, P.T);

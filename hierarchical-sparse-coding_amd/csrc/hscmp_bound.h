@@ -7,60 +7,42 @@
 // stay bit-identical: the arg-max over bounds and exact scores, refined until the winner is exact, is the
 // arg-max over exact scores with the same tie rule.
 //
-// The products: every float32 operand v splits into bf16 hi = rn(v), lo = rn(v - hi) (v - hi is exact in
-// float32).  The bound pass of the initial correlation and the loop's tile sum hi.hi alone on v_mfma_f32_32x32x16_bf16
-// (NP = 1: 4 MFMAs of 32 cycles per 32 x 32 tile and atom group at W = 64, where the float32 form takes 32 of 64 cycles);
-// the initial pass under HSCMP_BOUND_PRODUCTS=3, and a library built with -DHSCMP_LOOP_BOUND_PRODUCTS=3 in its loop, sum
-// hi.hi + hi.lo + lo.hi (NP = 3: 12 MFMAs).  One product is 64 times looser (2^-7 against 2^-13 of ||x_win|| cmax); what
-// the loop pays for that is a refine of a position that outranks the exact winner by less than the slack, and a winner
-// that more often holds its exact score from an earlier selection's refine (the cache of committed refines keeps that
-// refine's (k, c) for it), both measured in DESIGN.md section 11.
+// The products: every float32 operand v is rounded to bf16, vh = rn(v), and the bound pass of the initial correlation and the
+// loop's tile sum ONE product xh dh per tap on v_mfma_f32_32x32x16_bf16: 4 MFMAs of 32 cycles per 32 x 32 tile and atom group at
+// W = 64, where the float32 form takes 32 of 64 cycles.  The slack is 2^-7 of ||x_win|| cmax; what the loop pays for it is a
+// refine of a position that outranks the exact winner by less than the slack, and a winner that more often holds its exact score
+// from an earlier selection's refine (the cache of committed refines keeps that refine's (k, c) for it), both measured in
+// DESIGN.md section 11.
 //
-// ---- derivation of the error constant, one product (NP = 1, kBoundEps1) ----------------------------------------
-// u, u', u'' as below; n = 16 * SB <= 64 products per output, W <= 64 taps.  The tile sees xh and dh only.
-// (1) dropped terms: x d - xh dh = xh (d - dh) + (x - xh) d with |d - dh| <= u|d|, |x - xh| <= u|x|, |xh| <= (1+u)|x|:
-//       |dropped| <= u ((1+u) + 1) |x||d| = u (2 + u) |x||d| = 7.82776e-3 |x||d|  per tap.
-// (2) the matrix core: every product exact in float32 and normal (below), n of them summed in any order with relative
-//       error <= u' per step: gamma_64(u') sum|xh dh| <= 7.6295e-6 (1+u)^2 |x||d| = 7.6892e-6 |x||d|; the flush of a
-//       cancelling partial sum is covered by kBoundAbs as below.
-// (3) the pinned float32 chain against the real sum: 3.8147e-6 |x||d|, as below.
-//   Together  |chain_k - acc_k| <= eps_1 sum_w |x_w||d_kw| <= eps_1 ||x_win|| ||d_k||,
+// ---- derivation of the error constant kBoundEps1 ------------------------------------------------------------------
+// u = 2^-8 (bf16 round to nearest), u' = 2^-23 (one accumulation step of the matrix core, ANY order and ANY rounding
+// direction), u'' = 2^-24 (float32 round to nearest), n = 16 * SB <= 64 products per output, W <= 16 * SB <= 64 taps.
+// For x (signal) and d (atom): |x - xh| <= u|x|, |xh| <= (1+u)|x|, and the same for d.  The tile sees xh and dh only.
+// (1) dropped terms: x d - xh dh = xh (d - dh) + (x - xh) d, so per tap
+//       |dropped| <= u ((1+u) + 1) |x||d| = u (2 + u) |x||d| = 7.82776e-3 |x||d|.
+// (2) the matrix core: each bf16 product is exact in float32 (8 x 8 significant bits; the input ranges below keep every
+//       product normal), the sum of n products with relative error <= u' per step in any order is off by at most
+//       gamma_n(u') sum|products| (gamma_64 = 64 u' / (1 - 64 u') = 7.6295e-6), and
+//       sum|xh dh| <= (1+u)^2 |x||d| = 1.007828 |x||d|  ->  7.6892e-6 |x||d|.
+//     A partial sum that cancels below 2^-126 may be flushed to zero: at most n 2^-126 |w_k| < 2^-88 absolute,
+//     covered by kBoundAbs.
+// (3) the score is NOT the exact real sum but the pinned float32 fmaf chain over the W taps (DESIGN.md section 5):
+//       |chain - sum| <= gamma_W(u'') sum|x||d| <= 64 2^-24 / (1 - 64 2^-24) = 3.8147e-6 per |x||d|.
+//   Together, per atom:  |chain_k - acc_k| <= eps_1 sum_w |x_w||d_kw| <= eps_1 ||x_win||_2 ||d_k||_2   (Cauchy-Schwarz)
 //       eps_1 = 7.82776e-3 + 7.6892e-6 + 3.8147e-6 = 7.83926e-3  (= 2^-6.995).
-// (4) the bound's own arithmetic is that of NP = 3 with one difference: ss is the float32 sum of xh^2 (the lo halves are
-//     never formed), and |x| <= |xh| / (1-u) tap by tap, so ||x_win|| <= ||xh_win|| / (1-u):
+// (4) the bound's own arithmetic.  score_k = rn(|chain_k w_k|) <= (1+u'')|chain_k||w_k|, and the tile's
+//     v_k = rn(acc_k w_k) >= (1-u'')|acc_k w_k|, so
+//       score <= (1+u'')/(1-u'') max_k v_k + (1+u'') eps_1 ||x_win|| max_k ||d_k|| |w_k|.
+//     The tile forms ub = fmaf(M, 1 + 2^-20, rn(rn(kBoundEps1 * rn(sqrt(ss))) * cmax) + 2^-80), with M = max_k v_k,
+//     cmax >= max_k ||d_k|| |w_k| rounded up on the host, and ss the float32 sum of xh^2 over the 16 SB taps of the window:
+//     |x| <= |xh| / (1-u) tap by tap, so ||x_win|| <= ||xh_win|| / (1-u) and
 //       score <= (1+u'')/(1-u'') max_k v_k + (1+u'') eps_1 / (1-u) ||xh_win|| cmax,   (1+u'') eps_1 / (1-u) = 7.87001e-3.
 //     kBoundEps1 = 2^-7 (1 + 2^-6) = 7.93457e-3 is 1.0082 times that.  The margin of 0.82 % is there for the roundings of
 //     rn(rn(kBoundEps1 * rn(sqrt(ss))) * cmax) + 2^-80 and of ss itself (at most 64 fmaf, a sqrt good to 2 ulp, three more
 //     roundings: together below a factor 1 - 2^-17 = 1 - 0.0008 %), a thousand times over; it is not needed for anything
 //     else, and the constant is not tuned on data (tests/test_bound_one_product.py puts it against the pinned chain).
+//     M's factor 1 + 2^-20 after the final rounding still exceeds (1+u'')/(1-u'') = 1 + 2^-23.
 //     xh = 0 only where x = 0 (|x| >= 2^-60 in the model), so ss == 0 still means an all-zero window: an exact 0.
-//
-// ---- derivation of the error constant, three products (NP = 3, kBoundEps) --------------------------------------
-// u = 2^-8 (bf16 round to nearest), u' = 2^-23 (one accumulation step of the matrix core, ANY order and ANY
-// rounding direction), u'' = 2^-24 (float32 round to nearest), n = 3 * 16 * SB <= 192 products per output,
-// W <= 16 * SB <= 64 taps.  For x (signal) and d (atom) write x = xh + xl + xr (xr the split remainder):
-//   |x - xh| <= u|x|,  |xl| <= (1+u) u |x|,  |xr| <= u |x - xh| <= u^2 |x|, and the same for d.
-// (1) dropped terms: x d - (xh dh + xh dl + xl dh) = xh dr + xl dl + xl dr + xr d, so per tap
-//       |dropped| <= u^2 ((1+u) + (1+u)^2 + (1+u) u + 1) |x||d| = u^2 (3 + 4u + 2u^2) |x||d| = 4.6020e-5 |x||d|.
-// (2) the matrix core: each bf16 product is exact in float32 (8 x 8 significant bits; the input ranges below keep
-//       every product normal), the sum of n products with relative error <= u' per step in any order is off by at
-//       most gamma_n(u') sum|products| (gamma_n = n u' / (1 - n u') = 2.2889e-5), and
-//       sum|products| <= (1+u)^2 (1 + 2u) |x||d| = 1.015686 |x||d|  ->  2.3248e-5 |x||d|.
-//     A partial sum that cancels below 2^-126 may be flushed to zero: at most n 2^-126 |w_k| < 2^-88 absolute,
-//     covered by kBoundAbs.
-// (3) the score is NOT the exact real sum but the pinned float32 fmaf chain over the W taps (DESIGN.md section 5):
-//       |chain - sum| <= gamma_W(u'') sum|x||d| <= 64 2^-24 / (1 - 64 2^-24) = 3.8147e-6 per |x||d|.
-//   Together, per atom:  |chain_k - acc_k| <= eps_0 sum_w |x_w||d_kw| <= eps_0 ||x_win||_2 ||d_k||_2   (Cauchy-Schwarz)
-//       eps_0 = 4.6020e-5 + 2.3248e-5 + 3.8147e-6 = 7.3083e-5  (= 2^-13.74).
-// (4) the bound's own arithmetic.  score_k = rn(|chain_k w_k|) <= (1+u'')|chain_k||w_k|, and the tile's
-//     v_k = rn(acc_k w_k) >= (1-u'')|acc_k w_k|, so
-//       score <= (1+u'')/(1-u'') max_k v_k + (1+u'') eps_0 ||x_win|| max_k ||d_k|| |w_k|.
-//     The tile forms ub = fmaf(M, 1 + 2^-20, rn(rn(kBoundEps * rn(sqrt(ss))) * cmax) + 2^-80), with M = max_k v_k,
-//     ss the float32 sum of (xh+xl)^2 over the 16 SB taps of the window (xh + xl is exact; ||x|| <= ||xh+xl|| / (1-u^2)),
-//     cmax >= max_k ||d_k|| |w_k| rounded up on the host.  Every rounding of that expression (at most 40 float32
-//     roundings and a sqrt good to 2 ulp) loses less than a factor 1 - 2^-17, and kBoundEps = 2^-13 = 1.2207e-4 is
-//     1.67 eps_0: ub >= score with room to spare.  M's factor 1 + 2^-20 after the final rounding still exceeds
-//     (1+u'')/(1-u'') = 1 + 2^-23.
 //
 // Inputs outside the model run the exact float32 tile (same kernel, same result as corr_init_mfma_kernel):
 //   a chunk (with its halo) that holds a sample that is not finite, or a non-zero |x| outside [2^-60, 2^60];
@@ -69,10 +51,10 @@
 // tools/bf16_bound_probe.hip checks assumption (2) on the hardware (profiles/r05_bf16_probe.txt).
 //
 // The four-signal loop (MfmaRecorr with BOUND) re-correlates the rows around an applied atom with the same tile
-// (bound_tile<SB, HAS_W, 1>, hscmp_mfma.h) over its reflect-padded window: the derivation above holds unchanged whenever
+// (bound_tile<SB, HAS_W>, hscmp_mfma.h) over its reflect-padded window: the derivation above holds unchanged whenever
 // every sample the tile reads is inside the model, and a tile whose window holds one outside it (a wave-wide vote, every
 // atom) runs the exact float32 tile on the planes (planes_tile_score).  Split, epilogue and constants have one definition.
-// The assumptions of the one-product derivation, one by one, for the loop's caller:
+// The assumptions of the derivation, one by one, for the loop's caller:
 //   * n <= 64 products per output, W <= 64 taps: the tile runs SB <= 4 k-steps of 16 taps; past W the planes hold zeros, whose
 //     products are exact zeros, and the window norm over 16 SB >= W samples is only larger than the one the derivation needs.
 //   * xh = rn(x) of the very samples the pinned chain reads: window_split rounds the float32 value it writes to the window
@@ -178,17 +160,17 @@ inline bool bound_build_dict_image(const float* D, const float* wts, int K, int 
 
 
 // ------------------------------------------------------------------------------------------------
-// The bound pass: the persistent grid of corr_init_mfma_kernel over (signal, 2048-position chunk) items.
-// NP = 1 (one product per tap, the default) or 3 (HSCMP_BOUND_PRODUCTS=3): the tile of bound_tile<SB, HAS_W, NP>.
-// LDS: [bf16 hi image][NP = 3: bf16 lo image][weights 32*G][chunk: bf16 hi halves (NP = 3: and the lo halves behind them), or
-// the float32 chunk of a chunk outside the model].  NP = 1 rounds every sample once and never forms a lo half.
+// The bound pass: the persistent grid of corr_init_mfma_kernel over (signal, 2048-position chunk) items, the tile of
+// bound_tile<SB, HAS_W>.
+// LDS: [bf16 image (plane 0 of Bimg)][weights 32*G][chunk: every sample rounded to bf16, or the float32 chunk of a chunk
+// outside the model].
 // A chunk outside the model (see the header) runs mfma_tile_score on the float32 image in global
 // memory (L2-resident): the exact score and group hint, bit for bit what corr_init_mfma_kernel writes.
 // A position whose bound came out as an exact 0 (all-zero window) gets the hint 0 like the exact tile: it is exact.
 // ------------------------------------------------------------------------------------------------
 template <int SB> __host__ __device__ constexpr int bound_chunk_samples() { return kMfmaChunk + 16 * SB + 32; }
 
-template <int SB, bool HAS_W, int NP>
+template <int SB, bool HAS_W>
 __global__ __launch_bounds__(kThreads) void corr_bound_kernel(DevParams P, State<float> S, MfmaArgs A,
                                                               const unsigned short* __restrict__ bimg, float cmax)
 {
@@ -197,21 +179,18 @@ __global__ __launch_bounds__(kThreads) void corr_bound_kernel(DevParams P, State
     static_assert(nx <= kMfmaChunkLoads * kThreads, "staging registers");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int G = A.G;
-    const int nimg = G * SB * 64;                       // 16-byte fragments per image
-    constexpr int NI = NP == 3 ? 2 : 1;                 // images in LDS: hi (plane 0 of Bimg), and lo (plane 1) behind it
+    const int nimg = G * SB * 64;                       // 16-byte fragments of the image
     bf16x8* bh = reinterpret_cast<bf16x8*>(smem);
-    bf16x8* bl = bh + nimg;                             // (NP = 1: never read)
-    float* wts = reinterpret_cast<float*>(bh + NI * nimg);
+    float* wts = reinterpret_cast<float*>(bh + nimg);
     char* xbuf = reinterpret_cast<char*>(wts + 32 * G);
     unsigned short* xh = reinterpret_cast<unsigned short*>(xbuf);
-    unsigned short* xl = xh + nx;                       // (NP = 1: never written or read)
     float* xs = reinterpret_cast<float*>(xbuf);         // (same bytes: a chunk is staged in one form or the other)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int T = P.T;
     const int cps = (T + kMfmaChunk - 1) / kMfmaChunk;
     const int nitems = cps * P.B;
 
-    lds_copy16(bh, bimg, NI * nimg * 16);
+    lds_copy16(bh, bimg, nimg * 16);
     if (HAS_W) for (int i = tid; i < 32 * G; i += kThreads) wts[i] = i < P.K ? S.weights[i] : 0.0f;
 
     float xr[kMfmaChunkLoads];
@@ -238,8 +217,7 @@ __global__ __launch_bounds__(kThreads) void corr_bound_kernel(DevParams P, State
             const int i = u * kThreads + tid;
             if (i < nx) {
                 if (exact) xs[i] = xr[u];
-                else if constexpr (NP == 1) xh[i] = (unsigned short)(bf16_rn_bits(__float_as_uint(xr[u])) >> 16);
-                else { unsigned short hi, lo; bf16_split(xr[u], hi, lo); xh[i] = hi; xl[i] = lo; }
+                else xh[i] = (unsigned short)(bf16_rn_bits(__float_as_uint(xr[u])) >> 16);
             }
         }
         __syncthreads();
@@ -254,7 +232,7 @@ __global__ __launch_bounds__(kThreads) void corr_bound_kernel(DevParams P, State
             int grp;
             if (exact) sc = mfma_tile_score<S4C, HAS_W>(A.dimg, xs + 32 * q, wts, G, S4C, lane, grp);
             else {
-                sc = bound_tile<SB, HAS_W, NP>(bh, bl, xh + 32 * q, xl + 32 * q, wts, G, lane, cmax);
+                sc = bound_tile<SB, HAS_W>(bh, xh + 32 * q, wts, G, lane, cmax);
                 grp = sc == 0.0f ? 0 : -1;              // an exact 0 is a score (hint 0, as the exact tile); else a bound
             }
             const int t = c0 + 32 * q + lane;
@@ -266,51 +244,32 @@ __global__ __launch_bounds__(kThreads) void corr_bound_kernel(DevParams P, State
     }
 }
 
-// LDS bytes of the bound pass: one image (NP = 1) or two, the weights, the chunk as float32 (the exact tile's form, the larger one)
-inline size_t bound_lds_bytes(int G, int SB, int NP)
+// LDS bytes of the bound pass: the image, the weights, the chunk as float32 (the exact tile's form, the larger one)
+inline size_t bound_lds_bytes(int G, int SB)
 {
-    return (size_t)(NP == 3 ? 2 : 1) * G * SB * 1024 + (size_t)32 * G * 4 + (size_t)(kMfmaChunk + 16 * SB + 32) * 4;
+    return (size_t)G * SB * 1024 + (size_t)32 * G * 4 + (size_t)(kMfmaChunk + 16 * SB + 32) * 4;
 }
 
-template <int SB, bool HAS_W, int NP>
+template <int SB, bool HAS_W>
 static int bound_launch_t(hipStream_t stream, const DevParams& P, const State<float>& S, const MfmaArgs& A,
                           const unsigned short* bimg, float cmax, bool dry)
 {
-    const size_t lds = bound_lds_bytes(A.G, SB, NP);
-    auto kern = corr_bound_kernel<SB, HAS_W, NP>;
-    if (set_dyn_lds((const void*)kern, lds) != hipSuccess) return -1;
-    if (dry) return 0;
-    const int cus = mfma_device_cus();
-    const int per_cu = cached_blocks_per_cu((const void*)kern, kThreads, lds);
+    const size_t lds = bound_lds_bytes(A.G, SB);
+    auto kern = corr_bound_kernel<SB, HAS_W>;
     const int64_t nitems = (int64_t)((P.T + kMfmaChunk - 1) / kMfmaChunk) * P.B;
-    int64_t grid = (int64_t)cus * per_cu;
-    if (grid > nitems) grid = nitems;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), lds, stream, P, S, A, bimg, cmax);
-    return 0;
-}
-
-template <int SB>
-static int bound_launch_sb(hipStream_t stream, const DevParams& P, const State<float>& S, const MfmaArgs& A,
-                           const unsigned short* bimg, float cmax, int products, bool dry)
-{
-    const bool hw = A.has_w != 0;
-    if (products == 3) return hw ? bound_launch_t<SB, true, 3>(stream, P, S, A, bimg, cmax, dry) : bound_launch_t<SB, false, 3>(stream, P, S, A, bimg, cmax, dry);
-    return hw ? bound_launch_t<SB, true, 1>(stream, P, S, A, bimg, cmax, dry) : bound_launch_t<SB, false, 1>(stream, P, S, A, bimg, cmax, dry);
+    return launch_tile_kernel(kern, persistent_grid((const void*)kern, lds, nitems, dry), dim3(kThreads), lds, kLdsDevice, 0, dry, stream, P, S, A,
+                              bimg, cmax);
 }
 
 // The bound pass for this shape, or -1 when it does not cover it (the caller then runs the exact corr_init):
 // the float32 chunk counts 2, 4, 8 of the compile-time MFMA kernels (W in 9..16, 25..32, 57..64).
-// products: bf16 products per tap, 1 or 3 (Knobs::bound_products).
 inline int bound_launch_corr_init(hipStream_t stream, const DevParams& P, const State<float>& S, const float* dimg,
-                                  const unsigned short* bimg, float cmax, int products, bool dry = false)
+                                  const unsigned short* bimg, float cmax, bool dry = false)
 {
     const MfmaArgs A = mfma_args<float>(P, S, dimg);
-    switch (A.S4) {
-    case 8: return bound_launch_sb<4>(stream, P, S, A, bimg, cmax, products, dry);
-    case 4: return bound_launch_sb<2>(stream, P, S, A, bimg, cmax, products, dry);
-    case 2: return bound_launch_sb<1>(stream, P, S, A, bimg, cmax, products, dry);
-    default: return -1;
-    }
+    return dispatch_chunks<false>(A.S4, A.has_w != 0, [&](auto s4c, auto hw) {
+        return bound_launch_t<decltype(s4c)::value / 2, decltype(hw)::value>(stream, P, S, A, bimg, cmax, dry);
+    });
 }
 
 }  // namespace hscmp

@@ -12,6 +12,7 @@
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 #include <utility>
 #include <stdint.h>
 #include <limits.h>
@@ -78,30 +79,10 @@ __device__ __forceinline__ void lds_barrier()
 // 256-thread kernels: threadIdx.x itself.  Four signals per 1024-thread workgroup: signal i owns threads 256i..256i+255
 // -- waves 4i..4i+3, which the hardware spreads over the four SIMDs (tools/simd_map_probe.hip: waves w, w+4, w+8, w+12
 // of a workgroup share a SIMD) -- and its waves are rotated by i roles, so that the wave that does a signal's one-lane
-// bookkeeping (and every other per-wave role) sits on a different SIMD for each of the four signals.
-// -DHSCMP_QUAD_SIMD_AFFINE=1 (measurement only) gives every signal one SIMD to itself instead (signal = wave & 3): its
-// serial phases then never meet another signal's matrix instructions, but its four waves also share one vector ALU
-// and nothing fills the matrix pipe of that SIMD meanwhile -- measured 10.7 ms against 9.6 ms for the greedy loop of
-// config 2.
-#ifndef HSCMP_QUAD_SIMD_AFFINE
-#define HSCMP_QUAD_SIMD_AFFINE 0
-#endif
-__device__ __forceinline__ int ltid()
-{
-#if HSCMP_QUAD_SIMD_AFFINE
-    return blockDim.x > 256u ? (int)(((threadIdx.x >> 8) << 6) | (threadIdx.x & 63u)) : (int)threadIdx.x;
-#else
-    return (int)((threadIdx.x + ((threadIdx.x >> 8) << 6)) & 255u);
-#endif
-}
-__device__ __forceinline__ int gsig()
-{
-#if HSCMP_QUAD_SIMD_AFFINE
-    return __builtin_amdgcn_readfirstlane((int)((threadIdx.x >> 6) & 3u));
-#else
-    return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
-#endif
-}
+// bookkeeping (and every other per-wave role) sits on a different SIMD for each of the four signals.  (One SIMD per signal,
+// signal = wave & 3, was measured and lost: 10.7 ms against 9.6 ms for the greedy loop of config 2)
+__device__ __forceinline__ int ltid() { return (int)((threadIdx.x + ((threadIdx.x >> 8) << 6)) & 255u); }
+__device__ __forceinline__ int gsig() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)); }
 
 // threadIdx.x the compiler cannot see through: what is derived from it inside a per-atom function is recomputed there
 // instead of being hoisted out of the atom loop (where it would be live across everything and, in the 128-VGPR builds,
@@ -261,6 +242,70 @@ inline int cached_blocks_per_cu(const void* kern, int threads, size_t lds)
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds) != hipSuccess || per_cu < 1) per_cu = 1;
     seen[key] = per_cu;
     return per_cu;
+}
+
+// CUs of the current device (queried per device: a process may drive several GPUs)
+inline int mfma_device_cus()
+{
+    static int cus_of[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (cus_of[dev] == 0) {
+        hipDeviceProp_t prop;
+        cus_of[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
+    }
+    return cus_of[dev];
+}
+
+// ---- launching the tile kernels ------------------------------------------------------------------------------------
+// The dynamic LDS a kernel family may ask for.  kLdsDevice is the LDS of a gfx950 CU, above which set_dyn_lds fails: the limit
+// of the four-signal matrix-core loop (MfmaRecorr) and of the round-parallel matrix-core loop (RpMfma), and what the launchers
+// without a limit of their own pass (the two initial correlations, the one-signal matrix-core loop).  kLdsLoop is the limit of
+// the loops that launch_policy queues (iterate_kernel with the generic, sparse and LoCOMP policies) and of the round-parallel
+// level loop (RpSparse).  The 2 KiB between them: RpSparse's limit went from 160 to 158 KiB when its LDS budget got "a margin:
+// the kernel's own static bytes count too", and the LoCOMP loops took the value over with the same words -- the compiler books 256 B
+// of static LDS on every iterate_rp_kernel and most iterate_kernel instances, which the hardware counts beside the dynamic bytes.
+// Why the two matrix-core loops were not given the same margin the history does not say; both values stay as they were.
+constexpr size_t kLdsDevice = (size_t)160 * 1024;
+constexpr size_t kLdsLoop = (size_t)158 * 1024;
+
+// Queue one kernel with `lds` bytes of dynamic LDS.  -1: the shape does not fit (more than the family's `limit`, or the
+// attribute cannot be raised); dry: only tell whether it fits (0), queue nothing.  lds_pad: bytes added on top, behind the
+// limit test (HSCMP_LDS_PAD: forces a lower occupancy).
+template <typename... KArgs, typename... Args>
+inline int launch_tile_kernel(void (*kern)(KArgs...), dim3 grid, dim3 block, size_t lds, size_t limit, size_t lds_pad, bool dry,
+                              hipStream_t stream, const Args&... args)
+{
+    if (lds > limit) return -1;
+    lds += lds_pad;
+    if (set_dyn_lds((const void*)kern, lds) != hipSuccess) return -1;
+    if (dry) return 0;
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
+    return 0;
+}
+
+// Persistent grid of the two initial-correlation kernels: as many workgroups as are resident at once (LDS-bound), capped by
+// the (signal, chunk) items.  (A dry run needs no grid, and the occupancy is asked only of a kernel whose LDS has been allowed.)
+inline dim3 persistent_grid(const void* kern, size_t lds, int64_t nitems, bool dry)
+{
+    if (dry || set_dyn_lds(kern, lds) != hipSuccess) return dim3(1);
+    const int64_t resident = (int64_t)mfma_device_cus() * cached_blocks_per_cu(kern, kThreads, lds);
+    return dim3((unsigned)(resident < nitems ? resident : nitems));
+}
+
+// (S4, has_w) -> f(std::integral_constant<int, S4C>, std::bool_constant<HAS_W>) for the compile-time chunk counts 8, 4, 2 of the
+// tile kernels (W in 57..64, 25..32, 9..16); any other count: S4C = 0, the runtime count, where RUNTIME_TOO, else -1.
+template <bool RUNTIME_TOO, typename F> inline int dispatch_chunks(int S4, bool has_w, F&& f)
+{
+    auto with_w = [&](auto s4c) { return has_w ? f(s4c, std::true_type()) : f(s4c, std::false_type()); };
+    switch (S4) {
+    case 8: return with_w(std::integral_constant<int, 8>());
+    case 4: return with_w(std::integral_constant<int, 4>());
+    case 2: return with_w(std::integral_constant<int, 2>());
+    default:
+        if constexpr (RUNTIME_TOO) return with_w(std::integral_constant<int, 0>());
+        else return -1;
+    }
 }
 
 enum { ST_NNZ = 0, ST_DUP = 1, ST_ROUNDS = 2, ST_STOP = 3, ST_ITERS = 4, ST_EVENTS = 5, ST_SLOTS = 6,

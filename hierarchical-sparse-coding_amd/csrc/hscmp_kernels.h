@@ -898,12 +898,29 @@ __device__ __forceinline__ R wave_window_energy(const DevParams& P, const Sig<R>
     return a01 + a23;
 }
 
+// The hooks of iterate_kernel that only the sparse policies fill (SparseRecorr: its own weights in LDS, the row lists, the merged
+// update): the dense and the matrix-core policies inherit these, which do nothing and say so.  Args: the policy's kernel
+// arguments, deduced (GenericRecorr's are a type of its own, nested in it).
+template <typename R> struct NoPolicyHooks {
+    template <typename Args> static __device__ __forceinline__ const R* weights(const DevParams&, const State<R>& S, const Args&, char*) { return S.weights; }
+    template <typename Args> static __device__ __forceinline__ void on_atom(const DevParams&, const State<R>&, const Args&, char*, int, int) {}
+    template <typename Args>
+    static __device__ __forceinline__ bool update_residual(const DevParams&, const State<R>&, const Sig<R>&, const Args&, char*, int, int, R,
+                                                           int, int, int, R&, R&) { return false; }
+    template <typename Args> static __device__ __forceinline__ bool window_partials(const DevParams&, const Sig<R>&, const Args&, char*, int, int, R&) { return false; }
+    template <typename Args>
+    static __device__ __forceinline__ bool wave_window_listed(const DevParams&, const Sig<R>&, const Args&, char*, int, int, int, int, R&) { return false; }
+    template <typename Args>
+    static __device__ __forceinline__ bool row_results(const DevParams&, const Args&, char*, int, const int*&, const R*&, const R*&, int&, int&) { return false; }
+    template <typename Args> static __device__ __forceinline__ bool residual_copy_in_lds(const Args&, char*) { return false; }
+};
+
 // ------------------------------------------------------------------------------------------------
 // GenericRecorr: re-correlate rows p-(W-1)..p+(W-1) against the reflect-padded residual span
 // (modeling.py:1018-1051), reduce each row to its per-position best, write best_c/best_k.
 // Threads = (row, atom group); the per-atom fma chain order is the pinned one (f outer, w inner).
 // ------------------------------------------------------------------------------------------------
-template <typename R> struct GenericRecorr {
+template <typename R> struct GenericRecorr : NoPolicyHooks<R> {
     static constexpr int kMaxSegments = kMaxSeg;
     static constexpr bool kFused = false;               // uses the step-by-step atom body of iterate_kernel
     static constexpr bool kLocomp = false;              // (hscmp_locomp.h: LocompRecorr re-fits the atom's neighbourhood)
@@ -920,14 +937,6 @@ template <typename R> struct GenericRecorr {
     static __device__ __forceinline__ void epilogue(const DevParams&, const State<R>&, const Args&, char*, int) {}
     static __device__ __forceinline__ void resolve_wave(const DevParams&, const State<R>&, const Sig<R>&, const Args&, char*,
                                                         int, int, int&, R&) {}
-    static __device__ __forceinline__ const R* weights(const DevParams&, const State<R>& S, const Args&, char*) { return S.weights; }
-    static __device__ __forceinline__ void on_atom(const DevParams&, const State<R>&, const Args&, char*, int, int) {}
-    static __device__ __forceinline__ bool update_residual(const DevParams&, const State<R>&, const Sig<R>&, const Args&, char*, int, int, R,
-                                                           int, int, int, R&, R&) { return false; }
-    static __device__ __forceinline__ bool window_partials(const DevParams&, const Sig<R>&, const Args&, char*, int, int, R&) { return false; }
-    static __device__ __forceinline__ bool wave_window_listed(const DevParams&, const Sig<R>&, const Args&, char*, int, int, int, int, R&) { return false; }
-    static __device__ __forceinline__ bool row_results(const DevParams&, const Args&, char*, int, const int*&, const R*&, const R*&, int&, int&) { return false; }
-    static __device__ __forceinline__ bool residual_copy_in_lds(const Args&, char*) { return false; }
     static constexpr int kWinBytes = 16384;            // LDS window of the residual span, when it fits
     static size_t extra_lds_bytes(const DevParams&) { return kWinBytes; }
     static size_t total_lds_bytes(const DevParams& P, const Args&) { return ((sizeof(Shared) + 15) / 16) * 16 + extra_lds_bytes(P); }

@@ -435,7 +435,7 @@ __device__ __forceinline__ void mfma_tile_best(const float* __restrict__ dimg, c
 // signals' tiles to run while one is in its serial steps (the 64 KB image leaves no room for a second workgroup); each signal's four
 // waves meet at their own LDS counter (SoftSync), as in the four-signal greedy loop.
 // LDS: [dictionary image | weights] then per signal [control block][window][LocompLds]
-template <int S4C, bool HAS_W, int GS = 1> struct LocompMfma {
+template <int S4C, bool HAS_W, int GS = 1> struct LocompMfma : NoPolicyHooks<float> {
     using R = float;
     // four signals per workgroup: the per-signal state must fit a quarter of what the image leaves -- 256 segment maxima, the Gram
     // matrix of a group in LDS up to 32 atoms
@@ -462,14 +462,6 @@ template <int S4C, bool HAS_W, int GS = 1> struct LocompMfma {
     }
     static __device__ __forceinline__ void epilogue(const DevParams&, const State<R>&, const Args&, char*, int) {}
     static __device__ __forceinline__ void resolve_wave(const DevParams&, const State<R>&, const Sig<R>&, const Args&, char*, int, int, int&, R&) {}
-    static __device__ __forceinline__ const R* weights(const DevParams&, const State<R>& S, const Args&, char*) { return S.weights; }
-    static __device__ __forceinline__ void on_atom(const DevParams&, const State<R>&, const Args&, char*, int, int) {}
-    static __device__ __forceinline__ bool update_residual(const DevParams&, const State<R>&, const Sig<R>&, const Args&, char*, int, int, R,
-                                                           int, int, int, R&, R&) { return false; }
-    static __device__ __forceinline__ bool window_partials(const DevParams&, const Sig<R>&, const Args&, char*, int, int, R&) { return false; }
-    static __device__ __forceinline__ bool wave_window_listed(const DevParams&, const Sig<R>&, const Args&, char*, int, int, int, int, R&) { return false; }
-    static __device__ __forceinline__ bool row_results(const DevParams&, const Args&, char*, int, const int*&, const R*&, const R*&, int&, int&) { return false; }
-    static __device__ __forceinline__ bool residual_copy_in_lds(const Args&, char*) { return false; }
     static __device__ __forceinline__ void before_runs(const Args&, char*) {}
     static __device__ __forceinline__ bool atom_lists(const DevParams&, const Args&, char*, const int*&, const int*&, const R*&) { return false; }
 

@@ -70,15 +70,6 @@ inline void mfma_build_dict_image(const float* D, int K, int W, int F, std::vect
                 }
 }
 
-// ------------------------------------------------------------------------------------------------
-// One 32-position tile against all atom groups: per-position best (coefficient, atom).
-//   dimg : LDS dictionary image;  win : LDS floats, win[j + kk + 2s] is the B operand (see above)
-//   wts  : LDS weights [32*G] (HAS_W) ;  result valid in lanes 0..31 (position = lane)
-// S4C > 0: compile-time chunk count -- B operands live in registers, A operands and accumulators
-// are double buffered: group g+1's A fragments are fetched while group g's MFMA chain runs, and
-// the lane-local arg-max of group g-1 is interleaved between the MFMA issues of group g.
-// S4C == 0: runtime chunk count (any W), simple loop.
-// ------------------------------------------------------------------------------------------------
 // value of the same lane index in the OTHER half-wave (lane ^ 32) through v_permlane32_swap:
 // swap(a, a) leaves r[0] = {low half of a, low half of a} and r[1] = {high half, high half}
 __device__ __forceinline__ int swap_halves_i(int v, int h)
@@ -108,13 +99,8 @@ __device__ __forceinline__ float swap_halves_f(float v, int h) { return __int_as
 template <bool HAS_W>
 __device__ __forceinline__ void mfma_reduce_pair(float v0, float v1, int k0, int k1, const float* __restrict__ wts, float& bs)
 {
-#ifdef HSCMP_DBG_NO_REDUCE   // diagnostic build: keep the accumulator live, skip the reduction
-    asm volatile("" :: "v"(v0), "v"(v1));
-    (void)k0; (void)k1; (void)wts; (void)bs;
-#else
     if (HAS_W) { v0 = v0 * wts[k0]; v1 = v1 * wts[k1]; }      // modeling.py:906, one rounded product each
     bs = fmaxf(fmaxf(fabsf(v0), fabsf(v1)), bs);              // v_max3_f32 |v0|, |v1|, bs
-#endif
 }
 
 // The group hint: next to the score the tile reports WHICH 32-atom group holds the first atom that attains it (two
@@ -151,13 +137,8 @@ __device__ __forceinline__ float mfma_tile_score(const float* __restrict__ dimg,
         f32x16 acc0, acc1;
 
         auto load_a = [&](f32x4 (&a)[S4C], int g) {
-#ifdef HSCMP_DBG_NO_AREAD    // diagnostic build: A operands from registers, no LDS reads
-#pragma unroll
-            for (int s4 = 0; s4 < S4C; ++s4) { a[s4][0] = bop[s4]; a[s4][1] = bop[s4 + 1]; a[s4][2] = (float)g; a[s4][3] = bop[0]; }
-#else
 #pragma unroll
             for (int s4 = 0; s4 < S4C; ++s4) a[s4] = dv[(g * S4C + s4) * 64];
-#endif
         };
         auto run_first = [&](const f32x4 (&a)[S4C], f32x16& acc) {
 #pragma unroll
@@ -283,9 +264,7 @@ __device__ __forceinline__ float mfma_tile_score_lean(const float* __restrict__ 
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], b2, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[3], b3, acc, 0, 0, 0);
             a = an; b0 = bn0; b1 = bn1; b2 = bn2; b3 = bn3;
-#ifndef HSCMP_LEAN_NO_SCHED_BARRIER
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            __builtin_amdgcn_sched_barrier(0);                  // nothing crosses a chunk boundary (see above: 145 VGPRs, spills)
         }
         if constexpr (REDUCE) bg = bs > before ? g - 1 : bg;
     };
@@ -316,17 +295,15 @@ __device__ __forceinline__ float mfma_tile_score_lean(const float* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------
-// The bound tile: certified UPPER BOUNDS of a 32-position tile's scores on the bf16 matrix cores (float32 operands
-// split into bf16 hi + lo; NP = 3 products hi.hi + hi.lo + lo.hi, or NP = 1: hi.hi alone, on v_mfma_f32_32x32x16_bf16).
-// One definition for the bound pass of the initial correlation (corr_bound_kernel: NP = 1, or 3 on request) and the
-// re-correlation of the four-signal loop (MfmaRecorr, BOUND: NP = 1, or 3 in a -DHSCMP_LOOP_BOUND_PRODUCTS=3 build):
-// hscmp_bound.h derives the constants and states the model the inputs must lie in.
+// The bound tile: certified UPPER BOUNDS of a 32-position tile's scores on the bf16 matrix cores: every float32 operand
+// rounded to bf16, one product per tap on v_mfma_f32_32x32x16_bf16.  One definition for the bound pass of the initial
+// correlation (corr_bound_kernel) and the re-correlation of the four-signal loop (MfmaRecorr, BOUND): hscmp_bound.h derives
+// the slack and states the model the inputs must lie in.
 // ------------------------------------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr float kBoundEps = 0x1p-13f;        // three products: >= 1.67 eps_0 (hscmp_bound.h)
-constexpr float kBoundEps1 = 0x1p-7f * (1.0f + 0x1p-6f);     // one product: >= 1.008 eps_0 / (1 - 2^-8) (hscmp_bound.h)
+constexpr float kBoundEps1 = 0x1p-7f * (1.0f + 0x1p-6f);     // the slack of one product per tap: 1.0082 (1 + 2^-24) eps_1 / (1 - 2^-8) (hscmp_bound.h)
 constexpr float kBoundRel = 1.0f + 0x1p-20f;
 constexpr float kBoundAbs = 0x1p-80f;
 constexpr float kBoundXMin = 0x1p-60f, kBoundXMax = 0x1p60f;     // signal samples (per chunk, on the device)
@@ -352,40 +329,30 @@ __device__ __forceinline__ float bf16_lo_f(unsigned w) { return __uint_as_float(
 __device__ __forceinline__ float bf16_hi_f(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
 
 // One 32-position tile against all atom groups: the bound of every position (lanes 0..31: position = lane).
-//   bimg: LDS [hi image][lo image];  xh, xl: the chunk's bf16 halves in LDS, 4-byte aligned, index 0 = the first tap
-//   of the tile's first position.  B operand of k-step s, lane (r, h): samples r + 16s + 8h + j, j = 0..7 -- 8
-//   consecutive bf16 at an odd or even start: five aligned dwords and v_alignbit.
-// NP = 1: only the hi image and the hi halves are read (bimg_l and xl may be null), one MFMA per k-step, and the window norm
-// comes from the hi halves (||x|| <= ||xh|| / (1 - 2^-8), inside kBoundEps1).
-template <int SB, bool HAS_W, int NP>
-__device__ __forceinline__ float bound_tile(const bf16x8* __restrict__ bimg_h, const bf16x8* __restrict__ bimg_l,
-                                            const unsigned short* __restrict__ xh, const unsigned short* __restrict__ xl,
+//   bimg: LDS, the bf16 image of the dictionary (plane 0 of Bimg);  xh: the window's samples rounded to bf16 in LDS, 4-byte
+//   aligned, index 0 = the first tap of the tile's first position.  B operand of k-step s, lane (r, h): samples
+//   r + 16s + 8h + j, j = 0..7 -- 8 consecutive bf16 at an odd or even start: five aligned dwords and v_alignbit.
+// One MFMA per k-step; the window norm comes from the rounded samples (||x|| <= ||xh|| / (1 - 2^-8), inside kBoundEps1).
+template <int SB, bool HAS_W>
+__device__ __forceinline__ float bound_tile(const bf16x8* __restrict__ bimg, const unsigned short* __restrict__ xh,
                                             const float* __restrict__ wts, int G, int lane, float cmax)
 {
-    static_assert(NP == 1 || NP == 3, "hi.hi, or hi.hi + hi.lo + lo.hi");
-    constexpr bool LO = NP == 3;
     const int r = lane & 31, h = lane >> 5;
     const unsigned* xh32 = reinterpret_cast<const unsigned*>(xh);
-    const unsigned* xl32 = reinterpret_cast<const unsigned*>(xl);
     const unsigned sh = 16u * (unsigned)(r & 1);
-    u32x4 bh[SB], bl[LO ? SB : 1];
+    u32x4 bh[SB];
     float ss = 0.0f;
 #pragma unroll
     for (int s = 0; s < SB; ++s) {
         const int w0 = (r >> 1) + 8 * s + 4 * h;
-        unsigned a[5], b[5];
+        unsigned a[5];
 #pragma unroll
-        for (int i = 0; i < 5; ++i) { a[i] = xh32[w0 + i]; if constexpr (LO) b[i] = xl32[w0 + i]; }
+        for (int i = 0; i < 5; ++i) a[i] = xh32[w0 + i];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            bh[s][i] = __builtin_amdgcn_alignbit(a[i + 1], a[i], sh);
-            if constexpr (LO) bl[s][i] = __builtin_amdgcn_alignbit(b[i + 1], b[i], sh);
-        }
+        for (int i = 0; i < 4; ++i) bh[s][i] = __builtin_amdgcn_alignbit(a[i + 1], a[i], sh);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {                           // ||xh + xl||^2 over this half-wave's taps (xh + xl exact); NP = 1: ||xh||^2
-            float y0, y1;
-            if constexpr (LO) { y0 = bf16_lo_f(bh[s][i]) + bf16_lo_f(bl[s][i]); y1 = bf16_hi_f(bh[s][i]) + bf16_hi_f(bl[s][i]); }
-            else { y0 = bf16_lo_f(bh[s][i]); y1 = bf16_hi_f(bh[s][i]); }
+        for (int i = 0; i < 4; ++i) {                           // ||xh||^2 over this half-wave's taps
+            const float y0 = bf16_lo_f(bh[s][i]), y1 = bf16_hi_f(bh[s][i]);
             ss = fmaf(y0, y0, ss);
             ss = fmaf(y1, y1, ss);
         }
@@ -400,15 +367,8 @@ __device__ __forceinline__ float bound_tile(const bf16x8* __restrict__ bimg_h, c
         acc = z;
 #pragma unroll
         for (int s = 0; s < SB; ++s) {
-            const bf16x8 ah = bimg_h[(g * SB + s) * 64 + lane];
-            bf16x8 al;
-            if constexpr (LO) al = bimg_l[(g * SB + s) * 64 + lane];
-            const bf16x8 xbh = __builtin_bit_cast(bf16x8, bh[s]);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xbh, acc, 0, 0, 0);
-            if constexpr (LO) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, __builtin_bit_cast(bf16x8, bl[s]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xbh, acc, 0, 0, 0);
-            }
+            const bf16x8 ah = bimg[(g * SB + s) * 64 + lane];
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, __builtin_bit_cast(bf16x8, bh[s]), acc, 0, 0, 0);
         }
     };
     auto reduce = [&](const f32x16& acc, int g) {
@@ -435,7 +395,7 @@ __device__ __forceinline__ float bound_tile(const bf16x8* __restrict__ bimg_h, c
     }
     bs = fmaxf(bs, swap_halves_f(bs, h));
     if (ss == 0.0f) return bs;                                  // all-zero window (xh == 0 only where x == 0): every product and sum is an exact 0
-    const float e = __fmul_rn(__fmul_rn(LO ? kBoundEps : kBoundEps1, __fsqrt_rn(ss)), cmax) + kBoundAbs;
+    const float e = __fmul_rn(__fmul_rn(kBoundEps1, __fsqrt_rn(ss)), cmax) + kBoundAbs;
     return fmaf(bs, kBoundRel, e);
 }
 
@@ -902,41 +862,14 @@ template <typename R> inline bool mfma_supported(int K, int W, int F)
 // BOUND (four signals, float32, compile-time chunk count): the re-correlation writes upper bounds on the bf16 matrix cores
 // (bound_tile, as the bound pass of the initial correlation) and the selection refines the rows that win; the workgroup
 // holds the dictionary as the three bf16 planes of hscmp_bound.h instead of the float32 image.
-template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> struct MfmaRecorr {
+template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> struct MfmaRecorr : NoPolicyHooks<typename Tile::R> {
     static constexpr int kMaxSegments = kMfmaMaxSeg;
     static constexpr bool kFused = true;
     static constexpr bool kLocomp = false;
     static constexpr int kGroup = GS;
     static_assert(!BOUND || (GS == 4 && S4C > 0 && std::is_same<Tile, TileF32>::value), "the bound loop: four signals, float32, W <= 8 S4C");
     static constexpr int SB = S4C / 2;          // (BOUND) k-steps of 16 taps of the bf16 tile
-    // -DHSCMP_QUAD_LOCKSTEP=1 (measurement only): barriers B1 and B4 of the atom body become hardware barriers across
-    // the four signals of the workgroup, which lines their tiles up -- all serial phases then run together without a
-    // matrix instruction beside them, all tiles together.  Measured 10.1-10.2 ms against 9.6 ms for the greedy loop of
-    // config 2: what the serial phases gain by running alone (tools/serial_stretch_probe.hip) is less than what the
-    // matrix pipe loses by idling through them.
-#ifndef HSCMP_QUAD_LOCKSTEP
-#define HSCMP_QUAD_LOCKSTEP 0
-#endif
-    // -DHSCMP_REFINE_HANDOVER=0 (measurement only): the bound loop's atom body resolves (k, c) again instead of taking them from
-    // the refine of its selection (DESIGN.md section 11 times the two steps apart).
-#ifndef HSCMP_REFINE_HANDOVER
-#define HSCMP_REFINE_HANDOVER 1
-#endif
-    // -DHSCMP_LOOP_BOUND_PRODUCTS=3 (measurement only): the bound loop's tile sums hi.hi + hi.lo + lo.hi and its window is split
-    // into hi and lo halves, as before the one-product tile.  The default, 1, is the tile of the bound pass.
-#ifndef HSCMP_LOOP_BOUND_PRODUCTS
-#define HSCMP_LOOP_BOUND_PRODUCTS 1
-#endif
-    // -DHSCMP_REFINE_CACHE=0 (measurement only): no cache of committed refines; a winner that holds an exact score from memory
-    // resolves (k, c) from its window and hint.
-#ifndef HSCMP_REFINE_CACHE
-#define HSCMP_REFINE_CACHE 1
-#endif
-    static constexpr int kLoopNP = HSCMP_LOOP_BOUND_PRODUCTS;   // (BOUND) bf16 products per tap of the loop's tile
-    static_assert(kLoopNP == 1 || kLoopNP == 3, "HSCMP_LOOP_BOUND_PRODUCTS: 1 or 3");
-    static constexpr bool kCache = BOUND && HSCMP_REFINE_CACHE != 0;
-    static constexpr int kCacheEntries = 64;    // (kCache) one 16-byte entry {t, k, c bits, age} per lane: see cache_commit
-    static constexpr bool kLockstep = GS > 1 && HSCMP_QUAD_LOCKSTEP != 0;
+    static constexpr int kCacheEntries = 64;    // (BOUND) one 16-byte entry {t, k, c bits, age} per lane: see cache_commit
     static constexpr int kMinWavesPerSimd = GS;         // (launch bounds: 4 signals x 4 waves = 4 waves per SIMD)
     using Sync = typename std::conditional<GS == 1, HwSync, SoftSync>::type;
     static constexpr int kEnergyWaves = kWaves;
@@ -948,14 +881,6 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     static constexpr int TP = Tile::TP;
     // (BOUND) the refine's exchange: two sets of one 16-byte record {score bits, k, c bits, -} per wave of the signal
     static constexpr int kRefineSlotBytes = 2 * kWaves * 16;
-    static __device__ __forceinline__ const R* weights(const DevParams&, const State<R>& S, const MfmaArgsT<R>&, char*) { return S.weights; }
-    static __device__ __forceinline__ void on_atom(const DevParams&, const State<R>&, const MfmaArgsT<R>&, char*, int, int) {}
-    static __device__ __forceinline__ bool update_residual(const DevParams&, const State<R>&, const Sig<R>&, const MfmaArgsT<R>&, char*, int, int, R,
-                                                           int, int, int, R&, R&) { return false; }
-    static __device__ __forceinline__ bool window_partials(const DevParams&, const Sig<R>&, const MfmaArgsT<R>&, char*, int, int, R&) { return false; }
-    static __device__ __forceinline__ bool wave_window_listed(const DevParams&, const Sig<R>&, const MfmaArgsT<R>&, char*, int, int, int, int, R&) { return false; }
-    static __device__ __forceinline__ bool row_results(const DevParams&, const MfmaArgsT<R>&, char*, int, const int*&, const R*&, const R*&, int&, int&) { return false; }
-    static __device__ __forceinline__ bool residual_copy_in_lds(const MfmaArgsT<R>&, char*) { return false; }
     using Shared = IterSharedT<R, kMfmaMaxSeg, false, false>;
     using Args = MfmaArgsT<R>;
     static __device__ __forceinline__ Sync make_sync(Shared& sh)
@@ -967,9 +892,9 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     struct Layout {
         R* dimg; R* wts; R* win; R* esq; R* sbs; unsigned* bloom;
         R* rwin; R* rwin_w; unsigned long long* edge;
-        unsigned short* bimg; unsigned short* xh; unsigned short* xl;      // (BOUND) the planes; the window's bf16 hi (kLoopNP = 3: and lo)
+        unsigned short* bimg; unsigned short* xh;                          // (BOUND) the planes; the window rounded to bf16
         int* rx;                                                           // (BOUND) the refine's exchange slots (see refine)
-        int4* rc;                                                          // (kCache) the cache of committed refines (see cache_commit)
+        int4* rc;                                                          // (BOUND) the cache of committed refines (see cache_commit)
         int nwin, wp, nsbmax, nplane;
     };
 
@@ -992,8 +917,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     {
         const size_t relems = (size_t)window_floats(P.W, A.S4) + 2 * 8 * A.S4 + (size_t)segbuf_len_p(P) + 8 * A.S4 + kWaves * 8 * A.S4;
         return relems * sizeof(R) + kBloomWords * sizeof(unsigned) + kEdgeWords * sizeof(unsigned long long) +
-               (BOUND ? (size_t)(kLoopNP == 3 ? 2 : 1) * window_floats(P.W, A.S4) * sizeof(unsigned short) + kRefineSlotBytes : 0) +
-               (kCache ? (size_t)kCacheEntries * 16 : 0);
+               (BOUND ? (size_t)window_floats(P.W, A.S4) * sizeof(unsigned short) + kRefineSlotBytes + (size_t)kCacheEntries * 16 : 0);
     }
     static __host__ __device__ size_t per_signal_lds_bytes(const DevParams& P, const Args& A)
     {
@@ -1031,9 +955,8 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
         L.rwin_w = L.rwin + L.wp;
         L.edge = reinterpret_cast<unsigned long long*>(L.rwin_w + kWaves * L.wp);
         L.xh = reinterpret_cast<unsigned short*>(L.edge + kEdgeWords);
-        L.xl = kLoopNP == 3 ? L.xh + L.nwin : nullptr;
         // (16-byte aligned: every region in front is a multiple of 16 bytes -- window_floats is a multiple of 8)
-        L.rx = reinterpret_cast<int*>(L.xh + (kLoopNP == 3 ? 2 : 1) * L.nwin);
+        L.rx = reinterpret_cast<int*>(L.xh + L.nwin);
         L.rc = reinterpret_cast<int4*>(L.rx) + 2 * kWaves;
         return L;
     }
@@ -1067,9 +990,9 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
             if (HAS_W) for (int i = tid; i < Tile::GA * A.G; i += kThreads) L.wts[i] = i < P.K ? S.weights[i] : (R)0;
         }
         for (int i = tid; i < L.nwin; i += kThreads) L.win[i] = (R)0;   // the tail behind the span stays zero
-        if constexpr (BOUND) for (int i = tid; i < L.nwin; i += kThreads) { L.xh[i] = 0; if constexpr (kLoopNP == 3) L.xl[i] = 0; }
+        if constexpr (BOUND) for (int i = tid; i < L.nwin; i += kThreads) L.xh[i] = 0;
         // the cache starts empty on every launch: a resumed encode resolves its first from-memory winners from window and hint
-        if constexpr (kCache) if (tid < kCacheEntries) L.rc[tid] = make_int4(-1, 0, 0, 0);
+        if constexpr (BOUND) if (tid < kCacheEntries) L.rc[tid] = make_int4(-1, 0, 0, 0);
         for (int i = tid; i < kBloomWords; i += kThreads) L.bloom[i] = 0u;
         for (int i = tid; i < (1 + kWaves) * L.wp; i += kThreads) L.rwin[i] = (R)0;   // padded taps stay zero
         if (tid < kEdgeWords) L.edge[tid] = S.edge[kEdgeWords * b + tid];
@@ -1106,18 +1029,10 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
             return L.dimg[Tile::dindex(k, w, S4)];
         }
     }
-    // (BOUND) sample i of the re-correlation's window as the bound tile's B operand: its bf16 hi half, one rounding (the
-    // one-product tile never reads a lo half); kLoopNP = 3: hi and lo
+    // (BOUND) sample i of the re-correlation's window as the bound tile's B operand: rounded to bf16, one rounding
     static __device__ __forceinline__ void window_split(const Layout& L, int i, R v)
     {
-        if constexpr (kLoopNP == 1) {
-            L.xh[i] = (unsigned short)(bf16_rn_bits(__float_as_uint((float)v)) >> 16);
-        } else {
-            unsigned short hi, lo;
-            bf16_split(v, hi, lo);
-            L.xh[i] = hi;
-            L.xl[i] = lo;
-        }
+        L.xh[i] = (unsigned short)(bf16_rn_bits(__float_as_uint((float)v)) >> 16);
     }
     static __device__ __forceinline__ R dchain(const Layout& L, const R* rw, int k, int S4)
     {
@@ -1272,7 +1187,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
         const int sg = t >> P.seg_shift;
         // (constant indices only: the list stays in registers)
 #pragma unroll
-        for (int j = 0; j < kRefineCap; ++j) if (j == i) { rl.t[j] = t; rl.s[j] = s_ex; rl.g[j] = g_ex; if constexpr (kCache) { rl.k[j] = k_ex; rl.c[j] = c_ex; } }
+        for (int j = 0; j < kRefineCap; ++j) if (j == i) { rl.t[j] = t; rl.s[j] = s_ex; rl.g[j] = g_ex; if constexpr (BOUND) { rl.k[j] = k_ex; rl.c[j] = c_ex; } }
         if constexpr (BOUND) { rl.lead(t, s_ex, k_ex, c_ex); rl.nx += 1u; }
         rl.n = i + 1;
         const int t0 = sg << P.seg_shift, t1 = min(P.T, t0 + P.seg);
@@ -1330,7 +1245,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     // rlo..rhi: the rows the atom re-correlates (empty for the full list's commit).
     static __device__ __forceinline__ void cache_commit(const DevParams& P, const Args& A, char* lds, const RefineList<R>& rl, int rlo, int rhi)
     {
-        if constexpr (kCache) {
+        if constexpr (BOUND) {
             const int tid = ltid();
             if ((tid >> 6) != 0) return;
             const int lane = tid & 63;
@@ -1400,9 +1315,9 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
         // the group's chains; the null test and the duplicate check run as for a resolved-here (k, c).  A winner that holds
         // an exact score from memory (the exact fallback tile, HSCMP_EXACT_RECORR=1) was not refined and resolves below.
         bool handed = false;
-        if constexpr (BOUND && HSCMP_REFINE_HANDOVER != 0) { if (!resolved) handed = rl.find_atom(p, k, c); }
+        if constexpr (BOUND) { if (!resolved) handed = rl.find_atom(p, k, c); }
         // ... but by an earlier one, whose commit kept its (k, c) in the signal's cache (cache_commit): the same path
-        if constexpr (kCache) {
+        if constexpr (BOUND) {
             if (!resolved && !handed) {
                 const int4 ce = L.rc[lane];
                 const unsigned long long hit = __builtin_amdgcn_ballot_w64(ce.x == p);
@@ -1589,11 +1504,11 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
             }
         }
         HSCMP_STAMP(0);                                         // phase A + resolve + update, up to B1
-        // B1: window, squares, segment buffer in LDS.  (Lockstep build: waves of a signal that has finished have ended
-        // and the hardware barrier does not count them; every wave passes exactly two hardware barriers per atom, B1
-        // and B4, and leaves the loop only between atoms, so all signals are always at the same one of the two.)
-        if constexpr (kLockstep) { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-        else sy.lds();
+        // B1: window, squares, segment buffer in LDS.  (The signal's own barrier, SoftSync, with four signals per workgroup: hardware
+        // barriers here and at B4 would line the four signals' tiles up, measured 10.1-10.2 ms against 9.6 ms for the greedy loop
+        // of config 2 -- what the serial phases gain by running alone is less than what the matrix pipe loses by idling through
+        // them)
+        sy.lds();
         // The new samples go to memory only BEHIND this barrier.  Near a signal end a sample of the atom's support is
         // loaded twice in phase A -- by its own thread and, through the reflection, by a thread of another wave -- and
         // with blocked selection nothing else separates those loads from this store: a wave that left the previous
@@ -1620,7 +1535,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
             }
             if (lane == 0) { sh.red[wv] = pb; sh.red[kWaves + wv] = pa; }
         };
-        if constexpr (!kLockstep) energy_partials();
+        energy_partials();
         HSCMP_STAMP(2);                                         // energy partials
 
         HSCMP_MARK("tile");
@@ -1628,7 +1543,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
         // Four waves per SIMD: serial code runs at priority 3, the tiles at priority 0.  Against waves that issue MFMAs
         // back to back a raised priority buys nothing (tools/serial_stretch_probe.hip), but the tiles of this kernel wait
         // for their LDS operands often enough that it is worth 2.5 % here (loop of config 2: 9.56 ms with, 9.84 without).
-        if constexpr (GS > 1 && !kLockstep) __builtin_amdgcn_s_setprio(0);
+        if constexpr (GS > 1) __builtin_amdgcn_s_setprio(0);
         for (int q = wv; q < ntiles; q += kWaves) {
             R sc;
             int grp;
@@ -1643,9 +1558,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
                 if (__builtin_amdgcn_ballot_w64(out) != 0) {
                     sc = planes_tile_score<SB, HAS_W>(L.bimg, L.nplane, L.win + TP * q, L.wts, A.G, lane, grp);
                 } else {
-                    const bf16x8* ph = reinterpret_cast<const bf16x8*>(L.bimg);
-                    sc = bound_tile<SB, HAS_W, kLoopNP>(ph, ph + L.nplane / 8, L.xh + TP * q, kLoopNP == 3 ? L.xl + TP * q : nullptr, L.wts, A.G,
-                                                        lane, A.cmax);
+                    sc = bound_tile<SB, HAS_W>(reinterpret_cast<const bf16x8*>(L.bimg), L.xh + TP * q, L.wts, A.G, lane, A.cmax);
                     grp = sc == 0.0f ? 0 : -1;                  // an exact 0 is a score (hint 0, as the exact tile); else a bound
                 }
             } else if constexpr (GS > 1 && S4C > 0) sc = Tile::template tile_score_lean<S4C, HAS_W>(L.dimg, L.win + TP * q, L.wts, A.G, S4, lane, grp);
@@ -1657,11 +1570,10 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
                 L.sbs[t - segbase] = sc;
             }
         }
-        if constexpr (GS > 1 && !kLockstep) __builtin_amdgcn_s_setprio(3);
+        if constexpr (GS > 1) __builtin_amdgcn_s_setprio(3);
         HSCMP_STAMP(3);                                         // MFMA tile(s) of this wave
         // B4: per-row scores in the segment buffer
-        if constexpr (kLockstep) { energy_partials(); asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-        else sy.lds();
+        sy.lds();
         HSCMP_STAMP(4);                                         // B4
 
         HSCMP_MARK("segmax");
@@ -1787,20 +1699,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     }
 };
 
-// host-side dispatch -----------------------------------------------------------------------------
-// CUs of the current device (queried per device: a process may drive several GPUs)
-inline int mfma_device_cus()
-{
-    static int cus_of[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (cus_of[dev] == 0) {
-        hipDeviceProp_t prop;
-        cus_of[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-    }
-    return cus_of[dev];
-}
-
+// host-side dispatch (launch_tile_kernel, persistent_grid, dispatch_chunks: hscmp_device.h) --------------------
 template <typename Tile, int S4C, bool HAS_W>
 static int mfma_launch_corr_init_t(hipStream_t stream, const DevParams& P, const State<typename Tile::R>& S,
                                    const MfmaArgsT<typename Tile::R>& A, bool dry = false)
@@ -1808,15 +1707,8 @@ static int mfma_launch_corr_init_t(hipStream_t stream, const DevParams& P, const
     using R = typename Tile::R;
     const size_t lds = ((size_t)A.G * A.S4 * Tile::kChunkElems + Tile::GA * A.G + kMfmaChunk + 8 * A.S4 + 32) * sizeof(R);
     auto kern = corr_init_mfma_kernel<Tile, S4C, HAS_W>;
-    if (set_dyn_lds((const void*)kern, lds) != hipSuccess) return -1;
-    if (dry) return 0;
-    // persistent grid: as many workgroups as are resident at once (LDS-bound), capped by the work
-    const int cus = mfma_device_cus();
-    const int per_cu = cached_blocks_per_cu((const void*)kern, kThreads, lds);
     const int64_t nitems = (int64_t)((P.T + kMfmaChunk - 1) / kMfmaChunk) * P.B;
-    const int64_t grid = std::min((int64_t)cus * per_cu, nitems);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), lds, stream, P, S, A);
-    return 0;
+    return launch_tile_kernel(kern, persistent_grid((const void*)kern, lds, nitems, dry), dim3(kThreads), lds, kLdsDevice, 0, dry, stream, P, S, A);
 }
 
 // lds_pad: bytes of LDS added on top (HSCMP_LDS_PAD: forces a lower occupancy)
@@ -1827,14 +1719,9 @@ static int mfma_launch_iterate_g(hipStream_t stream, const DevParams& P0, const 
     using Pol = MfmaRecorr<Tile, S4C, HAS_W, GS, BOUND>;
     DevParams P = P0;
     set_segments(P, Pol::kMaxSegments);
-    size_t lds = Pol::total_lds_bytes(P, A);
-    if (GS > 1 && lds > (size_t)160 * 1024) return -1;
-    lds += (size_t)lds_pad;
     auto kern = S.geom ? iterate_kernel<typename Tile::R, Pol, true> : iterate_kernel<typename Tile::R, Pol, false>;     // (ragged batch)
-    if (set_dyn_lds((const void*)kern, lds) != hipSuccess) return -1;
-    if (dry) return 0;
-    hipLaunchKernelGGL(kern, dim3((P.B + GS - 1) / GS), dim3(GS * kThreads), lds, stream, P, S, A);
-    return 0;
+    return launch_tile_kernel(kern, dim3((P.B + GS - 1) / GS), dim3(GS * kThreads), Pol::total_lds_bytes(P, A), kLdsDevice, (size_t)lds_pad, dry,
+                              stream, P, S, A);
 }
 
 // The loop with `group` signals per workgroup: 1, or 4 (float32 with a compile-time chunk count: one round of four overlapping
@@ -1860,23 +1747,14 @@ template <typename R> inline MfmaArgsT<R> mfma_args(const DevParams& P, const St
     return A;
 }
 
-#define HSCMP_MFMA_DISPATCH(FN, ...)                                                                                          \
-    do {                                                                                                                      \
-        const bool hw = A.has_w != 0;                                                                                         \
-        switch (A.S4) {                                                                                                       \
-        case 8: return hw ? FN<Tile, 8, true>(stream, P, S, A, __VA_ARGS__) : FN<Tile, 8, false>(stream, P, S, A, __VA_ARGS__);  \
-        case 4: return hw ? FN<Tile, 4, true>(stream, P, S, A, __VA_ARGS__) : FN<Tile, 4, false>(stream, P, S, A, __VA_ARGS__);  \
-        case 2: return hw ? FN<Tile, 2, true>(stream, P, S, A, __VA_ARGS__) : FN<Tile, 2, false>(stream, P, S, A, __VA_ARGS__);  \
-        default: return hw ? FN<Tile, 0, true>(stream, P, S, A, __VA_ARGS__) : FN<Tile, 0, false>(stream, P, S, A, __VA_ARGS__); \
-        }                                                                                                                     \
-    } while (0)
-
 // dry: only check that the kernel can be configured for this shape (LDS attribute), queue nothing
 template <typename R> inline int mfma_launch_corr_init(hipStream_t stream, const DevParams& P, const State<R>& S, const R* dimg, bool dry = false)
 {
     using Tile = typename TileOf<R>::type;
     const MfmaArgsT<R> A = mfma_args<R>(P, S, dimg);
-    HSCMP_MFMA_DISPATCH(mfma_launch_corr_init_t, dry);
+    return dispatch_chunks<true>(A.S4, A.has_w != 0, [&](auto s4c, auto hw) {
+        return mfma_launch_corr_init_t<Tile, decltype(s4c)::value, decltype(hw)::value>(stream, P, S, A, dry);
+    });
 }
 
 // bimg, cmax: the bound loop's planes (hscmp_bound.h), or nullptr for the exact loop
@@ -1888,7 +1766,9 @@ inline int mfma_launch_iterate(hipStream_t stream, const DevParams& P, const Sta
     MfmaArgsT<R> A = mfma_args<R>(P, S, dimg);
     A.bimg = bimg;
     A.cmax = cmax;
-    HSCMP_MFMA_DISPATCH(mfma_launch_iterate_t, group, lds_pad, dry);
+    return dispatch_chunks<true>(A.S4, A.has_w != 0, [&](auto s4c, auto hw) {
+        return mfma_launch_iterate_t<Tile, decltype(s4c)::value, decltype(hw)::value>(stream, P, S, A, group, lds_pad, dry);
+    });
 }
 
 }  // namespace hscmp

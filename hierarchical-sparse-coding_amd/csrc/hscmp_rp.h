@@ -843,13 +843,8 @@ static int rp_mfma_launch_t(hipStream_t stream, const DevParams& P0, const State
     using Pol = RpMfma<S4C, HAS_W>;
     DevParams P = P0;
     set_segments(P, Pol::kMaxSegments);
-    const size_t lds = Pol::total_lds_bytes(A);
-    if (lds > (size_t)160 * 1024) return -1;
     auto kern = S.geom ? iterate_rp_kernel<float, Pol, true> : iterate_rp_kernel<float, Pol, false>;     // (ragged batch)
-    if (set_dyn_lds((const void*)kern, lds) != hipSuccess) return -1;
-    if (dry) return 0;
-    hipLaunchKernelGGL(kern, dim3(P.B), dim3(kRpThreads), lds, stream, P, S, A);
-    return 0;
+    return launch_tile_kernel(kern, dim3(P.B), dim3(kRpThreads), Pol::total_lds_bytes(A), kLdsDevice, 0, dry, stream, P, S, A);
 }
 
 // 0: launched (or, dry, could be); -1: this shape has no round-parallel form
@@ -857,13 +852,9 @@ inline int rp_mfma_launch(hipStream_t stream, const DevParams& P, const State<fl
 {
     if (!rp_params_ok(P, 512) || P.F != 1 || P.T < 3 * P.W - 2) return -1;
     const MfmaArgs A = mfma_args<float>(P, S, dimg);
-    const bool hw = A.has_w != 0;
-    switch (A.S4) {
-    case 8: return hw ? rp_mfma_launch_t<8, true>(stream, P, S, A, dry) : rp_mfma_launch_t<8, false>(stream, P, S, A, dry);
-    case 4: return hw ? rp_mfma_launch_t<4, true>(stream, P, S, A, dry) : rp_mfma_launch_t<4, false>(stream, P, S, A, dry);
-    case 2: return hw ? rp_mfma_launch_t<2, true>(stream, P, S, A, dry) : rp_mfma_launch_t<2, false>(stream, P, S, A, dry);
-    default: return -1;
-    }
+    return dispatch_chunks<false>(A.S4, A.has_w != 0, [&](auto s4c, auto hw) {
+        return rp_mfma_launch_t<decltype(s4c)::value, decltype(hw)::value>(stream, P, S, A, dry);
+    });
 }
 
 }  // namespace hscmp

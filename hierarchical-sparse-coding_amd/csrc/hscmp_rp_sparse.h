@@ -710,13 +710,7 @@ static int rp_sparse_launch(hipStream_t stream, const DevParams& P0, const State
     A.sp = sp;
     A.caps = rp_sparse_caps<R>(P, sp, ((sizeof(typename Pol::Shared) + 15) / 16) * 16);
     if (A.caps.teams < 2) return -1;
-    const size_t lds = Pol::total_lds_bytes(P, A);
-    if (lds > (size_t)158 * 1024) return -1;
-    auto kern = iterate_rp_kernel<R, Pol>;
-    if (set_dyn_lds((const void*)kern, lds) != hipSuccess) return -1;
-    if (dry) return 0;
-    hipLaunchKernelGGL(kern, dim3(P.B), dim3(kRpThreads), lds, stream, P, S, A);
-    return 0;
+    return launch_tile_kernel(iterate_rp_kernel<R, Pol>, dim3(P.B), dim3(kRpThreads), Pol::total_lds_bytes(P, A), kLdsLoop, 0, dry, stream, P, S, A);
 }
 
 }  // namespace hscmp

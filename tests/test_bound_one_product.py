@@ -1,4 +1,4 @@
-"""The one-product bound tile (csrc/hscmp_mfma.h bound_tile with NP = 1, derived in csrc/hscmp_bound.h), restated in numpy.
+"""The one-product bound tile (csrc/hscmp_mfma.h bound_tile, derived in csrc/hscmp_bound.h), restated in numpy.
 
 The tile rounds every float32 sample and dictionary entry to bf16 once (bf16_rn_bits), sums the products xh * dh, and
 adds kBoundEps1 * ||xh_win|| * ||d_k|| as slack.  Here the products are summed in float64 (the matrix core's own error

@@ -1,5 +1,4 @@
-"""The bound pass of the initial correlation with one bf16 product per tap (the default) and with three
-(HSCMP_BOUND_PRODUCTS=3): csrc/hscmp_bound.h, DESIGN.md section 11.
+"""The bound pass of the initial correlation, one bf16 product per tap: csrc/hscmp_bound.h, DESIGN.md section 11.
 
 1. Validity: the bound pass alone (HSCMP_INIT_ONLY=1) against the exact pass alone (HSCMP_EXACT_INIT=1): ub[t] >= score[t]
    at every bound position, exact positions equal bit for bit.  Seven input families, two of them built to line the
@@ -96,9 +95,9 @@ def _weights(K, shape, weights):
     return (0.5 + np.random.RandomState(shape).random_sample(K)).astype(np.float32) if weights else None
 
 
-def _init_state(eng, x, exact, products=None, L0=8):
+def _init_state(eng, x, exact, L0=8):
     from hsc_amd import _native
-    with _env(HSCMP_INIT_ONLY='1', HSCMP_EXACT_INIT='1' if exact else None, HSCMP_BOUND_PRODUCTS=products):
+    with _env(HSCMP_INIT_ONLY='1', HSCMP_EXACT_INIT='1' if exact else None):
         eng.encode_batch(x[:, :, None], _native.make_params(nbNonzeroCoefs=L0, eps=1e-30, maxEvents=4 * L0))
     v = eng.device_view()
     B, T = x.shape
@@ -107,10 +106,10 @@ def _init_state(eng, x, exact, products=None, L0=8):
     return bc, bk, eng.last_variant()
 
 
-def _encode_all(eng, x, params, exact, products=None, quad=None, rounds=None, scramble=None):
+def _encode_all(eng, x, params, exact, quad=None, rounds=None, scramble=None):
     """One whole encode (or one resumed in rounds, the caller's buffer overwritten in between) and everything it leaves."""
     from hsc_amd import _native
-    with _env(HSCMP_EXACT_INIT='1' if exact else None, HSCMP_BOUND_PRODUCTS=products, HSCMP_MFMA_QUAD=quad, HSCMP_INIT_ONLY=None):
+    with _env(HSCMP_EXACT_INIT='1' if exact else None, HSCMP_MFMA_QUAD=quad, HSCMP_INIT_ONLY=None):
         if rounds is None:
             eng.encode_batch(x[:, :, None], params)
         else:
@@ -150,14 +149,13 @@ def _check_valid(ub, uk, ex, ek, label=None):
 
 FAMILIES = ['planted', 'noise', 'magnitudes', 'zero_const', 'repeated', 'adversarial', 'tight']
 SHAPES = [(2, 4500, 40, 64), (2, 4500, 33, 31), (2, 3000, 20, 16)]     # SB = 4, 2, 1; K not a multiple of 32; T across a chunk and its halo
-PRODUCTS = [None, '3']
+PRODUCTS = [None]       # one product per tap is the only pass there is; the parameter stays, and with it the ids of the cases
 
 _exact_cache = {}
 
 
 def _init_case(kind, shape, weights):
-    """The inputs of a validity case and its exact init state, computed once and shared by the product counts; nothing
-    changes them afterwards."""
+    """The inputs of a validity case and its exact init state, computed once; nothing changes them afterwards."""
     B, T, K, W = SHAPES[shape]
     key = (kind, shape, weights)
     if key not in _exact_cache:
@@ -173,7 +171,7 @@ def _init_case(kind, shape, weights):
 @pytest.mark.parametrize('weights', [False, True])
 def test_bound_is_valid(kind, shape, weights, products):
     x, D, w, (ex, ek, var_e) = _init_case(kind, shape, weights)
-    ub, uk, var_b = _init_state(_engine(D, w), x, False, products)
+    ub, uk, var_b = _init_state(_engine(D, w), x, False)
     assert var_b == 'bound_init' and var_e == 'mfma_init'
     bound = _check_valid(ub, uk, ex, ek, '%s W=%d weights=%d products=%s' % (kind, SHAPES[shape][3], weights, products or '1'))
     if kind not in ('zero_const',):
@@ -184,8 +182,8 @@ def test_bound_is_valid(kind, shape, weights, products):
 @pytest.mark.parametrize('shape', range(len(SHAPES)))
 @pytest.mark.parametrize('weights', [False, True])
 def test_encode_identity(kind, shape, weights):
-    """Both product counts against one exact reference, all three on one engine: the slot arrays are compared whole, and
-    what lies behind a signal's last slot is whatever the engine's buffer held before."""
+    """The bound pass against the exact reference, both on one engine: the slot arrays are compared whole, and what lies
+    behind a signal's last slot is whatever the engine's buffer held before."""
     from hsc_amd import _native
     B, T, K, W = SHAPES[shape]
     x, D = _family(kind, B, T, K, W, 31 + shape)
@@ -193,10 +191,9 @@ def test_encode_identity(kind, shape, weights):
     params = _native.make_params(nbNonzeroCoefs=40, eps=1e-30, maxEvents=4096)
     ref = _encode_all(eng, x, params, True)
     assert '_bound' not in ref['variant']
-    for products in PRODUCTS:
-        a = _encode_all(eng, x, params, False, products)
-        assert a['variant'].startswith('mfma_init+mfma_loop_f32_bound'), a['variant']
-        _same(a, ref)
+    a = _encode_all(eng, x, params, False)
+    assert a['variant'].startswith('mfma_init+mfma_loop_f32_bound'), a['variant']
+    _same(a, ref)
 
 
 # ---- near ties: more winning bounds in front of the exact winner than a RefineList holds ------------------------------
@@ -232,7 +229,6 @@ def test_near_tie_identity(quad):
     params = _native.make_params(nbNonzeroCoefs=30, eps=1e-30, maxEvents=1024)
     ref = _encode_all(eng, x, params, True, quad=quad)
     _same(_encode_all(eng, x, params, False, quad=quad), ref)
-    _same(_encode_all(eng, x, params, False, products='3', quad=quad), ref)
     rparams = _native.make_params(nbNonzeroCoefs=30, eps=1e-30, maxEvents=1024, maxRounds=5)
     _same(_encode_all(eng, x, rparams, False, quad=quad, rounds=5, scramble=np.float32(123.0)), ref)
 
@@ -265,7 +261,7 @@ def test_out_of_model_chunks(products):
     x[1, 4100] = 1e-30
     x[2, 2500] = np.nan
     eng = _engine(D, None)
-    ub, uk, _ = _init_state(eng, x, False, products)
+    ub, uk, _ = _init_state(eng, x, False)
     ex, ek, _ = _init_state(eng, x, True)
     assert np.all(uk[0, :2048] >= 0) and np.all(uk[0, 2048:] == -1)
     assert np.all(uk[1, 2048:] >= 0) and np.all(uk[1, :2048] == -1)          # (sample 4100 is in the halo of chunk 1 too)
@@ -274,7 +270,7 @@ def test_out_of_model_chunks(products):
     assert np.array_equal(ub[same].view(np.int32), ex[same].view(np.int32)) and np.array_equal(uk[same], ek[same])
     assert np.all(ub[~same] >= ex[~same])
     params = _native.make_params(nbNonzeroCoefs=30, eps=1e-30, maxEvents=4096)
-    _same(_encode_all(eng, x, params, False, products), _encode_all(eng, x, params, True))
+    _same(_encode_all(eng, x, params, False), _encode_all(eng, x, params, True))
 
 
 @pytest.mark.parametrize('products', PRODUCTS)
@@ -285,11 +281,11 @@ def test_every_chunk_or_none_out_of_model(every, products):
     if every:
         x[:, 1000::2048] = 1e-30
     eng = _engine(D, None)
-    ub, uk, _ = _init_state(eng, x, False, products)
+    ub, uk, _ = _init_state(eng, x, False)
     ex, ek, _ = _init_state(eng, x, True)
     if every:
         assert np.array_equal(ub.view(np.int32), ex.view(np.int32)) and np.array_equal(uk, ek)
     else:
         assert np.all(uk == -1) and np.all(ub >= ex)
     params = _native.make_params(nbNonzeroCoefs=30, eps=1e-30, maxEvents=4096)
-    _same(_encode_all(eng, x, params, False, products), _encode_all(eng, x, params, True))
+    _same(_encode_all(eng, x, params, False), _encode_all(eng, x, params, True))

@@ -69,6 +69,15 @@ ROWS = {
                            'generic_init+locomp_loop_f32'),
     'locomp_f64': (lambda: _dense_f1(F64), 1, {}, dict(toleranceSnr=15.0, nbBlocks=3), 'generic_init+locomp_loop_f64'),
     'locomp_level_sparse': (lambda: _level(), 1, {}, dict(toleranceSnr=25.0, nbBlocks=4), 'dictlist_init+locomp_dictlist_loop_f64'),
+    # One encode on each side of each dictionary-image limit of mfma_supported (64 KiB float32, 128 KiB float64): the last shape
+    # whose image fits, and one atom more (a ninth / seventeenth group).  The variants are those the commit before the shared
+    # launch helper reported for these rows.
+    'f32_image_at_limit_w64': (lambda: _dense_f1(F32, K=256, W=64, T=512), 0, {}, dict(nbNonzeroCoefs=10), 'mfma_init+mfma_loop_f32_bound'),
+    'f32_image_past_limit_w64': (lambda: _dense_f1(F32, K=257, W=64, T=512), 0, {}, dict(nbNonzeroCoefs=10), 'generic_init+generic_loop_f32'),
+    'f32_image_at_limit_w32': (lambda: _dense_f1(F32, K=512, W=32, T=512), 0, {}, dict(nbNonzeroCoefs=10), 'mfma_init+mfma_loop_f32_bound'),
+    'f32_image_past_limit_w32': (lambda: _dense_f1(F32, K=513, W=32, T=512), 0, {}, dict(nbNonzeroCoefs=10), 'generic_init+generic_loop_f32'),
+    'f64_image_at_limit_w64': (lambda: _dense_f1(F64, K=256, W=64, T=512), 0, {}, dict(nbNonzeroCoefs=10), 'mfma_init+mfma_loop_f64'),
+    'f64_image_past_limit_w64': (lambda: _dense_f1(F64, K=257, W=64, T=512), 0, {}, dict(nbNonzeroCoefs=10), 'generic_init+generic_loop_f64'),
 }
 
 

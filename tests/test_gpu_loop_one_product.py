@@ -1,4 +1,4 @@
-"""The four-signal loop's tile with one bf16 product per tap (MfmaRecorr with BOUND, bound_tile<SB, HAS_W, 1>; csrc/hscmp_bound.h,
+"""The four-signal loop's tile with one bf16 product per tap (MfmaRecorr with BOUND, bound_tile<SB, HAS_W>; csrc/hscmp_bound.h,
 DESIGN.md section 11): a bound written by the LOOP whose slack is nearly used up.
 
 The `tight` dictionary of tests/test_gpu_bound_products.py (every magnitude just under a bf16 rounding midpoint, m = 128: the
