@@ -138,9 +138,8 @@ struct Dictionary {
     DevBuf D;
     DevBuf w;                 // empty when no weights
     DevBuf Dfrag;             // MFMA fragment-ordered copy (F == 1)
-    DevBuf Bimg;              // bf16 hi / lo (/ rem) planes of the bound passes (f32, F == 1, dictionary inside its model: hscmp_bound.h)
+    DevBuf Bimg;              // bf16 image of the bound passes (f32, F == 1, dictionary inside its model: hscmp_bound.h)
     float bound_cmax = 0.0f;            // >= max_k ||d_k|| |w_k|
-    bool bound_loop_image = false;      // Bimg also holds the rem plane: hi, lo, rem rebuild every element (the bound loop's image)
     DevBuf Dt;                // [W][F][K] transposed copy for the sparsity-aware kernels (F > 1)
     DevBuf Dc;                // [K][F][W] chain-ordered copy for the dense chains (F > 1)
     DevBuf nzptr, nzwf, nzval;          // CSR of the dictionary's non-zeros per atom, chain order (sparse level dictionaries)
@@ -421,15 +420,12 @@ extern "C" int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W,
         if ((rc = upload(ctx, d.Dfrag, frag.data(), frag.size() * sizeof(float)))) return rc;
         // the bound pass of the initial correlation (hscmp_bound.h): bf16 images no larger than the float32 one, and a
         // dictionary and weights inside the error model; otherwise every encode runs the exact initial correlation
-        // (the third plane, rem, is for the four-signal loop's own bound tile: only if it rebuilds every element exactly)
         std::vector<unsigned short> bimg;
         float cmax = 0.0f;
-        bool rem_exact = false;
         if ((size_t)2 * mfma_groups(K) * bound_steps(W) * 1024 <= TileF32::kMaxImageBytes &&
-            bound_build_dict_image((const float*)D, (const float*)weights, K, W, bimg, cmax, rem_exact)) {
+            bound_build_dict_image((const float*)D, (const float*)weights, K, W, bimg, cmax)) {
             if ((rc = upload(ctx, d.Bimg, bimg.data(), bimg.size() * sizeof(unsigned short)))) return rc;
             d.bound_cmax = cmax;
-            d.bound_loop_image = rem_exact;
         }
     } else if (dtype == HSCMP_F64 && mfma_supported<double>(K, W, F)) {
         std::vector<double> frag;
@@ -530,6 +526,10 @@ static int ensure_workspace_g(hscmp_ctx* ctx, const DevParams& P, bool need_x, s
         ctx->listed_rows = 0;                   // (a fresh buffer knows nothing of the previous batch)
         const hipError_t e = b.buf.replace(b.bytes);
         if (e != hipSuccess) return alloc_failed(ctx, b.bytes, e);
+        // the event and slot lists are fetched whole (hscmp_fetch_events, hscmp_fetch_slots): what lies behind a signal's last entry
+        // is zero, not whatever the allocation held before
+        for (DevBuf* l : {&w.ev_t, &w.ev_k, &w.ev_c, &w.slot_t, &w.slot_k, &w.slot_a})
+            if (l == &b.buf) HIP_TRY(ctx, hipMemsetAsync(b.buf.p, 0, b.bytes, ctx->stream));
     }
     return HSCMP_OK;
 }
@@ -653,9 +653,9 @@ template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const Knobs&
             if (!P.blocked && !P.select_only && ctx->dict.Bimg.p && !kn.exact_init &&
                 bound_launch_corr_init(ctx->stream, P, S, dimg, ctx->dict.Bimg.as<unsigned short>(), ctx->dict.bound_cmax, true) == 0)
                 plan.init = EncodePlan::kInitBound;
-            // ... and the four-signal loop re-correlates as upper bounds too, on the bf16 planes (HSCMP_EXACT_RECORR=1: the
+            // ... and the four-signal loop re-correlates as upper bounds too, on the bf16 matrix cores (HSCMP_EXACT_RECORR=1: the
             // exact re-correlation behind the bound pass; HSCMP_EXACT_INIT=1 keeps both exact)
-            if (plan.init == EncodePlan::kInitBound && plan.group == 4 && ctx->dict.bound_loop_image && !kn.exact_recorr &&
+            if (plan.init == EncodePlan::kInitBound && plan.group == 4 && !kn.exact_recorr &&
                 mfma_launch_iterate<R>(ctx->stream, P, S, dimg, 4, kn.lds_pad, true, ctx->dict.Bimg.as<unsigned short>(), ctx->dict.bound_cmax) == 0)
                 plan.bound_loop = true;
             plan.rp = rp_mfma && rp_mfma_launch(ctx->stream, P, S, dimg, true) == 0;
@@ -1031,6 +1031,7 @@ extern "C" int hscmp_grow_events(hscmp_ctx* ctx, int new_max_events)
     size_t failed_bytes = 0;
     for (int i = 0; i < 8 && e == hipSuccess; ++i)
         if ((i < 6 || !bufs[i]->holds(bytes[i])) && (e = fresh[i].replace(bytes[i])) != hipSuccess) failed_bytes = bytes[i];
+    for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipMemset(fresh[i].p, 0, bytes[i]);      // (the new tail of every list: see ensure_workspace_g)
     for (int i = 0; i < 6 && e == hipSuccess; ++i)
         e = hipMemcpy2D(fresh[i].p, nc * elem[i], bufs[i]->p, oc * elem[i], oc * elem[i], B, hipMemcpyDeviceToDevice);
     std::vector<int> stats(B * ST_COUNT);

@@ -53,15 +53,15 @@
 // The four-signal loop (MfmaRecorr with BOUND) re-correlates the rows around an applied atom with the same tile
 // (bound_tile<SB, HAS_W>, hscmp_mfma.h) over its reflect-padded window: the derivation above holds unchanged whenever
 // every sample the tile reads is inside the model, and a tile whose window holds one outside it (a wave-wide vote, every
-// atom) runs the exact float32 tile on the planes (planes_tile_score).  Split, epilogue and constants have one definition.
+// atom) runs the exact float32 tile on the loop's float32 image (mfma_tile_score_small).  Split, epilogue and constants have one definition.
 // The assumptions of the derivation, one by one, for the loop's caller:
-//   * n <= 64 products per output, W <= 64 taps: the tile runs SB <= 4 k-steps of 16 taps; past W the planes hold zeros, whose
+//   * n <= 64 products per output, W <= 64 taps: the tile runs SB <= 4 k-steps of 16 taps; past W the image holds zeros, whose
 //     products are exact zeros, and the window norm over 16 SB >= W samples is only larger than the one the derivation needs.
 //   * xh = rn(x) of the very samples the pinned chain reads: window_split rounds the float32 value it writes to the window
 //     (the reflected copy near a signal end included, one rounding, bf16_rn_bits), and the refine reads that window again through
 //     edge_window_value -- the invariant that makes the refined score the row's score (MfmaRecorr::refine) whatever the tile.
-//   * dh = rn(d) of the float32 tap the chain uses: plane 0 is rn(d), and the exact chains rebuild d = (hi + lo) + rem bit for
-//     bit (bf16_rem below), so tile and chain speak of the same d.
+//   * dh = rn(d) of the float32 tap the chain uses: Bimg is rn(d) of the dictionary the float32 image holds, element by
+//     element (bound_build_dict_image, mfma_build_dict_image), so tile and chain speak of the same d.
 //   * every product normal, no sample outside [2^-60, 2^60] or not finite: the vote in front of the tile, over every sample
 //     the tile reads (taps past W included); dictionary and weights were checked on the host (bound_build_dict_image).
 //   * xh = 0 only where x = 0: by the same vote, so the ss == 0 return is an exact 0 and the rule "sc == 0 -> hint 0" stands.
@@ -79,50 +79,13 @@ namespace hscmp {
 // k-steps of 16 taps for the filter width (the bound pass is built for SB = 1, 2, 4: the float32 chunk counts 2, 4, 8)
 inline int bound_steps(int W) { return (W + 15) / 16; }
 
-// The third plane (the four-signal loop): rem = (v - hi) - lo, so that every float32 tap the exact
-// chains need is rebuilt from the bf16 image as (hi + lo) + rem, and the loop keeps no float32 image at all (three bf16
-// planes are 96 KB at K = 256, W = 64; the float32 image and two bf16 planes would not fit a CU's 160 KB beside four
-// signals).  Why the rebuild is exact for v inside the model (|v| in [2^-30, 2^30], or 0): let e be the exponent of v,
-// so v is a multiple of 2^(e-23).  hi = rn(v) has 8 significant bits and is a multiple of 2^(e-7) (or of 2^(e-6) after
-// a carry), so r = v - hi is a multiple of 2^(e-23) with |r| <= 2^(e-8): at most 16 significant bits, exact in float32.
-// lo = rn(r) is a multiple of 2^(e-23) too (rounding r to 8 bits never goes below r's own last bit), so
-// rem = r - lo is exact, a multiple of 2^(e-23) with |rem| <= 2^-8 |r| <= 2^(e-16): at most 8 significant bits, a
-// bf16 (its exponent, >= -30 - 23, is far inside bf16's normal range).  hi + lo = v - rem is a multiple of 2^(e-23) of
-// magnitude at most 2^(e+1) (it passes |v| only if hi rounded up to 2^(e+1), and then lo <= 0): exact in float32, and
-// (hi + lo) + rem = v exactly.  The argument is what makes the plane possible;
-// what the engine relies on is the check below, element by element (tests/test_bound_planes.py runs it over every
-// float32 of the model range).
-__host__ __device__ inline bool bf16_rem(float v, unsigned short hi, unsigned short lo, unsigned short& rem)
-{
-    const unsigned hb = (unsigned)hi << 16, lb = (unsigned)lo << 16;
-    float hf, lf;
-    memcpy(&hf, &hb, 4);
-    memcpy(&lf, &lb, 4);
-    const float rf = (v - hf) - lf;
-    unsigned rb;
-    memcpy(&rb, &rf, 4);
-    rem = (unsigned short)(rb >> 16);
-    const unsigned qb = (unsigned)rem << 16;
-    float q;
-    memcpy(&q, &qb, 4);
-    const float back = (hf + lf) + q;                           // the rebuild of the exact chains (bf16_tap)
-    unsigned vb, bb;
-    memcpy(&vb, &v, 4);
-    memcpy(&bb, &back, 4);
-    return (rb & 0xffffu) == 0u && bb == vb;
-}
-
-// host: the bf16 planes Bimg[plane][g][s][lane][8] (plane 0 = hi, 1 = lo, 2 = rem): element j of lane l in (group g,
+// host: the bf16 image Bimg[g][s][lane][8], every entry rounded to nearest even: element j of lane l in (group g,
 // k-step s) is D[32g + (l&31)][16s + 8(l>>5) + j] -- the A-operand map of v_mfma_f32_32x32x16_bf16; zero padded.  Also
 // cmax >= max_k ||d_k|| |w_k| (rounded up).  Returns false when the dictionary or the weights lie outside the model.
-// rem_exact: every element is rebuilt bitwise by (hi + lo) + rem (else the loop keeps its float32 image).
-inline bool bound_build_dict_image(const float* D, const float* wts, int K, int W, std::vector<unsigned short>& out, float& cmax,
-                                   bool& rem_exact)
+inline bool bound_build_dict_image(const float* D, const float* wts, int K, int W, std::vector<unsigned short>& out, float& cmax)
 {
     const int G = mfma_groups(K), SB = bound_steps(W);
-    const size_t per = (size_t)G * SB * 64 * 8;
-    out.assign(3 * per, 0);
-    rem_exact = true;
+    out.assign((size_t)G * SB * 64 * 8, 0);
     double cm = 0.0;
     auto in_model = [](double a) { return std::isfinite(a) && (a == 0.0 || (std::fabs(a) >= kBoundDMin && std::fabs(a) <= kBoundDMax)); };
     for (int k = 0; k < K; ++k) {
@@ -143,13 +106,9 @@ inline bool bound_build_dict_image(const float* D, const float* wts, int K, int 
                     const int k = 32 * g + (lane & 31), w = 16 * s + 8 * (lane >> 5) + j;
                     if (k >= K || w >= W) continue;
                     const float v = D[(size_t)k * W + w];
-                    unsigned short hi, lo, rem;
+                    unsigned short hi, lo;
                     bf16_split(v, hi, lo);
-                    rem_exact = bf16_rem(v, hi, lo, rem) && rem_exact;
-                    const size_t i = (((size_t)g * SB + s) * 64 + lane) * 8 + j;
-                    out[i] = hi;
-                    out[per + i] = lo;
-                    out[2 * per + i] = rem;
+                    out[(((size_t)g * SB + s) * 64 + lane) * 8 + j] = hi;
                 }
     cm *= 1.0 + 0x1p-30;                                        // (the double sum and sqrt: relative error < 2^-45)
     float f = (float)cm;
@@ -162,7 +121,7 @@ inline bool bound_build_dict_image(const float* D, const float* wts, int K, int 
 // ------------------------------------------------------------------------------------------------
 // The bound pass: the persistent grid of corr_init_mfma_kernel over (signal, 2048-position chunk) items, the tile of
 // bound_tile<SB, HAS_W>.
-// LDS: [bf16 image (plane 0 of Bimg)][weights 32*G][chunk: every sample rounded to bf16, or the float32 chunk of a chunk
+// LDS: [bf16 image (Bimg)][weights 32*G][chunk: every sample rounded to bf16, or the float32 chunk of a chunk
 // outside the model].
 // A chunk outside the model (see the header) runs mfma_tile_score on the float32 image in global
 // memory (L2-resident): the exact score and group hint, bit for bit what corr_init_mfma_kernel writes.

@@ -46,7 +46,7 @@ template <typename R> struct MfmaArgsT {
     int G;               // atom groups (32 atoms for float32, 16 for float64)
     int S4;              // chunks of 8 taps (one 16-byte A-operand word per lane)
     int has_w;
-    const unsigned short* bimg = nullptr;   // the bound loop (MfmaRecorr, BOUND): bf16 planes hi, lo, rem (hscmp_bound.h)
+    const unsigned short* bimg = nullptr;   // the bound loop (MfmaRecorr, BOUND): the bf16 image of the bound tile (hscmp_bound.h)
     float cmax = 0.0f;                      // ... and its cmax >= max_k ||d_k|| |w_k|
 };
 using MfmaArgs = MfmaArgsT<float>;
@@ -329,7 +329,7 @@ __device__ __forceinline__ float bf16_lo_f(unsigned w) { return __uint_as_float(
 __device__ __forceinline__ float bf16_hi_f(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
 
 // One 32-position tile against all atom groups: the bound of every position (lanes 0..31: position = lane).
-//   bimg: LDS, the bf16 image of the dictionary (plane 0 of Bimg);  xh: the window's samples rounded to bf16 in LDS, 4-byte
+//   bimg: LDS, the bf16 image of the dictionary (Bimg);  xh: the window's samples rounded to bf16 in LDS, 4-byte
 //   aligned, index 0 = the first tap of the tile's first position.  B operand of k-step s, lane (r, h): samples
 //   r + 16s + 8h + j, j = 0..7 -- 8 consecutive bf16 at an odd or even start: five aligned dwords and v_alignbit.
 // One MFMA per k-step; the window norm comes from the rounded samples (||x|| <= ||xh|| / (1 - 2^-8), inside kBoundEps1).
@@ -407,59 +407,19 @@ __device__ __forceinline__ bool bound_sample_out(float x)
     return !(a <= kBoundXMax) || (a != 0.0f && a < kBoundXMin);      // (NaN fails the first test)
 }
 
-// ---- the bf16 planes as the float32 dictionary ---------------------------------------------------------------
-// The bound loop keeps no float32 image: its exact chains rebuild every tap as (hi + lo) + rem from the three planes
-// Bimg[plane][g][s][lane][8] (hscmp_bound.h: bitwise the float32 value, checked for every element on the host).
-// Element of D[k][w] in a plane: lane (k & 31) + 32 ((w >> 3) & 1), k-step w >> 4, element w & 7.
-__device__ __forceinline__ int bf16_plane_index(int k, int w, int SB)
+// The exact float32 tile of the bound loop, for a window outside the model of the bound tile: mfma_tile_score's products
+// in mfma_tile_score's order (chunk s4 of group g: the lane's word of the float32 image against the window's taps
+// 8 s4 + 2 i + h), so score and group hint are bit for bit the float32 tile's.  One accumulator, no operand prefetch,
+// one group at a time: the rare path, kept small in registers (mfma_tile_score_lean's two accumulators and operands in
+// flight cost the kernel around it spills).
+template <int S4C, bool HAS_W>
+__device__ __forceinline__ float mfma_tile_score_small(const float* __restrict__ dimg, const float* __restrict__ win,
+                                                       const float* __restrict__ wts, int G, int lane, int& grp)
 {
-    return (((k >> 5) * SB + (w >> 4)) * 64 + (k & 31) + 32 * ((w >> 3) & 1)) * 8 + (w & 7);
-}
-__device__ __forceinline__ float bf16_tap(unsigned hi, unsigned lo, unsigned rem)      // (the bf16 bits in the low half)
-{
-    return (__uint_as_float(hi << 16) + __uint_as_float(lo << 16)) + __uint_as_float(rem << 16);
-}
-// the taps 2i + h of a dword pair of elements (2i, 2i + 1) of the three planes
-__device__ __forceinline__ float bf16_tap_of(unsigned h, unsigned l, unsigned r, int odd)
-{
-    return odd ? (bf16_hi_f(h) + bf16_hi_f(l)) + bf16_hi_f(r) : (bf16_lo_f(h) + bf16_lo_f(l)) + bf16_lo_f(r);
-}
-
-// resolve_chain on the planes: D[k][.] . rwin[.] as the pinned sequential fma chain, taps ascending.  Chunk c of 8
-// taps is one 16-byte word per plane (lane (k & 31) + 32 (c & 1) of k-step c >> 1).  Bit-identical to resolve_chain.
-template <int SB>
-__device__ __forceinline__ float resolve_chain_planes(const unsigned short* __restrict__ img, int nplane, const float* __restrict__ rwin, int k)
-{
-    const u32x4* p0 = reinterpret_cast<const u32x4*>(img) + ((k >> 5) * SB) * 64 + (k & 31);
-    const u32x4* p1 = p0 + nplane / 8;
-    const u32x4* p2 = p1 + nplane / 8;
-    float acc = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 2 * SB; ++c) {
-        const int o = (c >> 1) * 64 + 32 * (c & 1);
-        const u32x4 h = p0[o], l = p1[o], r = p2[o];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            acc = fmaf(rwin[8 * c + 2 * i], (bf16_lo_f(h[i]) + bf16_lo_f(l[i])) + bf16_lo_f(r[i]), acc);
-            acc = fmaf(rwin[8 * c + 2 * i + 1], (bf16_hi_f(h[i]) + bf16_hi_f(l[i])) + bf16_hi_f(r[i]), acc);
-        }
-    }
-    return acc;
-}
-
-// The exact float32 tile on the planes (the bound loop's tile for a window outside the model): mfma_tile_score's
-// products in mfma_tile_score's order -- lane (j, h) of k-step 4c + i needs tap 8c + 2i + h, element 2i + h of the
-// word of chunk c -- so score and group hint are bit for bit the float32 tile's.  One accumulator, no operand
-// prefetch: the rare path, kept small in registers.
-template <int SB, bool HAS_W>
-__device__ __forceinline__ float planes_tile_score(const unsigned short* __restrict__ img, int nplane, const float* __restrict__ win,
-                                                   const float* __restrict__ wts, int G, int lane, int& grp)
-{
+    static_assert(S4C > 0, "compile-time chunk count only");
     const int j = lane & 31, h = lane >> 5;
     const float* wb = win + j + h;
-    const u32x4* p0 = reinterpret_cast<const u32x4*>(img) + j;
-    const u32x4* p1 = p0 + nplane / 8;
-    const u32x4* p2 = p1 + nplane / 8;
+    const f32x4* dv = reinterpret_cast<const f32x4*>(dimg) + lane;
     float bs = 0.0f;
     int bg = 0;
     auto katom = [&](int kbase, int r) { return kbase + (r & 3) + 8 * (r >> 2); };
@@ -469,12 +429,11 @@ __device__ __forceinline__ float planes_tile_score(const unsigned short* __restr
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
 #pragma unroll
-        for (int c = 0; c < 2 * SB; ++c) {
-            const int o = (g * SB + (c >> 1)) * 64 + 32 * (c & 1);
-            const u32x4 wh = p0[o], wl = p1[o], wr = p2[o];
+        for (int s4 = 0; s4 < S4C; ++s4) {
+            const f32x4 a = dv[(g * S4C + s4) * 64];
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bf16_tap_of(wh[i], wl[i], wr[i], h), wb[8 * c + 2 * i], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], wb[8 * s4 + 2 * i], acc, 0, 0, 0);
         }
         const int kbase = 32 * g + 4 * h;
         const float before = bs;
@@ -861,7 +820,7 @@ template <typename R> inline bool mfma_supported(int K, int W, int F)
 // rules) the matrix pipe has three other signals' tiles to run.  The waves of a signal meet at SoftSync barriers.
 // BOUND (four signals, float32, compile-time chunk count): the re-correlation writes upper bounds on the bf16 matrix cores
 // (bound_tile, as the bound pass of the initial correlation) and the selection refines the rows that win; the workgroup
-// holds the dictionary as the three bf16 planes of hscmp_bound.h instead of the float32 image.
+// holds the bf16 image of hscmp_bound.h in front of the float32 image.
 template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> struct MfmaRecorr : NoPolicyHooks<typename Tile::R> {
     static constexpr int kMaxSegments = kMfmaMaxSeg;
     static constexpr bool kFused = true;
@@ -892,10 +851,10 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     struct Layout {
         R* dimg; R* wts; R* win; R* esq; R* sbs; unsigned* bloom;
         R* rwin; R* rwin_w; unsigned long long* edge;
-        unsigned short* bimg; unsigned short* xh;                          // (BOUND) the planes; the window rounded to bf16
+        unsigned short* bimg; unsigned short* xh;                          // (BOUND) the bf16 image; the window rounded to bf16
         int* rx;                                                           // (BOUND) the refine's exchange slots (see refine)
         int4* rc;                                                          // (BOUND) the cache of committed refines (see cache_commit)
-        int nwin, wp, nsbmax, nplane;
+        int nwin, wp, nsbmax;
     };
 
     static __host__ __device__ int window_floats(int W, int S4) { return ((2 * W - 1 + TP - 1) / TP) * TP + 8 * S4 + 32; }
@@ -904,10 +863,11 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     static __host__ __device__ int segbuf_len_p(const DevParams& P) { return (((2 * P.W - 2) >> P.seg_shift) + 2) << P.seg_shift; }
     // LDS: what the signals of a workgroup share (dictionary image, weights), then per signal the control block and
     // its windows.  GS == 1: [control][image | weights | windows ...] as one region behind the control block.
+    // BOUND: [bf16 image, the bound tile's operand][float32 image, the exact chains' and the fallback tile's][weights].
+    static __host__ __device__ size_t bound_image_lds_bytes(const Args& A) { return BOUND ? (size_t)A.G * SB * 1024 : 0; }
     static __host__ __device__ size_t image_lds_bytes(const Args& A)
     {
-        if constexpr (BOUND) return (size_t)3 * A.G * SB * 1024;                    // three bf16 planes
-        else return (size_t)A.G * A.S4 * Tile::kChunkElems * sizeof(R);
+        return bound_image_lds_bytes(A) + (size_t)A.G * A.S4 * Tile::kChunkElems * sizeof(R);
     }
     static __host__ __device__ size_t shared_lds_bytes(const Args& A)
     {
@@ -940,10 +900,10 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     {
         const int S4 = S4C > 0 ? S4C : A.S4;
         Layout L;
-        L.dimg = reinterpret_cast<R*>(GS == 1 ? lds : dyn_lds());
-        L.bimg = reinterpret_cast<unsigned short*>(L.dimg);
-        L.nplane = A.G * SB * 512;
-        L.wts = reinterpret_cast<R*>(reinterpret_cast<char*>(L.dimg) + image_lds_bytes(A));
+        char* img = GS == 1 ? lds : dyn_lds();
+        L.bimg = reinterpret_cast<unsigned short*>(img);
+        L.dimg = reinterpret_cast<R*>(img + bound_image_lds_bytes(A));
+        L.wts = reinterpret_cast<R*>(img + image_lds_bytes(A));
         L.nwin = window_floats(P.W, S4);
         L.wp = 8 * S4;
         L.nsbmax = segbuf_len_p(P);
@@ -967,10 +927,10 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     {
         if constexpr (GS > 1) {
             const int S4 = S4C > 0 ? S4C : A.S4;
-            R* dimg = reinterpret_cast<R*>(smem);
+            R* dimg = reinterpret_cast<R*>(smem + bound_image_lds_bytes(A));
             R* wts = reinterpret_cast<R*>(smem + image_lds_bytes(A));
-            if constexpr (BOUND) lds_copy16(dimg, A.bimg, (int)image_lds_bytes(A), (int)threadIdx.x, GS * kThreads);
-            else lds_copy16(dimg, A.dimg, A.G * S4 * Tile::kChunkElems * (int)sizeof(R), (int)threadIdx.x, GS * kThreads);
+            if constexpr (BOUND) lds_copy16(smem, A.bimg, (int)bound_image_lds_bytes(A), (int)threadIdx.x, GS * kThreads);
+            lds_copy16(dimg, A.dimg, A.G * S4 * Tile::kChunkElems * (int)sizeof(R), (int)threadIdx.x, GS * kThreads);
             if (HAS_W) for (int i = threadIdx.x; i < Tile::GA * A.G; i += GS * kThreads) wts[i] = i < P.K ? S.weights[i] : (R)0;
             if (ltid() == 0) {
                 Shared* sh = reinterpret_cast<Shared*>(smem + signal_lds_offset(P, A));
@@ -1018,17 +978,9 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     template <typename SH>
     static __device__ __forceinline__ void run(const DevParams&, const State<R>&, const Sig<R>&, SH&, const Args&, char*, int, int) {}
 
-    // The float32 tap D[k][w] and the pinned chain of atom k over a window: from the float32 image, or (BOUND) rebuilt
-    // from the bf16 planes as (hi + lo) + rem -- the same float32 values, so the same chains bit for bit.
-    static __device__ __forceinline__ R dtap(const Layout& L, int k, int w, int S4)
-    {
-        if constexpr (BOUND) {
-            const int i = bf16_plane_index(k, w, SB);
-            return bf16_tap(L.bimg[i], L.bimg[L.nplane + i], L.bimg[2 * L.nplane + i]);
-        } else {
-            return L.dimg[Tile::dindex(k, w, S4)];
-        }
-    }
+    // The tap D[k][w] and the pinned chain of atom k over a window, from the image in LDS (the bound loop keeps the
+    // float32 image behind its bf16 one: the chains are those of the exact loops).
+    static __device__ __forceinline__ R dtap(const Layout& L, int k, int w, int S4) { return L.dimg[Tile::dindex(k, w, S4)]; }
     // (BOUND) sample i of the re-correlation's window as the bound tile's B operand: rounded to bf16, one rounding
     static __device__ __forceinline__ void window_split(const Layout& L, int i, R v)
     {
@@ -1036,8 +988,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     }
     static __device__ __forceinline__ R dchain(const Layout& L, const R* rw, int k, int S4)
     {
-        if constexpr (BOUND) return resolve_chain_planes<SB>(L.bimg, L.nplane, rw, k);
-        else return Tile::template resolve<S4C>(L.dimg, rw, k, S4);
+        return Tile::template resolve<S4C>(L.dimg, rw, k, S4);
     }
 
     // (k, c) of position t by ONE wave (blocked selection, modeling.py:935-946): the window goes to
@@ -1097,8 +1048,7 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
     // The residual is the engine's own buffer: a caller's input that changes between resumed rounds does not matter.
     //
     // Who computes it.  The exact loops: every wave for itself, all K chains, no barrier (k_out = -1: nothing to hand on).
-    // The bound loop (its vector ALU is the full unit, and a chain over the planes is ~400 vector instructions): the
-    // signal's four waves share the K chains.  Every wave still loads the window into its own strip (no exchange in
+    // The bound loop (its vector ALU is the full unit): the signal's four waves share the K chains.  Every wave still loads the window into its own strip (no exchange in
     // front of the chains); wave q takes the atoms 64 q + lane + 256 j and reduces them to one record -- the largest
     // |c w_k| as bits, the lowest k attaining it, the c of that k; a wave or lane without atoms carries score -1, k =
     // INT_MAX, as in the one-wave reduction.  Lane 0 writes the record to the wave's slot, the waves meet at ONE barrier,
@@ -1549,14 +1499,14 @@ template <typename Tile, int S4C, bool HAS_W, int GS = 1, bool BOUND = false> st
             int grp;
             if constexpr (BOUND) {
                 // upper bounds on the bf16 matrix cores (bound_tile), unless the tile reads a sample outside the model: rows
-                // TP q .. TP q + TP-1, taps 0 .. 16 SB - 1 (past W the planes are zero, but zero times a non-finite sample is
+                // TP q .. TP q + TP-1, taps 0 .. 16 SB - 1 (past W the image is zero, but zero times a non-finite sample is
                 // not).  A wave-wide vote; the window changes with every atom.
                 bool out = false;
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
                     if (lane + 64 * u < TP - 1 + 16 * SB) out |= bound_sample_out(L.win[TP * q + lane + 64 * u]);
                 if (__builtin_amdgcn_ballot_w64(out) != 0) {
-                    sc = planes_tile_score<SB, HAS_W>(L.bimg, L.nplane, L.win + TP * q, L.wts, A.G, lane, grp);
+                    sc = mfma_tile_score_small<S4C, HAS_W>(L.dimg, L.win + TP * q, L.wts, A.G, lane, grp);
                 } else {
                     sc = bound_tile<SB, HAS_W>(reinterpret_cast<const bf16x8*>(L.bimg), L.xh + TP * q, L.wts, A.G, lane, A.cmax);
                     grp = sc == 0.0f ? 0 : -1;                  // an exact 0 is a score (hint 0, as the exact tile); else a bound
@@ -1726,7 +1676,7 @@ static int mfma_launch_iterate_g(hipStream_t stream, const DevParams& P0, const 
 
 // The loop with `group` signals per workgroup: 1, or 4 (float32 with a compile-time chunk count: one round of four overlapping
 // signals per CU instead of two rounds of two).  0: launched (or, dry, could be); -1: no such form for this shape.
-// A.bimg set (four signals only): the bound loop on the bf16 planes.
+// A.bimg set (four signals only): the bound loop.
 template <typename Tile, int S4C, bool HAS_W>
 static int mfma_launch_iterate_t(hipStream_t stream, const DevParams& P, const State<typename Tile::R>& S,
                                  const MfmaArgsT<typename Tile::R>& A, int group, int lds_pad, bool dry)
@@ -1757,7 +1707,7 @@ template <typename R> inline int mfma_launch_corr_init(hipStream_t stream, const
     });
 }
 
-// bimg, cmax: the bound loop's planes (hscmp_bound.h), or nullptr for the exact loop
+// bimg, cmax: the bound loop's bf16 image (hscmp_bound.h), or nullptr for the exact loop
 template <typename R>
 inline int mfma_launch_iterate(hipStream_t stream, const DevParams& P, const State<R>& S, const R* dimg, int group, int lds_pad, bool dry = false,
                                const unsigned short* bimg = nullptr, float cmax = 0.0f)
