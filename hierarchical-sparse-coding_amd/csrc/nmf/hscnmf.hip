@@ -10,7 +10,9 @@
 // reading A from one buffer of a ping-pong pair and writing the other.  After the W steps of an iteration
 // nmf_residual_kernel reconstructs once more (residual, per-tile max|r| and sum r^2) and nmf_decide_kernel takes
 // the reference's stop decision per signal on the device; a finished signal's workgroups return at once.
-// hscnmf_learn (the dictionary learner) adds, per iteration, the ratio, partial and update kernels of section 12.
+// hscnmf_learn (the dictionary learner) adds, per iteration, the ratio, partial and update kernels of section 12;
+// hscnmf_learn_corpus (one dictionary from many signals of different lengths) runs the same kernel bodies over a ragged
+// geometry and sums the update over the signals, section 18.
 #include "../../../include/hscnmf.h"
 #include "../common/hsc_lib.h"
 
@@ -139,29 +141,64 @@ __device__ void tile_recon(const T* __restrict__ A, int L, int K, const T* __res
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kThreads) void nmf_step_kernel(const T* __restrict__ Ain, T* __restrict__ Aout,
-                                                            const T* __restrict__ X, const T* __restrict__ D,
-                                                            size_t dstride, const int* __restrict__ done, int L, int Tn,
-                                                            int K, int W, int F, int t, int PR, int slab)
+// Where a workgroup's signal and tile lie.  Uniform: B signals of one length, the signal on blockIdx.y and the tile on
+// blockIdx.x (hscnmf_compute, hscnmf_learn).  Ragged: signals of different lengths stacked without padding
+// (hscnmf_learn_corpus), a 1-D grid with one (signal, tile) pair per workgroup and one stop flag for the corpus.
+struct Uniform {
+    int L, Tn;
+    __device__ int signal() const { return blockIdx.y; }
+    __device__ int tile() const { return blockIdx.x; }
+    __device__ int flag(int b) const { return b; }
+    __device__ int rows(int) const { return L; }
+    __device__ int samples(int) const { return Tn; }
+    __device__ size_t row0(int b) const { return (size_t)b * L; }           // first coefficient row of signal b
+    __device__ size_t sample0(int b) const { return (size_t)b * Tn; }       // first sample of signal b
+    __device__ size_t slot(int b) const { return (size_t)b * gridDim.x + blockIdx.x; }   // the workgroup's partials
+};
+
+// one signal of a corpus: its first sample and coefficient row in the stacks, its first row tile and sample tile in the
+// flat tile tables (a signal's tiles are consecutive and ascending), its length and its L = T - W + 1
+struct SignalInfo {
+    long long x0, a0, rt0, st0;
+    int T, L;
+};
+
+struct Ragged {
+    const SignalInfo* __restrict__ sig;
+    const int2* __restrict__ tiles;                                         // (signal, tile) of workgroup blockIdx.x
+    __device__ int signal() const { return tiles[blockIdx.x].x; }
+    __device__ int tile() const { return tiles[blockIdx.x].y; }
+    __device__ int flag(int) const { return 0; }
+    __device__ int rows(int b) const { return sig[b].L; }
+    __device__ int samples(int b) const { return sig[b].T; }
+    __device__ size_t row0(int b) const { return (size_t)sig[b].a0; }
+    __device__ size_t sample0(int b) const { return (size_t)sig[b].x0; }
+    __device__ size_t slot(int) const { return blockIdx.x; }
+};
+
+template <typename T, typename G>
+__device__ __forceinline__ void step_body(const G g, const T* __restrict__ Ain, T* __restrict__ Aout,
+                                          const T* __restrict__ X, const T* __restrict__ D, size_t dstride,
+                                          const int* __restrict__ done, int K, int W, int F, int t, int PR, int slab)
 {
-    const int b = blockIdx.y;
-    if (done[b]) return;
+    const int b = g.signal();
+    if (done[g.flag(b)]) return;
+    const int L = g.rows(b), Tn = g.samples(b);
     D += (size_t)b * dstride;                                        // 0: one dictionary for the batch (the coder)
     extern __shared__ __align__(16) unsigned char smem[];
     T* rec = reinterpret_cast<T*>(smem);
     T* Pl = rec + kRows * F;
-    const int s0 = blockIdx.x * kRows;
-    const T* A = Ain + (size_t)b * L * K;
+    const int s0 = g.tile() * kRows;
+    const T* A = Ain + g.row0(b) * K;
     const int nbase = s0 + t;                                        // R[s+t] for the own rows s
     tile_recon(A, L, K, D, W, F, nbase, PR, slab, rec, Pl);
     for (int e = threadIdx.x; e < kRows * F; e += kThreads) {
         const int nl = e / F, f = e - nl * F, n = nbase + nl;
-        rec[e] = n < Tn ? X[((size_t)b * Tn + n) * F + f] / fabs(rec[e]) : T(0);
+        rec[e] = n < Tn ? X[(g.sample0(b) + n) * F + f] / fabs(rec[e]) : T(0);
     }
     __syncthreads();
     const int rows = min(kRows, L - s0);
-    T* Ao = Aout + (size_t)b * L * K;
+    T* Ao = Aout + g.row0(b) * K;
     for (int e = threadIdx.x; e < rows * K; e += kThreads) {
         const int sl = e / K, k = e - sl * K;
         const T* d = D + ((size_t)k * W + t) * F;
@@ -177,25 +214,43 @@ __global__ __launch_bounds__(kThreads) void nmf_step_kernel(const T* __restrict_
 }
 
 template <typename T>
-__global__ __launch_bounds__(kThreads) void nmf_residual_kernel(const T* __restrict__ Abuf, const T* __restrict__ X,
-                                                                const T* __restrict__ D, size_t dstride,
-                                                                const int* __restrict__ done, T* __restrict__ resid,
-                                                                double* __restrict__ part, int L, int Tn, int K, int W, int F,
-                                                                int PR, int slab)
+__global__ __launch_bounds__(kThreads) void nmf_step_kernel(const T* __restrict__ Ain, T* __restrict__ Aout,
+                                                            const T* __restrict__ X, const T* __restrict__ D,
+                                                            size_t dstride, const int* __restrict__ done, int L, int Tn,
+                                                            int K, int W, int F, int t, int PR, int slab)
 {
-    const int b = blockIdx.y;
-    if (done[b]) return;
+    step_body(Uniform{L, Tn}, Ain, Aout, X, D, dstride, done, K, W, F, t, PR, slab);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void nmf_step_ragged_kernel(const T* __restrict__ Ain, T* __restrict__ Aout,
+                                                                   const T* __restrict__ X, const T* __restrict__ D,
+                                                                   const int* __restrict__ done, Ragged g, int K, int W,
+                                                                   int F, int t, int PR, int slab)
+{
+    step_body(g, Ain, Aout, X, D, (size_t)0, done, K, W, F, t, PR, slab);
+}
+
+template <typename T, typename G>
+__device__ __forceinline__ void residual_body(const G g, const T* __restrict__ Abuf, const T* __restrict__ X,
+                                              const T* __restrict__ D, size_t dstride, const int* __restrict__ done,
+                                              T* __restrict__ resid, double* __restrict__ part, int K, int W, int F,
+                                              int PR, int slab)
+{
+    const int b = g.signal();
+    if (done[g.flag(b)]) return;
+    const int L = g.rows(b), Tn = g.samples(b);
     D += (size_t)b * dstride;
     extern __shared__ __align__(16) unsigned char smem[];
     T* rec = reinterpret_cast<T*>(smem);
     T* Pl = rec + kRows * F;
-    const int n0 = blockIdx.x * kRows;
-    tile_recon(Abuf + (size_t)b * L * K, L, K, D, W, F, n0, PR, slab, rec, Pl);
+    const int n0 = g.tile() * kRows;
+    tile_recon(Abuf + g.row0(b) * K, L, K, D, W, F, n0, PR, slab, rec, Pl);
     double mx = 0.0, ss = 0.0;
     for (int e = threadIdx.x; e < kRows * F; e += kThreads) {
         const int n = n0 + e / F;
         if (n >= Tn) break;
-        const size_t o = ((size_t)b * Tn + n0) * F + e;
+        const size_t o = (g.sample0(b) + n0) * F + e;
         const T r = X[o] - rec[e];
         resid[o] = r;
         const double rd = (double)r;
@@ -214,9 +269,28 @@ __global__ __launch_bounds__(kThreads) void nmf_residual_kernel(const T* __restr
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        part[((size_t)b * gridDim.x + blockIdx.x) * 2] = red[0];
-        part[((size_t)b * gridDim.x + blockIdx.x) * 2 + 1] = red[kThreads];
+        part[g.slot(b) * 2] = red[0];
+        part[g.slot(b) * 2 + 1] = red[kThreads];
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void nmf_residual_kernel(const T* __restrict__ Abuf, const T* __restrict__ X,
+                                                                const T* __restrict__ D, size_t dstride,
+                                                                const int* __restrict__ done, T* __restrict__ resid,
+                                                                double* __restrict__ part, int L, int Tn, int K, int W, int F,
+                                                                int PR, int slab)
+{
+    residual_body(Uniform{L, Tn}, Abuf, X, D, dstride, done, resid, part, K, W, F, PR, slab);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void nmf_residual_ragged_kernel(const T* __restrict__ Abuf, const T* __restrict__ X,
+                                                                       const T* __restrict__ D, const int* __restrict__ done,
+                                                                       T* __restrict__ resid, double* __restrict__ part,
+                                                                       Ragged g, int K, int W, int F, int PR, int slab)
+{
+    residual_body(g, Abuf, X, D, (size_t)0, done, resid, part, K, W, F, PR, slab);
 }
 
 // one workgroup (64 threads) per signal: the stop rules of hsc/modeling.py:729-740, in that order
@@ -261,25 +335,43 @@ __global__ __launch_bounds__(64) void nmf_decide_kernel(const double* __restrict
 // ---- the dictionary update of the learner (hsc/modeling.py:383-395), DESIGN.md section 12 ----------------------------
 
 // R[n][f] = X[n][f] / |recon[n][f]| for the samples n0 .. n0+kRows-1 of the tile (the updated A, the old D)
+template <typename T, typename G>
+__device__ __forceinline__ void ratio_body(const G g, const T* __restrict__ Abuf, const T* __restrict__ X,
+                                           const T* __restrict__ D, size_t dstride, const int* __restrict__ done,
+                                           T* __restrict__ R, int K, int W, int F, int PR, int slab)
+{
+    const int b = g.signal();
+    if (done[g.flag(b)]) return;
+    const int L = g.rows(b), Tn = g.samples(b);
+    extern __shared__ __align__(16) unsigned char smem[];
+    T* rec = reinterpret_cast<T*>(smem);
+    T* Pl = rec + kRows * F;
+    const int n0 = g.tile() * kRows;
+    tile_recon(Abuf + g.row0(b) * K, L, K, D + (size_t)b * dstride, W, F, n0, PR, slab, rec, Pl);
+    for (int e = threadIdx.x; e < kRows * F; e += kThreads) {
+        const int n = n0 + e / F;
+        if (n >= Tn) break;
+        const size_t o = (g.sample0(b) + n0) * F + e;
+        R[o] = X[o] / fabs(rec[e]);
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(kThreads) void nmf_ratio_kernel(const T* __restrict__ Abuf, const T* __restrict__ X,
                                                              const T* __restrict__ D, size_t dstride,
                                                              const int* __restrict__ done, T* __restrict__ R, int L, int Tn,
                                                              int K, int W, int F, int PR, int slab)
 {
-    const int b = blockIdx.y;
-    if (done[b]) return;
-    extern __shared__ __align__(16) unsigned char smem[];
-    T* rec = reinterpret_cast<T*>(smem);
-    T* Pl = rec + kRows * F;
-    const int n0 = blockIdx.x * kRows;
-    tile_recon(Abuf + (size_t)b * L * K, L, K, D + (size_t)b * dstride, W, F, n0, PR, slab, rec, Pl);
-    for (int e = threadIdx.x; e < kRows * F; e += kThreads) {
-        const int n = n0 + e / F;
-        if (n >= Tn) break;
-        const size_t o = ((size_t)b * Tn + n0) * F + e;
-        R[o] = X[o] / fabs(rec[e]);
-    }
+    ratio_body(Uniform{L, Tn}, Abuf, X, D, dstride, done, R, K, W, F, PR, slab);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void nmf_ratio_ragged_kernel(const T* __restrict__ Abuf, const T* __restrict__ X,
+                                                                    const T* __restrict__ D, const int* __restrict__ done,
+                                                                    T* __restrict__ R, Ragged g, int K, int W, int F, int PR,
+                                                                    int slab)
+{
+    ratio_body(g, Abuf, X, D, (size_t)0, done, R, K, W, F, PR, slab);
 }
 
 // One RB x CB block of C[k][c] = sum_{sl < rows} A[s0+sl][k] Rl[sl*F + c] (c = t*F+f: the Hankel matrix of the R tile,
@@ -329,25 +421,26 @@ __device__ __forceinline__ void dpart_block(const double* __restrict__ A, int ro
     }
 }
 
-// Partials of one row tile (s0 .. s0+kRows-1, rows < L only): part[b][tile][k][c] = sum_s A[s][k] R[s+t][f]
-// (c = t*F+f < NW) and part[b][tile][k][NW] = sum_s A[s][k] (ascending s), for the update kernel to sum.
-template <typename T>
-__global__ __launch_bounds__(kThreads) void nmf_dpart_kernel(const T* __restrict__ Abuf, const T* __restrict__ R,
-                                                             const int* __restrict__ done, T* __restrict__ part, int L,
-                                                             int Tn, int K, int W, int F)
+// Partials of one row tile (s0 .. s0+kRows-1, rows < L only): part[slot][k][c] = sum_s A[s][k] R[s+t][f]
+// (c = t*F+f < NW) and part[slot][k][NW] = sum_s A[s][k] (ascending s), for the update kernel to sum; slot: the
+// signal's tiles in ascending order, signal after signal.
+template <typename T, typename G>
+__device__ __forceinline__ void dpart_body(const G g, const T* __restrict__ Abuf, const T* __restrict__ R,
+                                           const int* __restrict__ done, T* __restrict__ part, int K, int W, int F)
 {
     constexpr int RB = Tile<T>::RB, CB = Tile<T>::CB;
-    const int b = blockIdx.y;
-    if (done[b]) return;
+    const int b = g.signal();
+    if (done[g.flag(b)]) return;
+    const int L = g.rows(b), Tn = g.samples(b);
     extern __shared__ __align__(16) unsigned char smem[];
     T* Rl = reinterpret_cast<T*>(smem);                              // R samples s0 .. s0+kRows+W-2 (0 past T)
-    const int s0 = blockIdx.x * kRows, NW = W * F, ld = NW + 1, nr = (kRows + W - 1) * F;
-    const T* Rb = R + ((size_t)b * Tn + s0) * F;
+    const int s0 = g.tile() * kRows, NW = W * F, ld = NW + 1, nr = (kRows + W - 1) * F;
+    const T* Rb = R + (g.sample0(b) + s0) * F;
     for (int e = threadIdx.x; e < nr; e += kThreads) Rl[e] = s0 + e / F < Tn ? Rb[e] : T(0);
     __syncthreads();
     const int rows = min(kRows, L - s0);
-    const T* A = Abuf + ((size_t)b * L + s0) * K;
-    T* out = part + ((size_t)b * gridDim.x + blockIdx.x) * K * ld;
+    const T* A = Abuf + (g.row0(b) + s0) * K;
+    T* out = part + g.slot(b) * K * ld;
     for (int k = threadIdx.x; k < K; k += kThreads) {
         T acc = T(0);
         for (int sl = 0; sl < rows; ++sl) acc = acc + A[(size_t)sl * K + k];
@@ -356,6 +449,22 @@ __global__ __launch_bounds__(kThreads) void nmf_dpart_kernel(const T* __restrict
     const int nkb = (K + RB - 1) / RB, ncb = (NW + CB - 1) / CB;
     for (int it = threadIdx.x >> 6; it < nkb * ncb; it += kThreads / 64)
         dpart_block(A, rows, K, Rl, F, NW, (it % nkb) * RB, (it / nkb) * CB, out, ld);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void nmf_dpart_kernel(const T* __restrict__ Abuf, const T* __restrict__ R,
+                                                             const int* __restrict__ done, T* __restrict__ part, int L,
+                                                             int Tn, int K, int W, int F)
+{
+    dpart_body(Uniform{L, Tn}, Abuf, R, done, part, K, W, F);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void nmf_dpart_ragged_kernel(const T* __restrict__ Abuf, const T* __restrict__ R,
+                                                                    const int* __restrict__ done, T* __restrict__ part,
+                                                                    Ragged g, int K, int W, int F)
+{
+    dpart_body(g, Abuf, R, done, part, K, W, F);
 }
 
 // One workgroup per (atom k, learner b): N and den summed over the tiles in ascending order, D[k] *= N / den, then
@@ -394,6 +503,143 @@ __global__ __launch_bounds__(kThreads) void nmf_dupdate_kernel(const T* __restri
     }
     const T nrm = sqrt(red[0]);
     for (int c = threadIdx.x; c < NW; c += kThreads) d[c] = nrm > T(0) ? sum[c] / nrm : sum[c];
+}
+
+// ---- one dictionary for a corpus (hscnmf_learn_corpus), DESIGN.md section 18 -----------------------------------------
+
+// First level of the corpus update: S[b][k][c] = the sum of signal b's tile partials in ascending tile order, c <= NW
+// (nmf_dupdate_kernel's sum, kept per signal).  The partials of a tile are [K][NW + 1] values in a row, so a workgroup
+// takes kThreads consecutive ones of them: nchunk workgroups per signal, signal after signal on a 1-D grid.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void nmf_dsum_kernel(const T* __restrict__ part, const SignalInfo* __restrict__ sig,
+                                                            const int* __restrict__ done, T* __restrict__ S,
+                                                            unsigned nchunk, size_t tstride)
+{
+    if (done[0]) return;
+    const unsigned b = blockIdx.x / nchunk;
+    const size_t e = (size_t)(blockIdx.x - b * nchunk) * kThreads + threadIdx.x;
+    if (e >= tstride) return;
+    const int ntiles = (sig[b].L + kRows - 1) / kRows;
+    const T* p = part + (size_t)sig[b].rt0 * tstride + e;
+    T acc = T(0);
+    for (int i = 0; i < ntiles; ++i) acc = acc + p[(size_t)i * tstride];
+    S[(size_t)b * tstride + e] = acc;
+}
+
+// One workgroup per atom k: N and den summed over the signals in ascending order, then nmf_dupdate_kernel's update and
+// normalisation of the one dictionary.  IEEE division and sqrt; no atomics.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void nmf_dupdate_corpus_kernel(const T* __restrict__ S, int B,
+                                                                      const int* __restrict__ done, T* __restrict__ D,
+                                                                      int K, int NW)
+{
+    const int k = blockIdx.x;
+    if (done[0]) return;
+    extern __shared__ __align__(16) unsigned char smem[];
+    T* red = reinterpret_cast<T*>(smem);                             // [kThreads] sums of squares, then [NW + 1] sums
+    T* sum = red + kThreads;
+    const int ld = NW + 1;
+    const size_t tstride = (size_t)K * ld;
+    const T* p = S + (size_t)k * ld;
+    for (int c = threadIdx.x; c < ld; c += kThreads) {
+        T acc = T(0);
+        for (int b = 0; b < B; ++b) acc = acc + p[(size_t)b * tstride + c];
+        sum[c] = acc;
+    }
+    __syncthreads();
+    T* d = D + (size_t)k * NW;
+    const T den = sum[NW];
+    T ss = T(0);
+    for (int c = threadIdx.x; c < NW; c += kThreads) {
+        const T v = d[c] * (sum[c] / den);
+        sum[c] = v;
+        ss = ss + v * v;
+    }
+    red[threadIdx.x] = ss;
+    __syncthreads();
+    for (int w = kThreads / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + w];
+        __syncthreads();
+    }
+    const T nrm = sqrt(red[0]);
+    for (int c = threadIdx.x; c < NW; c += kThreads) d[c] = nrm > T(0) ? sum[c] / nrm : sum[c];
+}
+
+// one workgroup (64 threads) per signal: max|r| and sum r^2 of the signal as nmf_decide_kernel forms them, and the
+// signal's own SNR and residual scale
+__global__ __launch_bounds__(64) void nmf_signal_stats_kernel(const double* __restrict__ part,
+                                                              const SignalInfo* __restrict__ sig,
+                                                              const double* __restrict__ energy, const int* __restrict__ done,
+                                                              double* __restrict__ sigmx, double* __restrict__ sigss,
+                                                              double* __restrict__ snr, double* __restrict__ rscale)
+{
+    const int b = blockIdx.x;
+    if (done[0]) return;
+    __shared__ double smx[64], sss[64];
+    const int ntiles = (sig[b].T + kRows - 1) / kRows;
+    const double* pb = part + (size_t)sig[b].st0 * 2;
+    double mx = 0.0, ss = 0.0;
+    for (int i = threadIdx.x; i < ntiles; i += 64) {
+        mx = fmax(mx, pb[(size_t)i * 2]);
+        ss = ss + pb[(size_t)i * 2 + 1];
+    }
+    smx[threadIdx.x] = mx;
+    sss[threadIdx.x] = ss;
+    __syncthreads();
+    for (int w = 32; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            smx[threadIdx.x] = fmax(smx[threadIdx.x], smx[threadIdx.x + w]);
+            sss[threadIdx.x] = sss[threadIdx.x] + sss[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        sigmx[b] = smx[0];
+        sigss[b] = sss[0];
+        snr[b] = 10.0 * log10(energy[b] / sss[0]);
+        rscale[b] = smx[0];
+    }
+}
+
+// One workgroup: the signals' statistics combined in ascending signal order (staged through LDS kThreads at a time, summed
+// by one thread), then the stop rules of nmf_decide_kernel on the corpus.  state: done, iterations, stop; out: snr, scale.
+__global__ __launch_bounds__(kThreads) void nmf_decide_corpus_kernel(const double* __restrict__ sigmx,
+                                                                     const double* __restrict__ sigss,
+                                                                     const double* __restrict__ energy, int B,
+                                                                     int* __restrict__ state, double* __restrict__ out,
+                                                                     int it1, hscnmf_params p)
+{
+    if (state[0]) return;
+    __shared__ double lmx[kThreads], lss[kThreads], len[kThreads];
+    double mx = 0.0, ss = 0.0, en = 0.0;
+    for (int b0 = 0; b0 < B; b0 += kThreads) {
+        const int n = min(kThreads, B - b0);
+        if ((int)threadIdx.x < n) {
+            lmx[threadIdx.x] = sigmx[b0 + threadIdx.x];
+            lss[threadIdx.x] = sigss[b0 + threadIdx.x];
+            len[threadIdx.x] = energy[b0 + threadIdx.x];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int i = 0; i < n; ++i) {
+                mx = fmax(mx, lmx[i]);
+                ss = ss + lss[i];
+                en = en + len[i];
+            }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double s = 10.0 * log10(en / ss);
+        int code = HSCNMF_STOP_RUNNING;
+        if (it1 >= p.max_iterations) code = HSCNMF_STOP_MAX_ITERATIONS;
+        else if (p.has_residual_scale && mx <= p.tolerance_residual_scale) code = HSCNMF_STOP_RESIDUAL_SCALE;
+        else if (p.has_snr && s >= p.tolerance_snr) code = HSCNMF_STOP_SNR;
+        state[1] = it1;
+        state[2] = code;
+        out[0] = s;
+        out[1] = mx;
+        if (code != HSCNMF_STOP_RUNNING) state[0] = 1;
+    }
 }
 
 }  // namespace
@@ -697,4 +943,206 @@ extern "C" int hscnmf_learn(hscnmf_ctx* ctx, int dtype, const void* x, int B, in
                               (float*)D_out, iterations, stop, snr, residual_scale, timing_ms);
     return learn_t<double>(ctx, (const double*)x, B, T, F, (const double*)D_init, K, W, (const double*)a_init, energy, *params,
                            (double*)D_out, iterations, stop, snr, residual_scale, timing_ms);
+}
+
+// ---- hscnmf_learn_corpus: one dictionary from B signals of different lengths, DESIGN.md section 18 --------------------
+
+namespace {
+
+constexpr int kMaxCorpusSignals = 1 << 22;
+// HIP refuses a launch with gridDim.x * blockDim.x >= 2^32: with workgroups of kThreads = 256 a 1-D grid has at most
+// 2^24 - 1 workgroups.  The sample tiles (the row tiles are no more) and nmf_dsum_kernel's B * nchunk lie on such grids.
+constexpr long long kMaxCorpusGrid = (1LL << 32) / kThreads - 1;
+
+// the device memory of one hscnmf_learn_corpus call, freed (after a stream sync) when the call returns
+struct CorpusBuffers {
+    hscnmf_ctx* ctx;
+    std::vector<void*> ptrs;
+    explicit CorpusBuffers(hscnmf_ctx* c) : ctx(c) {}
+    ~CorpusBuffers()
+    {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (void* q : ptrs) (void)hipFree(q);
+    }
+    template <typename U> int get(U** out, size_t bytes)
+    {
+        void* q = nullptr;
+        hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 256));
+        if (e != hipSuccess)
+            return fail(ctx, HSCNMF_ERR_ALLOC, "hscnmf_learn_corpus: hipMalloc of %zu bytes failed (%s)", bytes, hipGetErrorString(e));
+        ptrs.push_back(q);
+        *out = static_cast<U*>(q);
+        return hsc::OK;
+    }
+};
+
+}  // namespace
+
+// As learn_t with ONE dictionary and the ragged geometry: per iteration the W steps, R = X/|recon|, the tile partials,
+// their sums per signal (nmf_dsum_kernel) and over the signals (nmf_dupdate_corpus_kernel), the residual with the new D,
+// the signals' statistics and the corpus decision.  No synchronisation inside an iteration; the whole corpus is resident.
+template <typename T>
+static int learn_corpus_t(hscnmf_ctx* ctx, const T* x, const int64_t* lengths, int B, int F, const T* D_init, int K, int W,
+                          const T* a_init, const double* energy, const hscnmf_params& p, T* D_out, int32_t* iters,
+                          int32_t* stop, double* snr, double* rscale, double* sig_snr, double* sig_rscale, double* timing)
+{
+    const int NW = W * F, ld = NW + 1;
+    const size_t dsz = (size_t)K * NW, tstride = (size_t)K * ld;
+    const size_t lds_part = (size_t)(kRows + W - 1) * F * sizeof(T), lds_upd = (size_t)(kThreads + NW + 1) * sizeof(T);
+    int PR = 0, slab = 0;
+    size_t lds = 0;
+    if (!lds_plan<T>(W, F, PR, slab, lds) || lds_part > (size_t)kLdsBytes || lds_upd > (size_t)kLdsBytes)
+        return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_learn_corpus: W = %d, F = %d needs more than %d bytes of LDS per workgroup",
+                    W, F, kLdsBytes);
+    // the per-signal table and the flat tile tables
+    std::vector<SignalInfo> sig((size_t)B);
+    long long rows = 0, arows = 0, nrt = 0, nst = 0;
+    for (int b = 0; b < B; ++b) {
+        const long long Tb = lengths[b], Lb = Tb - W + 1;
+        sig[b] = SignalInfo{rows, arows, nrt, nst, (int)Tb, (int)Lb};
+        rows += Tb;
+        arows += Lb;
+        nrt += (Lb + kRows - 1) / kRows;
+        nst += (Tb + kRows - 1) / kRows;
+    }
+    const size_t nchunk = (tstride + kThreads - 1) / kThreads;
+    if (nst > kMaxCorpusGrid || (long long)B * (long long)nchunk > kMaxCorpusGrid)
+        return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_learn_corpus: %lld tiles of %d samples, B * ceil(K * (W * F + 1) / %d) = %lld "
+                    "(each at most %lld: a 1-D grid of workgroups of %d threads)", nst, kRows, kThreads,
+                    (long long)B * (long long)nchunk, kMaxCorpusGrid, kThreads);
+    std::vector<int2> rtiles((size_t)nrt), stiles((size_t)nst);
+    for (int b = 0; b < B; ++b) {
+        const int nr = (sig[b].L + kRows - 1) / kRows, ns = (sig[b].T + kRows - 1) / kRows;
+        for (int i = 0; i < nr; ++i) rtiles[(size_t)sig[b].rt0 + i] = make_int2(b, i);
+        for (int i = 0; i < ns; ++i) stiles[(size_t)sig[b].st0 + i] = make_int2(b, i);
+    }
+    // the bytes of the call, before the first allocation (each buffer rounded up as hipMalloc hands it out)
+    const size_t sizes[] = {
+        (size_t)arows * K * sizeof(T), (size_t)arows * K * sizeof(T),            // the A pair
+        (size_t)rows * F * sizeof(T), (size_t)rows * F * sizeof(T),              // X, R
+        dsz * sizeof(T), (size_t)nrt * tstride * sizeof(T), (size_t)B * tstride * sizeof(T),   // D, the tile partials, S
+        (size_t)nst * 2 * sizeof(double), (size_t)B * 5 * sizeof(double),        // residual partials; energy, max, sum, snr, scale
+        (size_t)B * sizeof(SignalInfo), (size_t)(nrt + nst) * sizeof(int2),      // the tables
+        3 * sizeof(int) + 2 * sizeof(double)};                                   // the corpus state
+    size_t need = 0;
+    for (size_t v : sizes) need += (std::max<size_t>(v, 256) + 255) / 256 * 256;
+    HSC_TRY(hipSetDevice(ctx->device));
+    size_t freeb = 0, totalb = 0;
+    HSC_TRY(hipMemGetInfo(&freeb, &totalb));
+    const size_t budget = p.memory_budget ? (size_t)p.memory_budget : freeb / 10 * 6;
+    if (need > budget)
+        return fail(ctx, HSCNMF_ERR_ALLOC, "hscnmf_learn_corpus: the corpus needs %zu bytes of device memory, the budget is %zu bytes "
+                    "(a corpus is resident as a whole: there is no chunking)", need, budget);
+    CorpusBuffers buf(ctx);
+    T *dA[2], *dX, *dR, *dD, *dPD, *dS;
+    double *dPart, *dStat, *dOut;
+    SignalInfo* dSig;
+    int2* dTiles;
+    int* dState;
+    if (int rc = buf.get(&dA[0], sizes[0])) return rc;
+    if (int rc = buf.get(&dA[1], sizes[1])) return rc;
+    if (int rc = buf.get(&dX, sizes[2])) return rc;
+    if (int rc = buf.get(&dR, sizes[3])) return rc;
+    if (int rc = buf.get(&dD, sizes[4])) return rc;
+    if (int rc = buf.get(&dPD, sizes[5])) return rc;
+    if (int rc = buf.get(&dS, sizes[6])) return rc;
+    if (int rc = buf.get(&dPart, sizes[7])) return rc;
+    if (int rc = buf.get(&dStat, sizes[8])) return rc;
+    if (int rc = buf.get(&dSig, sizes[9])) return rc;
+    if (int rc = buf.get(&dTiles, sizes[10])) return rc;
+    if (int rc = buf.get(&dOut, sizes[11])) return rc;
+    dState = reinterpret_cast<int*>(dOut + 2);
+    double *dEn = dStat, *dMx = dStat + B, *dSs = dStat + 2 * (size_t)B, *dSnr = dStat + 3 * (size_t)B, *dRs = dStat + 4 * (size_t)B;
+    const Ragged grow{dSig, dTiles}, gsmp{dSig, dTiles + nrt};
+
+    hipStream_t st = ctx->stream;
+    HSC_TRY(hipEventRecord(ctx->ev[0], st));
+    HSC_TRY(hipMemcpyAsync(dX, x, sizes[2], hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(dA[0], a_init, sizes[0], hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(dD, D_init, sizes[4], hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(dEn, energy, (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(dSig, sig.data(), sizes[9], hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(dTiles, rtiles.data(), (size_t)nrt * sizeof(int2), hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(dTiles + nrt, stiles.data(), (size_t)nst * sizeof(int2), hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemsetAsync(dOut, 0, sizes[11], st));
+    HSC_TRY(hipEventRecord(ctx->ev[1], st));
+    // (the host tables are declared before `buf`, whose destructor synchronises the stream: they outlive their copies)
+    int it = 0, hdone = 0;
+    for (; it < p.max_iterations; ++it) {
+        for (int t = 0; t < W; ++t) {
+            const int g = it * W + t;
+            hipLaunchKernelGGL(nmf_step_ragged_kernel<T>, dim3((unsigned)nrt), dim3(kThreads), lds, st, dA[g & 1], dA[(g + 1) & 1],
+                               dX, dD, dState, grow, K, W, F, t, PR, slab);
+        }
+        const T* dAn = dA[((it + 1) * W) & 1];
+        hipLaunchKernelGGL(nmf_ratio_ragged_kernel<T>, dim3((unsigned)nst), dim3(kThreads), lds, st, dAn, dX, dD, dState, dR, gsmp,
+                           K, W, F, PR, slab);
+        hipLaunchKernelGGL(nmf_dpart_ragged_kernel<T>, dim3((unsigned)nrt), dim3(kThreads), lds_part, st, dAn, dR, dState, dPD, grow,
+                           K, W, F);
+        hipLaunchKernelGGL(nmf_dsum_kernel<T>, dim3((unsigned)((size_t)B * nchunk)), dim3(kThreads), 0, st, dPD, dSig, dState, dS,
+                           (unsigned)nchunk, tstride);
+        hipLaunchKernelGGL(nmf_dupdate_corpus_kernel<T>, dim3(K), dim3(kThreads), lds_upd, st, dS, B, dState, dD, K, NW);
+        hipLaunchKernelGGL(nmf_residual_ragged_kernel<T>, dim3((unsigned)nst), dim3(kThreads), lds, st, dAn, dX, dD, dState, dR, dPart,
+                           gsmp, K, W, F, PR, slab);
+        hipLaunchKernelGGL(nmf_signal_stats_kernel, dim3(B), dim3(64), 0, st, dPart, dSig, dEn, dState, dMx, dSs, dSnr, dRs);
+        hipLaunchKernelGGL(nmf_decide_corpus_kernel, dim3(1), dim3(kThreads), 0, st, dMx, dSs, dEn, B, dState, dOut, it + 1, p);
+        HSC_TRY(hipGetLastError());
+        // the flag is read once per iteration, only with a tolerance and another iteration to go
+        if ((p.has_residual_scale || p.has_snr) && it + 1 < p.max_iterations) {
+            HSC_TRY(hipMemcpyAsync(&hdone, dState, sizeof(int), hipMemcpyDeviceToHost, st));
+            HSC_TRY(hipStreamSynchronize(st));
+            if (hdone) { ++it; break; }
+        }
+    }
+    HSC_TRY(hipEventRecord(ctx->ev[2], st));
+    int hstate[3] = {0, 0, 0};
+    double hout[2] = {0.0, 0.0};
+    HSC_TRY(hipMemcpyAsync(hstate, dState, sizeof(hstate), hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipMemcpyAsync(hout, dOut, sizeof(hout), hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipMemcpyAsync(sig_snr, dSnr, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipMemcpyAsync(sig_rscale, dRs, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipMemcpyAsync(D_out, dD, dsz * sizeof(T), hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipEventRecord(ctx->ev[3], st));
+    HSC_TRY(hipStreamSynchronize(st));
+    if (hstate[1] != it) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn_corpus: the corpus has no result");
+    *iters = hstate[1];
+    *stop = hstate[2];
+    *snr = hout[0];
+    *rscale = hout[1];
+    double tm[5] = {0, 0, 0, 1, (double)it};
+    if (int rc = hsc::add_times(ctx, 3, tm)) return rc;
+    if (timing) std::memcpy(timing, tm, sizeof(tm));
+    return HSCNMF_OK;
+}
+
+extern "C" int hscnmf_learn_corpus(hscnmf_ctx* ctx, int dtype, const void* x, const int64_t* lengths, int B, int F,
+                                   const void* D_init, int K, int W, const void* a_init, const double* energy,
+                                   const hscnmf_params* params, void* D_out, int32_t* iterations, int32_t* stop, double* snr,
+                                   double* residual_scale, double* signal_snr, double* signal_residual_scale, double* timing_ms)
+{
+    if (!ctx) return fail(nullptr, HSCNMF_ERR_INVALID, "hscnmf_learn_corpus: ctx is NULL");
+    if (!x || !lengths || !D_init || !a_init || !energy || !params || !D_out || !iterations || !stop || !snr || !residual_scale ||
+        !signal_snr || !signal_residual_scale)
+        return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn_corpus: NULL argument");
+    if (dtype != HSCNMF_F32 && dtype != HSCNMF_F64) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn_corpus: unknown dtype %d", dtype);
+    if (B < 1 || K < 1 || F < 1) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn_corpus: B = %d, K = %d, F = %d", B, K, F);
+    if (W < 2) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn_corpus: filter width %d (the reference needs W >= 2)", W);
+    if (params->max_iterations < 1)
+        return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn_corpus: max_iterations = %d", params->max_iterations);
+    for (int b = 0; b < B; ++b)
+        if (lengths[b] < W)
+            return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn_corpus: signal %d: length %lld is shorter than the filter width %d", b,
+                        (long long)lengths[b], W);
+    if (B > kMaxCorpusSignals) return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_learn_corpus: %d signals (at most %d)", B, kMaxCorpusSignals);
+    if ((int64_t)W * F > (1 << 24) || K > 65535) return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_learn_corpus: shape out of range");
+    for (int b = 0; b < B; ++b)
+        if ((lengths[b] - W + 1) * K > ((int64_t)1 << 31) / 8)
+            return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_learn_corpus: signal %d: shape out of range", b);
+    if (dtype == HSCNMF_F32)
+        return learn_corpus_t<float>(ctx, (const float*)x, lengths, B, F, (const float*)D_init, K, W, (const float*)a_init, energy,
+                                     *params, (float*)D_out, iterations, stop, snr, residual_scale, signal_snr,
+                                     signal_residual_scale, timing_ms);
+    return learn_corpus_t<double>(ctx, (const double*)x, lengths, B, F, (const double*)D_init, K, W, (const double*)a_init, energy,
+                                  *params, (double*)D_out, iterations, stop, snr, residual_scale, signal_snr,
+                                  signal_residual_scale, timing_ms);
 }

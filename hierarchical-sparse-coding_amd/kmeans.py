@@ -114,9 +114,10 @@ def _rng(rng):
     return np.random if rng is None else rng
 
 
-def corpus_signals(sequences, lengths=None):
+def corpus_signals(sequences, lengths=None, who='k-means'):
     """The signals of a corpus as a list of [T_b] or [T_b,F] views: `sequences` [B,T] / [B,T,F], a list / tuple of
-    arrays, or a padded array with `lengths` [B] (the ragged forms of modeling.is_ragged).  The padding is not read."""
+    arrays, or a padded array with `lengths` [B] (the ragged forms of modeling.is_ragged).  The padding is not read.
+    `who` heads the messages (the learner that calls)."""
     if isinstance(sequences, (list, tuple)):
         if lengths is not None:
             raise ValueError('lengths= goes with a padded array, not with a list of signals')
@@ -124,7 +125,7 @@ def corpus_signals(sequences, lengths=None):
     else:
         seq = np.asarray(sequences)
         if seq.ndim != 2 and seq.ndim != 3:
-            raise ValueError('k-means: the corpus must be [B,T] or [B,T,F] (got %d dimensions)' % seq.ndim)
+            raise ValueError('%s: the corpus must be [B,T] or [B,T,F] (got %d dimensions)' % (who, seq.ndim))
         if lengths is None:
             seqs = list(seq)
         else:
@@ -135,11 +136,11 @@ def corpus_signals(sequences, lengths=None):
                 raise ValueError('a length is outside the padded length %d' % seq.shape[1])
             seqs = [seq[b, :int(lens[b])] for b in range(seq.shape[0])]
     if len(seqs) == 0:
-        raise ValueError('k-means: a corpus needs at least one signal')
+        raise ValueError('%s: a corpus needs at least one signal' % who)
     if seqs[0].ndim not in (1, 2) or any(q.ndim != seqs[0].ndim or q.shape[1:] != seqs[0].shape[1:] for q in seqs):
-        raise ValueError('k-means: the signals of a corpus must all be [T_b] or all be [T_b,F] with the same F')
+        raise ValueError('%s: the signals of a corpus must all be [T_b] or all be [T_b,F] with the same F' % who)
     if any(q.dtype != seqs[0].dtype for q in seqs):
-        raise ValueError('k-means: the signals of a corpus must share one dtype')
+        raise ValueError('%s: the signals of a corpus must share one dtype' % who)
     return seqs
 
 

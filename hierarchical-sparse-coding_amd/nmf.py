@@ -12,7 +12,8 @@ Reference behaviour kept:
     the residual is squeezed to [T] for a [K,W] dictionary or a [T] signal.
 
 Added: computeCoefficientsBatch (signals [B,T(,F)] sharing D), ConvolutionalNMFLearner.trainBatch (one dictionary
-per signal).  There is no CPU path: without libhscnmf.so or a visible GPU the calls raise hsc_amd._native.HscmpError.
+per signal) and trainCorpus (ONE dictionary from many signals, ragged corpora included).
+There is no CPU path: without libhscnmf.so or a visible GPU the calls raise hsc_amd._native.HscmpError.
 """
 import ctypes
 import logging
@@ -26,7 +27,8 @@ from .modeling import SparseApproximator, _compute_dtype
 logger = logging.getLogger(__name__)
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'nmf', 'libhscnmf.so')
-EXPORTS = ['hscnmf_version', 'hscnmf_create', 'hscnmf_destroy', 'hscnmf_last_error', 'hscnmf_compute', 'hscnmf_learn']
+EXPORTS = ['hscnmf_version', 'hscnmf_create', 'hscnmf_destroy', 'hscnmf_last_error', 'hscnmf_compute', 'hscnmf_learn',
+           'hscnmf_learn_corpus']
 STOP_NAMES = {0: 'running', 1: 'max_iterations', 2: 'residual_scale', 3: 'snr'}
 
 
@@ -45,7 +47,9 @@ def load_library():
     if _lib is None:
         vp, ci = ctypes.c_void_p, ctypes.c_int
         head = [vp, ci, vp, ci, ci, ci, vp, ci, ci, vp, vp, ctypes.POINTER(HscnmfParams)]
-        _lib = _native.load_satellite(LIB_PATH, 'hscnmf', {'hscnmf_compute': head + [vp] * 7, 'hscnmf_learn': head + [vp] * 6})
+        corpus = [vp, ci, vp, vp, ci, ci, vp, ci, ci, vp, vp, ctypes.POINTER(HscnmfParams)] + [vp] * 8
+        _lib = _native.load_satellite(LIB_PATH, 'hscnmf', {'hscnmf_compute': head + [vp] * 7, 'hscnmf_learn': head + [vp] * 6,
+                                                           'hscnmf_learn_corpus': corpus})
     return _lib
 
 
@@ -181,6 +185,29 @@ def _call_learn(device, dt, x, D0, a0, energy, params):
     return D, NMFStats(iters, stop, snr, rscale, timing)
 
 
+def _call_learn_corpus(device, dt, x, lengths, D0, a0, energy, params):
+    """hscnmf_learn_corpus on the stack x [rows,F], lengths [B] int64, D0 [K,W,F], the stacked coefficients a0 [sum L_b,K]
+    (all of dtype dt).  Returns (D [K,W,F], NMFStats of the corpus with signal_snr and signal_residual_scale [B])."""
+    B, F = lengths.shape[0], x.shape[1]
+    K, W = D0.shape[0], D0.shape[1]
+    ctx = _context(device)
+    D = np.empty((K, W, F), dtype=dt)
+    iters = np.zeros((1,), dtype=np.int32)
+    stop = np.zeros((1,), dtype=np.int32)
+    snr = np.zeros((1,), dtype=np.float64)
+    rscale = np.zeros((1,), dtype=np.float64)
+    sig_snr = np.zeros((B,), dtype=np.float64)
+    sig_rscale = np.zeros((B,), dtype=np.float64)
+    timing = np.zeros((5,), dtype=np.float64)
+    p = _native._ptr
+    ctx.call('learn_corpus', _native.dtype_code(dt), p(x), p(lengths), B, F, p(D0), K, W, p(a0), p(energy), ctypes.byref(params),
+             p(D), p(iters), p(stop), p(snr), p(rscale), p(sig_snr), p(sig_rscale), p(timing))
+    stats = NMFStats(iters, stop, snr, rscale, timing)
+    stats.signal_snr = sig_snr                    # float64 [B], dB, of each signal at the last iteration
+    stats.signal_residual_scale = sig_rscale      # float64 [B], max |residual| of each signal
+    return D, stats
+
+
 class ConvolutionalNMFLearner(object):
     """The reference's convolutional NMF dictionary learner (ConvolutionalDictionaryLearner._train_nmf,
     hsc/modeling.py:330-417) on the GPU, and a batch of independent learners (one dictionary per signal).
@@ -258,3 +285,84 @@ class ConvolutionalNMFLearner(object):
         assert X.ndim == 1 or X.ndim == 2
         D, _ = self.trainBatch(X[np.newaxis], initMethod, nbMaxIterations, toleranceResidualScale, toleranceSnr)
         return D[0]
+
+    def _prepare_corpus(self, sequences, initMethod, lengths, initialDictionary, initialCoefficients):
+        """The checks and draws of trainCorpus, before any device call.  Returns (dt, x [rows,F], lengths [B] int64,
+        D3 [K,W,F], a0 [sum L_b,K], energy [B], D0 the initial dictionary as drawn or given, ndim of a signal)."""
+        from .kmeans import corpus_signals, corpus_windows
+        from .utils import normalize
+        who = 'ConvolutionalNMFLearner'
+        K, W = self.k, self.windowSize
+        seqs = corpus_signals(sequences, lengths, who)
+        drawD = initialDictionary is None
+        for b, q in enumerate(seqs):
+            try:
+                self._check_shapes(q.shape[0], initMethod, drawD)
+            except Exception as e:
+                raise type(e)('signal %d: %s' % (b, e))
+        B = len(seqs)
+        F = 1 if seqs[0].ndim == 1 else seqs[0].shape[1]
+        if F < 1:
+            raise ValueError('%s: no features' % who)
+        if initialCoefficients is not None and len(initialCoefficients) != B:
+            raise ValueError('%s: %d initial coefficient arrays for %d signals' % (who, len(initialCoefficients), B))
+        rng = np.random if self.rng is None else self.rng
+        lens = np.array([q.shape[0] for q in seqs], dtype=np.int64)
+        stack = np.concatenate(seqs).reshape((-1, F))     # the signals' own samples, no padding
+        if drawD:                                         # first the dictionary (_init_D over the corpus) ...
+            if initMethod == 'noise':
+                D0 = normalize(rng.uniform(low=np.min(stack), high=np.max(stack), size=(K, W, F)))
+            else:
+                ib, it = corpus_windows(seqs, K, W, rng)
+                offsets = np.concatenate([[0], np.cumsum(lens)[:-1]])
+                D0 = normalize(stack[(offsets[ib] + it)[:, np.newaxis] + np.arange(W)[np.newaxis, :]])
+            if seqs[0].ndim == 1:
+                D0 = np.squeeze(D0, axis=2)
+        else:
+            D0 = np.asarray(initialDictionary)
+            if D0.shape[:2] != (K, W) or D0.ndim not in (2, 3) or D0.size != K * W * F:
+                raise ValueError('%s: the initial dictionary must be [%d,%d] or [%d,%d,%d] (got %s)' % (who, K, W, K, W, F, D0.shape))
+        a0s = []
+        for b in range(B):                                # ... then the coefficients, signal by signal (modeling.py:344)
+            if initialCoefficients is None:
+                a = rng.random_sample((int(lens[b]), K)).astype(seqs[0].dtype) + 2.0
+            else:
+                a = np.asarray(initialCoefficients[b])
+                if a.shape != (lens[b], K):
+                    raise ValueError('%s: the initial coefficients of signal %d must be [%d,%d] (got %s)' % (who, b, lens[b], K, a.shape))
+            a0s.append(a[:int(lens[b]) - W + 1])          # rows past L_b never reach a reconstruction
+        dt = _compute_dtype(seqs[0].dtype, D0.dtype)
+        x = np.ascontiguousarray(stack, dtype=dt)
+        D3 = np.ascontiguousarray(D0.reshape((K, W, F)), dtype=dt)
+        a0 = np.ascontiguousarray(np.concatenate(a0s), dtype=dt)
+        ends = np.cumsum(lens)
+        energy = np.array([np.sum(np.square(x[e - n:e])) for e, n in zip(ends, lens)], dtype=np.float64)   # modeling.py:341
+        return dt, x, lens, D3, a0, energy, D0, seqs[0].ndim
+
+    def trainCorpus(self, sequences, initMethod='random_samples', nbMaxIterations=None, toleranceResidualScale=None,
+                    toleranceSnr=None, lengths=None, initialDictionary=None, initialCoefficients=None):
+        """`train` for ONE dictionary over a corpus of B signals: `sequences` [B,T] / [B,T,F], a list / tuple of [T_b] or
+        [T_b,F] arrays, or a padded array with `lengths` (its padding is never read and may hold NaN); one dtype, one F.
+        Every iteration runs the coefficient steps of each signal against the shared D, sums the update's N and den over
+        all signals' own rows (no atom straddles two signals) and stops on the corpus' residual scale max_b max|r_b| and
+        SNR 10 log10(sum_b energy_b / sum_b sum r_b^2): the reference's _train_nmf on the concatenation with the
+        straddling coefficient rows held at zero.
+        Draws (from `rng` or numpy's global generator): first the dictionary ('random_samples': K windows of W samples over
+        the admissible starts of all signals, kmeans.corpus_windows, every signal longer than W; 'noise': uniform between
+        the smallest and largest sample of the corpus), then per signal in corpus order random_sample((T_b, K)) + 2.0 in
+        the data's dtype: for one signal, `train`'s draws and, bit for bit, `train`'s result.
+        initialDictionary [K,W(,F)] / initialCoefficients (a list of [T_b,K] arrays): used instead of the draws.
+        Returns D [K,W] or [K,W,F] in the initial dictionary's dtype; lastStats: the corpus' NMFStats (length 1) with
+        signal_snr and signal_residual_scale [B]."""
+        dt, x, lens, D3, a0, energy, D0, ndim = self._prepare_corpus(sequences, initMethod, lengths, initialDictionary,
+                                                                     initialCoefficients)
+        params = _params(nbMaxIterations, toleranceResidualScale, toleranceSnr, self.memoryBudget)
+        D, stats = _call_learn_corpus(self.device, dt, x, lens, D3, a0, energy, params)
+        if np.issubdtype(D0.dtype, np.floating) and D.dtype != D0.dtype:
+            D = D.astype(D0.dtype)
+        if ndim == 1:
+            D = np.squeeze(D, axis=2)                                                           # modeling.py:414-415
+        self.lastStats = stats
+        logger.debug('corpus of %d signals: SNR of %f dB after %d iterations, stop: %s' % (
+            len(lens), stats.snr[0], stats.iterations[0], STOP_NAMES.get(int(stats.stop[0]))))
+        return D

@@ -1,6 +1,7 @@
 /* hscnmf.h -- C ABI of libhscnmf.so: batched convolutional NMF coefficients (the reference's
  * ConvolutionalNMF.computeCoefficients, hsc/modeling.py:662-747) and the convolutional NMF dictionary
- * learner (ConvolutionalDictionaryLearner(algorithm='nmf'), hsc/modeling.py:330-417) on MI355X / gfx950.
+ * learner (ConvolutionalDictionaryLearner(algorithm='nmf'), hsc/modeling.py:330-417), for one signal per dictionary
+ * (hscnmf_learn) or one dictionary over a corpus of signals (hscnmf_learn_corpus), on MI355X / gfx950.
  *
  * One context per host thread (contexts are not thread safe).  Every entry point returns
  * HSCNMF_OK (0) or a negative status; hscnmf_last_error() describes the last failure.
@@ -38,10 +39,11 @@ typedef struct {
     int32_t reserved;
     double tolerance_residual_scale;
     double tolerance_snr;
-    uint64_t memory_budget;           /* device bytes for one chunk of signals (learners); 0: 60% of the free memory */
+    uint64_t memory_budget;           /* device bytes for one chunk of signals (learners), for the whole corpus in
+                                         hscnmf_learn_corpus; 0: 60% of the free memory */
 } hscnmf_params;
 
-int hscnmf_version(void);                          /* 2: hscnmf_learn */
+int hscnmf_version(void);                          /* 2: hscnmf_learn (hscnmf_learn_corpus was added without a new version) */
 int hscnmf_create(hscnmf_ctx** out, int device_id);
 void hscnmf_destroy(hscnmf_ctx* ctx);
 const char* hscnmf_last_error(hscnmf_ctx* ctx);   /* ctx may be NULL (errors of hscnmf_create) */
@@ -80,6 +82,38 @@ int hscnmf_compute(hscnmf_ctx* ctx, int dtype, const void* x, int B, int T, int 
 int hscnmf_learn(hscnmf_ctx* ctx, int dtype, const void* x, int B, int T, int F, const void* D_init, int K, int W,
                  const void* a_init, const double* energy, const hscnmf_params* params, void* D_out,
                  int32_t* iterations, int32_t* stop, double* snr, double* residual_scale, double* timing_ms);
+
+/* Trains ONE dictionary from a corpus of B signals of different lengths.  One iteration: for every signal the W
+ * multiplicative steps of hscnmf_compute against the shared D and R_b = x_b / |recon(A_b, D)|; then D *= N / den with
+ * N[k][t][f] = sum_b sum_{s < L_b} A_b[s][k] R_b[s+t][f], den[k] = sum_b sum_{s < L_b} A_b[s][k] (L_b = T_b-W+1), each
+ * atom divided by its l2 norm when that is > 0; then the residuals with the new D and the stop rules of hscnmf_compute
+ * on the corpus: residual scale max_b max|r_b|, SNR 10 log10(sum_b energy_b / sum_b sum r_b^2).
+ * Order of every floating-point sum (no atomics): within a signal exactly hscnmf_learn's (tiles of 128 rows in
+ * ascending order for N and den, its strided partials and tree for the residual sums), then the signals in ascending
+ * order.  A corpus of one signal gives hscnmf_learn's result on that signal bit for bit.
+ * All pointers are host memory, C order:
+ *   x        [rows][F]      the signals stacked without padding, rows = sum_b T_b
+ *   lengths  [B] int64      T_b
+ *   D_init   [K][W][F]      the one initial dictionary
+ *   a_init   [sum_b L_b][K] the signals' initial coefficients stacked (rows 0 .. T_b-W of each signal only)
+ *   energy   [B]            sum of squares of each signal (float64)
+ * outputs:
+ *   D_out    [K][W][F]      the learnt dictionary
+ *   iterations, stop, snr, residual_scale: one value each, for the corpus
+ *   signal_snr, signal_residual_scale [B] float64: the same statistics of each signal at the last iteration
+ *   timing_ms [5] float64 (may be NULL): upload, iterations, download, 1, number of iterations run
+ * Requires W >= 2, B >= 1 and every T_b >= W.  Limits, answered with HSCNMF_ERR_UNSUPPORTED before anything is allocated:
+ * B <= 4 194 304; sum_b ceil(T_b / 128) <= 2^24 - 1 tiles of 128 samples over all signals (at most 2^31 - 128 samples);
+ * B * ceil(K * (W*F + 1) / 256) <= 2^24 - 1; per signal and for K, W, F the limits of hscnmf_learn.  (Signals and tiles
+ * lie on 1-D grids of 256-thread workgroups, which HIP launches only below 2^32 threads in all; the offsets into the
+ * stacks are 64-bit on the device.)
+ * The whole corpus is resident for the call: the bytes needed are worked out before the first allocation, and a corpus
+ * that needs more than params->memory_budget (0: 60% of the free memory) fails with HSCNMF_ERR_ALLOC, the message naming
+ * both numbers, with nothing allocated.  There is no chunking: an iteration needs every signal. */
+int hscnmf_learn_corpus(hscnmf_ctx* ctx, int dtype, const void* x, const int64_t* lengths, int B, int F, const void* D_init,
+                        int K, int W, const void* a_init, const double* energy, const hscnmf_params* params, void* D_out,
+                        int32_t* iterations, int32_t* stop, double* snr, double* residual_scale, double* signal_snr,
+                        double* signal_residual_scale, double* timing_ms);
 
 #ifdef __cplusplus
 }
