@@ -18,7 +18,9 @@
 // wide_sum_kernel: one workgroup per (centroid, tile of 256 elements) that stages its members' rows, divided by their
 // norms, through a double-buffered LDS ring and adds them in list order, one lane per element.
 // hsckmeans_set_corpus stacks signals of different lengths as one learner's data [rows][F]: every kernel reads it as
-// B = 1, T = rows, with window starts that are stacked rows.
+// B = 1, T = rows, with window starts that are stacked rows.  hsckmeans_set_corpus_sparse takes the stack as CSR and
+// holds the window stack [N * 2W][F] instead: gather_kernel builds every window's dense block from the entries the
+// windows cover, and the step's kernels read it with window n at row n * 2W.
 // Compiled with -ffp-contract=off: no product is fused into a sum outside the explicit MFMA chains.
 #include "../../../include/hsckmeans.h"
 #include "../common/hsc_lib.h"
@@ -576,37 +578,230 @@ extern "C" int hsckmeans_set_data(hsckmeans_ctx* ctx, const void* x, int dtype, 
     return upload(ctx, x, dtype, B, T, F, s32, N, W, "hsckmeans_set_data");
 }
 
+// the signal rules of a corpus: row_offsets ascend from 0 and every signal is longer than 2W; `fn` heads the messages
+static int check_corpus_signals(hsckmeans_ctx* ctx, const char* fn, int B, const int64_t* row_offsets, int W)
+{
+    if (row_offsets[0] != 0) return fail(ctx, HSCKMEANS_ERR_INVALID, "%s: row_offsets[0] = %lld, must be 0", fn, (long long)row_offsets[0]);
+    for (int b = 0; b < B; ++b) {
+        const int64_t len = row_offsets[b + 1] - row_offsets[b];
+        if (len < 0) return fail(ctx, HSCKMEANS_ERR_INVALID, "%s: row_offsets descend at signal %d (%lld after %lld)", fn, b,
+                                 (long long)row_offsets[b + 1], (long long)row_offsets[b]);
+        if (len <= 2 * W)
+            return fail(ctx, HSCKMEANS_ERR_INVALID, "%s: signal %d has %lld samples, windows of 2W = %d samples need more than %d", fn, b,
+                        (long long)len, 2 * W, 2 * W);
+    }
+    return HSCKMEANS_OK;
+}
+
+// the window rule of a corpus: every window lies inside one signal
+static int check_corpus_windows(hsckmeans_ctx* ctx, const char* fn, int B, const int64_t* row_offsets, const int64_t* starts, int N, int W)
+{
+    const int64_t rows = row_offsets[B];
+    for (int n = 0; n < N; ++n) {
+        const int64_t st = starts[n];
+        if (st < 0 || st >= rows) return fail(ctx, HSCKMEANS_ERR_INVALID, "%s: start %lld of window %d is outside the stack of %lld rows", fn, (long long)st, n, (long long)rows);
+        const int b = (int)(std::upper_bound(row_offsets, row_offsets + B + 1, st) - row_offsets) - 1;     // row_offsets[b] <= st
+        if (st + 2 * W > row_offsets[b + 1])
+            return fail(ctx, HSCKMEANS_ERR_INVALID, "%s: window %d (rows %lld .. %lld) crosses the end of signal %d at row %lld", fn, n,
+                        (long long)st, (long long)(st + 2 * W), b, (long long)row_offsets[b + 1]);
+    }
+    return HSCKMEANS_OK;
+}
+
 extern "C" int hsckmeans_set_corpus(hsckmeans_ctx* ctx, const void* x, int dtype, int B, const int64_t* row_offsets, int F,
                                     const int64_t* starts, int N, int W)
 {
+    const char* fn = "hsckmeans_set_corpus";
     if (!ctx) return fail(nullptr, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: ctx is NULL");
     if (!x || !row_offsets || !starts) return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: x, row_offsets or starts is NULL");
     if (dtype != HSCKMEANS_F32 && dtype != HSCKMEANS_F64) return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: bad dtype %d", dtype);
     if (B < 1 || F < 1 || N < 1 || W < 1)
         return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: bad shape B = %d, F = %d, N = %d, W = %d", B, F, N, W);
     if (W > kMaxW) return fail(ctx, HSCKMEANS_ERR_UNSUPPORTED, "hsckmeans_set_corpus: W = %d exceeds the limit of %d", W, kMaxW);
-    if (row_offsets[0] != 0) return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: row_offsets[0] = %lld, must be 0", (long long)row_offsets[0]);
-    for (int b = 0; b < B; ++b) {
-        const int64_t len = row_offsets[b + 1] - row_offsets[b];
-        if (len < 0) return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: row_offsets descend at signal %d (%lld after %lld)", b,
-                                 (long long)row_offsets[b + 1], (long long)row_offsets[b]);
-        if (len <= 2 * W)
-            return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: signal %d has %lld samples, windows of 2W = %d samples need more than %d", b,
-                        (long long)len, 2 * W, 2 * W);
-    }
+    if (int rc = check_corpus_signals(ctx, fn, B, row_offsets, W)) return rc;
     const int64_t rows = row_offsets[B];
     if (rows > INT_MAX / F) return fail(ctx, HSCKMEANS_ERR_UNSUPPORTED, "hsckmeans_set_corpus: the stack of %lld x %d elements exceeds 2^31 - 1", (long long)rows, F);
+    if (int rc = check_corpus_windows(ctx, fn, B, row_offsets, starts, N, W)) return rc;
     std::vector<int> s32((size_t)N);
-    for (int n = 0; n < N; ++n) {
-        const int64_t st = starts[n];
-        if (st < 0 || st >= rows) return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: start %lld of window %d is outside the stack of %lld rows", (long long)st, n, (long long)rows);
-        const int b = (int)(std::upper_bound(row_offsets, row_offsets + B + 1, st) - row_offsets) - 1;     // row_offsets[b] <= st
-        if (st + 2 * W > row_offsets[b + 1])
-            return fail(ctx, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus: window %d (rows %lld .. %lld) crosses the end of signal %d at row %lld", n,
-                        (long long)st, (long long)(st + 2 * W), b, (long long)row_offsets[b + 1]);
-        s32[n] = (int)st;
+    for (int n = 0; n < N; ++n) s32[n] = (int)starts[n];
+    return upload(ctx, x, dtype, 1, (int)rows, F, s32, N, W, fn);
+}
+
+namespace {
+
+// The covered part of a CSR corpus, as the host packs it for gather_kernel: the rows that some window covers, laid end
+// to end in ascending row order (`crow` rows), with their entries.
+//   rowptr [crow + 1]  entries of packed row i: rowptr[i] .. rowptr[i + 1] of cols / vals
+//   wrow   [N]         the packed row of window n's first row; its 2W rows follow it (a window lies in one run of rows)
+struct SparseArgs {
+    const int* rowptr;
+    const int* cols;
+    const int* wrow;
+    int N, L2, F, R, chunks;       // L2 = 2W rows per window, cut into `chunks` pieces of R rows: one piece per wave
+};
+
+// grid = ceil(N * chunks / 4), block = 256: wave u of the grid builds rows [c * R, c * R + R) of window n = u / chunks,
+// c = u % chunks, in the window stack out [N * L2][F].  The piece is one contiguous span of the stack: the wave zeroes it
+// with 16-byte stores (single elements up to the first and after the last aligned address), then writes the rows'
+// entries at (row, column), one entry per lane and trip, the row found by bisection of the piece's row pointers.
+// The zero of a cell and its entry may come from different lanes, in different store instructions of the SAME wave, and
+// nothing but their order of issue puts the entry last: this rests on the hardware performing one wave's vector stores
+// to one address in the order the wave issued them (so on gfx950; the wavefront-scope fence below emits no instruction,
+// it only keeps the compiler from reordering).  No other wave writes the span.  Zeroing and entries split across waves,
+// or a target that may reorder a wave's stores, would need a real barrier or a second kernel here.
+template <typename X>
+__global__ __launch_bounds__(256) void gather_kernel(const X* __restrict__ vals, X* __restrict__ out, SparseArgs a)
+{
+    typedef X vec_t __attribute__((ext_vector_type(16 / sizeof(X))));
+    constexpr int V = 16 / sizeof(X);
+    const int lane = threadIdx.x & 63;
+    const long long u = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (u >= (long long)a.N * a.chunks) return;
+    const int n = (int)(u / a.chunks), c = (int)(u - (long long)n * a.chunks);
+    const int r0 = c * a.R, r1 = min(a.L2, r0 + a.R);
+    const size_t lo = ((size_t)n * a.L2 + r0) * a.F, len = (size_t)(r1 - r0) * a.F;      // elements of the stack
+    X* span = out + lo;
+    const size_t head = min(len, (size_t)((V - lo % V) % V)), nvec = (len - head) / V, tail0 = head + nvec * V;
+    if ((size_t)lane < head) span[lane] = (X)0;
+    vec_t* vp = reinterpret_cast<vec_t*>(span + head);
+    const vec_t zero = {};
+    for (size_t i = lane; i < nvec; i += 64) vp[i] = zero;
+    if (tail0 + lane < len) span[tail0 + lane] = (X)0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");         // the zeroes before the entries: same wave, stores in issue order
+    const int* rp = a.rowptr + a.wrow[n] + r0;                    // rp[0 .. r1 - r0]: the piece's row pointers
+    const int nr = r1 - r0, e1 = rp[nr];
+    for (int e = rp[0] + lane; e < e1; e += 64) {
+        int ra = 0, rb = nr - 1;                                   // the last row r with rp[r] <= e
+        while (ra < rb) {
+            const int m = (ra + rb + 1) >> 1;
+            if (rp[m] <= e) ra = m;
+            else rb = m - 1;
+        }
+        span[(size_t)ra * a.F + a.cols[e]] = vals[e];
     }
-    return upload(ctx, x, dtype, 1, (int)rows, F, s32, N, W, "hsckmeans_set_corpus");
+}
+
+}  // namespace
+
+extern "C" int hsckmeans_set_corpus_sparse(hsckmeans_ctx* ctx, int dtype, int B, const int64_t* row_offsets, int F,
+                                           const int64_t* indptr, const int32_t* indices, const void* data,
+                                           const int64_t* starts, int N, int W)
+{
+    const char* fn = "hsckmeans_set_corpus_sparse";
+    if (!ctx) return fail(nullptr, HSCKMEANS_ERR_INVALID, "hsckmeans_set_corpus_sparse: ctx is NULL");
+    if (!row_offsets || !indptr || !starts) return fail(ctx, HSCKMEANS_ERR_INVALID, "%s: row_offsets, indptr or starts is NULL", fn);
+    if (dtype != HSCKMEANS_F32 && dtype != HSCKMEANS_F64) return fail(ctx, HSCKMEANS_ERR_INVALID, "%s: bad dtype %d", fn, dtype);
+    if (B < 1 || F < 1 || N < 1 || W < 1) return fail(ctx, HSCKMEANS_ERR_INVALID, "%s: bad shape B = %d, F = %d, N = %d, W = %d", fn, B, F, N, W);
+    if (W > kMaxW) return fail(ctx, HSCKMEANS_ERR_UNSUPPORTED, "%s: W = %d exceeds the limit of %d", fn, W, kMaxW);
+    if (int rc = check_corpus_signals(ctx, fn, B, row_offsets, W)) return rc;
+    const int64_t rows = row_offsets[B];
+    const int L2 = 2 * W;
+    if ((int64_t)N * L2 > INT_MAX / F)
+        return fail(ctx, HSCKMEANS_ERR_UNSUPPORTED, "%s: the window stack of %lld x %d elements exceeds 2^31 - 1", fn, (long long)N * L2, F);
+    if (int rc = check_corpus_windows(ctx, fn, B, row_offsets, starts, N, W)) return rc;
+    // CSR validity, row by row (the whole corpus: the host learner cuts its patches from rows no window covers)
+    if (indptr[0] != 0) return fail(ctx, HSCKMEANS_ERR_INVALID, "%s: indptr[0] = %lld, must be 0", fn, (long long)indptr[0]);
+    for (int64_t r = 0; r < rows; ++r) {
+        if (indptr[r + 1] < indptr[r])
+            return fail(ctx, HSCKMEANS_ERR_INVALID, "%s: indptr descends at row %lld (%lld after %lld)", fn, (long long)r,
+                        (long long)indptr[r + 1], (long long)indptr[r]);
+        if (indptr[r + 1] > INT_MAX)
+            return fail(ctx, HSCKMEANS_ERR_INVALID, "%s: indptr exceeds 2^31 - 1 entries at row %lld", fn, (long long)r);
+    }
+    if (rows > 0 && indptr[rows] > 0 && (!indices || !data)) return fail(ctx, HSCKMEANS_ERR_INVALID, "%s: indices or data is NULL", fn);
+    for (int64_t r = 0; r < rows; ++r)
+        for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
+            if (indices[e] < 0 || indices[e] >= F)
+                return fail(ctx, HSCKMEANS_ERR_INVALID, "%s: column %d of row %lld is outside [0, %d)", fn, (int)indices[e], (long long)r, F);
+            if (e > indptr[r] && indices[e] <= indices[e - 1])
+                return fail(ctx, HSCKMEANS_ERR_INVALID, "%s: the columns of row %lld do not ascend (%d after %d)", fn, (long long)r,
+                            (int)indices[e], (int)indices[e - 1]);
+        }
+
+    // pack the covered rows: the windows in start order, their row intervals merged into runs
+    std::vector<int> order((size_t)N);
+    for (int n = 0; n < N; ++n) order[n] = n;
+    std::sort(order.begin(), order.end(), [&](int p, int q) { return starts[p] < starts[q]; });
+    std::vector<int> wrow((size_t)N), rowptr;
+    std::vector<int64_t> run_lo, run_hi;           // the runs of covered rows [lo, hi), ascending and disjoint
+    int64_t crow = 0;
+    for (int i = 0; i < N; ++i) {
+        const int64_t st = starts[order[i]];
+        if (run_hi.empty() || st > run_hi.back()) {
+            if (!run_hi.empty()) crow += run_hi.back() - run_lo.back();
+            run_lo.push_back(st);
+            run_hi.push_back(st + L2);
+        } else {
+            run_hi.back() = std::max(run_hi.back(), st + L2);
+        }
+        wrow[order[i]] = (int)(crow + (st - run_lo.back()));          // crow < N * L2 <= 2^31 - 1
+    }
+    crow += run_hi.back() - run_lo.back();
+    int64_t cent = 0;
+    for (size_t j = 0; j < run_lo.size(); ++j) cent += indptr[run_hi[j]] - indptr[run_lo[j]];
+    const size_t xs = dtype == HSCKMEANS_F32 ? 4 : 8;
+    rowptr.reserve((size_t)crow + 1);
+    std::vector<int> cols((size_t)cent);
+    std::vector<unsigned char> vals((size_t)cent * xs);
+    int64_t pos = 0;
+    for (size_t j = 0; j < run_lo.size(); ++j) {
+        const int64_t e0 = indptr[run_lo[j]], ne = indptr[run_hi[j]] - e0;
+        for (int64_t r = run_lo[j]; r < run_hi[j]; ++r) rowptr.push_back((int)(pos + indptr[r] - e0));
+        if (ne > 0) {
+            std::memcpy(cols.data() + pos, indices + e0, (size_t)ne * sizeof(int));
+            std::memcpy(vals.data() + (size_t)pos * xs, (const char*)data + (size_t)e0 * xs, (size_t)ne * xs);
+        }
+        pos += ne;
+    }
+    rowptr.push_back((int)pos);
+    std::vector<int> s32((size_t)N);
+    for (int n = 0; n < N; ++n) s32[n] = n * L2;
+
+    // the window stack: allocated, never uploaded; the context holds no data if anything below fails
+    HSC_TRY(hipSetDevice(ctx->device));
+    HSC_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->d_x) (void)hipFree(ctx->d_x);
+    if (ctx->d_starts) (void)hipFree(ctx->d_starts);
+    ctx->d_x = nullptr;
+    ctx->d_starts = nullptr;
+    ctx->dtype = -1;
+    const size_t bytes[4] = {rowptr.size() * sizeof(int), std::max<size_t>(cols.size(), 1) * sizeof(int), std::max<size_t>(vals.size(), xs),
+                             wrow.size() * sizeof(int)};
+    const void* src[4] = {rowptr.data(), cols.data(), vals.data(), wrow.data()};
+    const size_t copy[4] = {bytes[0], cols.size() * sizeof(int), vals.size(), bytes[3]};
+    void* d[4] = {};
+    hipError_t e = hipMalloc(&ctx->d_x, (size_t)N * L2 * F * xs);
+    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_starts, s32.size() * sizeof(int));
+    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipMalloc(&d[i], bytes[i]);
+    auto release = [&]() { for (void* q : d) if (q) (void)hipFree(q); };
+    if (e != hipSuccess) {
+        release();
+        return fail(ctx, HSCKMEANS_ERR_ALLOC, "%s: hipMalloc failed (%s)", fn, hipGetErrorString(e));
+    }
+    e = hipMemcpyAsync(ctx->d_starts, s32.data(), s32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+    for (int i = 0; i < 4 && e == hipSuccess; ++i)
+        if (copy[i] > 0) e = hipMemcpyAsync(d[i], src[i], copy[i], hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        // rows per wave: as many pieces as a window has spans of 4 KiB (four 16-byte stores per lane), begun ones included,
+        // then the rows shared evenly among them, so that no wave is launched for a tail of a few rows
+        SparseArgs a;
+        a.rowptr = (const int*)d[0]; a.cols = (const int*)d[1]; a.wrow = (const int*)d[3];
+        a.N = N; a.L2 = L2; a.F = F;
+        const int r4k = (int)std::min<size_t>((size_t)L2, std::max<size_t>(1, (4096 + F * xs - 1) / (F * xs)));
+        const int pieces = (L2 + r4k - 1) / r4k;
+        a.R = (L2 + pieces - 1) / pieces;
+        a.chunks = (L2 + a.R - 1) / a.R;
+        const unsigned grid = (unsigned)(((size_t)N * a.chunks + 3) / 4);      // N * chunks <= N * 2W <= 2^31 - 1
+        if (dtype == HSCKMEANS_F32) hipLaunchKernelGGL((gather_kernel<float>), dim3(grid), dim3(256), 0, ctx->stream, (const float*)d[2], (float*)ctx->d_x, a);
+        else hipLaunchKernelGGL((gather_kernel<double>), dim3(grid), dim3(256), 0, ctx->stream, (const double*)d[2], (double*)ctx->d_x, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    release();
+    if (e != hipSuccess) return fail(ctx, HSCKMEANS_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
+    ctx->dtype = dtype;
+    ctx->B = 1; ctx->T = N * L2; ctx->F = F; ctx->N = N; ctx->W = W;
+    return HSCKMEANS_OK;
 }
 
 extern "C" int hsckmeans_set_plan(hsckmeans_ctx* ctx, int plan)

@@ -16,6 +16,9 @@ window draw (extractRandomWindows) taken over the admissible starts of all signa
 initial atom or reset patch straddles two signals.  The signals go to the device as one stack without padding
 (hsckmeans_set_corpus).  The centroid half of a step has two plans with the same bits (hsckmeans_set_plan): per-centroid
 member tables and one thread per element, or the wide plan for corpus-sized window counts.
+A corpus may also be a list of scipy.sparse matrices (the representations of a level): the library
+then builds the windows' dense rows on the device from the entries they cover (hsckmeans_set_corpus_sparse), and the
+result equals the dense corpus' bit for bit.
 
 There is no CPU path: without libhsckmeans.so or a visible GPU the calls raise hsc_amd._native.HscmpError.
 ConvolutionalDictionaryLearner(algorithm='kmean') keeps its host path and is not routed here.
@@ -34,7 +37,7 @@ logger = logging.getLogger(__name__)
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'kmeans', 'libhsckmeans.so')
 EXPORTS = ['hsckmeans_version', 'hsckmeans_create', 'hsckmeans_destroy', 'hsckmeans_last_error', 'hsckmeans_set_data',
-           'hsckmeans_set_corpus', 'hsckmeans_set_plan', 'hsckmeans_step']
+           'hsckmeans_set_corpus', 'hsckmeans_set_corpus_sparse', 'hsckmeans_set_plan', 'hsckmeans_step']
 INIT_METHODS = ('random_samples', 'noise')
 RESET_METHODS = ('random_samples', 'random_samples_average', 'noise')
 MAX_WINDOW_SIZE = 255                    # include/hsckmeans.h: W + 1 positions per workgroup column set
@@ -43,7 +46,7 @@ WIDE_CHUNK_WINDOWS = 1024                # HSCKMEANS_WIDE_CHUNK_WINDOWS: windows
 WIDE_RING_ROWS = 16                      # HSCKMEANS_WIDE_RING_ROWS: rows of a 256-element tile per half of its LDS ring
 WIDE_MAX_K = 1024                        # HSCKMEANS_WIDE_MAX_K
 WIDE_FROM_WINDOWS = 1000                 # HSCKMEANS_WIDE_FROM_WINDOWS: auto takes the wide plan from this many windows
-MAX_STACK_ELEMENTS = 2 ** 31 - 1         # sum T_b * F of a corpus
+MAX_STACK_ELEMENTS = 2 ** 31 - 1         # sum T_b * F of a corpus; of a sparse corpus: its window stack N * 2W * F
 F32, F64 = 0, 1                          # HSCKMEANS_F32 / _F64
 SKIP, ASSIGN_F32, ASSIGN_F64 = 0, 1, 2   # modes of hsckmeans_step
 TIMES = 4                                # upload, assignment, centroids, download
@@ -58,6 +61,7 @@ def load_library():
         vp, ci = ctypes.c_void_p, ctypes.c_int
         _lib = _native.load_satellite(LIB_PATH, 'hsckmeans', {'hsckmeans_set_data': [vp, vp, ci, ci, ci, ci, vp, ci, ci],
                                                               'hsckmeans_set_corpus': [vp, vp, ci, ci, vp, ci, vp, ci, ci],
+                                                              'hsckmeans_set_corpus_sparse': [vp, ci, ci, vp, ci, vp, vp, vp, vp, ci, ci],
                                                               'hsckmeans_set_plan': [vp, ci],
                                                               'hsckmeans_step': [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]})
     return _lib
@@ -82,6 +86,15 @@ class _Context(_native.LibraryContext):
         self.B, self.N, self.W, self.F, self.dtype = 1, N, W, F, x.dtype
         self.call('set_corpus', _native._ptr(x), F32 if x.dtype == np.float32 else F64, row_offsets.shape[0] - 1,
                   _native._ptr(row_offsets), F, _native._ptr(starts), N, W)
+
+    def set_corpus_sparse(self, indptr, indices, data, F, row_offsets, starts, W):
+        """The stacked signals [rows,F] as CSR: indptr [rows+1] int64, indices int32 (ascending in a row), data float32 /
+        float64; row_offsets [B+1], starts [N] (stacked rows) int64.  Afterwards the context holds one learner (B = 1) on
+        the window stack [N * 2W, F] built on the device; a step's t stays relative to the window."""
+        N = starts.shape[0]
+        self.B, self.N, self.W, self.F, self.dtype = 1, N, W, F, data.dtype
+        self.call('set_corpus_sparse', F32 if data.dtype == np.float32 else F64, row_offsets.shape[0] - 1, _native._ptr(row_offsets), F,
+                  _native._ptr(indptr), _native._ptr(indices), _native._ptr(data), _native._ptr(starts), N, W)
 
     def set_plan(self, plan):
         """PLAN_AUTO, PLAN_LISTS or PLAN_WIDE for the centroid half of the later steps (the same bits either way)."""
@@ -158,16 +171,111 @@ def corpus_windows(signals, nb, width, rng=None):
     return b, g - (C[b] - A[b])
 
 
-def check_corpus_arguments(k, W, seqs, nbRandomWindows, initMethod, resetMethod):
+def sparse_corpus_signals(sequences, lengths=None, who='k-means'):
+    """The signals of a sparse corpus, or None when `sequences` is not one: a list / tuple whose items are all scipy.sparse
+    matrices [T_b,F] of one dtype and one F.  Returns them as CSR in canonical form (sorted columns, no duplicates), so
+    that their entries are the non-zeros of .toarray(); matrices already in that form are not copied."""
+    import scipy.sparse
+    if not isinstance(sequences, (list, tuple)) or not any(scipy.sparse.issparse(q) for q in sequences):
+        return None
+    if not all(scipy.sparse.issparse(q) for q in sequences):
+        raise ValueError('%s: a corpus is all dense arrays or all scipy.sparse matrices, not a mix of both' % who)
+    if lengths is not None:
+        raise ValueError('lengths= goes with a padded array, not with a list of sparse signals')
+    if any(q.ndim != 2 or q.shape[1] != sequences[0].shape[1] for q in sequences):
+        raise ValueError('%s: the sparse signals of a corpus must all be [T_b,F] with the same F' % who)
+    if any(q.dtype != sequences[0].dtype for q in sequences):
+        raise ValueError('%s: the signals of a corpus must share one dtype' % who)
+    seqs = []
+    for q in sequences:
+        m = q.tocsr()
+        if not m.has_canonical_format:
+            m = m.copy() if m is q else m
+            m.sum_duplicates()
+        seqs.append(m)
+    return seqs
+
+
+class DenseStack(object):
+    """What trainCorpus reads of a corpus of dense signals stacked without padding: `host` (what the loop cuts its reset
+    patches from: the stack [rows] or [rows,F]), the extremes of its elements, the initial atoms, and the upload."""
+
+    def __init__(self, seqs, F):
+        self.host = np.concatenate(seqs)                     # the signals' own samples, no padding
+        self.dtype, self.F = self.host.dtype, F
+        self.row_offsets = np.zeros((len(seqs) + 1,), dtype=np.int64)
+        self.row_offsets[1:] = np.cumsum([q.shape[0] for q in seqs])
+
+    def bounds(self):
+        return np.min(self.host), np.max(self.host)
+
+    def atoms(self, at, W):
+        """[len(at), W, F]: the rows at[i] .. at[i] + W of the stack."""
+        return self.host.reshape((-1, self.F))[at[:, np.newaxis] + np.arange(W)[np.newaxis, :]]
+
+    def upload(self, ctx, starts, W):
+        ctx.set_corpus(np.ascontiguousarray(self.host.reshape((-1, self.F))), self.row_offsets, starts, W)
+
+
+class SparseStack(object):
+    """DenseStack for a sparse corpus (CSR signals [T_b,F]): every value is the one the dense stack would give.  It is its
+    own `host`: dtype, ndim and dense patches stack[s:e], cut from the one signal that holds the stacked rows s .. e."""
+    ndim = 2
+
+    def __init__(self, seqs):
+        self.seqs = seqs
+        self.host = self
+        self.dtype = seqs[0].dtype
+        self.F = seqs[0].shape[1]
+        self.row_offsets = np.zeros((len(seqs) + 1,), dtype=np.int64)
+        self.row_offsets[1:] = np.cumsum([q.shape[0] for q in seqs])
+
+    def bounds(self):
+        """(np.min, np.max) of the dense stack: the stored entries, and 0 wherever a cell holds none."""
+        data = np.concatenate([q.data for q in self.seqs] + [np.zeros((0,), dtype=self.dtype)])
+        if data.shape[0] < int(self.row_offsets[-1]) * self.F:
+            data = np.concatenate([data, np.zeros((1,), dtype=self.dtype)])
+        return np.min(data), np.max(data)
+
+    def __getitem__(self, rows):
+        s, e = int(rows.start), int(rows.stop)
+        b = int(np.searchsorted(self.row_offsets, s, side='right')) - 1
+        assert e <= self.row_offsets[b + 1], 'a patch lies inside one signal'
+        lo = int(self.row_offsets[b])
+        return self.seqs[b][s - lo:e - lo].toarray()
+
+    def atoms(self, at, W):
+        return np.stack([self[int(s):int(s) + W] for s in at])
+
+    def upload(self, ctx, starts, W):
+        indptr, indices, data = self.csr()
+        ctx.set_corpus_sparse(indptr, indices, data, self.F, self.row_offsets, starts, W)
+
+    def csr(self):
+        """(indptr [rows+1] int64, indices int32, data) of the whole stack, as hsckmeans_set_corpus_sparse takes them."""
+        indptr = np.zeros((int(self.row_offsets[-1]) + 1,), dtype=np.int64)
+        base = 0
+        for b, q in enumerate(self.seqs):
+            indptr[self.row_offsets[b] + 1:self.row_offsets[b + 1] + 1] = base + q.indptr[1:].astype(np.int64)
+            base += int(q.indptr[-1])
+        indices = np.concatenate([q.indices.astype(np.int32, copy=False) for q in self.seqs])
+        data = np.concatenate([q.data for q in self.seqs])
+        return indptr, np.ascontiguousarray(indices), np.ascontiguousarray(data)
+
+
+def check_corpus_arguments(k, W, seqs, nbRandomWindows, initMethod, resetMethod, sparse=False):
     """The argument checks of trainCorpus (raised before any device call): the rules of check_arguments, the length
-    rule for every signal, and the element limit of the stack."""
+    rule for every signal, and the element limit of the stack (sparse: of the window stack, the only dense thing)."""
     W = int(W)
     _, F = check_arguments(k, W, (2 * max(W, 0) + 1,) + seqs[0].shape[1:], seqs[0].dtype, nbRandomWindows, initMethod, resetMethod)
     for b, q in enumerate(seqs):
         if 2 * W >= q.shape[0]:
             raise ValueError('k-means: signal %d has %d samples, windows of 2 * windowSize = %d samples need a longer signal' % (
                 b, q.shape[0], 2 * W))
-    if sum(q.shape[0] for q in seqs) * F > MAX_STACK_ELEMENTS:
+    if sparse:
+        if int(nbRandomWindows) * 2 * W * F > MAX_STACK_ELEMENTS:
+            raise NotImplementedError('k-means on the GPU: the window stack of a sparse corpus has more than 2^31 - 1 elements')
+    elif sum(q.shape[0] for q in seqs) * F > MAX_STACK_ELEMENTS:
         raise NotImplementedError('k-means on the GPU: the corpus has more than 2^31 - 1 elements in all')
     return F
 
@@ -219,6 +327,7 @@ class ConvolutionalKMeansLearner(object):
         self.rng = rng
         self.lastStats = None
         self.lastWindows = None                              # after trainCorpus: (signal [N], start [N]) of the drawn windows
+        self.lastSetupSeconds = None                         # after trainCorpus: wall time before the first step (draws, upload)
 
     def train(self, data, nbRandomWindows, maxIterations=100, tolerance=0.0, initMethod='random_samples',
               resetMethod='noise', nbAveragedPatches=8):
@@ -265,28 +374,35 @@ class ConvolutionalKMeansLearner(object):
         rule; 'noise': uniform between the smallest and largest sample of the signals), then per iteration the resets
         in centroid order, a reset's randint(0, N) naming a drawn window whose matched patch is cut from its own
         signal.  A corpus of one signal gives `train`'s result on that signal, bit for bit (values and dtype).
+        A list / tuple of scipy.sparse matrices [T_b,F] is a sparse corpus (the representations of a level, DESIGN.md section
+        19): the same draws and the same result as on [m.toarray() for m in sequences], bit for bit, with no dense copy of
+        the corpus on the host or the device; the element limit is then that of the window stack N * 2W * F.
         Returns D [K,W] or [K,W,F]; lastStats as after train, lastWindows = (signal [N], start [N])."""
-        seqs = corpus_signals(sequences, lengths)
+        t0 = time.perf_counter()
+        seqs = sparse_corpus_signals(sequences, lengths)
+        sparse = seqs is not None
+        if not sparse:
+            seqs = corpus_signals(sequences, lengths)
         W, K, N = self.windowSize, self.k, int(nbRandomWindows)
-        F = check_corpus_arguments(K, W, seqs, nbRandomWindows, initMethod, resetMethod)
+        F = check_corpus_arguments(K, W, seqs, nbRandomWindows, initMethod, resetMethod, sparse=sparse)
         load_library()                                       # no CPU path: fail before the first draw
         rng = _rng(self.rng)
-        row_offsets = np.zeros((len(seqs) + 1,), dtype=np.int64)
-        row_offsets[1:] = np.cumsum([q.shape[0] for q in seqs])
-        stack = np.concatenate(seqs)                         # [rows] or [rows,F]: the signals' own samples, no padding
+        stack = SparseStack(seqs) if sparse else DenseStack(seqs, F)
+        row_offsets = stack.row_offsets
         sig, start = corpus_windows(seqs, N, 2 * W, rng)
         if initMethod == 'noise':                            # _init_D (modeling.py:308-328) over the corpus
-            D = normalize(rng.uniform(low=np.min(stack), high=np.max(stack), size=(K, W, F)))
+            low, high = stack.bounds()
+            D = normalize(rng.uniform(low=low, high=high, size=(K, W, F)))
         else:
             ib, it = corpus_windows(seqs, K, W, rng)
-            rows = (row_offsets[ib] + it)[:, np.newaxis] + np.arange(W)[np.newaxis, :]
-            D = normalize(stack.reshape((-1, F))[rows])
-        if stack.ndim == 1:
+            D = normalize(stack.atoms(row_offsets[ib] + it, W))
+        if stack.host.ndim == 1:
             D = np.squeeze(D, axis=2)
-        starts = (row_offsets[sig] + start)[np.newaxis]      # stacked rows
+        starts = (row_offsets[sig] + start)[np.newaxis]      # stacked rows (a sparse corpus: the host's, for the reset patches)
         ctx = _context(self.device)
-        ctx.set_corpus(np.ascontiguousarray(stack.reshape((-1, F))), row_offsets, np.ascontiguousarray(starts[0]), W)
-        Ds, stats = self._loop(ctx, [stack], starts, [D], [self.rng], stack.dtype, F, maxIterations, tolerance, resetMethod,
+        stack.upload(ctx, np.ascontiguousarray(starts[0]), W)
+        self.lastSetupSeconds = time.perf_counter() - t0
+        Ds, stats = self._loop(ctx, [stack.host], starts, [D], [self.rng], stack.dtype, F, maxIterations, tolerance, resetMethod,
                                nbAveragedPatches)
         self.lastStats = stats[0]
         self.lastWindows = (sig, start)

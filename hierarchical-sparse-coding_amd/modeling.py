@@ -501,4 +501,7 @@ def __getattr__(name):
     if name in ('ConvolutionalDictionaryLearner', 'extractRandomWindows', 'extractWindows', 'extractWindowsBatch'):
         from . import learning
         return getattr(learning, name)
+    if name == 'MultilevelDictionaryLearner':
+        from . import multilevel
+        return multilevel.MultilevelDictionaryLearner
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

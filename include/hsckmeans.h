@@ -1,7 +1,7 @@
 /* hsckmeans.h -- C ABI of libhsckmeans.so: one iteration of the convolutional k-means learner
  * (ConvolutionalDictionaryLearner(algorithm='kmean'), hsc/modeling.py:420-524) on MI355X / gfx950, for a batch
  * of independent learners (hsckmeans_set_data), or for one learner over a corpus of signals of different lengths
- * (hsckmeans_set_corpus).  DESIGN.md sections 14 and 17.
+ * (hsckmeans_set_corpus, or hsckmeans_set_corpus_sparse for signals given as CSR).  DESIGN.md sections 14, 17 and 19.
  *
  * One context per host thread (contexts are not thread safe).  Every entry point returns HSCKMEANS_OK (0) or a
  * negative status; hsckmeans_last_error() describes the last failure.  There is no CPU path: without a visible
@@ -83,6 +83,26 @@ int hsckmeans_set_data(hsckmeans_ctx* ctx, const void* x, int dtype, int B, int 
  * learner: hsckmeans_step takes D [1][K][W][F] and mode [1] and returns [1][N] / [1][K] outputs. */
 int hsckmeans_set_corpus(hsckmeans_ctx* ctx, const void* x, int dtype, int B, const int64_t* row_offsets, int F,
                          const int64_t* starts, int N, int W);
+
+/* Upload a sparse corpus: the stacked signals of hsckmeans_set_corpus given as CSR, for representations that are a
+ * handful of non-zeros per thousand rows.  Replaces the data of an earlier hsckmeans_set_data /
+ * _set_corpus / _set_corpus_sparse (and the other way round).
+ *   row_offsets [B + 1]              as above: signal b is rows row_offsets[b] .. row_offsets[b + 1] of the stack
+ *   indptr      [rows + 1]           rows = row_offsets[B]; row r holds the entries indptr[r] .. indptr[r + 1]
+ *   indices     [indptr[rows]]       columns, strictly ascending within a row, in [0, F)
+ *   data        [indptr[rows]]       the entries' values, dtype as above (a stored zero is a zero)
+ *   starts      [N]                  stacked rows: window n is the dense rows starts[n] .. starts[n] + 2W
+ * The context afterwards holds ONE learner whose data is the window stack [N * 2W][F]: block n is the dense form of
+ * window n's rows, built on the device from the entries the windows cover (only those are uploaded), and the device
+ * start of window n is n * 2W.  hsckmeans_step then runs as after hsckmeans_set_corpus with these starts; out_t stays
+ * relative to the window.  Device memory is proportional to N * 2W * F plus the covered entries, never to rows * F.
+ * Checked on the host before any allocation or read of data: the rules of hsckmeans_set_corpus for the signals and
+ * windows; indptr[0] = 0, indptr non-decreasing, indptr[rows] <= 2^31 - 1, every row's columns ascending and in range,
+ * else HSCKMEANS_ERR_INVALID naming the row; N * 2W * F > 2^31 - 1: HSCKMEANS_ERR_UNSUPPORTED.  There is no limit on
+ * rows * F. */
+int hsckmeans_set_corpus_sparse(hsckmeans_ctx* ctx, int dtype, int B, const int64_t* row_offsets, int F,
+                                const int64_t* indptr, const int32_t* indices, const void* data,
+                                const int64_t* starts, int N, int W);
 
 /* The centroid plan of the later steps: HSCKMEANS_PLAN_AUTO, _LISTS or _WIDE (anything else: HSCKMEANS_ERR_INVALID).
  * Kept across hsckmeans_set_data / _set_corpus.  A step under plan 2 with K > HSCKMEANS_WIDE_MAX_K is refused. */
