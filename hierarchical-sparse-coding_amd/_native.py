@@ -18,8 +18,8 @@ F32, F64 = 0, 1
 STAT_NNZ, STAT_DUPLICATES, STAT_ROUNDS, STAT_STOP, STAT_ITERATIONS, STAT_EVENTS, STAT_SLOTS, STAT_OFFSET = range(8)
 STAT_COUNT = 8
 STOP_NAMES = {0: 'running', 1: 'energy_eps', 2: 'nnz', 3: 'snr', 4: 'residual_scale', 5: 'empty',
-              6: 'callback', 7: 'capacity', 8: 'stalled', 9: 'group', 100: 'host'}
-STOP_RUNNING, STOP_CAPACITY, STOP_STALLED, STOP_GROUP = 0, 7, 8, 9
+              6: 'callback', 7: 'capacity', 8: 'stalled', 9: 'group', 10: 'loaded', 100: 'host'}
+STOP_RUNNING, STOP_CAPACITY, STOP_STALLED, STOP_GROUP, STOP_LOADED = 0, 7, 8, 9, 10
 STOP_HOST = 100      # (host side only: the device loop gave the signal up -- stop reason 'group' -- and the host loop finished it)
 METHOD_CMP, METHOD_LOCOMP = 0, 1
 
@@ -27,7 +27,7 @@ METHOD_CMP, METHOD_LOCOMP = 0, 1
 EXPORTS = ['hscmp_version', 'hscmp_create', 'hscmp_destroy', 'hscmp_last_error', 'hscmp_set_stream', 'hscmp_set_method',
            'hscmp_synchronize', 'hscmp_set_dictionary', 'hscmp_convolve1d', 'hscmp_select_best_atoms',
            'hscmp_update_inner_products', 'hscmp_table_open', 'hscmp_table_select', 'hscmp_table_update', 'hscmp_table_read', 'hscmp_assign_windows', 'hscmp_host_overlap_add', 'hscmp_host_slots_to_csc', 'hscmp_hierarchy_epilogue', 'hscmp_encode_batch',
-           'hscmp_encode_batch_device', 'hscmp_encode_batch_ragged', 'hscmp_encode_batch_ragged_device', 'hscmp_encode_batch_from_level', 'hscmp_continue', 'hscmp_grow_events', 'hscmp_mem_info', 'hscmp_copy_from_device', 'hscmp_stop_signal', 'hscmp_fetch_events',
+           'hscmp_encode_batch_device', 'hscmp_encode_batch_ragged', 'hscmp_encode_batch_ragged_device', 'hscmp_encode_batch_from_level', 'hscmp_load_level', 'hscmp_continue', 'hscmp_grow_events', 'hscmp_mem_info', 'hscmp_copy_from_device', 'hscmp_stop_signal', 'hscmp_fetch_events',
            'hscmp_fetch_stats', 'hscmp_fetch_residual', 'hscmp_fetch_energies', 'hscmp_fetch_slots',
            'hscmp_get_device_view', 'hscmp_last_kernel_ms', 'hscmp_last_variant']
 
@@ -66,6 +66,8 @@ class HscmpError(RuntimeError):
 
 ERR_ALLOC = -6
 ERR_UNSUPPORTED = -5
+ERR_STATE = -4
+ERR_INVALID = -1
 
 
 _lib = None
@@ -108,6 +110,7 @@ def load_library():
     lib.hscmp_encode_batch_ragged.argtypes = [vp, vp, ci, ci, vp, ctypes.POINTER(HscmpParams)]
     lib.hscmp_encode_batch_ragged_device.argtypes = [vp, vp, ci, ci, vp, ctypes.POINTER(HscmpParams)]
     lib.hscmp_encode_batch_from_level.argtypes = [vp, vp, ci, ci, ctypes.c_double, ctypes.POINTER(HscmpParams)]
+    lib.hscmp_load_level.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp]
     lib.hscmp_continue.argtypes = [vp, ci]
     lib.hscmp_grow_events.argtypes = [vp, ci]
     lib.hscmp_mem_info.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
@@ -474,6 +477,21 @@ class Engine(object):
                                                             ctypes.byref(params)), 'hscmp_encode_batch_from_level')
         self._batch = (int(count), prev._batch[1], int(params.max_events))
 
+    def load_level(self, x, T, matrices):
+        """hscmp_load_level: the B scipy.sparse matrices [T, K] of `matrices` become this engine's batch, as if it had encoded
+        them (prev of encode_batch_from_level, fetch_slots, fetch_stats).  x: None, or the signals [B, T, F] in the
+        dictionary's dtype, which make the engine the level0 of hierarchy_epilogue.  Every matrix goes in as canonical CSC
+        (duplicates summed, zeros dropped, rows ascending inside a column); the caller's matrices are not changed."""
+        offsets, rows, cols, data, cap = pack_level(matrices, T, self.K)
+        B = len(matrices)
+        x3 = None
+        if x is not None:
+            x3 = np.ascontiguousarray(x, dtype=self.dtype)
+            assert x3.shape == (B, int(T), self.F)
+        self._batch = None                       # (a failure may leave the context without one)
+        self._check(self._lib.hscmp_load_level(self._h, _ptr(x3), B, int(T), _ptr(offsets), _ptr(rows), _ptr(cols), _ptr(data)), 'hscmp_load_level')
+        self._batch = (B, int(T), cap)
+
     def hierarchy_epilogue(self, level0, first, levels, minCoefficients, slot_counts, want_events=True, want_residual=True,
                            residual_out=None, energy_out=None):
         """hscmp_hierarchy_epilogue on this (last-level) engine.  levels: list of (col0, col1, representations [K,scale(,Fd)]).
@@ -596,6 +614,33 @@ class Engine(object):
 
     def last_variant(self):
         return self._lib.hscmp_last_variant(self._h).decode()
+
+
+def pack_level(matrices, T, K):
+    """The arguments of hscmp_load_level from B scipy.sparse matrices [T, K]: (offsets int64 [B + 1], rows int32, cols int32,
+    data float64, cap) -- every matrix as canonical CSC (tocsc, duplicates summed, explicit zeros dropped, row indices
+    sorted; copies: the caller's matrices stay as they are), its entries in (column, row) order; cap = max(1, longest)."""
+    import scipy.sparse
+    B = len(matrices)
+    offsets = np.zeros(B + 1, dtype=np.int64)
+    parts = []
+    for b, m in enumerate(matrices):
+        if not scipy.sparse.issparse(m) or m.shape != (int(T), int(K)):
+            raise ValueError('load_level: signal %d: expected a sparse matrix of shape (%d, %d), got %s' % (
+                b, T, K, getattr(m, 'shape', type(m).__name__)))
+        c = m.tocsc(copy=True)
+        c.sum_duplicates()
+        c.eliminate_zeros()
+        c.sort_indices()
+        parts.append((c.indices, np.repeat(np.arange(int(K), dtype=np.int32), np.diff(c.indptr)), c.data))
+        offsets[b + 1] = offsets[b] + c.nnz
+    n = int(offsets[-1])
+    rows, cols, data = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float64)
+    for b, (r, c, d) in enumerate(parts):
+        lo, hi = int(offsets[b]), int(offsets[b + 1])
+        rows[lo:hi], cols[lo:hi], data[lo:hi] = r, c, d
+    cap = max(1, int(np.diff(offsets).max())) if B else 1
+    return offsets, rows, cols, data, cap
 
 
 def _dictionary_key(D3, w):

@@ -162,7 +162,7 @@ struct Workspace {
 // Workspace arena of the entry points outside the batch encode (grow-only, lives as long as the context): the hierarchical
 // epilogue's buffers, then those of the row-level entry points and the device-resident table
 enum { kArenaEpiRep, kArenaEpiOffsets, kArenaEpiN, kArenaEpiColptr, kArenaEpiIndices, kArenaEpiData, kArenaEpiOut, kArenaEpiKeys,
-       kArenaRowA, kArenaRowB, kArenaRowC, kArenaRowD, kArenaTable, kArenaTabRes, kArenaTabW, kArenaEpiEnergy, kArenaSlots };
+       kArenaRowA, kArenaRowB, kArenaRowC, kArenaRowD, kArenaTable, kArenaTabRes, kArenaTabW, kArenaEpiEnergy, kArenaLoad, kArenaSlots };
 
 // The batch state and what it rests on (include/hscmp.h, "What a failed call leaves behind"):
 //  - a call that may replace the dictionary or a workspace buffer first drops what depends on it (drop_batch), in front of its
@@ -189,6 +189,9 @@ struct hscmp_ctx {
     // the batch
     int B = 0, T = 0, cap = 0, maxsel = 0;
     bool have_batch = false;
+    // the batch was handed over by hscmp_load_level, not encoded: only slot_t / slot_k / slot_a, stats and (with signals) x belong
+    // to it.  What resumes or reads an encode's state answers HSCMP_ERR_STATE (NEED_ENCODED)
+    bool loaded = false;
     DevParams P{};
     // ragged batch (hscmp_encode_batch_ragged): per signal {length, block size, block count} on the host and in ws.geom, until the
     // next encode of any kind; the batch's P.T is the longest length and every per-signal array keeps that stride
@@ -209,7 +212,7 @@ struct hscmp_ctx {
 // table and the listed rows belong to as well).
 static void drop_batch(hscmp_ctx* ctx, bool dictionary = false)
 {
-    ctx->have_batch = false; ctx->ragged = false; ctx->geom.clear();
+    ctx->have_batch = false; ctx->loaded = false; ctx->ragged = false; ctx->geom.clear();
     if (dictionary) { ctx->tab_T = 0; ctx->listed_rows = 0; }
 }
 
@@ -991,10 +994,104 @@ extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, in
     return HSCMP_OK;
 }
 
+// hscmp_load_level: the validation pass reads only the staged entries, so a rejected entry is known before anything of the
+// context changes; the buffers of the batch are replaced behind it, as an encode replaces them.
+extern "C" int hscmp_load_level(hscmp_ctx* ctx, const void* x, int B, int T, const int64_t* offsets, const int32_t* rows, const int32_t* cols,
+                                const double* data)
+{
+    const char* who = "hscmp_load_level";
+    if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "%s: ctx is NULL", who);
+    if (ctx->dict.dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "%s: no dictionary set", who);
+    if (B <= 0 || T <= 0 || !offsets) return fail(ctx, HSCMP_ERR_INVALID, "%s: bad arguments (B=%d T=%d)", who, B, T);
+    if (offsets[0] != 0) return fail(ctx, HSCMP_ERR_INVALID, "%s: offsets[0] is %lld, not 0", who, (long long)offsets[0]);
+    long long longest = 0;
+    for (int b = 0; b < B; ++b) {
+        if (offsets[b + 1] < offsets[b]) return fail(ctx, HSCMP_ERR_INVALID, "%s: signal %d: offsets decrease", who, b);
+        longest = std::max<long long>(longest, offsets[b + 1] - offsets[b]);
+    }
+    const long long n = offsets[B];
+    if (longest > (long long)T * ctx->dict.K || longest >= (1ll << 30))
+        return fail(ctx, HSCMP_ERR_INVALID, "%s: a list of %lld entries is longer than T x K = %d x %d distinct slots (or 2^30)", who, longest, T, ctx->dict.K);
+    if (n > 0 && (!rows || !cols || !data)) return fail(ctx, HSCMP_ERR_INVALID, "%s: %lld entries without their arrays", who, n);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    (void)read_knobs();                         // (arms HSCMP_ALLOC_FAIL_AT)
+    const int cap = (int)std::max(1ll, longest), K = ctx->dict.K, F = ctx->dict.F;
+    // staging, one arena slot: flag record, offsets, values, rows, columns (each 16-byte aligned)
+    const auto pad = [](size_t v) { return (v + 15) / 16 * 16; };
+    const size_t o_off = 16, o_data = o_off + pad((size_t)(B + 1) * 8), o_rows = o_data + pad((size_t)n * 8), o_cols = o_rows + pad((size_t)n * 4),
+                 total = o_cols + pad((size_t)n * 4);
+    int rc = epi_buffer(ctx, kArenaLoad, total);
+    if (rc) { if (rc == HSCMP_ERR_ALLOC) drop_batch(ctx); return rc; }     // (out of memory: no batch, like every other entry)
+    char* const stage = ctx->arena[kArenaLoad].as<char>();
+    unsigned long long* const d_flag = (unsigned long long*)stage;
+    const long long* const d_off = (const long long*)(stage + o_off);
+    const double* const d_data = (const double*)(stage + o_data);
+    const int* const d_rows = (const int*)(stage + o_rows);
+    const int* const d_cols = (const int*)(stage + o_cols);
+    const unsigned grid = (unsigned)((std::max<long long>(n, B) + kThreads - 1) / kThreads);
+    HIP_TRY(ctx, hipMemsetAsync(d_flag, 0xff, sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(stage + o_off, offsets, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (n > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(stage + o_data, data, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(stage + o_rows, rows, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(stage + o_cols, cols, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL((load_level_kernel<false>), dim3(grid), dim3(kThreads), 0, ctx->stream, d_off, d_rows, d_cols, d_data, n, B, T, K, cap,
+                           (int*)nullptr, (int*)nullptr, (double*)nullptr, (int*)nullptr, d_flag);
+        HIP_TRY(ctx, hipGetLastError());
+        unsigned long long flag = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (flag != ~0ull) {
+            static const char* const why[] = {"", "row outside [0, T)", "column outside [0, K)", "value zero or not finite",
+                                              "(column, row) not above the entry before it"};
+            const long long i = (long long)(flag >> 3);
+            const int reason = (int)(flag & 7);
+            int b = 0;
+            while (b + 1 < B && offsets[b + 1] <= i) ++b;
+            return fail(ctx, HSCMP_ERR_INVALID, "%s: signal %d, entry %lld (row %d, column %d; T=%d K=%d): %s", who, b, i - (long long)offsets[b],
+                        (int)rows[i], (int)cols[i], T, K, why[reason >= 1 && reason <= 4 ? reason : 0]);
+        }
+    }
+    // from here on as an encode: the batch goes first, then its buffers are replaced
+    drop_batch(ctx);
+    Workspace& w = ctx->ws;
+    const size_t xbytes = x ? (size_t)B * T * F * esize(ctx->dict.dtype) : 0;
+    const struct { DevBuf& buf; size_t bytes; } want[] = {
+        {w.slot_t, (size_t)B * cap * 4}, {w.slot_k, (size_t)B * cap * 4}, {w.slot_a, (size_t)B * cap * 8}, {w.stats, (size_t)B * ST_COUNT * sizeof(int)}, {w.x, xbytes}};
+    bool stream_idle = false;
+    for (const auto& b : want) {
+        if (b.bytes == 0 || b.buf.holds(b.bytes)) continue;
+        if (!stream_idle) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); stream_idle = true; }
+        const hipError_t e = b.buf.replace(b.bytes);
+        if (e != hipSuccess) return alloc_failed(ctx, b.bytes, e);
+    }
+    // (the lists are fetched whole: zero behind every signal's last entry)
+    HIP_TRY(ctx, hipMemsetAsync(w.slot_t.p, 0, (size_t)B * cap * 4, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(w.slot_k.p, 0, (size_t)B * cap * 4, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(w.slot_a.p, 0, (size_t)B * cap * 8, ctx->stream));
+    if (x) HIP_TRY(ctx, hipMemcpyAsync(w.x.p, x, xbytes, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL((load_level_kernel<true>), dim3(grid), dim3(kThreads), 0, ctx->stream, d_off, d_rows, d_cols, d_data, n, B, T, K, cap,
+                       w.slot_t.as<int>(), w.slot_k.as<int>(), w.slot_a.as<double>(), w.stats.as<int>(), d_flag);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->B = B; ctx->T = T; ctx->cap = cap; ctx->maxsel = 0;
+    ctx->P = DevParams{}; ctx->plan = EncodePlan{}; ctx->last = hscmp_params{};
+    ctx->last_x_dev = x ? w.x.p : nullptr;
+    ctx->timed = false;
+    ctx->variant = "loaded";
+    ctx->loaded = true; ctx->have_batch = true;
+    return HSCMP_OK;
+}
+
+// What only an encode leaves behind (its loop state, events, residual, energies)
+#define NOT_LOADED(ctx, name)                                                                   \
+    if (ctx->loaded) return fail(ctx, HSCMP_ERR_STATE, name ": the batch was loaded (hscmp_load_level), not encoded: it has slots and counters only");
+
 extern "C" int hscmp_continue(hscmp_ctx* ctx, int max_rounds)
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_continue: ctx is NULL");
     if (!ctx->have_batch) return fail(ctx, HSCMP_ERR_STATE, "hscmp_continue: no batch encoded");
+    NOT_LOADED(ctx, "hscmp_continue");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevParams P = ctx->P;
     P.max_rounds = max_rounds;
@@ -1013,6 +1110,7 @@ extern "C" int hscmp_grow_events(hscmp_ctx* ctx, int new_max_events)
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_grow_events: ctx is NULL");
     if (!ctx->have_batch) return fail(ctx, HSCMP_ERR_STATE, "hscmp_grow_events: no batch encoded");
+    NOT_LOADED(ctx, "hscmp_grow_events");
     if (new_max_events <= ctx->cap) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_grow_events: %d is not above the current capacity %d", new_max_events, ctx->cap);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1052,6 +1150,7 @@ extern "C" int hscmp_stop_signal(hscmp_ctx* ctx, int b)
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_stop_signal: ctx is NULL");
     if (!ctx->have_batch || b < 0 || b >= ctx->B) return fail(ctx, HSCMP_ERR_STATE, "hscmp_stop_signal: bad signal index %d", b);
+    NOT_LOADED(ctx, "hscmp_stop_signal");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int v = STOP_CALLBACK;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1077,6 +1176,7 @@ static int fetch(hscmp_ctx* ctx, void* dst, const void* src, size_t bytes)
 extern "C" int hscmp_fetch_events(hscmp_ctx* ctx, int32_t* ev_t, int32_t* ev_k, void* ev_c)
 {
     NEED_BATCH(ctx, "hscmp_fetch_events");
+    NOT_LOADED(ctx, "hscmp_fetch_events");
     const size_t n = (size_t)ctx->B * ctx->cap;
     int rc;
     if ((rc = fetch(ctx, ev_t, ctx->ws.ev_t.as<int>(), n * 4))) return rc;
@@ -1110,6 +1210,7 @@ extern "C" int hscmp_fetch_stats(hscmp_ctx* ctx, int32_t* stats)
 extern "C" int hscmp_fetch_residual(hscmp_ctx* ctx, void* residual)
 {
     NEED_BATCH(ctx, "hscmp_fetch_residual");
+    NOT_LOADED(ctx, "hscmp_fetch_residual");
     int rc = fetch(ctx, residual, ctx->ws.resid.p, (size_t)ctx->B * ctx->T * ctx->dict.F * esize(ctx->dict.dtype));
     if (rc) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1119,6 +1220,7 @@ extern "C" int hscmp_fetch_residual(hscmp_ctx* ctx, void* residual)
 extern "C" int hscmp_fetch_energies(hscmp_ctx* ctx, double* energies)
 {
     NEED_BATCH(ctx, "hscmp_fetch_energies");
+    NOT_LOADED(ctx, "hscmp_fetch_energies");
     if (!energies) return HSCMP_OK;
     const size_t n = (size_t)ctx->B * 2;
     if (ctx->dict.dtype == HSCMP_F64) {
@@ -1138,6 +1240,7 @@ extern "C" int hscmp_fetch_energies(hscmp_ctx* ctx, double* energies)
 extern "C" int hscmp_get_device_view(hscmp_ctx* ctx, hscmp_device_view* v)
 {
     NEED_BATCH(ctx, "hscmp_get_device_view");
+    NOT_LOADED(ctx, "hscmp_get_device_view");
     if (!v) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_get_device_view: view is NULL");
     v->B = ctx->B; v->T = ctx->T; v->F = ctx->dict.F; v->K = ctx->dict.K; v->W = ctx->dict.W; v->max_events = ctx->cap;
     v->dtype = ctx->dict.dtype; v->reserved = 0;
@@ -1335,6 +1438,7 @@ extern "C" int hscmp_hierarchy_epilogue(hscmp_ctx* last, hscmp_ctx* level0, int 
     if (!last || !level0) return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: NULL context");
     if (!last->have_batch || !level0->have_batch) return fail(last, HSCMP_ERR_STATE, "hscmp_hierarchy_epilogue: no batch encoded");
     if (last->ragged || level0->ragged) return fail(last, HSCMP_ERR_UNSUPPORTED, "hscmp_hierarchy_epilogue: a ragged batch has no hierarchical epilogue");
+    NOT_LOADED(last, "hscmp_hierarchy_epilogue (last level)");
     if (last->device != level0->device) return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: contexts on different GPUs");
     if (!levels || nlevels < 1 || nlevels > kEpiMaxLevels || !offsets || !out_n || !out_colptr || !out_indices || !out_data)
         return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: bad arguments");

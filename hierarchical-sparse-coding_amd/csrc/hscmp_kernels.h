@@ -457,6 +457,51 @@ __global__ __launch_bounds__(kThreads) void scatter_slots_kernel(R* __restrict__
     }
 }
 
+// Coefficient matrices the caller already holds, back into the strided slot lists (hscmp_load_level): entry i of the packed
+// arrays (signal b owns [offsets[b], offsets[b+1]), column-major inside a signal) becomes slot i - offsets[b] of signal b.
+// Launched FLAT over the entries -- list lengths are as skewed as the signals are busy, a workgroup per signal would wait for
+// the longest -- every thread finds its signal by bisection of the offsets table (B + 1 words, cached).
+//   UNPACK = false  validates and writes nothing but *flag: row in [0, T), column in [0, K), value finite and non-zero,
+//                   (column, row) strictly above the entry before it in the same signal -- which proves the slots distinct,
+//                   as the chain's scatter and the epilogue's keys assume.  *flag (preset to all ones) receives the
+//                   smallest 8 * i + reason of the offending entries (kLoad* below): the first one, whatever the schedule.
+//   UNPACK = true   writes the slots, and thread b < B the counters row of signal b: ST_SLOTS = its entry count, ST_STOP =
+//                   STOP_LOADED, zero everywhere else.  The lists must be zero filled behind every signal's last entry.
+//   grid = ceil(max(n, B) / kThreads), block = kThreads
+enum { kLoadBadRow = 1, kLoadBadCol = 2, kLoadBadValue = 3, kLoadBadOrder = 4 };
+template <bool UNPACK>
+__global__ __launch_bounds__(kThreads) void load_level_kernel(const long long* __restrict__ offsets, const int* __restrict__ rows,
+                                                              const int* __restrict__ cols, const double* __restrict__ data, long long n,
+                                                              int B, int T, int K, int cap, int* __restrict__ slot_t, int* __restrict__ slot_k,
+                                                              double* __restrict__ slot_a, int* __restrict__ stats, unsigned long long* __restrict__ flag)
+{
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (UNPACK && i < B) {
+        int* st = stats + i * ST_COUNT;
+        for (int j = 0; j < ST_COUNT; ++j) st[j] = j == ST_SLOTS ? (int)(offsets[i + 1] - offsets[i]) : j == ST_STOP ? STOP_LOADED : 0;
+    }
+    if (i >= n) return;
+    int lo = 0, hi = B;                                    // the last b with offsets[b] <= i: empty signals before it share its offset
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (offsets[mid] <= i) lo = mid; else hi = mid;
+    }
+    const long long o = offsets[lo];
+    const int t = rows[i], k = cols[i];
+    const double a = data[i];
+    if (UNPACK) {
+        const long long s = (long long)lo * cap + (i - o);
+        slot_t[s] = t; slot_k[s] = k; slot_a[s] = a;
+        return;
+    }
+    int reason = 0;
+    if (t < 0 || t >= T) reason = kLoadBadRow;
+    else if (k < 0 || k >= K) reason = kLoadBadCol;
+    else if (!(fabs(a) <= 1.7976931348623157e308) || a == 0.0) reason = kLoadBadValue;
+    else if (i > o && !(cols[i - 1] < k || (cols[i - 1] == k && rows[i - 1] < t))) reason = kLoadBadOrder;
+    if (reason) atomicMin(flag, (unsigned long long)i * 8ull + (unsigned long long)reason);
+}
+
 // Zero the cells of x [rows][F] that the row lists name (a row whose list overflowed: all of it).  After an encode
 // whose loop kept the lists current these are the only cells of the dense level input / residual that can be
 // non-zero, so the next batch's "zero filled" buffer costs a pass over the list counters instead of a memset of

@@ -175,14 +175,20 @@ class HierarchicalConvolutionalMatchingPursuit(SparseApproximator):
         return pipe.run_chained() if chained else pipe.run_unchained()
 
     def _host_epilogue_chunk(self, engines, first, count, nbLevels, multilevelDict, returnDistributed, sequences, results, returnEvents,
-                             residual_out, energy_out):
+                             residual_out, energy_out, startLevel=1):
         """The chunk's epilogue on the host (:1556-1634, :1596-1611) from the slot lists of every level's engine -- level 0 holds
-        the whole batch, the levels above it this chunk.  Same results as the device epilogue (tests/test_hierarchical.py)."""
+        the whole batch, the levels above it this chunk.  Same results as the device epilogue (tests/test_hierarchical.py).
+        startLevel > 1 (a resumed encode): the levels below it were not run, and the post-processing reads nothing of a level
+        below the last but its shape -- they go in as empty matrices."""
         from . import _native
         from .modeling import _slots_to_csc
         levels = []
         for l in range(nbLevels):
-            eng, off = engines[l], (first if l == 0 else 0)
+            if l < startLevel - 1:
+                shape = (engines[-1]._batch[1], int(multilevelDict.getRawDictionary(l).shape[0]))
+                levels.append([scipy.sparse.csc_matrix(shape, dtype=np.float64) for _ in range(count)])
+                continue
+            eng, off = engines[l], (first if l == startLevel - 1 else 0)
             st, sk, sa = eng.fetch_slots()
             stats = eng.fetch_stats()
             T = eng._batch[1]
@@ -253,6 +259,55 @@ class HierarchicalConvolutionalMatchingPursuit(SparseApproximator):
         return self._postprocessCoefficients(coefficients, multilevelDict, returnDistributed)
 
 
+    def computeCoefficientsFromLevelBatch(self, sequences, coefficients, multilevelDict, toleranceSnr=None, nbBlocks=1, singletonWeight=0.5,
+                                          returnDistributed=True, memoryBudget=None, epilogue='device', returnEvents=False, residuals=None):
+        """Batch form of computeCoefficientsFromLevel (hsc/modeling.py:1494-1554, :1645-1654): `coefficients[b]` is signal b's list
+        of per-level matrices of levels 0 .. L-1 -- what computeCoefficientsBatch(..., returnDistributed=False)[0] returned for a
+        dictionary of L levels -- of which, as in the reference (:1494-1500), only the last is read.  Levels L .. last of
+        `multilevelDict` are encoded: the matrices go back to the device as the results of level L-1 (hscmp_load_level), and the
+        pipeline of computeCoefficientsBatch carries on from there, with the same chunks, epilogues and fallback; the levels
+        below L are not encoded again.  With the dictionaries and parameters of levels < L unchanged, the results equal an
+        uninterrupted computeCoefficientsBatch bit for bit.  L == getNbLevels() encodes nothing and returns the post-processed
+        input.  residuals: None (the second item returned is None), 'samples' or 'energy' as for computeCoefficientsBatch.
+        The per-level timings list a level that was not run with variant 'loaded' and zero kernel times."""
+        reject_ragged(sequences, None, 'HierarchicalConvolutionalMatchingPursuit.computeCoefficientsFromLevelBatch')
+        assert residuals in (None, 'samples', 'energy')
+        assert _is_multilevel_dict(multilevelDict)
+        if self.method not in ('cmp', 'locomp'):
+            raise Exception('Unsupported sparse coding method: %s' % (self.method))
+        sequences = np.asarray(sequences)
+        fromLevel = _check_given_levels(sequences, coefficients, multilevelDict)
+        pipe = _LevelPipeline(self, sequences, multilevelDict, toleranceSnr, nbBlocks, singletonWeight, returnDistributed, epilogue,
+                              returnEvents, None, residuals, memoryBudget)
+        return pipe.run_from_level(coefficients, fromLevel)
+
+
+def _check_given_levels(sequences, coefficients, multilevelDict):
+    """The arguments of computeCoefficientsFromLevelBatch, before any native call: returns L, the number of levels given."""
+    if sequences.ndim not in (2, 3):
+        raise ValueError('computeCoefficientsFromLevelBatch: the signals must be [B,T] or [B,T,F] (got %d dimensions)' % sequences.ndim)
+    B, T = sequences.shape[0], sequences.shape[1]
+    if len(coefficients) != B:
+        raise ValueError('computeCoefficientsFromLevelBatch: %d signals, but coefficients of %d' % (B, len(coefficients)))
+    nbLevels = multilevelDict.getNbLevels()
+    L = None
+    for b, levels in enumerate(coefficients):
+        n = len(levels)
+        if not 1 <= n <= nbLevels:
+            raise ValueError('computeCoefficientsFromLevelBatch: signal %d has the coefficients of %d levels, outside 1 .. %d' % (b, n, nbLevels))
+        if L is None:
+            L = n
+        if n != L:
+            raise ValueError('computeCoefficientsFromLevelBatch: signal %d has the coefficients of %d levels, signal 0 of %d' % (b, n, L))
+        want = (T, int(multilevelDict.getRawDictionary(L - 1).shape[0]))
+        if not scipy.sparse.issparse(levels[-1]) or tuple(levels[-1].shape) != want:
+            raise ValueError('computeCoefficientsFromLevelBatch: signal %d: the matrix of level %d must be sparse with shape %s, got %s' % (
+                b, L - 1, want, getattr(levels[-1], 'shape', type(levels[-1]).__name__)))
+    if L is None:
+        raise ValueError('computeCoefficientsFromLevelBatch: no signals')
+    return L
+
+
 class _LevelPipeline(object):
     """One call of HierarchicalConvolutionalMatchingPursuit.computeCoefficientsBatch, step by step (hsc/modeling.py:1432-1492 per
     level, :1556-1634 / :1596-1611 afterwards).  method='locomp' (the reference's default, :1429) is the same pipeline with every
@@ -261,7 +316,9 @@ class _LevelPipeline(object):
       level_setup      dictionary, weights (:1448-1450), SNR target (:1439-1442) of a level
       encode_level     one level over a batch / chunk, with the event-capacity regrowth (hscmp_grow_events + hscmp_continue)
       chunk_size       signals per chunk of the levels >= 1 (their dense float64 input [T, F_l] lives on the device)
-      run_chunk_levels levels 1 .. last over one chunk (device-chained hand-off)
+      run_chunk_levels levels start .. last over one chunk (device-chained hand-off)
+      run_chunks       the chunk loop: run_chunk_levels and the epilogue per chunk, then the fallback signals
+      run_from_level   computeCoefficientsFromLevelBatch: engines loaded with the caller's matrices and the signals, then run_chunks
       device_epilogue / host_epilogue   redistribution, CSC, events, residual of a chunk
       fallback_signal  a signal the device loop gave up on (stop reason 'group'): the per-signal entry
       host_signal      signal b on the host, from the device when the batch was handed over as a device pointer"""
@@ -273,7 +330,8 @@ class _LevelPipeline(object):
         self.returnDistributed, self.returnEvents, self.deviceInput, self.residuals = returnDistributed, returnEvents, deviceInput, residuals
         self.memoryBudget = memoryBudget
         self.device_epilogue_on = epilogue == 'device'
-        assert residuals == 'samples' or self.device_epilogue_on, "residuals='energy' needs the device epilogue"
+        assert residuals != 'energy' or self.device_epilogue_on, "residuals='energy' needs the device epilogue"
+        self.given = None                                  # run_from_level: the caller's per-signal lists of level matrices
         self.locomp = hcmp.method == 'locomp'
         self.nbLevels = multilevelDict.getNbLevels()
         self.B, self.T = sequences.shape[0], sequences.shape[1]
@@ -360,6 +418,11 @@ class _LevelPipeline(object):
 
     def fallback_signal(self, b):
         """(coefficients, residual) of signal b through the per-signal entry (host-loop methods have no group limit)."""
+        if self.given is not None:
+            seq = self.host_signal(b)
+            cb = self.hcmp.computeCoefficientsFromLevel(seq, self.given[b], self.mld, toleranceSnr=self.toleranceSnr, nbBlocks=self.nbBlocks,
+                                                        singletonWeight=self.singletonWeight, returnDistributed=self.returnDistributed)
+            return cb, (self.hcmp._calculateResidual(seq, cb, self.mld) if self.residuals is not None else None)
         return self.hcmp.computeCoefficients(self.host_signal(b), self.mld, toleranceSnr=self.toleranceSnr, nbBlocks=self.nbBlocks,
                                              singletonWeight=self.singletonWeight, returnDistributed=self.returnDistributed)
 
@@ -384,28 +447,30 @@ class _LevelPipeline(object):
         return self.finish_on_host()
 
     # ---- chained = True
-    def chunk_size(self, setups, stats0):
+    def chunk_size(self, setups, stats0, start=1):
         """Per signal on the device, for EVERY level >= 1 at once (each level's engine keeps its workspace while the chunk moves up
         the hierarchy): the dense float64 residual [T, F_l] (the input is scattered straight into it), per-row state, and the event
-        / slot / hash lists (about 80 bytes per list entry, sized from the level-0 counts)."""
+        / slot / hash lists (about 80 bytes per list entry, sized from the level-0 counts).  start: the first level that is
+        encoded in chunks (a resumed encode: the first level that is encoded at all; stats0 are then the loaded counters)."""
         from . import _native
-        if self.nbLevels == 1:
+        if self.nbLevels <= start:
             return self.B
         budget = self.memoryBudget
         if budget is None:
             budget = 0.6 * self.engines[0].mem_info()[1]      # (of the total: the cached engines already hold their workspaces)
         nin0 = int(stats0[:, _native.STAT_SLOTS].max()) if self.B else 0
-        per_signal = sum(1.05 * self.T * setups[l][0].shape[2] * 8 + 160 * self.T + 80.0 * max(4096, 2 * nin0) for l in range(1, self.nbLevels))
+        per_signal = sum(1.05 * self.T * setups[l][0].shape[2] * 8 + 160 * self.T + 80.0 * max(4096, 2 * nin0) for l in range(start, self.nbLevels))
         return int(max(1, min(self.B, budget // max(per_signal, 1.0))))
 
-    def run_chunk_levels(self, setups, first, count, stats0):
-        """Levels 1 .. last over signals [first, first + count); returns the last level's stats."""
+    def run_chunk_levels(self, setups, first, count, stats0, start=1):
+        """Levels start .. last over signals [first, first + count); returns the last level's stats.  The engine of level
+        start - 1 holds the whole batch -- encoded (level 0), or loaded (run_from_level) -- and stats0 are its counters."""
         from . import _native
         engines = self.engines
         last_stats = stats0
-        for l in range(1, self.nbLevels):
+        for l in range(start, self.nbLevels):
             _, _, targetSnr, eps = setups[l]
-            prev, pfirst = (engines[0], first) if l == 1 else (engines[l - 1], 0)
+            prev, pfirst = (engines[l - 1], first) if l == start else (engines[l - 1], 0)
             # every input non-zero is explained at least once (by its singleton): size the lists for that
             nin = int(last_stats[pfirst:pfirst + count, _native.STAT_SLOTS].max())
             coefs, tm, last_stats = self.encode_level(
@@ -420,7 +485,7 @@ class _LevelPipeline(object):
             acc['kernel_ms'] = [a + b for a, b in zip(acc['kernel_ms'], tm['kernel_ms'])]
         return last_stats
 
-    def epilogue_chunk(self, first, count, stats0, last_stats, results, residual_all, energy_all):
+    def epilogue_chunk(self, first, count, stats0, last_stats, results, residual_all, energy_all, start=1):
         from . import _native
         nbLevels = self.nbLevels
         o = first if nbLevels == 1 else 0
@@ -437,7 +502,7 @@ class _LevelPipeline(object):
                 raise
             seqs = _ChunkSignals(self, first)
             self.hcmp._host_epilogue_chunk(self.engines, first, count, nbLevels, self.mld, self.returnDistributed, seqs, results,
-                                           self.returnEvents, res_out, en_out)
+                                           self.returnEvents, res_out, en_out, startLevel=start)
 
     def run_chained(self):
         from . import _native
@@ -452,7 +517,6 @@ class _LevelPipeline(object):
         dt = self.dt0 = _compute_dtype(sequences.dtype, D.dtype)
         D3 = np.ascontiguousarray(D.reshape((D.shape[0], D.shape[1], -1)), dtype=dt)
         engines[0].set_dictionary(D3, np.asarray(weights, dtype=dt))
-        nfeat = int(np.prod(np.asarray(sequences).shape[2:])) if np.asarray(sequences).ndim > 2 else 1
         if self.deviceInput is not None:
             assert np.asarray(sequences).dtype == dt, 'deviceInput must hold the level-0 compute dtype'
             enc0 = lambda p: engines[0].encode_batch_device(int(self.deviceInput), B, T, p)
@@ -466,7 +530,61 @@ class _LevelPipeline(object):
         for l in range(1, nbLevels):
             engines[l].set_dictionary(setups[l][0], setups[l][1], dtype=np.float64)
             self.timings.append(dict(level=l, variant='', kernel_ms=[0.0, 0.0, 0.0, 0.0], selections=0, duplicates=0, rounds=0, chunks=0))
-        chunk = self.chunk_size(setups, stats0)
+        return self.run_chunks(setups, stats0, 1)
+
+    def run_from_level(self, coefficients, fromLevel):
+        """computeCoefficientsFromLevelBatch: levels fromLevel .. last, from the caller's matrices of level fromLevel - 1.  Engine
+        fromLevel - 1 is loaded with them (hscmp_load_level) and engine 0 -- always -- with the signals ([B][T][F0]: small beside
+        any level input), so that the epilogue has one path; the chunks, their levels and their epilogue are run_chained's."""
+        from . import _native
+        from .modeling import _compute_dtype
+        B, T, nbLevels = self.B, self.T, self.nbLevels
+        self.given = coefficients
+        loaded = lambda l: dict(level=l, variant='loaded', kernel_ms=[0.0, 0.0, 0.0, 0.0], selections=0, duplicates=0, rounds=0, chunks=0)
+        if fromLevel == nbLevels:
+            # nothing to encode: the post-processed input (:1645-1654 with an empty level loop)
+            for l in range(nbLevels):
+                self.per_level[l] = [coefficients[b][l] for b in range(B)]
+            self.timings = [loaded(l) for l in range(nbLevels)]
+            return self.second_as_asked(self.finish_on_host())
+        engines = self.engines = self.hcmp._level_engines(nbLevels)
+        for e in engines:
+            e.set_method(_native.METHOD_LOCOMP if self.locomp else _native.METHOD_CMP)
+        D, weights, _, _ = self.level_setup(0)
+        dt = self.dt0 = _compute_dtype(self.sequences.dtype, D.dtype)
+        engines[0].set_dictionary(np.ascontiguousarray(D.reshape((D.shape[0], D.shape[1], -1)), dtype=dt), np.asarray(weights, dtype=dt))
+        setups = [None] + [self.level_setup(l) for l in range(1, nbLevels)]
+        for l in range(1, nbLevels):
+            engines[l].set_dictionary(setups[l][0], setups[l][1], dtype=np.float64)
+        self.timings = [loaded(l) if l < fromLevel else dict(loaded(l), variant='') for l in range(nbLevels)]
+        x = np.ascontiguousarray(self.sequences.reshape((B, T, -1)), dtype=dt)
+        given = [coefficients[b][-1] for b in range(B)]
+        if fromLevel == 1:
+            engines[0].load_level(x, T, given)
+        else:
+            engines[0].load_level(x, T, [scipy.sparse.csc_matrix((T, engines[0].K), dtype=np.float64)] * B)
+            engines[fromLevel - 1].load_level(None, T, given)
+        for l in range(fromLevel):
+            self.per_level[l] = [coefficients[b][l] for b in range(B)]      # (host epilogue: the levels as given)
+        return self.second_as_asked(self.run_chunks(setups, engines[fromLevel - 1].fetch_stats(), fromLevel))
+
+    def second_as_asked(self, out):
+        """The second item a resumed encode returns: None unless residuals were asked for; energies from host residuals."""
+        second = out[1]
+        if self.residuals is None:
+            second = None
+        elif self.residuals == 'energy' and second is not None and np.ndim(second) > 1:
+            second = np.sum(np.square(np.asarray(second, dtype=np.float64)).reshape((self.B, -1)), axis=1)
+        return (out[0], second) + tuple(out[2:])
+
+    def run_chunks(self, setups, stats0, start):
+        """The chunks of the batch through levels start .. last and their epilogue; stats0: the counters of engine start - 1,
+        which holds the whole batch."""
+        from . import _native
+        B, T, nbLevels = self.B, self.T, self.nbLevels
+        sequences = self.sequences
+        nfeat = int(np.prod(np.asarray(sequences).shape[2:])) if np.asarray(sequences).ndim > 2 else 1
+        chunk = self.chunk_size(setups, stats0, start)
         dev_epi = self.device_epilogue_on
         results = [None] * B
         residual_all = np.empty((B, T, nfeat), dtype=np.float64) if (dev_epi and self.residuals == 'samples') else None
@@ -475,7 +593,7 @@ class _LevelPipeline(object):
         while first < B and (nbLevels > 1 or dev_epi):
             count = min(chunk, B - first)
             try:
-                last_stats = self.run_chunk_levels(setups, first, count, stats0)
+                last_stats = self.run_chunk_levels(setups, first, count, stats0, start)
             except _native.HscmpError as ex:
                 # out of device memory part-way through a chunk (the budget is an estimate): halve the chunk, run it again
                 if ex.code == _native.ERR_ALLOC and count > 1:
@@ -483,7 +601,7 @@ class _LevelPipeline(object):
                     continue
                 raise
             if dev_epi:
-                self.epilogue_chunk(first, count, stats0, last_stats, results, residual_all, energy_all)
+                self.epilogue_chunk(first, count, stats0, last_stats, results, residual_all, energy_all, start)
             first += count
         if not dev_epi:
             return self.finish_on_host()
@@ -500,6 +618,8 @@ class _LevelPipeline(object):
                 energy_all[b] = float(np.sum(np.square(np.asarray(res_b, dtype=np.float64))))
         if energy_all is not None:
             second = energy_all
+        elif residual_all is None:
+            second = None                                  # (a resumed encode that was not asked for residuals)
         else:
             second = residual_all[:, :, 0] if np.asarray(sequences).ndim == 2 else residual_all
         out = ([r[0] for r in results], second, self.timings)
@@ -517,7 +637,7 @@ class _LevelPipeline(object):
             levels = [self.per_level[l][b] for l in range(nbLevels)]
             levels = [_slots_to_csc(*c) if isinstance(c, tuple) else c for c in levels]
             cb = self.hcmp._postprocessCoefficients(levels, self.mld, self.returnDistributed)
-            return cb, self.hcmp._calculateResidual(self.host_signal(b), cb, self.mld)
+            return cb, (self.hcmp._calculateResidual(self.host_signal(b), cb, self.mld) if self.residuals is not None else None)
         workers = max(1, min(int(os.environ.get('HSC_EPILOGUE_WORKERS', '16')), os.cpu_count() or 1, B))
         if workers > 1 and self.deviceInput is None:
             from concurrent.futures import ThreadPoolExecutor
@@ -526,7 +646,7 @@ class _LevelPipeline(object):
         else:
             done = [finish(b) for b in range(B)]         # (device copies go through one engine: one thread)
         coefficients = [d[0] for d in done]
-        out = (coefficients, np.stack([d[1] for d in done], axis=0), self.timings)
+        out = (coefficients, np.stack([d[1] for d in done], axis=0) if self.residuals is not None else None, self.timings)
         if self.returnEvents:
             from .dataset import convertSparseMatricesToEvents
             out = out + ([convertSparseMatricesToEvents(c) for c in coefficients],)
@@ -580,6 +700,15 @@ class HierarchicalConvolutionalSparseCoder(object):
     def encodeFromLevel(self, sequence, coefficients, *args, **kwargs):
         assert len(coefficients) > 0
         return self.approximator.computeCoefficientsFromLevel(sequence, coefficients, self.multilevelDict, *args, **kwargs)
+
+    def encodeBatch(self, sequences, *args, **kwargs):
+        """encode for a batch [B,T] / [B,T,F]: the approximator's computeCoefficientsBatch."""
+        return self.approximator.computeCoefficientsBatch(sequences, self.multilevelDict, *args, **kwargs)
+
+    def encodeFromLevelBatch(self, sequences, coefficients, *args, **kwargs):
+        """encodeFromLevel for a batch: coefficients[b] is signal b's list of level matrices."""
+        assert len(coefficients) > 0
+        return self.approximator.computeCoefficientsFromLevelBatch(sequences, coefficients, self.multilevelDict, *args, **kwargs)
 
     def reconstruct(self, coefficients):
         assert len(coefficients) > 0

@@ -32,8 +32,9 @@ class MultilevelDictionaryLearner(object):
 
     lastStats (after trainCorpus): one dict per level with kmeans (the learner's lastStats), input_shape ((B, T, F) of
     the level's input), input_nnz (its stored non-zeros; level 0: None), setup_s (k-means before its first step: draws,
-    packing, upload and window build), learn_s, encode_s (wall time of the batch encode; the last level: None) and
-    encode_nnz (coefficients stored in the matrices handed to the next level)."""
+    packing, upload and window build), learn_s, encode_s (wall time of the batch encode -- of the resumed one under
+    resume=True; the last level: None), encode_timings (the encoder's per-level timings of that encode: a level that was
+    not run again has variant 'loaded') and encode_nnz (coefficients stored in the matrices handed to the next level)."""
 
     def __init__(self, counts, scales, method='locomp', device=0, rng=None):
         self.counts = [int(k) for k in counts]
@@ -69,10 +70,15 @@ class MultilevelDictionaryLearner(object):
         return self.trainCorpus(np.asarray(sequence)[np.newaxis], nbRandomWindows, **kwargs)
 
     def trainCorpus(self, sequences, nbRandomWindows, maxIterations=100, tolerance=0.0, initMethod='random_samples',
-                    resetMethod='noise', nbAveragedPatches=8, toleranceSnr=None, nbBlocks=1, singletonWeight=0.5, lengths=None):
+                    resetMethod='noise', nbAveragedPatches=8, toleranceSnr=None, nbBlocks=1, singletonWeight=0.5, lengths=None,
+                    resume=True):
         """`sequences` [B,T] or [B,T,F].  The k-means arguments go to every level's trainCorpus; toleranceSnr (one value, or
         one per level), nbBlocks and singletonWeight to every encode.  Returns the MultilevelDictionary of all levels
-        (levels >= 1 with their singleton bases, as the reference builds it)."""
+        (levels >= 1 with their singleton bases, as the reference builds it).
+        resume=True: from level 1 on, the hand-off encode carries on from the previous pass's coefficients
+        (computeCoefficientsFromLevelBatch, as the reference's script calls encodeFromLevel) and runs the new level only;
+        resume=False encodes the levels below again.  The dictionaries are the same bit for bit either way: the lower
+        levels' dictionaries and parameters have not changed."""
         from .hierarchical import HierarchicalConvolutionalMatchingPursuit
         sequences = self._check(sequences, lengths)
         if toleranceSnr is not None and isinstance(toleranceSnr, collections.abc.Iterable) and len(toleranceSnr) < len(self.counts) - 1:
@@ -83,7 +89,7 @@ class MultilevelDictionaryLearner(object):
         B = sequences.shape[0]
         hcmp = HierarchicalConvolutionalMatchingPursuit(method=self.method, device=self.device)
         dictionaries, stats = [], []
-        inputs, mld = sequences, None
+        inputs, mld, coefficients = sequences, None, None
         try:
             for level in range(nbLevels):
                 sparse = level > 0
@@ -100,11 +106,17 @@ class MultilevelDictionaryLearner(object):
                 t2 = time.perf_counter()
                 st = dict(kmeans=learner.lastStats, learn_s=t1 - t0, setup_s=learner.lastSetupSeconds,
                           input_shape=(B,) + tuple(inputs[0].shape) if sparse else tuple(sequences.shape),
-                          input_nnz=int(sum(m.nnz for m in inputs)) if sparse else None, encode_s=None, encode_nnz=None)
+                          input_nnz=int(sum(m.nnz for m in inputs)) if sparse else None, encode_s=None, encode_nnz=None, encode_timings=None)
                 if level < nbLevels - 1:
-                    # (the levels below are encoded again: their dictionaries and parameters are those of the last pass)
-                    coefficients = hcmp.computeCoefficientsBatch(sequences, mld, toleranceSnr=toleranceSnr, nbBlocks=nbBlocks,
-                                                                 singletonWeight=singletonWeight, returnDistributed=False)[0]
+                    if resume and level > 0:
+                        # (the levels below keep the last pass's dictionaries and parameters: their coefficients are in hand)
+                        coefficients, _, st['encode_timings'] = hcmp.computeCoefficientsFromLevelBatch(
+                            sequences, coefficients, mld, toleranceSnr=toleranceSnr, nbBlocks=nbBlocks, singletonWeight=singletonWeight,
+                            returnDistributed=False)
+                    else:
+                        # (resume=False: the levels below are encoded again, to the same bits)
+                        coefficients, _, st['encode_timings'] = hcmp.computeCoefficientsBatch(
+                            sequences, mld, toleranceSnr=toleranceSnr, nbBlocks=nbBlocks, singletonWeight=singletonWeight, returnDistributed=False)
                     inputs = [c[-1] for c in coefficients]
                     st['encode_s'] = time.perf_counter() - t2
                     st['encode_nnz'] = int(sum(m.nnz for m in inputs))

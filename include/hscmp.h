@@ -51,7 +51,9 @@ typedef enum hscmp_status {
  *    hscmp_hierarchy_epilogue answer HSCMP_ERR_STATE, and the next encode works.  The dictionary stays, and so does the
  *    batch of the previous level of a failed hscmp_encode_batch_from_level.
  *  - a failed hscmp_grow_events, hscmp_hierarchy_epilogue or hscmp_table_open leaves the batch (or batches) as they were;
- *    after a failed hscmp_table_open no table is open. */
+ *    after a failed hscmp_table_open no table is open.
+ *  - hscmp_load_level that rejects an argument or an entry (HSCMP_ERR_INVALID) leaves the context exactly as it was, batch
+ *    included; one that runs out of memory (HSCMP_ERR_ALLOC) leaves NO batch, like an encode. */
 
 typedef enum hscmp_dtype { HSCMP_F32 = 0, HSCMP_F64 = 1 } hscmp_dtype;
 
@@ -66,9 +68,10 @@ typedef enum hscmp_stop {
     HSCMP_STOP_CALLBACK = 6,       /* modeling.py:1155-1158, decided by the host between rounds */
     HSCMP_STOP_CAPACITY = 7,       /* event buffer full: re-run with a larger max_events */
     HSCMP_STOP_STALLED = 8,        /* LoCOMP only, modeling.py:1379-1383: an atom changed the residual energy by less than eps */
-    HSCMP_STOP_GROUP = 9           /* LoCOMP only: a neighbourhood beyond the signal's group scratch (more than 511 atoms around one
+    HSCMP_STOP_GROUP = 9,          /* LoCOMP only: a neighbourhood beyond the signal's group scratch (more than 511 atoms around one
                                       selection; HSCMP_LOCOMP_GROUP_CAP lowers it), modeling.py:1222-1241; nothing of that atom has been
                                       applied: repeat the signal through the hscmp_table_* loop (or the reference's own LoCOMP) */
+    HSCMP_STOP_LOADED = 10         /* no encode ran: the coefficients were handed over by the caller (hscmp_load_level) */
 } hscmp_stop;
 
 /* which loop hscmp_encode_batch* / hscmp_continue run: ConvolutionalMatchingPursuit.computeCoefficients (modeling.py:1053-1186)
@@ -188,6 +191,30 @@ int hscmp_encode_batch_ragged_device(hscmp_ctx* ctx, const void* x_dev, int B, i
  * contexts live on the same GPU. */
 int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, int first, int count, double min_coefficients,
                                   const hscmp_params* params);
+
+/* The inverse of hscmp_fetch_slots, for a hierarchy that is encoded one level at a time (the reference's encodeFromLevel,
+ * modeling.py:1494-1554, in batch form): coefficient matrices [T][K] the caller already holds -- K the atom count of ctx's
+ * dictionary, which must be set -- become the context's batch of B signals of length T, as if an encode had produced them.
+ *   - signal b owns entries [offsets[b], offsets[b+1]) of rows / cols / data (host arrays; offsets int64 [B + 1],
+ *     offsets[0] == 0); a signal may own none.  Inside a signal the entries are in column-major (CSC) order: column
+ *     ascending, then row ascending, strictly -- which is what proves them distinct;
+ *   - x: NULL, or the signals [B][T][F] in the dictionary's dtype (host): they become the context's resident input, so
+ *     that hscmp_hierarchy_epilogue accepts the context as `level0`.
+ * Every entry is checked on the device before anything of the context changes: row in [0, T), column in [0, K), value
+ * finite and non-zero, strict (column, row) order.  The first offending entry gives HSCMP_ERR_INVALID, hscmp_last_error
+ * names its signal and its index in the signal, and the context keeps the batch it had.
+ * The context then holds slot lists of capacity max(1, longest list), counters (HSCMP_STAT_SLOTS = the entry count,
+ * HSCMP_STAT_STOP = HSCMP_STOP_LOADED, zero elsewhere) and, with x, the input -- and nothing else: no residual, no table,
+ * no event lists are allocated (a level's [B][T][K] float64 buffer is exactly what this call avoids).  It serves
+ * hscmp_encode_batch_from_level as `prev`, hscmp_fetch_slots, hscmp_fetch_stats and, with x, hscmp_hierarchy_epilogue as
+ * `level0`.  hscmp_continue, hscmp_grow_events, hscmp_stop_signal, hscmp_fetch_events / _residual / _energies,
+ * hscmp_get_device_view and the epilogue's `last` role answer HSCMP_ERR_STATE ("the batch was loaded").
+ * The slot order differs from the first-selection order an encode leaves, and that is safe: the chain's scatter writes
+ * distinct cells in any order, and the prepare kernels of the chain sum the input energy in ascending cell index whatever
+ * the slot order (each of the 256 pinned partial sums sorts its own cells).  A chain from a loaded context therefore sees
+ * the same input and the same energy, bit for bit, as a chain from the context that computed those coefficients. */
+int hscmp_load_level(hscmp_ctx* ctx, const void* x, int B, int T, const int64_t* offsets, const int32_t* rows,
+                     const int32_t* cols, const double* data);
 
 /* Window assignment of the convolutional k-means dictionary learner (ConvolutionalDictionaryLearner.
  * _train_kmean, modeling.py:454-460 = convolve1d_batch(windows, D, 'valid') + arg-max of |c| per window):

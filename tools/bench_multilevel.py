@@ -11,11 +11,19 @@ set-up: draws, packing, upload and the window gather) and the batch encode that 
       does before its first step, and of the library call alone; alternating, median of 5 with [min, max]; the first
       step's outputs of both are compared byte for byte.
 
+  (a4), (b4) the same two with a fourth level (counts 16 / 32 / 64 / 64, scales 32 / 64 / 96 / 128): the shape at which the
+      hand-off encodes repeat the most lower-level work.
+  --resume 1 (the learner's default) hands every level from 1 on its input by a resumed encode
+  (computeCoefficientsFromLevelBatch: the new level only); --resume 0 encodes the levels below again, as before.  Every
+  encode row lists the encoder's own per-level kernel times, and (--resume 1) the time of Engine.load_level alone on the
+  matrices handed over: packing, upload and the unpack kernel, median of 5 with [min, max].
+
 Every figure is a host wall clock around work that ends in a device synchronise.
 
-  python tools/bench_multilevel.py [--out profiles/multilevel_bench.json] [--shape a|b|both] [--handoff] [--quick]
+  python tools/bench_multilevel.py [--out profiles/multilevel_bench.json] [--shape a|b|both|a4|b4] [--resume 0|1] [--handoff] [--quick]
 """
 import argparse
+import hashlib
 import json
 import os
 import re
@@ -35,6 +43,7 @@ from hsc_amd.kmeans import ConvolutionalKMeansLearner, SparseStack  # noqa: E402
 from hsc_amd.modeling import HierarchicalConvolutionalMatchingPursuit, MultilevelDictionaryLearner  # noqa: E402
 
 COUNTS, SCALES = [16, 32, 64], [32, 64, 96]
+COUNTS4, SCALES4 = [16, 32, 64, 64], [32, 64, 96, 128]
 ENCODE = dict(toleranceSnr=10.0, nbBlocks=10, singletonWeight=0.95)
 REPS = 5
 
@@ -44,20 +53,50 @@ def data(B, T):
     return gd.signals(truth, B, T, rate=2e-3, compression=None)[0]
 
 
-def learn(x, N, iterations, counts=COUNTS, scales=SCALES):
+def learn(x, N, iterations, counts=COUNTS, scales=SCALES, resume=True):
     learner = MultilevelDictionaryLearner(counts, scales, method='cmp', rng=np.random.RandomState(1))
     t0 = time.perf_counter()
-    learner.trainCorpus(x, N, maxIterations=iterations, tolerance=0.0, resetMethod='random_samples', **ENCODE)
+    learner.trainCorpus(x, N, maxIterations=iterations, tolerance=0.0, resetMethod='random_samples', resume=resume, **ENCODE)
     total = time.perf_counter() - t0
     levels = []
     for level, s in enumerate(learner.lastStats):
         row = dict(level=level, input_shape=list(s['input_shape']), input_nnz=s['input_nnz'], learn_s=s['learn_s'], setup_s=s['setup_s'],
                    step_ms=[it['step_ms'] for it in s['kmeans']], encode_s=s['encode_s'], encode_nnz=s['encode_nnz'])
+        if s['encode_timings'] is not None:                                    # the encoder's own account, level by level
+            row['encode_levels'] = [dict(level=t['level'], variant=t['variant'], kernel_ms=float(sum(t['kernel_ms']))) for t in s['encode_timings']]
         levels.append(row)
         print('level %d: input %s nnz %s, learnt in %.3f s (set-up %.3f s), encode %s s, stored %s' % (
             level, row['input_shape'], row['input_nnz'], row['learn_s'], row['setup_s'],
             'none' if row['encode_s'] is None else '%.3f' % row['encode_s'], row['encode_nnz']), flush=True)
-    return dict(total_s=total, levels=levels)
+    return dict(total_s=total, encode_total_s=float(sum(r['encode_s'] or 0.0 for r in levels)), resume=bool(resume), levels=levels,
+                dictionary_sha256=[hashlib.sha256(np.ascontiguousarray(D).tobytes()).hexdigest() for D in learner.lastDictionaries])
+
+
+def load_level_alone(x, N, iterations):
+    """Engine.load_level on the level-0 matrices of the corpus, as a resumed encode of level 1 does it: packing, upload, kernel."""
+    from hsc_amd import _native
+    reps, _ = level0_representations(x, N, iterations)
+    T, K = reps[0].shape
+    eng = _native.Engine(0)
+    try:
+        eng.set_dictionary(np.random.RandomState(0).standard_normal((K, 8)))
+        x3 = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape((len(reps), T, 1)))
+        times = dict(with_signals_s=[], matrices_only_s=[], pack_s=[])
+        for rep in range(REPS + 1):                                        # rep 0: allocations and the first launch
+            t0 = time.perf_counter()
+            eng.load_level(x3, T, reps)
+            t1 = time.perf_counter()
+            eng.load_level(None, T, reps)
+            t2 = time.perf_counter()
+            _native.pack_level(reps, T, K)
+            t3 = time.perf_counter()
+            if rep:
+                times['with_signals_s'].append(t1 - t0); times['matrices_only_s'].append(t2 - t1); times['pack_s'].append(t3 - t2)
+    finally:
+        eng.close()
+    row = dict(signals=len(reps), T=int(T), K=int(K), nnz=int(sum(m.nnz for m in reps)), signal_bytes=int(x3.nbytes))
+    row.update({k: median_range(v) for k, v in times.items()})
+    return row
 
 
 def dense_handoff(T):
@@ -143,31 +182,42 @@ def save(out, path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'multilevel_bench.json'))
-    ap.add_argument('--shape', default='both', choices=['a', 'b', 'both'])
+    ap.add_argument('--shape', default='both', choices=['a', 'b', 'both', 'a4', 'b4'])
+    ap.add_argument('--resume', type=int, default=1, choices=[0, 1], help='1: resumed hand-off encodes (the default of trainCorpus); 0: full re-encode')
     ap.add_argument('--handoff', action='store_true', help='(a): also run tools/learn_mlcsc.py with KMEANS=device')
     ap.add_argument('--quick', action='store_true', help='a rehearsal: short signals, few windows')
     a = ap.parse_args()
     N, iterations = (500, 2) if a.quick else (10000, 10)
-    out = dict(counts=COUNTS, scales=SCALES, windows=N, iterations=iterations, encode=ENCODE, method='cmp')
-    if a.shape in ('a', 'both'):
+    four = a.shape in ('a4', 'b4')
+    counts, scales = (COUNTS4, SCALES4) if four else (COUNTS, SCALES)
+    resume = bool(a.resume)
+    out = dict(counts=counts, scales=scales, windows=N, iterations=iterations, encode=ENCODE, method='cmp', resume=resume)
+    if a.shape in ('a', 'both', 'a4'):
         T = 3000 if a.quick else 20000
         x = data(1, T)
-        print('(a) one signal of %d samples' % T, flush=True)
-        learn(x, N, iterations)                                            # warm-up: libraries, engines, first launches
-        runs = [learn(x, N, iterations) for _ in range(1 if a.quick else 3)]
+        print('(%s) one signal of %d samples, resume=%d' % (a.shape, T, resume), flush=True)
+        learn(x, N, iterations, counts, scales, resume)                    # warm-up: libraries, engines, first launches
+        runs = [learn(x, N, iterations, counts, scales, resume) for _ in range(1 if a.quick else 3)]
         out['a'] = dict(B=1, T=T, runs=runs)
+        if resume:
+            out['a']['load_level'] = load_level_alone(x, N, 3)
+            print(json.dumps(out['a']['load_level']), flush=True)
         if a.handoff:
             out['a']['dense_handoff_script'] = [dense_handoff(T) for _ in range(1 if a.quick else 2)]
             print(json.dumps(out['a']['dense_handoff_script']), flush=True)
         save(out, a.out)
-    if a.shape in ('b', 'both'):
+    if a.shape in ('b', 'both', 'b4'):
         B, T = (4, 3000) if a.quick else (64, 16384)
         x = data(B, T)
-        print('(b) %d signals of %d samples' % (B, T), flush=True)
-        out['b'] = dict(B=B, T=T, run=learn(x, N, iterations))
-        reps, W1 = level0_representations(x, N, 3)
-        out['b']['level1_setup'] = setup_both_ways(reps, N, W1)
-        print(json.dumps(out['b']['level1_setup']), flush=True)
+        print('(%s) %d signals of %d samples, resume=%d' % (a.shape, B, T, resume), flush=True)
+        out['b'] = dict(B=B, T=T, run=learn(x, N, iterations, counts, scales, resume))
+        if resume:
+            out['b']['load_level'] = load_level_alone(x, N, 3)
+            print(json.dumps(out['b']['load_level']), flush=True)
+        if not four:
+            reps, W1 = level0_representations(x, N, 3)
+            out['b']['level1_setup'] = setup_both_ways(reps, N, W1)
+            print(json.dumps(out['b']['level1_setup']), flush=True)
         save(out, a.out)
 
 
