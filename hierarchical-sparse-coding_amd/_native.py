@@ -27,7 +27,7 @@ METHOD_CMP, METHOD_LOCOMP = 0, 1
 EXPORTS = ['hscmp_version', 'hscmp_create', 'hscmp_destroy', 'hscmp_last_error', 'hscmp_set_stream', 'hscmp_set_method',
            'hscmp_synchronize', 'hscmp_set_dictionary', 'hscmp_convolve1d', 'hscmp_select_best_atoms',
            'hscmp_update_inner_products', 'hscmp_table_open', 'hscmp_table_select', 'hscmp_table_update', 'hscmp_table_read', 'hscmp_assign_windows', 'hscmp_host_overlap_add', 'hscmp_host_slots_to_csc', 'hscmp_hierarchy_epilogue', 'hscmp_encode_batch',
-           'hscmp_encode_batch_device', 'hscmp_encode_batch_ragged', 'hscmp_encode_batch_ragged_device', 'hscmp_encode_batch_from_level', 'hscmp_load_level', 'hscmp_continue', 'hscmp_grow_events', 'hscmp_mem_info', 'hscmp_copy_from_device', 'hscmp_stop_signal', 'hscmp_fetch_events',
+           'hscmp_encode_batch_device', 'hscmp_encode_batch_ragged', 'hscmp_encode_batch_ragged_device', 'hscmp_encode_batch_from_level', 'hscmp_load_level', 'hscmp_load_level_ragged', 'hscmp_continue', 'hscmp_grow_events', 'hscmp_mem_info', 'hscmp_copy_from_device', 'hscmp_stop_signal', 'hscmp_fetch_events',
            'hscmp_fetch_stats', 'hscmp_fetch_residual', 'hscmp_fetch_energies', 'hscmp_fetch_slots',
            'hscmp_get_device_view', 'hscmp_last_kernel_ms', 'hscmp_last_variant']
 
@@ -111,6 +111,7 @@ def load_library():
     lib.hscmp_encode_batch_ragged_device.argtypes = [vp, vp, ci, ci, vp, ctypes.POINTER(HscmpParams)]
     lib.hscmp_encode_batch_from_level.argtypes = [vp, vp, ci, ci, ctypes.c_double, ctypes.POINTER(HscmpParams)]
     lib.hscmp_load_level.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp]
+    lib.hscmp_load_level_ragged.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp]
     lib.hscmp_continue.argtypes = [vp, ci]
     lib.hscmp_grow_events.argtypes = [vp, ci]
     lib.hscmp_mem_info.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
@@ -492,6 +493,22 @@ class Engine(object):
         self._check(self._lib.hscmp_load_level(self._h, _ptr(x3), B, int(T), _ptr(offsets), _ptr(rows), _ptr(cols), _ptr(data)), 'hscmp_load_level')
         self._batch = (B, int(T), cap)
 
+    def load_level_ragged(self, x, T, lengths, matrices):
+        """hscmp_load_level_ragged: load_level for signals of different lengths.  matrices[b] is [lengths[b], K]; x: None, or the
+        padded signals [B, T, F] (rows t >= lengths[b] are never read).  The engine then holds a ragged batch of stride T."""
+        B = len(matrices)
+        lens = np.ascontiguousarray(lengths, dtype=np.int32)
+        assert lens.shape == (B,)
+        offsets, rows, cols, data, cap = pack_level_ragged(matrices, lens, self.K)
+        x3 = None
+        if x is not None:
+            x3 = np.ascontiguousarray(x, dtype=self.dtype)
+            assert x3.shape == (B, int(T), self.F)
+        self._batch = None                       # (a failure may leave the context without one)
+        self._check(self._lib.hscmp_load_level_ragged(self._h, _ptr(x3), B, int(T), _ptr(lens), _ptr(offsets), _ptr(rows), _ptr(cols), _ptr(data)),
+                    'hscmp_load_level_ragged')
+        self._batch = (B, int(T), cap)
+
     def hierarchy_epilogue(self, level0, first, levels, minCoefficients, slot_counts, want_events=True, want_residual=True,
                            residual_out=None, energy_out=None):
         """hscmp_hierarchy_epilogue on this (last-level) engine.  levels: list of (col0, col1, representations [K,scale(,Fd)]).
@@ -620,11 +637,17 @@ def pack_level(matrices, T, K):
     """The arguments of hscmp_load_level from B scipy.sparse matrices [T, K]: (offsets int64 [B + 1], rows int32, cols int32,
     data float64, cap) -- every matrix as canonical CSC (tocsc, duplicates summed, explicit zeros dropped, row indices
     sorted; copies: the caller's matrices stay as they are), its entries in (column, row) order; cap = max(1, longest)."""
+    return pack_level_ragged(matrices, [int(T)] * len(matrices), K)
+
+
+def pack_level_ragged(matrices, lengths, K):
+    """pack_level with a length per signal: matrices[b] is [lengths[b], K] (hscmp_load_level_ragged)."""
     import scipy.sparse
     B = len(matrices)
     offsets = np.zeros(B + 1, dtype=np.int64)
     parts = []
     for b, m in enumerate(matrices):
+        T = int(lengths[b])
         if not scipy.sparse.issparse(m) or m.shape != (int(T), int(K)):
             raise ValueError('load_level: signal %d: expected a sparse matrix of shape (%d, %d), got %s' % (
                 b, T, K, getattr(m, 'shape', type(m).__name__)))

@@ -568,6 +568,7 @@ template <typename R> static SparseArgs<R> sparse_args(hscmp_ctx* ctx, const Enc
     A.nnz = ctx->dict.dict_nnz; A.wts = ctx->dict.w.as<const R>();
     A.caps = sparse_caps(ctx->dict.W, packed);
     A.rl_cnt = plan.row_lists ? ctx->ws.rl_cnt.as<int>() : nullptr; A.rl_f = ctx->ws.rl_f.as<int>(); A.rl_cap = kRowListCap; A.rl_filled = ctx->rl_filled ? 1 : 0;
+    A.Ts = T;
     return A;
 }
 
@@ -726,7 +727,7 @@ template <typename R> static int launch_init(hscmp_ctx* ctx, const EncodePlan& p
         HIP_TRY(ctx, hipMemsetAsync(ctx->ws.rl_f.as<int>(), 0xff, (size_t)P.B * P.T * kRowListCap * sizeof(int), ctx->stream));
         const int split = std::max(1, std::min(256, 4096 / P.B));
         hipLaunchKernelGGL((build_row_lists_kernel<R>), dim3(P.B, split), dim3(kThreads), 0, ctx->stream, (const R*)x_dev, P.T, P.F,
-                           ctx->ws.rl_cnt.as<int>(), ctx->ws.rl_f.as<int>(), kRowListCap);
+                           ctx->ws.rl_cnt.as<int>(), ctx->ws.rl_f.as<int>(), kRowListCap, S.geom);
     }
     int rc = 0;
     switch (plan.init) {
@@ -737,7 +738,7 @@ template <typename R> static int launch_init(hscmp_ctx* ctx, const EncodePlan& p
     case EncodePlan::kInitSparse: {
         const SparseArgs<R> A = sparse_args<R>(ctx, plan, P.T);
         const size_t lds = sparse_lds_bytes<R>(A.caps) + staged_dict_bytes(P, A) + (size_t)((P.T + 31) / 32) * sizeof(unsigned);
-        auto kern = corr_init_sparse_kernel<R>;
+        auto kern = plan.ragged ? corr_init_sparse_kernel<R, true> : corr_init_sparse_kernel<R, false>;
         HIP_TRY(ctx, set_dyn_lds((const void*)kern, lds));
         hipLaunchKernelGGL(kern, dim3(P.B, sparse_init_split(P.B, P.T, P.W)), dim3(kThreads), lds, ctx->stream, P, S, A);
         break;
@@ -767,8 +768,12 @@ template <typename R> static int launch_loop(hscmp_ctx* ctx, const EncodePlan& p
     case EncodePlan::kLoopSparse:
         if constexpr (sizeof(R) == 8)
             if (plan.rp) { rc = rp_sparse_launch<R>(ctx->stream, P, make_state<R>(ctx, plan.ragged), sparse_args<R>(ctx, plan, P.T), false); break; }
-        rc = plan.packed ? launch_policy<R, SparseRecorr<R, true>>(ctx, P, sparse_args<R>(ctx, plan, P.T, true), 1, false)
-                         : launch_policy<R, SparseRecorr<R, false>>(ctx, P, sparse_args<R>(ctx, plan, P.T), 1, false);
+        if (plan.ragged)
+            rc = plan.packed ? launch_policy<R, SparseRecorr<R, true, true>, true>(ctx, P, sparse_args<R>(ctx, plan, P.T, true), 1, false)
+                             : launch_policy<R, SparseRecorr<R, false, true>, true>(ctx, P, sparse_args<R>(ctx, plan, P.T), 1, false);
+        else
+            rc = plan.packed ? launch_policy<R, SparseRecorr<R, true>>(ctx, P, sparse_args<R>(ctx, plan, P.T, true), 1, false)
+                             : launch_policy<R, SparseRecorr<R, false>>(ctx, P, sparse_args<R>(ctx, plan, P.T), 1, false);
         break;
     case EncodePlan::kLoopGeneric:
         rc = plan.ragged ? launch_policy<R, GenericRecorr<R>, true>(ctx, P, {}, 1, false) : launch_policy<R, GenericRecorr<R>>(ctx, P, {}, 1, false);
@@ -883,8 +888,9 @@ static int encode_common(hscmp_ctx* ctx, const void* x, bool host, int B, int T,
     if ((rc = ensure_workspace(ctx, P, host, row_lists, geom.size() * sizeof(int)))) return rc;
     const EncodePlan plan = ctx->dict.dtype == HSCMP_F32 ? plan_encode<float>(ctx, kn, P, row_lists, min_T, lengths != nullptr)
                                                          : plan_encode<double>(ctx, kn, P, row_lists, min_T, lengths != nullptr);
-    if (plan.ragged && ((plan.loop != EncodePlan::kLoopMfma && plan.loop != EncodePlan::kLoopGeneric) || plan.init == EncodePlan::kInitSparse))
-        return fail(ctx, HSCMP_ERR_UNSUPPORTED, "%s: %s has no ragged form (dense level-0 kernels only)", who, variant_of(plan).c_str());
+    // (every CMP plan has its ragged form, DESIGN.md sections 15 and 21; the LoCOMP loops have none -- encode_ragged refuses them first)
+    if (plan.ragged && plan.loop != EncodePlan::kLoopMfma && plan.loop != EncodePlan::kLoopGeneric && plan.loop != EncodePlan::kLoopSparse)
+        return fail(ctx, HSCMP_ERR_UNSUPPORTED, "%s: %s has no ragged form (the LoCOMP loops)", who, variant_of(plan).c_str());
     if (lengths) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the previous batch's kernels may still read the old geometry)
         HIP_TRY(ctx, hipMemcpyAsync(ctx->ws.geom.p, geom.data(), geom.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
@@ -940,7 +946,9 @@ extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, in
     if (ctx->device != prev->device) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: contexts on different GPUs");
     if (ctx->dict.F != prev->dict.K) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: F=%d of this level != K=%d of the previous one", ctx->dict.F, prev->dict.K);
     if (!params || first < 0 || count <= 0 || first + count > prev->B) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: bad signal range");
-    if (prev->ragged) return fail(ctx, HSCMP_ERR_UNSUPPORTED, "hscmp_encode_batch_from_level: the previous level holds a ragged batch (level chaining has no ragged form)");
+    const bool ragged = prev->ragged;
+    if (ragged && ctx->method == HSCMP_METHOD_LOCOMP)
+        return fail(ctx, HSCMP_ERR_UNSUPPORTED, "hscmp_encode_batch_from_level: the previous level holds a ragged batch, and the LoCOMP loop has no ragged form");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(prev->stream));           // the previous level's results are final
     const int T = prev->T;
@@ -948,10 +956,22 @@ extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, in
     DevParams P;
     int rc = make_params(ctx, kn, count, T, params, &P);
     if (rc) return rc;
+    // a ragged previous level: the lengths are its signals', the block geometry this level's (its W and nbBlocks)
+    int min_T = T;
+    std::vector<int> geom;
+    if (ragged) {
+        std::vector<int32_t> lens((size_t)count);
+        for (int i = 0; i < count; ++i) lens[(size_t)i] = prev->geom[(size_t)(first + i) * kGeomWords];
+        if ((rc = ragged_geometry(ctx, "hscmp_encode_batch_from_level", count, T, lens.data(), params, P, geom, &min_T))) return rc;
+    }
     const bool row_lists = use_row_lists(ctx, kn);
     drop_batch(ctx);                            // (this level's batch; prev is only read)
-    if ((rc = ensure_workspace(ctx, P, false, row_lists))) return rc;        // no input buffer: the slots are scattered straight into the residual
-    const EncodePlan plan = plan_encode<double>(ctx, kn, P, row_lists, P.T);
+    if ((rc = ensure_workspace(ctx, P, false, row_lists, geom.size() * sizeof(int)))) return rc;        // no input buffer: the slots are scattered straight into the residual
+    const EncodePlan plan = plan_encode<double>(ctx, kn, P, row_lists, min_T, ragged);
+    if (ragged) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the previous batch's kernels may still read the old geometry)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ws.geom.p, geom.data(), geom.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    }
     const bool lists = plan.row_lists;          // (the scatter writes them)
     const size_t bytes = (size_t)count * T * ctx->dict.F * sizeof(double);
     if (ctx->listed_rows > 0 && ctx->listed_F == ctx->dict.F && !kn.no_lazy_clear) {
@@ -987,7 +1007,7 @@ extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, in
     rc = run_encode<double>(ctx, plan, P, ctx->ws.resid.p, &chain);
     ctx->rowflag_valid = false; ctx->rl_filled = false;
     if (rc) return rc;
-    commit_batch(ctx, plan, P, *params, nullptr, {});      // (no input of its own on the device: the slots were scattered)
+    commit_batch(ctx, plan, P, *params, nullptr, std::move(geom));      // (no input of its own on the device: the slots were scattered)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // (only now: a failed launch leaves the buffer in an unknown state, and so does any other writer -- see the resets)
     if (plan.kept_lists) { ctx->listed_rows = (int64_t)count * T; ctx->listed_F = ctx->dict.F; }
@@ -996,13 +1016,16 @@ extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, in
 
 // hscmp_load_level: the validation pass reads only the staged entries, so a rejected entry is known before anything of the
 // context changes; the buffers of the batch are replaced behind it, as an encode replaces them.
-extern "C" int hscmp_load_level(hscmp_ctx* ctx, const void* x, int B, int T, const int64_t* offsets, const int32_t* rows, const int32_t* cols,
-                                const double* data)
+// lengths: NULL for a uniform batch, else host int32 [B] (hscmp_load_level_ragged): an entry's row must lie below its signal's length
+static int load_level_common(hscmp_ctx* ctx, const void* x, int B, int T, const int32_t* lengths, const int64_t* offsets, const int32_t* rows,
+                             const int32_t* cols, const double* data, const char* who)
 {
-    const char* who = "hscmp_load_level";
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "%s: ctx is NULL", who);
     if (ctx->dict.dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "%s: no dictionary set", who);
     if (B <= 0 || T <= 0 || !offsets) return fail(ctx, HSCMP_ERR_INVALID, "%s: bad arguments (B=%d T=%d)", who, B, T);
+    if (lengths)
+        for (int b = 0; b < B; ++b)
+            if (lengths[b] < 1 || lengths[b] > T) return fail(ctx, HSCMP_ERR_INVALID, "%s: signal %d has length %d outside [1, T=%d]", who, b, (int)lengths[b], T);
     if (offsets[0] != 0) return fail(ctx, HSCMP_ERR_INVALID, "%s: offsets[0] is %lld, not 0", who, (long long)offsets[0]);
     long long longest = 0;
     for (int b = 0; b < B; ++b) {
@@ -1019,7 +1042,7 @@ extern "C" int hscmp_load_level(hscmp_ctx* ctx, const void* x, int B, int T, con
     // staging, one arena slot: flag record, offsets, values, rows, columns (each 16-byte aligned)
     const auto pad = [](size_t v) { return (v + 15) / 16 * 16; };
     const size_t o_off = 16, o_data = o_off + pad((size_t)(B + 1) * 8), o_rows = o_data + pad((size_t)n * 8), o_cols = o_rows + pad((size_t)n * 4),
-                 total = o_cols + pad((size_t)n * 4);
+                 o_len = o_cols + pad((size_t)n * 4), total = o_len + pad(lengths ? (size_t)B * 4 : 0);
     int rc = epi_buffer(ctx, kArenaLoad, total);
     if (rc) { if (rc == HSCMP_ERR_ALLOC) drop_batch(ctx); return rc; }     // (out of memory: no batch, like every other entry)
     char* const stage = ctx->arena[kArenaLoad].as<char>();
@@ -1028,6 +1051,7 @@ extern "C" int hscmp_load_level(hscmp_ctx* ctx, const void* x, int B, int T, con
     const double* const d_data = (const double*)(stage + o_data);
     const int* const d_rows = (const int*)(stage + o_rows);
     const int* const d_cols = (const int*)(stage + o_cols);
+    const int* const d_len = lengths ? (const int*)(stage + o_len) : nullptr;
     const unsigned grid = (unsigned)((std::max<long long>(n, B) + kThreads - 1) / kThreads);
     HIP_TRY(ctx, hipMemsetAsync(d_flag, 0xff, sizeof(unsigned long long), ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(stage + o_off, offsets, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -1035,8 +1059,9 @@ extern "C" int hscmp_load_level(hscmp_ctx* ctx, const void* x, int B, int T, con
         HIP_TRY(ctx, hipMemcpyAsync(stage + o_data, data, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(stage + o_rows, rows, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(stage + o_cols, cols, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (lengths) HIP_TRY(ctx, hipMemcpyAsync(stage + o_len, lengths, (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL((load_level_kernel<false>), dim3(grid), dim3(kThreads), 0, ctx->stream, d_off, d_rows, d_cols, d_data, n, B, T, K, cap,
-                           (int*)nullptr, (int*)nullptr, (double*)nullptr, (int*)nullptr, d_flag);
+                           (int*)nullptr, (int*)nullptr, (double*)nullptr, (int*)nullptr, d_flag, d_len);
         HIP_TRY(ctx, hipGetLastError());
         unsigned long long flag = 0;
         HIP_TRY(ctx, hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, ctx->stream));
@@ -1048,6 +1073,9 @@ extern "C" int hscmp_load_level(hscmp_ctx* ctx, const void* x, int B, int T, con
             const int reason = (int)(flag & 7);
             int b = 0;
             while (b + 1 < B && offsets[b + 1] <= i) ++b;
+            if (lengths)
+                return fail(ctx, HSCMP_ERR_INVALID, "%s: signal %d, entry %lld (row %d, column %d; T_b=%d K=%d): %s", who, b, i - (long long)offsets[b],
+                            (int)rows[i], (int)cols[i], (int)lengths[b], K, reason == kLoadBadRow ? "row outside [0, T_b)" : why[reason >= 1 && reason <= 4 ? reason : 0]);
             return fail(ctx, HSCMP_ERR_INVALID, "%s: signal %d, entry %lld (row %d, column %d; T=%d K=%d): %s", who, b, i - (long long)offsets[b],
                         (int)rows[i], (int)cols[i], T, K, why[reason >= 1 && reason <= 4 ? reason : 0]);
         }
@@ -1071,7 +1099,7 @@ extern "C" int hscmp_load_level(hscmp_ctx* ctx, const void* x, int B, int T, con
     HIP_TRY(ctx, hipMemsetAsync(w.slot_a.p, 0, (size_t)B * cap * 8, ctx->stream));
     if (x) HIP_TRY(ctx, hipMemcpyAsync(w.x.p, x, xbytes, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL((load_level_kernel<true>), dim3(grid), dim3(kThreads), 0, ctx->stream, d_off, d_rows, d_cols, d_data, n, B, T, K, cap,
-                       w.slot_t.as<int>(), w.slot_k.as<int>(), w.slot_a.as<double>(), w.stats.as<int>(), d_flag);
+                       w.slot_t.as<int>(), w.slot_k.as<int>(), w.slot_a.as<double>(), w.stats.as<int>(), d_flag, (const int*)nullptr);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->B = B; ctx->T = T; ctx->cap = cap; ctx->maxsel = 0;
@@ -1079,8 +1107,28 @@ extern "C" int hscmp_load_level(hscmp_ctx* ctx, const void* x, int B, int T, con
     ctx->last_x_dev = x ? w.x.p : nullptr;
     ctx->timed = false;
     ctx->variant = "loaded";
+    // a ragged batch: the geometry holds the lengths only (the block geometry belongs to an encode: the level above computes its own)
+    ctx->ragged = lengths != nullptr;
+    ctx->geom.clear();
+    if (lengths) {
+        ctx->geom.assign((size_t)B * kGeomWords, 0);
+        for (int b = 0; b < B; ++b) ctx->geom[(size_t)b * kGeomWords] = lengths[b];
+    }
     ctx->loaded = true; ctx->have_batch = true;
     return HSCMP_OK;
+}
+
+extern "C" int hscmp_load_level(hscmp_ctx* ctx, const void* x, int B, int T, const int64_t* offsets, const int32_t* rows, const int32_t* cols,
+                                const double* data)
+{
+    return load_level_common(ctx, x, B, T, nullptr, offsets, rows, cols, data, "hscmp_load_level");
+}
+
+extern "C" int hscmp_load_level_ragged(hscmp_ctx* ctx, const void* x, int B, int T, const int32_t* lengths, const int64_t* offsets, const int32_t* rows,
+                                       const int32_t* cols, const double* data)
+{
+    if (ctx && !lengths) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_load_level_ragged: lengths is NULL");
+    return load_level_common(ctx, x, B, T, lengths, offsets, rows, cols, data, "hscmp_load_level_ragged");
 }
 
 // What only an encode leaves behind (its loop state, events, residual, energies)
@@ -1437,13 +1485,25 @@ extern "C" int hscmp_hierarchy_epilogue(hscmp_ctx* last, hscmp_ctx* level0, int 
 {
     if (!last || !level0) return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: NULL context");
     if (!last->have_batch || !level0->have_batch) return fail(last, HSCMP_ERR_STATE, "hscmp_hierarchy_epilogue: no batch encoded");
-    if (last->ragged || level0->ragged) return fail(last, HSCMP_ERR_UNSUPPORTED, "hscmp_hierarchy_epilogue: a ragged batch has no hierarchical epilogue");
     NOT_LOADED(last, "hscmp_hierarchy_epilogue (last level)");
     if (last->device != level0->device) return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: contexts on different GPUs");
     if (!levels || nlevels < 1 || nlevels > kEpiMaxLevels || !offsets || !out_n || !out_colptr || !out_indices || !out_data)
         return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: bad arguments");
     const int count = last->B, T = last->T, Fd = level0->dict.F, Ktot = last->dict.K;
     if (first < 0 || first + count > level0->B || level0->T != T) return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: signal range / length mismatch");
+    // ragged batches: the last level's lengths are level 0's, rows [first, first + count)
+    const bool ragged = last->ragged;
+    if (ragged != level0->ragged) return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: one of the two levels holds a ragged batch, the other a uniform one");
+    std::vector<int> lens;
+    if (ragged) {
+        lens.resize((size_t)count);
+        for (int b = 0; b < count; ++b) {
+            lens[(size_t)b] = last->geom[(size_t)b * kGeomWords];
+            const int l0 = level0->geom[(size_t)(first + b) * kGeomWords];
+            if (l0 != lens[(size_t)b])
+                return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: signal %d has length %d at the last level, %d at level 0 (signal %d)", b, lens[(size_t)b], l0, first + b);
+        }
+    }
     if (!level0->last_x_dev) return fail(last, HSCMP_ERR_STATE, "hscmp_hierarchy_epilogue: the level-0 input is not on the device any more");
     if (Ktot >= (1 << kEpiColBits) || T >= (1 << kEpiTBits) || last->cap >= (1 << kEpiIdxBits))
         return fail(last, HSCMP_ERR_UNSUPPORTED, "hscmp_hierarchy_epilogue: shape outside the key layout (K < 2^20, T < 2^24, list < 2^20)");
@@ -1483,13 +1543,18 @@ extern "C" int hscmp_hierarchy_epilogue(hscmp_ctx* last, hscmp_ctx* level0, int 
     const size_t nres = out_residual ? (size_t)count * T * Fd * sizeof(double) : 0;
     const size_t nev = out_events ? (size_t)total * 16 : 0;      // (a multiple of 16: the residual behind the events stays aligned)
     // by arena slot, kArenaEpiOffsets .. kArenaEpiKeys (kArenaEpiOut: the events, then the residual)
-    const size_t sizes[8] = {0, (size_t)(count + 1) * sizeof(long long), (size_t)count * sizeof(int), (size_t)count * (Ktot + 1) * sizeof(int),
+    const size_t off_bytes = (size_t)(count + 1) * sizeof(long long);      // (a ragged batch: the lengths ride behind the offsets)
+    const size_t sizes[8] = {0, off_bytes + (ragged ? (size_t)count * sizeof(int) : 0), (size_t)count * sizeof(int), (size_t)count * (Ktot + 1) * sizeof(int),
                              std::max<size_t>(16, (size_t)total * sizeof(int)), std::max<size_t>(16, (size_t)total * sizeof(double)),
                              std::max<size_t>(16, nev + nres),
                              (size_t)count * nmax * sizeof(unsigned long long)};       // (the t-sorted keys move there while the LDS holds residual tiles)
     for (int i = kArenaEpiOffsets; i <= kArenaEpiKeys; ++i) if (sizes[i] && (rc = epi_buffer(last, i, sizes[i]))) return rc;
     DevBuf* const arena = last->arena;
-    HIP_TRY(last, hipMemcpyAsync(arena[kArenaEpiOffsets].p, offsets, sizes[kArenaEpiOffsets], hipMemcpyHostToDevice, last->stream));
+    HIP_TRY(last, hipMemcpyAsync(arena[kArenaEpiOffsets].p, offsets, off_bytes, hipMemcpyHostToDevice, last->stream));
+    if (ragged) {
+        HIP_TRY(last, hipMemcpyAsync(arena[kArenaEpiOffsets].as<char>() + off_bytes, lens.data(), (size_t)count * sizeof(int), hipMemcpyHostToDevice, last->stream));
+        A.lens = (const int*)(arena[kArenaEpiOffsets].as<char>() + off_bytes);
+    }
     A.slot_t = last->ws.slot_t.as<int>(); A.slot_k = last->ws.slot_k.as<int>(); A.slot_a = last->ws.slot_a.as<double>(); A.stats = last->ws.stats.as<int>(); A.cap = last->cap;
     A.offsets = arena[kArenaEpiOffsets].as<const long long>(); A.out_n = arena[kArenaEpiN].as<int>(); A.out_colptr = arena[kArenaEpiColptr].as<int>();
     A.out_indices = arena[kArenaEpiIndices].as<int>(); A.out_data = arena[kArenaEpiData].as<double>();

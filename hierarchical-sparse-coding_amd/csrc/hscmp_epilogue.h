@@ -40,7 +40,8 @@ struct EpiLevel {
 
 struct EpiArgs {
     EpiLevel lv[kEpiMaxLevels];
-    int nlevels, Ktot, T, Fd;
+    int nlevels, Ktot, T, Fd;            // T: rows between two signals of x and out_residual (a ragged batch: the longest length)
+    const int* lens;                     // [count] the signals' own lengths (a ragged batch), or nullptr: all T
     int has_min;
     double minc;
     int max_back, max_fwd;               // an entry at t can cover samples t - max_back' ... : window of t around a sample s is [s - max_back, s + max_fwd]
@@ -52,7 +53,7 @@ struct EpiArgs {
     int* out_colptr;                     // [count][Ktot + 1]
     int* out_indices; double* out_data;  // packed, CSC order
     int* out_events;                     // packed 16-byte records (t, level, index, float value), or nullptr
-    double* out_residual;                // [count][T][Fd] or nullptr
+    double* out_residual;                // [count][T][Fd] or nullptr (rows t >= lens[b]: zero)
     double* out_energy;                  // [count] sum of the squared residual samples, or nullptr
     unsigned long long* scratch;         // [count][scratch_n] keys of lists that do not fit LDS
     int scratch_n;
@@ -220,9 +221,14 @@ __global__ __launch_bounds__(kEpiThreads) void hier_epilogue_kernel(EpiArgs A, c
 
     // ---- 5. residual: x - sum over the levels of their synthesis, each level's terms in CSC order
     if (A.out_residual || A.out_energy) {
-        const int64_t nel = (int64_t)A.T * A.Fd;
-        const XR* xb = x + (int64_t)b * nel;
-        double* rb = A.out_residual ? A.out_residual + (int64_t)b * nel : nullptr;
+        // a signal of a ragged batch: its own Tb rows, as the lone signal of that length -- no sample s >= Tb is read from x,
+        // reconstructed or summed (the overlap-add clips at Tb: a pattern's taps beyond it land nowhere), and the residual rows
+        // above are zero.  The strides stay those of T.
+        const int Tb = A.lens ? A.lens[b] : A.T;
+        const int64_t nel = (int64_t)Tb * A.Fd;
+        const XR* xb = x + (int64_t)b * A.T * A.Fd;
+        double* rb = A.out_residual ? A.out_residual + (int64_t)b * A.T * A.Fd : nullptr;
+        if (rb) for (int64_t e = nel + tid; e < (int64_t)A.T * A.Fd; e += kEpiThreads) rb[e] = 0.0;
         const double* data = A.out_data + off;
         double esum = 0.0;                                   // this thread's samples, in index order
         // One-dimensional signals: tile by tile in LDS.  The entries whose patterns reach a tile of TS samples are a range of
@@ -298,8 +304,8 @@ __global__ __launch_bounds__(kEpiThreads) void hier_epilogue_kernel(EpiArgs A, c
             double* eval = reinterpret_cast<double*>(ekey + TS);                  // [TS]
             __shared__ int s_range[2 + kEpiMaxLevels + 1];
             const int lane = tid & 63, wv = tid >> 6, strip = TS / (kEpiThreads / 64);
-            for (int t0 = 0; t0 < A.T; t0 += TS) {
-                const int tn = min(TS, A.T - t0);
+            for (int t0 = 0; t0 < Tb; t0 += TS) {
+                const int tn = min(TS, Tb - t0);
                 const long long tbase = (long long)t0 - A.max_back;
                 if (tid < 2) {
                     // entries with t in [t0 - max_back, t0 + tn - 1 + max_fwd]

@@ -461,7 +461,8 @@ __global__ __launch_bounds__(kThreads) void scatter_slots_kernel(R* __restrict__
 // arrays (signal b owns [offsets[b], offsets[b+1]), column-major inside a signal) becomes slot i - offsets[b] of signal b.
 // Launched FLAT over the entries -- list lengths are as skewed as the signals are busy, a workgroup per signal would wait for
 // the longest -- every thread finds its signal by bisection of the offsets table (B + 1 words, cached).
-//   UNPACK = false  validates and writes nothing but *flag: row in [0, T), column in [0, K), value finite and non-zero,
+//   UNPACK = false  validates and writes nothing but *flag: row in [0, T) -- [0, lens[b]) with the per-signal lengths of a ragged
+//                   batch (lens, device, or nullptr) --, column in [0, K), value finite and non-zero,
 //                   (column, row) strictly above the entry before it in the same signal -- which proves the slots distinct,
 //                   as the chain's scatter and the epilogue's keys assume.  *flag (preset to all ones) receives the
 //                   smallest 8 * i + reason of the offending entries (kLoad* below): the first one, whatever the schedule.
@@ -473,7 +474,8 @@ template <bool UNPACK>
 __global__ __launch_bounds__(kThreads) void load_level_kernel(const long long* __restrict__ offsets, const int* __restrict__ rows,
                                                               const int* __restrict__ cols, const double* __restrict__ data, long long n,
                                                               int B, int T, int K, int cap, int* __restrict__ slot_t, int* __restrict__ slot_k,
-                                                              double* __restrict__ slot_a, int* __restrict__ stats, unsigned long long* __restrict__ flag)
+                                                              double* __restrict__ slot_a, int* __restrict__ stats, unsigned long long* __restrict__ flag,
+                                                              const int* __restrict__ lens)
 {
     const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (UNPACK && i < B) {
@@ -495,7 +497,7 @@ __global__ __launch_bounds__(kThreads) void load_level_kernel(const long long* _
         return;
     }
     int reason = 0;
-    if (t < 0 || t >= T) reason = kLoadBadRow;
+    if (t < 0 || t >= (lens ? lens[lo] : T)) reason = kLoadBadRow;
     else if (k < 0 || k >= K) reason = kLoadBadCol;
     else if (!(fabs(a) <= 1.7976931348623157e308) || a == 0.0) reason = kLoadBadValue;
     else if (i > o && !(cols[i - 1] < k || (cols[i - 1] == k && rows[i - 1] < t))) reason = kLoadBadOrder;
@@ -525,14 +527,15 @@ __global__ __launch_bounds__(kThreads) void clear_listed_cells_kernel(R* __restr
 // Per-row feature lists of a dense multi-feature input x [B][T][F]: rl_cnt[b][t] = number of non-zero
 // features of row t (may exceed rl_cap: the row is then treated as dense), rl_f[b][t][0..rl_cap) their
 // indices in any order (-1 = empty; both arrays must be pre-filled with 0 / -1).
+// geom: the per-signal geometry of a ragged batch (State::geom; nullptr: uniform) -- rows t >= T_b are not read and stay unlisted.
 //   grid = (B, splits), block = kThreads
 template <typename R>
 __global__ __launch_bounds__(kThreads) void build_row_lists_kernel(const R* __restrict__ x, int T, int F, int* __restrict__ rl_cnt,
-                                                                   int* __restrict__ rl_f, int rl_cap)
+                                                                   int* __restrict__ rl_f, int rl_cap, const int* __restrict__ geom)
 {
     const int b = blockIdx.x;
-    const int64_t n = (int64_t)T * F;
-    const R* xb = x + (int64_t)b * n;
+    const int64_t n = (int64_t)(geom ? geom[kGeomWords * b] : T) * F;
+    const R* xb = x + (int64_t)b * T * F;
     for (int64_t e = (int64_t)blockIdx.y * kThreads + threadIdx.x; e < n; e += (int64_t)gridDim.y * kThreads) {
         if (xb[e] != (R)0) {
             const int t = (int)(e / F), f = (int)(e - (int64_t)t * F);

@@ -135,7 +135,8 @@ template <typename R> __device__ __forceinline__ RpSparseSlot<R> rp_sparse_slot(
     return L;
 }
 
-template <typename R> struct RpSparse {
+// RAGGED: the hooks run on the signal's own P.T; the strides of the row lists are the batch's (SparseArgs::Ts, stride_rows)
+template <typename R, bool RAGGED = false> struct RpSparse {
     static constexpr int kMaxSegments = 512;
     static constexpr int kMaxSel = 64;
     static constexpr bool kScoreOnly = false;
@@ -196,8 +197,9 @@ template <typename R> struct RpSparse {
         const int T = P.T, F = P.F, W = P.W;
         int s, e, es;
         const int len = centered_span(T, W, t, s, e, es);
-        const int* cnt = A.rl_cnt + (int64_t)blockIdx.x * T;
-        const int* lf = A.rl_f + (int64_t)blockIdx.x * T * 8;
+        const int TS = stride_rows<RAGGED>(P, A);
+        const int* cnt = A.rl_cnt + (int64_t)blockIdx.x * TS;
+        const int* lf = A.rl_f + (int64_t)blockIdx.x * TS * 8;
         HSCMP_RP_SSTAMP_BEGIN();
         fence();                                              // (the slot's previous user -- this wave -- is done with it)
 #pragma unroll
@@ -390,8 +392,9 @@ template <typename R> struct RpSparse {
     {
         const SparseArgs<R> A = rp_dict_view(P, A0, lds);
         const int T = P.T, F = P.F;
-        int* cntw = A.rl_cnt + (int64_t)blockIdx.x * T;
-        int* lfw = A.rl_f + (int64_t)blockIdx.x * T * 8;
+        const int TS = stride_rows<RAGGED>(P, A);
+        int* cntw = A.rl_cnt + (int64_t)blockIdx.x * TS;
+        int* lfw = A.rl_f + (int64_t)blockIdx.x * TS * 8;
         const R nc = -c;
         const int e0 = A.nzptr[k], e1 = A.nzptr[k + 1];
         for (int q0 = e0; q0 < e1; q0 += 64) {
@@ -422,8 +425,9 @@ template <typename R> struct RpSparse {
     {
         const int T = P.T, F = P.F, W = P.W;
         const int row0 = p - (W - 1) + r0, nwin = nr + W - 1, g0 = row0 - P.off;
-        const int* cnt = A.rl_cnt + (int64_t)blockIdx.x * T;
-        const int* lf = A.rl_f + (int64_t)blockIdx.x * T * 8;
+        const int TS = stride_rows<RAGGED>(P, A);
+        const int* cnt = A.rl_cnt + (int64_t)blockIdx.x * TS;
+        const int* lf = A.rl_f + (int64_t)blockIdx.x * TS * 8;
         HSCMP_RP_SSTAMP_BEGIN();
         fence();
         if (lane < 4) L.ctl[lane] = 0;
@@ -701,6 +705,7 @@ template <typename R>
 static int rp_sparse_launch(hipStream_t stream, const DevParams& P0, const State<R>& S, const SparseArgs<R>& sp, bool dry)
 {
     using Pol = RpSparse<R>;
+    using PolR = RpSparse<R, true>;                                    // (same Shared, Args and LDS layout)
     if (!rp_params_ok(P0, Pol::kMaxSel)) return -1;
     // the row lists (8 features per row) and the per-atom / by-feature dictionary lists carry this policy
     if (!sp.rl_cnt || sp.rl_cap != 8 || !sp.nzptr || !sp.fptr || P0.W > 128 || P0.K > 65535 || P0.F > 32767) return -1;
@@ -710,7 +715,8 @@ static int rp_sparse_launch(hipStream_t stream, const DevParams& P0, const State
     A.sp = sp;
     A.caps = rp_sparse_caps<R>(P, sp, ((sizeof(typename Pol::Shared) + 15) / 16) * 16);
     if (A.caps.teams < 2) return -1;
-    return launch_tile_kernel(iterate_rp_kernel<R, Pol>, dim3(P.B), dim3(kRpThreads), Pol::total_lds_bytes(P, A), kLdsLoop, 0, dry, stream, P, S, A);
+    auto kern = S.geom ? iterate_rp_kernel<R, PolR, true> : iterate_rp_kernel<R, Pol, false>;       // (ragged batch)
+    return launch_tile_kernel(kern, dim3(P.B), dim3(kRpThreads), Pol::total_lds_bytes(P, A), kLdsLoop, 0, dry, stream, P, S, A);
 }
 
 }  // namespace hscmp

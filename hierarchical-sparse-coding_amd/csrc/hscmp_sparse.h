@@ -77,7 +77,16 @@ template <typename R> struct SparseArgs {
     SparseCaps caps;    // LDS list capacities
     int nnz;            // non-zeros of the dictionary (length of the lists)
     const R* wts;       // atom weights (State::weights, or their LDS copy)
+    int Ts;             // stride of the per-signal arrays (rowflag, rl_cnt, rl_f), in rows: the batch's T.  The RAGGED forms run on a
+                        // signal's own P.T and take strides and the LDS layout from here
 };
+
+// Rows between two signals of the per-signal arrays, and what the host sized the row bitmap with.  RAGGED = false: P.T itself,
+// so the uniform instantiations compile to the code they were.
+template <bool RAGGED, typename R> __host__ __device__ __forceinline__ int stride_rows(const DevParams& P, const SparseArgs<R>& A)
+{
+    if constexpr (RAGGED) return A.Ts; else return P.T;
+}
 
 constexpr int kDictLdsBytes = 12288;    // the by-feature lists are copied to LDS when they fit this ...
 constexpr int kWeightLdsBytes = 8192;   // ... and so are the atom weights
@@ -218,7 +227,7 @@ __device__ __forceinline__ int list_count(const int* p)
 // order.  With per-row feature lists (A.rl_cnt) only the listed cells are read; otherwise rows are scanned,
 // and with rowbits (LDS, may be nullptr) only those whose bit is set.  Returns the number
 // of non-zeros found (> caps.nz: the list overflowed and is unusable).  Contains barriers.
-template <typename R, bool LAUNDER = false>
+template <typename R, bool LAUNDER = false, bool RAGGED = false>
 __device__ __forceinline__ int gather_window(const DevParams& P, const Sig<R>& G, const SparseArgs<R>& A, const SparseLds<R>& L,
                                              const unsigned* rowbits, int g0, int nwin, bool reflect, int sidx, int nslice)
 {
@@ -229,8 +238,9 @@ __device__ __forceinline__ int gather_window(const DevParams& P, const Sig<R>& G
     if (A.rl_cnt) {
         // listed cells: items = (window row, list slot); first the feature indices, then the values
         const int C = A.rl_cap, shift = __ffs(C) - 1;
-        const int* cnt = A.rl_cnt + (int64_t)blockIdx.x * T;
-        const int* lf = A.rl_f + (int64_t)blockIdx.x * T * C;
+        const int TS = stride_rows<RAGGED>(P, A);
+        const int* cnt = A.rl_cnt + (int64_t)blockIdx.x * TS;
+        const int* lf = A.rl_f + (int64_t)blockIdx.x * TS * C;
         constexpr int kV = 4;
         const int items = C == 8 ? 0 : nwin << shift;
         if (C == 8) {
@@ -343,7 +353,7 @@ __device__ __forceinline__ unsigned long long score_bits(float s) { return (unsi
 
 // Rows [row0, row0+nrows) x all atoms -> per-position best (best_c, best_k), sparsity aware.
 //   nrows <= 2W-1 (table capacity).  All threads of the workgroup call it (contains barriers).
-template <typename R, bool LAUNDER = false>
+template <typename R, bool LAUNDER = false, bool RAGGED = false>
 __device__ __forceinline__ void sparse_rows(const DevParams& P, const State<R>& S, const Sig<R>& G, const SparseArgs<R>& A,
                                             const SparseLds<R>& L, const unsigned* rowbits, int row0, int nrows, bool reflect,
                                             int sidx, int nslice, bool gathered = false)
@@ -364,7 +374,7 @@ __device__ __forceinline__ void sparse_rows(const DevParams& P, const State<R>& 
         if (tid == 0) { L.ctl[1] = 0; L.ctl[2] = 0; L.ctl[3] = 0; }
         lds_barrier();
     } else {
-        n = gather_window<R, LAUNDER>(P, G, A, L, rowbits, g0, nwin, reflect, sidx, nslice);
+        n = gather_window<R, LAUNDER, RAGGED>(P, G, A, L, rowbits, g0, nwin, reflect, sidx, nslice);
     }
     HSCMP_STAMP(40);
     HSCMP_TALLY(0, 1); HSCMP_TALLY(1, n); HSCMP_TALLY(2, n > nzcap); HSCMP_TALLY(5, L.ctl[1]);
@@ -617,7 +627,10 @@ __device__ __forceinline__ void sparse_rows(const DevParams& P, const State<R>& 
 // PACKED: the same loop compiled for four workgroups per CU (128 VGPRs -- it spills --, half the segment table): the loop
 // is latency-bound and co-resident workgroups overlap perfectly, so a batch of more than 2 x CUs signals finishes in
 // fewer rounds; smaller batches run the roomier form.
-template <typename R, bool PACKED = false> struct SparseRecorr {
+// RAGGED: the loop of a ragged batch.  The hooks receive the signal's own parameters (P.T = T_b: every clip, reflection and
+// interior test is the lone signal's); the strides of rowflag / rl_cnt / rl_f and the LDS layout the host sized come from
+// Args::Ts, the batch's T (stride_rows).
+template <typename R, bool PACKED = false, bool RAGGED = false> struct SparseRecorr {
     // LDS per workgroup is kept near 40 KB (4 workgroups per CU): the loop is latency bound, not compute bound
     static constexpr int kMaxSegments = PACKED ? 256 : 512;
     static constexpr bool kFused = false;
@@ -632,12 +645,13 @@ template <typename R, bool PACKED = false> struct SparseRecorr {
     static __device__ __forceinline__ Sync make_sync(Shared&) { return Sync(); }
     static __device__ __forceinline__ void prologue_shared(const DevParams&, const State<R>&, const Args&, char*) {}
     static __device__ __forceinline__ int signal_lds_offset(const DevParams&, const Args&) { return 0; }
-    static __host__ __device__ bool has_bits(const DevParams& P, const Args& A) { return A.rl_cnt == nullptr && A.rowflag != nullptr && P.T <= kRowBitsMaxT; }
+    static __host__ __device__ int stride(const DevParams& P, const Args& A) { return stride_rows<RAGGED>(P, A); }
+    static __host__ __device__ bool has_bits(const DevParams& P, const Args& A) { return A.rl_cnt == nullptr && A.rowflag != nullptr && stride(P, A) <= kRowBitsMaxT; }
     // policy LDS: SparseLds | staged dictionary lists + weights (when small) | row bitmap (when T allows)
     static __host__ __device__ size_t bits_offset(const DevParams& P, const Args& A) { return sparse_lds_bytes<R>(A.caps) + staged_dict_bytes(P, A); }
     static size_t extra_lds_bytes(const DevParams& P, const Args& A)
     {
-        return bits_offset(P, A) + (has_bits(P, A) ? (size_t)((P.T + 31) / 32) * sizeof(unsigned) : 0);
+        return bits_offset(P, A) + (has_bits(P, A) ? (size_t)((stride(P, A) + 31) / 32) * sizeof(unsigned) : 0);
     }
     static size_t total_lds_bytes(const DevParams& P, const Args& A) { return ((sizeof(Shared) + 15) / 16) * 16 + extra_lds_bytes(P, A); }
     static __device__ __forceinline__ unsigned* bits_of(const DevParams& P, const Args& A, char* lds) { return reinterpret_cast<unsigned*>(lds + bits_offset(P, A)); }
@@ -651,7 +665,7 @@ template <typename R, bool PACKED = false> struct SparseRecorr {
         stage_dict(P, A, lds + sparse_lds_bytes<R>(A.caps));
         if (!has_bits(P, A)) { __syncthreads(); return; }                  // (row lists need no per-launch state)
         unsigned* bits = bits_of(P, A, lds);
-        const unsigned char* rf = A.rowflag + (int64_t)blockIdx.x * P.T;
+        const unsigned char* rf = A.rowflag + (int64_t)blockIdx.x * stride(P, A);
         const int nwords = (P.T + 31) / 32;
         for (int i = threadIdx.x; i < nwords; i += kThreads) {
             unsigned word = 0;
@@ -665,7 +679,7 @@ template <typename R, bool PACKED = false> struct SparseRecorr {
     {
         if (!has_bits(P, A)) return;                        // (the caller's barrier made all bits visible)
         const unsigned* bits = bits_of(P, A, lds);
-        unsigned char* rf = A.rowflag + (int64_t)blockIdx.x * P.T;
+        unsigned char* rf = A.rowflag + (int64_t)blockIdx.x * stride(P, A);
         for (int t = threadIdx.x; t < P.T; t += kThreads)
             if ((bits[t >> 5] >> (t & 31)) & 1u) rf[t] = 1;  // kept for resumed launches (hscmp_continue)
     }
@@ -687,12 +701,13 @@ template <typename R, bool PACKED = false> struct SparseRecorr {
     static __device__ __forceinline__ bool merged_update(const DevParams& P, const Sig<R>& G, const Args& A, const SparseLds<R>& L,
                                                          int p, int k, R c, int s, int e, R& pb, R& pa)
     {
-        const int T = P.T, F = P.F, W = P.W, tid = laundered_tid<PACKED>();
-        const int g0 = p - P.off - (W - 1), nwin = 3 * W - 2;
-        const int* cnt = A.rl_cnt + (int64_t)blockIdx.x * T;
-        const int* lf = A.rl_f + (int64_t)blockIdx.x * T * 8;
-        int* cntw = A.rl_cnt + (int64_t)blockIdx.x * T;
-        int* lfw = A.rl_f + (int64_t)blockIdx.x * T * 8;
+        const int F = P.F, W = P.W, tid = laundered_tid<PACKED>();
+        const int g0 = p - P.off - (W - 1), nwin = 3 * W - 2;                       // (inside the signal: update_residual's test)
+        const int TS = stride(P, A);
+        const int* cnt = A.rl_cnt + (int64_t)blockIdx.x * TS;
+        const int* lf = A.rl_f + (int64_t)blockIdx.x * TS * 8;
+        int* cntw = A.rl_cnt + (int64_t)blockIdx.x * TS;
+        int* lfw = A.rl_f + (int64_t)blockIdx.x * TS * 8;
         int* key = L.key; R* cur = L.val; R* before = L.rx;
         int* members = L.perm; int* slot0 = reinterpret_cast<int*>(L.okey); int* slot1 = reinterpret_cast<int*>(L.rkey);   // [256] each
         const int e0 = A.nzptr[k], e1 = A.nzptr[k + 1], na = e1 - e0;
@@ -826,9 +841,9 @@ template <typename R, bool PACKED = false> struct SparseRecorr {
         if (!A0.rl_cnt) return false;
         const Args A = dict_view(P, A0, lds + sparse_lds_bytes<R>(A0.caps));
         const SparseLds<R> L = sparse_lds_view<R>(lds, A0.caps);
-        const int T = P.T, F = P.F, tid = laundered_tid<PACKED>(), C = A.rl_cap, shift = __ffs(C) - 1;
-        const int* cnt = A.rl_cnt + (int64_t)blockIdx.x * T;
-        const int* lf = A.rl_f + (int64_t)blockIdx.x * T * C;
+        const int T = P.T, TS = stride(P, A0), F = P.F, tid = laundered_tid<PACKED>(), C = A.rl_cap, shift = __ffs(C) - 1;
+        const int* cnt = A.rl_cnt + (int64_t)blockIdx.x * TS;
+        const int* lf = A.rl_f + (int64_t)blockIdx.x * TS * C;
         {
             const int g0 = p - P.off - (P.W - 1);
             if (C == 8 && g0 >= 0 && g0 + 3 * P.W - 2 <= T && 3 * P.W - 2 <= 0xffff) {
@@ -849,8 +864,8 @@ template <typename R, bool PACKED = false> struct SparseRecorr {
         // still holds 0 and is skipped by (a) whether (a) sees it or not; a count pushed past the capacity is seen by
         // every later reader as "read the row densely".
         const int na = e1 - e0;
-        int* cntw = A.rl_cnt + (int64_t)blockIdx.x * T;
-        int* lfw = A.rl_f + (int64_t)blockIdx.x * T * C;
+        int* cntw = A.rl_cnt + (int64_t)blockIdx.x * TS;
+        int* lfw = A.rl_f + (int64_t)blockIdx.x * TS * C;
         if (C == 8) {
             for (int base = 0; base < max(e - s, na); base += kThreads) {
                 const int g = s + base + tid;                                // (a) this thread's row
@@ -991,9 +1006,9 @@ template <typename R, bool PACKED = false> struct SparseRecorr {
     {
         if (!A0.rl_cnt) return false;
         const SparseLds<R> L = sparse_lds_view<R>(lds, A0.caps);
-        const int T = P.T, F = P.F, tid = laundered_tid<PACKED>(), C = A0.rl_cap, shift = __ffs(C) - 1;
-        const int* cnt = A0.rl_cnt + (int64_t)blockIdx.x * T;
-        const int* lf = A0.rl_f + (int64_t)blockIdx.x * T * C;
+        const int TS = stride(P, A0), F = P.F, tid = laundered_tid<PACKED>(), C = A0.rl_cap, shift = __ffs(C) - 1;
+        const int* cnt = A0.rl_cnt + (int64_t)blockIdx.x * TS;
+        const int* lf = A0.rl_f + (int64_t)blockIdx.x * TS * C;
         int* key = L.key; R* val = L.val; int* order = L.perm;
         __syncthreads();                                                             // the lists of the previous window are consumed
         if (tid == 0) { L.ctl[0] = 0; L.ctl[1] = 0; }
@@ -1036,9 +1051,9 @@ template <typename R, bool PACKED = false> struct SparseRecorr {
                                                               int s, int e, int lane, int wv, R& out)
     {
         if (!A0.rl_cnt || A0.rl_cap != 8) return false;
-        const int T = P.T, F = P.F;
-        const int* cnt = A0.rl_cnt + (int64_t)blockIdx.x * T;
-        const int* lf = A0.rl_f + (int64_t)blockIdx.x * T * 8;
+        const int TS = stride(P, A0), F = P.F;
+        const int* cnt = A0.rl_cnt + (int64_t)blockIdx.x * TS;
+        const int* lf = A0.rl_f + (int64_t)blockIdx.x * TS * 8;
         // (wv < kEnergyWaves: the caller lets the waves in by turns when the table holds fewer than four windows)
         R* first = reinterpret_cast<R*>(lds) + (size_t)wv * kThreads;                       // [kEnergyWaves][256]
         R* second = reinterpret_cast<R*>(lds) + (size_t)(kEnergyWaves + wv) * kThreads;     // [kEnergyWaves][256]
@@ -1124,7 +1139,7 @@ template <typename R, bool PACKED = false> struct SparseRecorr {
         const int eidx = tend > T - 1 ? T - 1 : tend;      // :1039
         HSCMP_STAMP(45);
         const bool gathered = A.rl_cnt && L.ctl[3] == -2;     // uniform: written before the barriers of the energy tree
-        sparse_rows<R, PACKED>(P, S, G, A, L, bits, p - (W - 1), 2 * W - 1, true, sidx, eidx - sidx + 1, gathered);
+        sparse_rows<R, PACKED, RAGGED>(P, S, G, A, L, bits, p - (W - 1), 2 * W - 1, true, sidx, eidx - sidx + 1, gathered);
     }
 };
 
@@ -1135,20 +1150,22 @@ template <typename R, bool PACKED = false> struct SparseRecorr {
 //   block = kThreads;  dynamic LDS = SparseLds<R> + staged dictionary lists + T bits of row flags.
 //   A.scratch needs B * nsplit tables.
 // ------------------------------------------------------------------------------------------------
-template <typename R>
-__global__ __launch_bounds__(kThreads) void corr_init_sparse_kernel(DevParams P, State<R> S, SparseArgs<R> A0)
+//   RAGGED: PB is the batch (strides, LDS layout), P the signal (rows t >= T_b are neither scanned nor computed).
+template <typename R, bool RAGGED = false>
+__global__ __launch_bounds__(kThreads) void corr_init_sparse_kernel(DevParams PB, State<R> S, SparseArgs<R> A0)
 {
+    const DevParams P = signal_params<RAGGED>(PB, S, (int)blockIdx.x);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const SparseLds<R> L = sparse_lds_view<R>(smem, A0.caps);
-    unsigned* rowbits = reinterpret_cast<unsigned*>(smem + sparse_lds_bytes<R>(A0.caps) + staged_dict_bytes(P, A0));   // [ceil(T/32)]
+    unsigned* rowbits = reinterpret_cast<unsigned*>(smem + sparse_lds_bytes<R>(A0.caps) + staged_dict_bytes(PB, A0));   // [ceil(T/32)] of the batch's T
     const int b = blockIdx.x, tid = threadIdx.x, T = P.T, W = P.W, F = P.F;
-    stage_dict(P, A0, smem + sparse_lds_bytes<R>(A0.caps));               // (ordered by the barrier below)
-    SparseArgs<R> A = dict_view(P, A0, smem + sparse_lds_bytes<R>(A0.caps));
+    stage_dict(PB, A0, smem + sparse_lds_bytes<R>(A0.caps));               // (ordered by the barrier below)
+    SparseArgs<R> A = dict_view(PB, A0, smem + sparse_lds_bytes<R>(A0.caps));
     A.scratch = A0.scratch + ((int64_t)blockIdx.y * gridDim.x) * (2 * W - 1) * P.K;   // sparse_rows adds blockIdx.x tables
     Sig<R> G{};
-    G.r = S.residual + (int64_t)b * T * F;
-    G.bc = S.best_c + (int64_t)b * T;
-    G.bk = S.best_k + (int64_t)b * T;
+    G.r = S.residual + (int64_t)b * PB.T * F;
+    G.bc = S.best_c + (int64_t)b * PB.T;
+    G.bk = S.best_k + (int64_t)b * PB.T;
     // this workgroup's output rows [r_lo, r_hi) and the input rows they can see [in_lo, in_hi)
     const int blk = 2 * W - 1;
     const int nblocks = (T + blk - 1) / blk;
@@ -1160,9 +1177,9 @@ __global__ __launch_bounds__(kThreads) void corr_init_sparse_kernel(DevParams P,
     for (int t = r_lo + tid; t < r_hi; t += kThreads) { G.bc[t] = (R)0; G.bk[t] = 0; }
     __syncthreads();
     // input rows with a non-zero sample: handed over by the level chaining, or found by a scan
-    unsigned char* rf = A.rowflag ? A.rowflag + (int64_t)b * T : nullptr;
+    unsigned char* rf = A.rowflag ? A.rowflag + (int64_t)b * PB.T : nullptr;
     if (A.rl_cnt) {
-        const int* cnt = A.rl_cnt + (int64_t)b * T;
+        const int* cnt = A.rl_cnt + (int64_t)b * PB.T;
         for (int t = in_lo + tid; t < in_hi; t += kThreads) if (cnt[t] > 0) atomicOr(&rowbits[t >> 5], 1u << (t & 31));
     } else if (rf && A.rowflag_filled) {
         for (int t = in_lo + tid; t < in_hi; t += kThreads) if (rf[t]) atomicOr(&rowbits[t >> 5], 1u << (t & 31));
@@ -1180,7 +1197,7 @@ __global__ __launch_bounds__(kThreads) void corr_init_sparse_kernel(DevParams P,
         const int lo = max(0, row0 - P.off), hi = min(T - 1, row0 + nrows - 1 - P.off + W - 1);
         int any = 0;
         for (int t = lo + tid; t <= hi; t += kThreads) any |= (rowbits[t >> 5] >> (t & 31)) & 1u;
-        if (__syncthreads_or(any)) sparse_rows(P, S, G, A, L, rowbits, row0, nrows, false, 0, 0);
+        if (__syncthreads_or(any)) sparse_rows<R, false, RAGGED>(P, S, G, A, L, rowbits, row0, nrows, false, 0, 0);
     }
 }
 

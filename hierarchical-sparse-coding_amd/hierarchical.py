@@ -16,7 +16,8 @@ import os
 import numpy as np
 import scipy.sparse
 
-from .modeling import ConvolutionalMatchingPursuit, ConvolutionalSparseCoder, SparseApproximator, reconstructSignal, reject_ragged
+from .modeling import (ConvolutionalMatchingPursuit, ConvolutionalSparseCoder, SparseApproximator, reconstructSignal, reject_ragged,
+                       is_ragged, ragged_batch, ragged_signals)
 
 
 def _is_multilevel_dict(obj):
@@ -165,7 +166,8 @@ class HierarchicalConvolutionalMatchingPursuit(SparseApproximator):
         per-level kernel timings); with returnEvents=True a fourth item: per-signal event record arrays.
         The steps live in _LevelPipeline (below): level set-up, one level over one chunk with event-list regrowth, chunk sizing,
         the two epilogues, the per-signal fallback."""
-        reject_ragged(sequences, lengths, 'HierarchicalConvolutionalMatchingPursuit.computeCoefficientsBatch (levels >= 1, level chaining, epilogue)')
+        _reject_ragged(sequences, lengths, 'HierarchicalConvolutionalMatchingPursuit.computeCoefficientsBatch (levels >= 1, level chaining, epilogue)',
+                       'computeCoefficientsRaggedBatch')
         assert residuals in ('samples', 'energy')
         assert _is_multilevel_dict(multilevelDict)
         if self.method not in ('cmp', 'locomp'):
@@ -175,30 +177,32 @@ class HierarchicalConvolutionalMatchingPursuit(SparseApproximator):
         return pipe.run_chained() if chained else pipe.run_unchained()
 
     def _host_epilogue_chunk(self, engines, first, count, nbLevels, multilevelDict, returnDistributed, sequences, results, returnEvents,
-                             residual_out, energy_out, startLevel=1):
+                             residual_out, energy_out, startLevel=1, lengths=None):
         """The chunk's epilogue on the host (:1556-1634, :1596-1611) from the slot lists of every level's engine -- level 0 holds
         the whole batch, the levels above it this chunk.  Same results as the device epilogue (tests/test_hierarchical.py).
         startLevel > 1 (a resumed encode): the levels below it were not run, and the post-processing reads nothing of a level
-        below the last but its shape -- they go in as empty matrices."""
+        below the last but its shape -- they go in as empty matrices.  lengths: the lengths of ALL signals of a ragged batch
+        (signal first + b: lengths[first + b] rows; `sequences[i]` then has that many rows, and the rows of residual_out above are zero)."""
         from . import _native
         from .modeling import _slots_to_csc
+        rows = lambda b: engines[-1]._batch[1] if lengths is None else int(lengths[first + b])
         levels = []
         for l in range(nbLevels):
             if l < startLevel - 1:
-                shape = (engines[-1]._batch[1], int(multilevelDict.getRawDictionary(l).shape[0]))
-                levels.append([scipy.sparse.csc_matrix(shape, dtype=np.float64) for _ in range(count)])
+                K_l = int(multilevelDict.getRawDictionary(l).shape[0])
+                levels.append([scipy.sparse.csc_matrix((rows(b), K_l), dtype=np.float64) for b in range(count)])
                 continue
             eng, off = engines[l], (first if l == startLevel - 1 else 0)
             st, sk, sa = eng.fetch_slots()
             stats = eng.fetch_stats()
-            T = eng._batch[1]
-            levels.append([_slots_to_csc(st[off + b], sk[off + b], sa[off + b], int(stats[off + b, _native.STAT_SLOTS]), (T, eng.K), 1e-16)
+            levels.append([_slots_to_csc(st[off + b], sk[off + b], sa[off + b], int(stats[off + b, _native.STAT_SLOTS]), (rows(b), eng.K), 1e-16)
                            for b in range(count)])
         for b in range(count):
             cb = self._postprocessCoefficients([levels[l][b] for l in range(nbLevels)], multilevelDict, returnDistributed)
             residual = np.asarray(self._calculateResidual(sequences[first + b], cb, multilevelDict), dtype=np.float64)
             if residual_out is not None:
-                residual_out[b] = residual.reshape(residual_out[b].shape)
+                residual_out[b] = 0.0
+                residual_out[b, :rows(b)] = residual.reshape((rows(b),) + residual_out[b].shape[1:])
             if energy_out is not None:
                 energy_out[b] = float(np.sum(np.square(residual)))
             ev = None
@@ -208,7 +212,7 @@ class HierarchicalConvolutionalMatchingPursuit(SparseApproximator):
             results[first + b] = (cb, None, ev)
 
     def _device_epilogue(self, engines, first, count, nbLevels, multilevelDict, returnDistributed, slot_counts, results, returnEvents, residual_out,
-                         energy_out=None):
+                         energy_out=None, lengths=None):
         """hscmp_hierarchy_epilogue for one chunk: per signal the per-level coefficient matrices (:1556-1634), the residual
         (:1596-1611) and the event records (dataset.py:798-811), from the last level's device-resident slots."""
         import scipy.sparse
@@ -225,7 +229,7 @@ class HierarchicalConvolutionalMatchingPursuit(SparseApproximator):
         n, colptr, offsets, indices, data, events, residual = last.hierarchy_epilogue(
             engines[0], first if nbLevels > 1 else 0, levels, 1e-16, slot_counts, want_events=returnEvents, want_residual=residual_out is not None,
             residual_out=residual_out, energy_out=energy_out)
-        T = last._batch[1]
+        rows = lambda b: last._batch[1] if lengths is None else int(lengths[first + b])     # (a ragged batch: matrices of (T_b, K_l))
         # per-level column pointers of the whole chunk at once: level l is the slice [c0, c1) of the last level's columns
         ptrs, starts = [], []
         for l, (c0, c1, _) in enumerate(levels):
@@ -241,10 +245,10 @@ class HierarchicalConvolutionalMatchingPursuit(SparseApproximator):
             mats = []
             for l in range(nbLevels):
                 if ptrs[l] is None:
-                    mats.append(scipy.sparse.csc_matrix((T, counts[l]), dtype=np.float64))
+                    mats.append(scipy.sparse.csc_matrix((rows(b), counts[l]), dtype=np.float64))
                     continue
                 lo = o + int(starts[l][b]); hi = lo + int(ptrs[l][b, -1])
-                mats.append(_csc_from_checked_arrays(data[lo:hi], indices[lo:hi], ptrs[l][b], (T, counts[l])))
+                mats.append(_csc_from_checked_arrays(data[lo:hi], indices[lo:hi], ptrs[l][b], (rows(b), counts[l])))
             ev = events[o:o + int(n[b])] if events is not None else None
             results[first + b] = (mats, None, ev)
 
@@ -270,7 +274,7 @@ class HierarchicalConvolutionalMatchingPursuit(SparseApproximator):
         uninterrupted computeCoefficientsBatch bit for bit.  L == getNbLevels() encodes nothing and returns the post-processed
         input.  residuals: None (the second item returned is None), 'samples' or 'energy' as for computeCoefficientsBatch.
         The per-level timings list a level that was not run with variant 'loaded' and zero kernel times."""
-        reject_ragged(sequences, None, 'HierarchicalConvolutionalMatchingPursuit.computeCoefficientsFromLevelBatch')
+        _reject_ragged(sequences, None, 'HierarchicalConvolutionalMatchingPursuit.computeCoefficientsFromLevelBatch', 'computeCoefficientsFromLevelRaggedBatch')
         assert residuals in (None, 'samples', 'energy')
         assert _is_multilevel_dict(multilevelDict)
         if self.method not in ('cmp', 'locomp'):
@@ -280,6 +284,95 @@ class HierarchicalConvolutionalMatchingPursuit(SparseApproximator):
         pipe = _LevelPipeline(self, sequences, multilevelDict, toleranceSnr, nbBlocks, singletonWeight, returnDistributed, epilogue,
                               returnEvents, None, residuals, memoryBudget)
         return pipe.run_from_level(coefficients, fromLevel)
+
+    def computeCoefficientsRaggedBatch(self, sequences, multilevelDict, toleranceSnr=None, nbBlocks=1, singletonWeight=0.5,
+                                       returnDistributed=True, memoryBudget=None, epilogue='device', returnEvents=False,
+                                       residuals='samples', lengths=None):
+        """computeCoefficientsBatch for signals of different lengths (method='cmp'): `sequences` a list / tuple of arrays [T_b] or
+        [T_b,F], or a padded array [B,T(,F)] with `lengths` [B].  Signal b gets, at every level, exactly what it gets encoded
+        alone at its own length: the chained pipeline runs on per-signal lengths -- the ragged level-0
+        encode, the level hand-off on the device, either epilogue, chunks under `memoryBudget`.  Returns (per-signal lists of
+        per-level matrices of shape (T_b, K_l), residuals: a list of float64 arrays [T_b(,F)] -- or the float64 vector [B] of
+        their energies with residuals='energy' --, per-level kernel timings, whose variants end in '_ragged'); with
+        returnEvents=True a fourth item: per-signal event record arrays.  Every signal must be at least as long as the widest
+        filter of the hierarchy (ValueError naming signal, length and width, before any device work)."""
+        assert residuals in ('samples', 'energy')
+        x, lens = _ragged_input(self, sequences, lengths, multilevelDict, 0, 'computeCoefficientsBatch')
+        pipe = _LevelPipeline(self, x, multilevelDict, toleranceSnr, nbBlocks, singletonWeight, returnDistributed, epilogue, returnEvents,
+                              None, residuals, memoryBudget, lengths=lens)
+        return pipe.run_chained()
+
+    def computeCoefficientsFromLevelRaggedBatch(self, sequences, coefficients, multilevelDict, toleranceSnr=None, nbBlocks=1, singletonWeight=0.5,
+                                                returnDistributed=True, memoryBudget=None, epilogue='device', returnEvents=False, residuals=None,
+                                                lengths=None):
+        """computeCoefficientsFromLevelBatch for signals of different lengths (method='cmp'): `sequences` as for
+        computeCoefficientsRaggedBatch, `coefficients[b]` signal b's matrices of levels 0 .. L-1, the last of shape
+        (T_b, K_{L-1}).  They go back to the device through hscmp_load_level_ragged; levels L .. last are encoded, and the results
+        equal an uninterrupted computeCoefficientsRaggedBatch bit for bit.  Returns what that method returns, with the second
+        item as `residuals` asks (None: None)."""
+        assert residuals in (None, 'samples', 'energy')
+        assert _is_multilevel_dict(multilevelDict)
+        if not is_ragged(sequences, lengths):
+            raise ValueError('a plain array without lengths= is a uniform batch: use computeCoefficientsFromLevelBatch')
+        # (the lengths first: they size the matrices; then the widths of the levels that will run)
+        fromLevel = _check_given_ragged_levels(ragged_signals(sequences, lengths, 1)[0], coefficients, multilevelDict)
+        x, lens = _ragged_input(self, sequences, lengths, multilevelDict, fromLevel, 'computeCoefficientsFromLevelBatch')
+        pipe = _LevelPipeline(self, x, multilevelDict, toleranceSnr, nbBlocks, singletonWeight, returnDistributed, epilogue,
+                              returnEvents, None, residuals, memoryBudget, lengths=lens)
+        return pipe.run_from_level(coefficients, fromLevel)
+
+
+def _reject_ragged(sequences, lengths, what, ragged_name):
+    """The uniform entry points keep refusing ragged input (with the text they always had) and name the ragged form."""
+    try:
+        reject_ragged(sequences, lengths, what)
+    except NotImplementedError as ex:
+        raise NotImplementedError('%s; the ragged form of this method is %s' % (ex, ragged_name))
+
+
+def _ragged_input(hcmp, sequences, lengths, multilevelDict, fromLevel, uniform_name):
+    """The checks of the ragged entry points, before any device call: (padded x [B,T] or [B,T,F] in the level-0 compute dtype,
+    lengths int32 [B]).  Every signal must be at least as long as the widest filter of the levels fromLevel .. last."""
+    from .modeling import _compute_dtype
+    assert _is_multilevel_dict(multilevelDict)
+    if not is_ragged(sequences, lengths):
+        raise ValueError('a plain array without lengths= is a uniform batch: use %s' % uniform_name)
+    if hcmp.method == 'locomp':
+        raise NotImplementedError('the LoCOMP loop has no ragged form (signals of different lengths): use method=\'cmp\'')
+    if hcmp.method != 'cmp':
+        raise Exception('Unsupported sparse coding method: %s' % (hcmp.method))
+    D0 = multilevelDict.getRawDictionary(0)
+    F0 = 1 if D0.ndim == 2 else int(D0.shape[2])
+    src = np.result_type(*[np.asarray(q).dtype for q in sequences]) if isinstance(sequences, (list, tuple)) else np.asarray(sequences).dtype
+    dt = _compute_dtype(src, D0.dtype)
+    widths = [int(multilevelDict.getRawDictionary(l).shape[1]) for l in range(fromLevel, multilevelDict.getNbLevels())]
+    x, lens, seqs = ragged_batch(sequences, lengths, dt, max(widths + [1]), F0)
+    if seqs[0].ndim == 1 or (not isinstance(sequences, (list, tuple)) and np.asarray(sequences).ndim == 2):
+        x = x[:, :, 0]
+    return np.ascontiguousarray(x), lens
+
+
+def _check_given_ragged_levels(lens, coefficients, multilevelDict):
+    """_check_given_levels with a length per signal: the last given matrix of signal b must be sparse (T_b, K_{L-1})."""
+    who = 'computeCoefficientsFromLevelRaggedBatch'
+    B = len(lens)
+    if len(coefficients) != B:
+        raise ValueError('%s: %d signals, but coefficients of %d' % (who, B, len(coefficients)))
+    nbLevels = multilevelDict.getNbLevels()
+    L = None
+    for b, levels in enumerate(coefficients):
+        n = len(levels)
+        if not 1 <= n <= nbLevels:
+            raise ValueError('%s: signal %d has the coefficients of %d levels, outside 1 .. %d' % (who, b, n, nbLevels))
+        if L is None:
+            L = n
+        if n != L:
+            raise ValueError('%s: signal %d has the coefficients of %d levels, signal 0 of %d' % (who, b, n, L))
+        want = (int(lens[b]), int(multilevelDict.getRawDictionary(L - 1).shape[0]))
+        if not scipy.sparse.issparse(levels[-1]) or tuple(levels[-1].shape) != want:
+            raise ValueError('%s: signal %d: the matrix of level %d must be sparse with shape %s, got %s' % (
+                who, b, L - 1, want, getattr(levels[-1], 'shape', type(levels[-1]).__name__)))
+    return L
 
 
 def _check_given_levels(sequences, coefficients, multilevelDict):
@@ -324,7 +417,7 @@ class _LevelPipeline(object):
       host_signal      signal b on the host, from the device when the batch was handed over as a device pointer"""
 
     def __init__(self, hcmp, sequences, multilevelDict, toleranceSnr, nbBlocks, singletonWeight, returnDistributed, epilogue, returnEvents,
-                 deviceInput, residuals, memoryBudget):
+                 deviceInput, residuals, memoryBudget, lengths=None):
         self.hcmp, self.sequences, self.mld = hcmp, sequences, multilevelDict
         self.toleranceSnr, self.nbBlocks, self.singletonWeight = toleranceSnr, nbBlocks, singletonWeight
         self.returnDistributed, self.returnEvents, self.deviceInput, self.residuals = returnDistributed, returnEvents, deviceInput, residuals
@@ -335,11 +428,18 @@ class _LevelPipeline(object):
         self.locomp = hcmp.method == 'locomp'
         self.nbLevels = multilevelDict.getNbLevels()
         self.B, self.T = sequences.shape[0], sequences.shape[1]
+        # a ragged batch (computeCoefficientsRaggedBatch): `sequences` is its padded form [B,T(,F)], T the longest length and the
+        # stride of every device array; signal b owns rows [0, lengths[b]) -- of its input, its matrices (T_b, K_l) and its residual
+        self.lengths = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
         self.group_failed = set()
         self.per_level = [[None] * self.B for _ in range(self.nbLevels)]
         self.timings = []
         self.engines = None
         self.dt0 = None
+
+    def rows(self, b):
+        """Rows of signal b: T, or its own length in a ragged batch."""
+        return self.T if self.lengths is None else int(self.lengths[b])
 
     # ---- per level
     def level_setup(self, level):
@@ -397,9 +497,9 @@ class _LevelPipeline(object):
             st, sk, sa = eng.fetch_slots()
             if lazy:
                 # (the CSC assembly joins the per-signal host epilogue, which runs on all cores)
-                out = [(st[b], sk[b], sa[b], int(stats[b, _native.STAT_SLOTS]), (self.T, K), 1e-16) for b in range(count)]
+                out = [(st[b], sk[b], sa[b], int(stats[b, _native.STAT_SLOTS]), (self.rows(offset + b), K), 1e-16) for b in range(count)]
             else:
-                out = [_slots_to_csc(st[b], sk[b], sa[b], int(stats[b, _native.STAT_SLOTS]), (self.T, K), 1e-16) for b in range(count)]
+                out = [_slots_to_csc(st[b], sk[b], sa[b], int(stats[b, _native.STAT_SLOTS]), (self.rows(offset + b), K), 1e-16) for b in range(count)]
         tm = dict(variant=eng.last_variant(), kernel_ms=kernel_ms,
                   selections=int(stats[:, _native.STAT_ITERATIONS].sum()), duplicates=int(stats[:, _native.STAT_DUPLICATES].sum()),
                   rounds=int(stats[:, _native.STAT_ROUNDS].sum()),
@@ -411,7 +511,7 @@ class _LevelPipeline(object):
         """Signal b as a host array: from the device when the batch came as a device pointer (the host array may be a placeholder)."""
         seq = np.asarray(self.sequences)
         if self.deviceInput is None:
-            return seq[b]
+            return seq[b] if self.lengths is None else seq[b, :self.rows(b)]
         shape = seq.shape[1:]
         nbytes = int(np.prod(shape)) * np.dtype(self.dt0).itemsize
         return self.engines[0].copy_from_device(int(self.deviceInput) + b * nbytes, shape, self.dt0)
@@ -494,7 +594,7 @@ class _LevelPipeline(object):
         en_out = None if energy_all is None else energy_all[first:first + count]
         try:
             self.hcmp._device_epilogue(self.engines, first, count, nbLevels, self.mld, self.returnDistributed, slot_counts, results,
-                                       self.returnEvents, res_out, en_out)
+                                       self.returnEvents, res_out, en_out, lengths=self.lengths)
         except _native.HscmpError as ex:
             # a shape outside the epilogue kernel's key layout (2^20 atoms / list entries, 2^24 samples): this chunk's
             # redistribution and residual are done on the host from the fetched slot lists, as with epilogue='host'
@@ -502,7 +602,7 @@ class _LevelPipeline(object):
                 raise
             seqs = _ChunkSignals(self, first)
             self.hcmp._host_epilogue_chunk(self.engines, first, count, nbLevels, self.mld, self.returnDistributed, seqs, results,
-                                           self.returnEvents, res_out, en_out, startLevel=start)
+                                           self.returnEvents, res_out, en_out, startLevel=start, lengths=self.lengths)
 
     def run_chained(self):
         from . import _native
@@ -522,7 +622,10 @@ class _LevelPipeline(object):
             enc0 = lambda p: engines[0].encode_batch_device(int(self.deviceInput), B, T, p)
         else:
             x = np.ascontiguousarray(np.asarray(sequences).reshape((B, T, -1)), dtype=dt)
-            enc0 = lambda p: engines[0].encode_batch(x, p)
+            if self.lengths is not None:
+                enc0 = lambda p: engines[0].encode_batch_ragged(x, self.lengths, p)
+            else:
+                enc0 = lambda p: engines[0].encode_batch(x, p)
         self.per_level[0], tm, stats0 = self.encode_level(engines[0], enc0, B, targetSnr, eps, lazy=True)
         tm['level'] = 0
         self.timings.append(tm)
@@ -559,11 +662,15 @@ class _LevelPipeline(object):
         self.timings = [loaded(l) if l < fromLevel else dict(loaded(l), variant='') for l in range(nbLevels)]
         x = np.ascontiguousarray(self.sequences.reshape((B, T, -1)), dtype=dt)
         given = [coefficients[b][-1] for b in range(B)]
-        if fromLevel == 1:
-            engines[0].load_level(x, T, given)
+        if self.lengths is not None:
+            load = lambda e, x_, ms: e.load_level_ragged(x_, T, self.lengths, ms)
         else:
-            engines[0].load_level(x, T, [scipy.sparse.csc_matrix((T, engines[0].K), dtype=np.float64)] * B)
-            engines[fromLevel - 1].load_level(None, T, given)
+            load = lambda e, x_, ms: e.load_level(x_, T, ms)
+        if fromLevel == 1:
+            load(engines[0], x, given)
+        else:
+            load(engines[0], x, [scipy.sparse.csc_matrix((self.rows(b), engines[0].K), dtype=np.float64) for b in range(B)])
+            load(engines[fromLevel - 1], None, given)
         for l in range(fromLevel):
             self.per_level[l] = [coefficients[b][l] for b in range(B)]      # (host epilogue: the levels as given)
         return self.second_as_asked(self.run_chunks(setups, engines[fromLevel - 1].fetch_stats(), fromLevel))
@@ -573,6 +680,8 @@ class _LevelPipeline(object):
         second = out[1]
         if self.residuals is None:
             second = None
+        elif self.residuals == 'energy' and second is not None and isinstance(second, list):
+            second = np.array([np.sum(np.square(np.asarray(r, dtype=np.float64))) for r in second], dtype=np.float64)
         elif self.residuals == 'energy' and second is not None and np.ndim(second) > 1:
             second = np.sum(np.square(np.asarray(second, dtype=np.float64)).reshape((self.B, -1)), axis=1)
         return (out[0], second) + tuple(out[2:])
@@ -613,7 +722,8 @@ class _LevelPipeline(object):
                 ev = convertSparseMatricesToEvents(cb)
             results[b] = (cb, None, ev)
             if residual_all is not None:
-                residual_all[b] = np.asarray(res_b, dtype=np.float64).reshape(residual_all[b].shape)
+                residual_all[b] = 0.0
+                residual_all[b, :self.rows(b)] = np.asarray(res_b, dtype=np.float64).reshape((self.rows(b),) + residual_all[b].shape[1:])
             if energy_all is not None:
                 energy_all[b] = float(np.sum(np.square(np.asarray(res_b, dtype=np.float64))))
         if energy_all is not None:
@@ -622,6 +732,8 @@ class _LevelPipeline(object):
             second = None                                  # (a resumed encode that was not asked for residuals)
         else:
             second = residual_all[:, :, 0] if np.asarray(sequences).ndim == 2 else residual_all
+            if self.lengths is not None:                   # per-signal residuals of the signal's own length
+                second = [second[b, :self.rows(b)].copy() for b in range(B)]
         out = ([r[0] for r in results], second, self.timings)
         return out + ([r[2] for r in results],) if self.returnEvents else out
 
@@ -646,7 +758,13 @@ class _LevelPipeline(object):
         else:
             done = [finish(b) for b in range(B)]         # (device copies go through one engine: one thread)
         coefficients = [d[0] for d in done]
-        out = (coefficients, np.stack([d[1] for d in done], axis=0) if self.residuals is not None else None, self.timings)
+        if self.residuals is None:
+            second = None
+        elif self.lengths is not None:
+            second = [np.asarray(d[1], dtype=np.float64) for d in done]
+        else:
+            second = np.stack([d[1] for d in done], axis=0)
+        out = (coefficients, second, self.timings)
         if self.returnEvents:
             from .dataset import convertSparseMatricesToEvents
             out = out + ([convertSparseMatricesToEvents(c) for c in coefficients],)
@@ -709,6 +827,15 @@ class HierarchicalConvolutionalSparseCoder(object):
         """encodeFromLevel for a batch: coefficients[b] is signal b's list of level matrices."""
         assert len(coefficients) > 0
         return self.approximator.computeCoefficientsFromLevelBatch(sequences, coefficients, self.multilevelDict, *args, **kwargs)
+
+    def encodeRaggedBatch(self, sequences, *args, **kwargs):
+        """encodeBatch for signals of different lengths: the approximator's computeCoefficientsRaggedBatch."""
+        return self.approximator.computeCoefficientsRaggedBatch(sequences, self.multilevelDict, *args, **kwargs)
+
+    def encodeFromLevelRaggedBatch(self, sequences, coefficients, *args, **kwargs):
+        """encodeFromLevelBatch for signals of different lengths."""
+        assert len(coefficients) > 0
+        return self.approximator.computeCoefficientsFromLevelRaggedBatch(sequences, coefficients, self.multilevelDict, *args, **kwargs)
 
     def reconstruct(self, coefficients):
         assert len(coefficients) > 0

@@ -189,10 +189,13 @@ def reject_ragged(sequences, lengths, what):
                                   'ConvolutionalMatchingPursuit.computeCoefficientsBatch' % what)
 
 
-def ragged_batch(sequences, lengths, dtype, W, F):
-    """The padded form of a ragged batch, checked on the host: (x [B,T,F] of `dtype` with T the longest length, lengths int32 [B],
-    per-signal views [T_b] / [T_b,F] of the caller's data).  `sequences`: a list / tuple of arrays [T_b] or [T_b,F], or an array
-    [B,T(,F)] with lengths [B].  Rows of the padding are zero here; the engine never reads them."""
+def ragged_signals(sequences, lengths, W, F=None):
+    """The signals of a ragged batch, checked on the host: (lengths int64 [B], per-signal views [T_b] / [T_b,F] of the caller's
+    data).  `sequences`: a list / tuple of arrays [T_b] or [T_b,F], or an array [B,T(,F)] with lengths [B].  Every signal has F
+    features (None: those of the first signal) and at least W rows."""
+    if F is None:
+        first = np.asarray(sequences[0]) if len(sequences) > 0 else np.zeros((0,))
+        F = 1 if first.ndim <= 1 else int(first.shape[-1])
     if isinstance(sequences, (list, tuple)):
         if lengths is not None:
             raise ValueError('lengths= goes with a padded array, not with a list of signals')
@@ -224,6 +227,13 @@ def ragged_batch(sequences, lengths, dtype, W, F):
     if np.any(lens < W):
         b = int(np.argmax(lens < W))
         raise ValueError('signal %d: length %d is shorter than the filters (W=%d)' % (b, lens[b], W))
+    return lens, seqs
+
+
+def ragged_batch(sequences, lengths, dtype, W, F):
+    """The padded form of a ragged batch, checked on the host (ragged_signals): (x [B,T,F] of `dtype` with T the longest length,
+    lengths int32 [B], per-signal views of the caller's data).  Rows of the padding are zero here; the engine never reads them."""
+    lens, seqs = ragged_signals(sequences, lengths, W, F)
     B, T = len(seqs), int(lens.max())
     x = np.zeros((B, T, F), dtype=dtype)
     for b, q in enumerate(seqs):

@@ -18,7 +18,7 @@ import numpy as np
 
 from .dataset import MultilevelDictionary, addSingletonBases, scalesToWindowSizes
 from .kmeans import ConvolutionalKMeansLearner
-from .modeling import is_ragged
+from .modeling import is_ragged, ragged_signals
 
 logger = logging.getLogger(__name__)
 
@@ -45,7 +45,7 @@ class MultilevelDictionaryLearner(object):
         self.lastStats = None
         self.lastDictionaries = None                         # after trainCorpus: the learnt [K_l, W_l(, F_l)] of every level, without singleton bases
 
-    def _check(self, sequences, lengths):
+    def _check_setup(self):
         if self.method in ('mptk-mp', 'mptk-cmp'):
             raise NotImplementedError("method='%s' needs the external MPTK toolkit, which this engine does not bind; "
                                       "use method='cmp' or 'locomp'" % self.method)
@@ -55,9 +55,13 @@ class MultilevelDictionaryLearner(object):
             raise ValueError('multilevel learner: %d counts for %d scales' % (len(self.counts), len(self.scales)))
         if len(self.counts) < 1:
             raise ValueError('multilevel learner: needs at least one level')
+
+    def _check(self, sequences, lengths):
+        self._check_setup()
         if is_ragged(sequences, lengths):
             raise NotImplementedError('multilevel learner: signals of different lengths are not supported: the hierarchical batch encode '
-                                      '(HierarchicalConvolutionalMatchingPursuit.computeCoefficientsBatch) has no ragged form')
+                                      '(HierarchicalConvolutionalMatchingPursuit.computeCoefficientsBatch) has no ragged form; '
+                                      'use trainRaggedCorpus')
         sequences = np.asarray(sequences)
         if sequences.ndim not in (2, 3):
             raise ValueError('multilevel learner: the corpus must be [B,T] or [B,T,F] (got %d dimensions)' % sequences.ndim)
@@ -79,15 +83,47 @@ class MultilevelDictionaryLearner(object):
         (computeCoefficientsFromLevelBatch, as the reference's script calls encodeFromLevel) and runs the new level only;
         resume=False encodes the levels below again.  The dictionaries are the same bit for bit either way: the lower
         levels' dictionaries and parameters have not changed."""
-        from .hierarchical import HierarchicalConvolutionalMatchingPursuit
         sequences = self._check(sequences, lengths)
+        kmeans = dict(maxIterations=maxIterations, tolerance=tolerance, initMethod=initMethod, resetMethod=resetMethod, nbAveragedPatches=nbAveragedPatches)
+        encode = dict(toleranceSnr=toleranceSnr, nbBlocks=nbBlocks, singletonWeight=singletonWeight, returnDistributed=False)
+        return self._levels(sequences, False, nbRandomWindows, kmeans, encode, resume)
+
+    def trainRaggedCorpus(self, sequences, nbRandomWindows, maxIterations=100, tolerance=0.0, initMethod='random_samples',
+                          resetMethod='noise', nbAveragedPatches=8, toleranceSnr=None, nbBlocks=1, singletonWeight=0.5, lengths=None,
+                          resume=True):
+        """trainCorpus over a corpus of signals of different lengths (method='cmp'): `sequences` a list / tuple of arrays [T_b]
+        or [T_b,F], or a padded array [B,T(,F)] with `lengths` [B].  The level loop is trainCorpus's: k-means takes the ragged
+        list -- from level 1 the list of sparse (T_b, K) matrices --, and the hand-off encodes are
+        HierarchicalConvolutionalMatchingPursuit.computeCoefficientsRaggedBatch / computeCoefficientsFromLevelRaggedBatch, so
+        every signal is encoded at its own length.  A corpus whose lengths are all equal gives
+        trainCorpus's dictionaries.  lastStats is as for trainCorpus, with input_shape the list of per-signal input shapes."""
+        if self.method == 'locomp':
+            raise NotImplementedError('multilevel learner: the LoCOMP loop has no ragged form (signals of different lengths): use method=\'cmp\'')
+        self._check_setup()
+        if not is_ragged(sequences, lengths):
+            raise ValueError('multilevel learner: a plain array without lengths= is a uniform corpus: use trainCorpus')
+        wmax = int(max(scalesToWindowSizes(self.scales)))          # (every level's k-means draws windows of its width)
+        try:
+            _, seqs = ragged_signals(sequences, lengths, wmax)
+        except ValueError as ex:
+            raise ValueError('multilevel learner: %s' % str(ex).replace('the filters (W=', 'the widest filter of the levels (W='))
+        kmeans = dict(maxIterations=maxIterations, tolerance=tolerance, initMethod=initMethod, resetMethod=resetMethod, nbAveragedPatches=nbAveragedPatches)
+        encode = dict(toleranceSnr=toleranceSnr, nbBlocks=nbBlocks, singletonWeight=singletonWeight, returnDistributed=False)
+        return self._levels(seqs, True, nbRandomWindows, kmeans, encode, resume)
+
+    def _levels(self, sequences, ragged, nbRandomWindows, kmeans, encode, resume):
+        """The level loop of trainCorpus (`sequences` [B,T(,F)]) and trainRaggedCorpus (a list of [T_b(,F)] arrays)."""
+        from .hierarchical import HierarchicalConvolutionalMatchingPursuit
+        toleranceSnr = encode['toleranceSnr']
         if toleranceSnr is not None and isinstance(toleranceSnr, collections.abc.Iterable) and len(toleranceSnr) < len(self.counts) - 1:
             raise ValueError('multilevel learner: toleranceSnr has %d values, the encodes run up to level %d' % (
                 len(toleranceSnr), len(self.counts) - 2))
         nbLevels = len(self.counts)
         widths = scalesToWindowSizes(self.scales)
-        B = sequences.shape[0]
+        B = len(sequences)
         hcmp = HierarchicalConvolutionalMatchingPursuit(method=self.method, device=self.device)
+        encode_all = hcmp.computeCoefficientsRaggedBatch if ragged else hcmp.computeCoefficientsBatch
+        encode_from = hcmp.computeCoefficientsFromLevelRaggedBatch if ragged else hcmp.computeCoefficientsFromLevelBatch
         dictionaries, stats = [], []
         inputs, mld, coefficients = sequences, None, None
         try:
@@ -95,8 +131,7 @@ class MultilevelDictionaryLearner(object):
                 sparse = level > 0
                 t0 = time.perf_counter()
                 learner = ConvolutionalKMeansLearner(self.counts[level], int(widths[level]), device=self.device, rng=self.rng)
-                D = learner.trainCorpus(inputs, nbRandomWindows, maxIterations=maxIterations, tolerance=tolerance, initMethod=initMethod,
-                                        resetMethod=resetMethod, nbAveragedPatches=nbAveragedPatches)
+                D = learner.trainCorpus(inputs, nbRandomWindows, **kmeans)
                 t1 = time.perf_counter()
                 dictionaries.append(D)
                 if level > 0:
@@ -105,18 +140,15 @@ class MultilevelDictionaryLearner(object):
                     mld = MultilevelDictionary.fromRawDictionaries(dictionaries, self.scales[:1])
                 t2 = time.perf_counter()
                 st = dict(kmeans=learner.lastStats, learn_s=t1 - t0, setup_s=learner.lastSetupSeconds,
-                          input_shape=(B,) + tuple(inputs[0].shape) if sparse else tuple(sequences.shape),
+                          input_shape=[tuple(m.shape) for m in inputs] if ragged else (B,) + tuple(inputs[0].shape) if sparse else tuple(sequences.shape),
                           input_nnz=int(sum(m.nnz for m in inputs)) if sparse else None, encode_s=None, encode_nnz=None, encode_timings=None)
                 if level < nbLevels - 1:
                     if resume and level > 0:
                         # (the levels below keep the last pass's dictionaries and parameters: their coefficients are in hand)
-                        coefficients, _, st['encode_timings'] = hcmp.computeCoefficientsFromLevelBatch(
-                            sequences, coefficients, mld, toleranceSnr=toleranceSnr, nbBlocks=nbBlocks, singletonWeight=singletonWeight,
-                            returnDistributed=False)
+                        coefficients, _, st['encode_timings'] = encode_from(sequences, coefficients, mld, **encode)
                     else:
                         # (resume=False: the levels below are encoded again, to the same bits)
-                        coefficients, _, st['encode_timings'] = hcmp.computeCoefficientsBatch(
-                            sequences, mld, toleranceSnr=toleranceSnr, nbBlocks=nbBlocks, singletonWeight=singletonWeight, returnDistributed=False)
+                        coefficients, _, st['encode_timings'] = encode_all(sequences, mld, **encode)
                     inputs = [c[-1] for c in coefficients]
                     st['encode_s'] = time.perf_counter() - t2
                     st['encode_nnz'] = int(sum(m.nnz for m in inputs))

@@ -178,7 +178,8 @@ int hscmp_encode_batch_device(hscmp_ctx* ctx, const void* x_dev, int B, int T, c
  * anything.  The context keeps the lengths for hscmp_continue, hscmp_grow_events, hscmp_stop_signal and the fetches until
  * the next encode; fetched arrays keep the [B][T] strides, and hscmp_fetch_residual returns zeros in rows >= lengths[b].
  * HSCMP_ERR_INVALID for B < 1, lengths == NULL or a length out of range (hscmp_last_error names the signal);
- * HSCMP_ERR_UNSUPPORTED under HSCMP_METHOD_LOCOMP and for inputs that take the sparse (multi-feature) kernels.
+ * HSCMP_ERR_UNSUPPORTED under HSCMP_METHOD_LOCOMP.  Every plan of the CMP loop has a ragged form: multi-feature inputs take
+ * the sparse (level) kernels at their own lengths.
  * hscmp_last_variant ends in "_ragged".  The _device form takes x in GPU memory and is asynchronous on the context's stream. */
 int hscmp_encode_batch_ragged(hscmp_ctx* ctx, const void* x, int B, int T, const int32_t* lengths, const hscmp_params* params);
 int hscmp_encode_batch_ragged_device(hscmp_ctx* ctx, const void* x_dev, int B, int T, const int32_t* lengths, const hscmp_params* params);
@@ -188,7 +189,11 @@ int hscmp_encode_batch_ragged_device(hscmp_ctx* ctx, const void* x_dev, int B, i
  * (its distinct (t,k) slots, clipped like the CSC epilogue modeling.py:1171-1181 with
  * min_coefficients; NaN = None) become the dense input [count][T][K_prev] of `ctx`, which is then
  * encoded like hscmp_encode_batch_device.  ctx must hold a float64 dictionary with F == K_prev; both
- * contexts live on the same GPU. */
+ * contexts live on the same GPU.
+ * When `prev` holds a ragged batch (hscmp_encode_batch_ragged, hscmp_load_level_ragged, or a chain from one) so does ctx:
+ * signal i takes the length of signal first + i of `prev`, and the blocks of this level's W and nb_blocks on that length.
+ * HSCMP_ERR_INVALID, naming the signal and W, for a length below this level's W; HSCMP_ERR_UNSUPPORTED under
+ * HSCMP_METHOD_LOCOMP.  hscmp_last_variant then ends in "_ragged". */
 int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, int first, int count, double min_coefficients,
                                   const hscmp_params* params);
 
@@ -215,6 +220,15 @@ int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, int first, in
  * the same input and the same energy, bit for bit, as a chain from the context that computed those coefficients. */
 int hscmp_load_level(hscmp_ctx* ctx, const void* x, int B, int T, const int64_t* offsets, const int32_t* rows,
                      const int32_t* cols, const double* data);
+
+/* hscmp_load_level for signals of different lengths: lengths host int32 [B] with 1 <= lengths[b] <= T, T the stride of x
+ * (rows t >= lengths[b] of x are never read by what follows).  An entry's row must lie in [0, lengths[b]); the refusal
+ * names signal, entry, row and T_b, and is all-or-nothing like hscmp_load_level's.  The context then holds a ragged batch
+ * (the lengths, no block geometry: an encode chained from it computes its own), stop reason HSCMP_STOP_LOADED, and serves
+ * the same calls as a loaded uniform batch: hscmp_encode_batch_from_level as `prev` and, with x, hscmp_hierarchy_epilogue
+ * as `level0` of a ragged last level.  HSCMP_ERR_INVALID for lengths == NULL or a length out of range. */
+int hscmp_load_level_ragged(hscmp_ctx* ctx, const void* x, int B, int T, const int32_t* lengths, const int64_t* offsets,
+                            const int32_t* rows, const int32_t* cols, const double* data);
 
 /* Window assignment of the convolutional k-means dictionary learner (ConvolutionalDictionaryLearner.
  * _train_kmean, modeling.py:454-460 = convolve1d_batch(windows, D, 'valid') + arg-max of |c| per window):
