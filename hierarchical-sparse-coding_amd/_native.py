@@ -29,7 +29,7 @@ EXPORTS = ['hscmp_version', 'hscmp_create', 'hscmp_destroy', 'hscmp_last_error',
            'hscmp_update_inner_products', 'hscmp_table_open', 'hscmp_table_select', 'hscmp_table_update', 'hscmp_table_read', 'hscmp_assign_windows', 'hscmp_host_overlap_add', 'hscmp_host_slots_to_csc', 'hscmp_hierarchy_epilogue', 'hscmp_encode_batch',
            'hscmp_encode_batch_device', 'hscmp_encode_batch_ragged', 'hscmp_encode_batch_ragged_device', 'hscmp_encode_batch_from_level', 'hscmp_load_level', 'hscmp_load_level_ragged', 'hscmp_continue', 'hscmp_grow_events', 'hscmp_mem_info', 'hscmp_copy_from_device', 'hscmp_stop_signal', 'hscmp_fetch_events',
            'hscmp_fetch_stats', 'hscmp_fetch_residual', 'hscmp_fetch_energies', 'hscmp_fetch_slots',
-           'hscmp_get_device_view', 'hscmp_last_kernel_ms', 'hscmp_last_variant']
+           'hscmp_get_device_view', 'hscmp_last_kernel_ms', 'hscmp_last_variant', 'hscmp_wide_plan', 'hscmp_wide_counters']
 
 
 class HscmpParams(ctypes.Structure):
@@ -126,6 +126,8 @@ def load_library():
     lib.hscmp_last_kernel_ms.argtypes = [vp, vp]
     lib.hscmp_last_variant.argtypes = [vp]
     lib.hscmp_last_variant.restype = ctypes.c_char_p
+    lib.hscmp_wide_plan.argtypes = [ci, ci, ci, ci, ci, ci, ci, ctypes.POINTER(HscmpParams), vp]
+    lib.hscmp_wide_counters.argtypes = [vp, vp]
     for name in EXPORTS:   # also asserts that every declared symbol is exported
         fn = getattr(lib, name)
         if name not in ('hscmp_destroy', 'hscmp_last_error', 'hscmp_last_variant'):
@@ -629,6 +631,12 @@ class Engine(object):
         self._check(self._lib.hscmp_last_kernel_ms(self._h, _ptr(out)), 'hscmp_last_kernel_ms')
         return out
 
+    def wide_counters(self):
+        """(steps queued, control-block reads, (signal, step) pairs that found work, B) of the last encode if the wide loop ran it."""
+        out = np.zeros(4, dtype=np.int32)
+        self._check(self._lib.hscmp_wide_counters(self._h, _ptr(out)), 'hscmp_wide_counters')
+        return tuple(int(v) for v in out)
+
     def last_variant(self):
         return self._lib.hscmp_last_variant(self._h).decode()
 
@@ -731,3 +739,16 @@ def engine_for(device, D, weights=None):
     pool.append(eng)
     eng.set_dictionary(D3, w)
     return eng
+
+
+def wide_plan(K, W, F, dtype, has_weights, B, T, params):
+    """The wide loop's shape rule for such an encode (include/hscmp.h, hscmp_wide_plan; no device is touched):
+    dict(can_run, by_default, candidates, control_lds)."""
+    out = np.zeros(4, dtype=np.int32)
+    rc = load_library().hscmp_wide_plan(int(K), int(W), int(F), dtype_code(dtype), 1 if has_weights else 0, int(B), int(T),
+                                        ctypes.byref(params), _ptr(out))
+    if rc != 0:
+        err = HscmpError('hscmp_wide_plan failed (%d): %s' % (rc, load_library().hscmp_last_error(None).decode()))
+        err.code = rc
+        raise err
+    return dict(can_run=bool(out[0]), by_default=bool(out[1]), candidates=int(out[2]), control_lds=int(out[3]))

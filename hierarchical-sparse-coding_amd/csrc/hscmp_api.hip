@@ -12,6 +12,7 @@
 #include "hscmp_sparse.h"
 #include "hscmp_rp.h"
 #include "hscmp_rp_sparse.h"
+#include "hscmp_wide.h"
 #include "hscmp_locomp.h"
 #include "hscmp_epilogue.h"
 
@@ -33,7 +34,7 @@ using namespace hscmp;
 struct Knobs {
     bool no_dict_lists, no_row_lists, no_rowbits, no_pairing, force_gathered, force_generic;     // set or not
     bool init_only, exact_init, exact_recorr, locomp_no_mfma, no_sorted_prepare, no_lazy_clear;
-    int rp, mfma_quad, sparse_packed;     // 0 / 1 forces the choice; -1: not set, chosen by the shape
+    int rp, mfma_quad, sparse_packed, wide;     // 0 / 1 forces the choice; -1: not set, chosen by the shape
     int locomp_pack;                      // at most this many signals per workgroup; 0: not set, by the batch size
     int slot_hash_min, locomp_group_cap, locomp_ahead, sorted_prepare_min, lds_pad;     // the value, or the default
     int epi_lds_keys;                     // the value if a power of two in 64..kEpiLdsKeys, else kEpiLdsKeys
@@ -98,6 +99,7 @@ static Knobs read_knobs()
     k.rp = (v = getenv("HSCMP_RP")) ? atoi(v) != 0 : -1;
     k.mfma_quad = (v = getenv("HSCMP_MFMA_QUAD")) ? atoi(v) != 0 : -1;
     k.sparse_packed = (v = getenv("HSCMP_SPARSE_PACKED")) ? atoi(v) != 0 : -1;
+    k.wide = (v = getenv("HSCMP_WIDE")) ? atoi(v) != 0 : -1;
     k.locomp_pack = (v = getenv("HSCMP_LOCOMP_PACK")) ? std::max(1, atoi(v)) : 0;     // (0 and below pack like 1)
     k.slot_hash_min = (v = getenv("HSCMP_SLOT_HASH_MIN")) ? std::max(0, atoi(v)) : kSlotHashMin;
     k.locomp_group_cap = (v = getenv("HSCMP_LOCOMP_GROUP_CAP")) ? std::min(4096, std::max(2, atoi(v))) : kLocompGroupCap;
@@ -112,11 +114,36 @@ static Knobs read_knobs()
     return k;
 }
 
+constexpr int kWideStepsPerPoll = 4;
+constexpr int kWideMaxBatch = 16;         // default dispatch: at most this many signals
+
+// The wide loop's shape rule, host arithmetic only (plan_encode and hscmp_wide_plan go by it): can these parameters run it --
+// float32, one feature, blocked rounds of at most kWideMaxSel candidates, a width RpMfma is built for, none of the options that
+// keep today's loops, and the control workgroup's LDS within kLdsLoop -- and does the default dispatch choose it.
+struct WideShape { bool can = false, by_default = false; size_t control_lds = 0; };
+static WideShape wide_shape(const DevParams& P, bool f32, bool has_w, bool ragged, bool locomp)
+{
+    WideShape ws;
+    if (!f32 || ragged || locomp || !wide_params_ok(P)) return ws;
+    MfmaArgs A{};
+    A.G = mfma_groups(P.K); A.S4 = mfma_chunks(P.W); A.has_w = has_w ? 1 : 0;
+    const int rc = dispatch_chunks<false>(A.S4, has_w, [&](auto s4c, auto hw) {
+        ws.control_lds = wide_control_lds<RpMfma<decltype(s4c)::value, decltype(hw)::value>>(P, A);
+        return 0;
+    });
+    ws.can = rc == 0 && ws.control_lds <= kLdsLoop;
+    // Default: the encodes that nothing but the one-atom-at-a-time loop runs today (more candidates per round than the
+    // round-parallel workgroup holds) while the batch leaves most of the chip idle; one round per call (a stopCondition
+    // callback) keeps today's loop.  Bounds: DESIGN.md section 22.
+    ws.by_default = ws.can && P.maxsel > RpMfma<2, false>::kMaxSel && P.B <= kWideMaxBatch && P.max_rounds <= 0;
+    return ws;
+}
+
 // The kernels of one encode, chosen once by plan_encode before anything is queued: run_encode queues them (launch_init,
 // launch_loop) and hscmp_continue resumes the batch with the same loop and the same knobs.
 struct EncodePlan {
     enum Init { kInitMfma, kInitBound, kInitSparse, kInitOwn, kInitGeneric };
-    enum Loop { kLoopMfma, kLoopSparse, kLoopGeneric, kLoopLocomp, kLoopLocompSparse, kLoopLocompMfma };
+    enum Loop { kLoopMfma, kLoopSparse, kLoopGeneric, kLoopLocomp, kLoopLocompSparse, kLoopLocompMfma, kLoopWide };
     Init init = kInitGeneric;
     Loop loop = kLoopGeneric;
     bool rp = false;          // the round-parallel form of the loop (hscmp_rp.h, hscmp_rp_sparse.h)
@@ -157,6 +184,7 @@ struct Workspace {
     DevBuf head;              // [B][T] slot chains by position (round-parallel loop)
     DevBuf lgram;             // [B][kLgramDoubles] LoCOMP: Gram matrices beyond the LDS copy
     DevBuf geom;              // [B][kGeomWords] of a ragged batch
+    DevBuf wide;              // control blocks and candidate arrays of the wide loop (hscmp_wide.h: wide_scratch_bytes)
 };
 
 // Workspace arena of the entry points outside the batch encode (grow-only, lives as long as the context): the hierarchical
@@ -203,6 +231,7 @@ struct hscmp_ctx {
     bool timed_loop_only = false;   // the last timed launch was a hscmp_continue (no prepare / initial correlation)
     int method = 0;                 // hscmp_set_method: 0 = greedy pursuit (modeling.py:1053), 1 = LoCOMP (:1267)
     EncodePlan plan;                // the kernels of the last encode (hscmp_continue resumes its loop)
+    int wide_steps = 0, wide_polls = 0, wide_worked = 0;     // the last wide loop: steps queued, times the control blocks were read, (signal, step) pairs that found work
     const void* last_x_dev = nullptr;   // device address of the signals of the last encode (hscmp_hierarchy_epilogue reads them)
     // device-resident inner-product table of LoCOMP (hscmp_table_*): [T][K] in slot kArenaTable, its residual in kArenaTabRes
     int tab_T = 0;
@@ -521,6 +550,9 @@ static int ensure_workspace_g(hscmp_ctx* ctx, const DevParams& P, bool need_x, s
         {w.head, (P.blocked || locomp) ? B * T * sizeof(int) : 0},
         {w.lgram, locomp ? B * lgram_doubles(P.lg_cap) * sizeof(double) : 0},
         {w.geom, geom_bytes},
+        // every shape the wide loop could take, whatever HSCMP_WIDE and the batch size will make plan_encode choose behind this
+        // call (52 bytes per block of a round: wide_scratch_bytes)
+        {w.wide, es == 4 && !multi_feature && !locomp && geom_bytes == 0 && wide_params_ok(P) ? wide_scratch_bytes(P.B, P.maxsel) : 0},
     };
     bool stream_idle = false;
     for (const auto& b : want) {
@@ -663,6 +695,17 @@ template <typename R> static EncodePlan plan_encode(hscmp_ctx* ctx, const Knobs&
                 mfma_launch_iterate<R>(ctx->stream, P, S, dimg, 4, kn.lds_pad, true, ctx->dict.Bimg.as<unsigned short>(), ctx->dict.bound_cmax) == 0)
                 plan.bound_loop = true;
             plan.rp = rp_mfma && rp_mfma_launch(ctx->stream, P, S, dimg, true) == 0;
+            // The wide loop (hscmp_wide.h): a round's atoms over the whole chip, for few long signals.
+            // HSCMP_WIDE=1 forces it wherever it can run, 0 forbids it.  Unset, it takes the encodes that nothing but the
+            // one-atom-at-a-time loop runs today -- more candidates per round than the round-parallel workgroup holds -- while
+            // the batch leaves most of the chip idle (kWideMaxBatch); a set HSCMP_RP or HSCMP_MFMA_QUAD keeps what it selects.
+            const WideShape wsh = wide_shape(P, true, S.weights != nullptr, ragged, locomp);
+            if (wsh.can && ctx->ws.wide.holds(wide_scratch_bytes(P.B, P.maxsel)) &&
+                (kn.wide == 1 || (kn.wide < 0 && kn.rp < 0 && kn.mfma_quad < 0 && !plan.rp && wsh.by_default)) &&
+                wide_launch(ctx->stream, P, S, dimg, ctx->ws.wide.as<char>(), kWideDry) == 0) {
+                plan.loop = EncodePlan::kLoopWide;
+                plan.rp = false; plan.group = 1; plan.bound_loop = false;
+            }
         }
         return plan;
     }
@@ -706,11 +749,12 @@ static std::string variant_of(const EncodePlan& plan)
     const bool bound = plan.init == EncodePlan::kInitBound;
     if (plan.init_only) return bound ? "bound_init" : "mfma_init";
     static const char* const inits[] = {"mfma", "mfma", "sparse", "own", "generic"};
-    static const char* const loops[] = {"mfma", "gathered", "generic", "locomp", "locomp_dictlist", "locomp_mfma"};
+    static const char* const loops[] = {"mfma", "gathered", "generic", "locomp", "locomp_dictlist", "locomp_mfma", "mfma"};
     const char* init = plan.init == EncodePlan::kInitSparse && plan.dict_lists ? "dictlist" : inits[plan.init];
     const char* loop = plan.loop == EncodePlan::kLoopSparse && plan.dict_lists ? "dictlist" : loops[plan.loop];
     std::string v = std::string(init) + "_init+" + loop + "_loop_" + (plan.f64 ? "f64" : "f32") + (bound ? "_bound" : "");
-    if (plan.rp) v += "_rp";
+    if (plan.loop == EncodePlan::kLoopWide) v += "_wide";
+    else if (plan.rp) v += "_rp";
     else if (plan.loop == EncodePlan::kLoopMfma && plan.group > 1) v += "_x" + std::to_string(plan.group);
     if (plan.ragged) v += "_ragged";
     return v;
@@ -753,6 +797,41 @@ template <typename R> static int launch_init(hscmp_ctx* ctx, const EncodePlan& p
     return HSCMP_OK;
 }
 
+// The wide loop (hscmp_wide.h): the start of the call, then steps of four launches -- control, subtract, re-correlate, candidates --
+// queued kWideStepsPerPoll at a time; behind each batch of steps the control blocks are read (one small copy; the stream is
+// waited for), until every signal has stopped or run its max_rounds.  Steps queued past that point find no work.
+static int wide_loop(hscmp_ctx* ctx, const EncodePlan& plan, const DevParams& P)
+{
+    const State<float> S = make_state<float>(ctx, false);
+    const float* dimg = ctx->dict.Dfrag.as<const float>();
+    char* wbuf = ctx->ws.wide.as<char>();
+    if (!ctx->ws.wide.holds(wide_scratch_bytes(P.B, P.maxsel)))
+        return fail(ctx, HSCMP_ERR_STATE, "the loop of %s has no workspace", variant_of(plan).c_str());
+    HIP_TRY(ctx, hipMemsetAsync(S.head, 0xff, (size_t)P.B * P.T * sizeof(int), ctx->stream));
+    if (wide_launch(ctx->stream, P, S, dimg, wbuf, kWideBegin) != 0)
+        return fail(ctx, HSCMP_ERR_HIP, "the loop of %s could not be launched", variant_of(plan).c_str());
+    std::vector<int> ctl((size_t)P.B * WC_COUNT);
+    ctx->wide_steps = 0; ctx->wide_polls = 0; ctx->wide_worked = 0;
+    for (;;) {
+        for (int s = 0; s < kWideStepsPerPoll; ++s)
+            if (wide_launch(ctx->stream, P, S, dimg, wbuf, kWideStep) != 0)
+                return fail(ctx, HSCMP_ERR_HIP, "the loop of %s could not be launched", variant_of(plan).c_str());
+        ctx->wide_steps += kWideStepsPerPoll; ctx->wide_polls += 1;
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(ctl.data(), wbuf, ctl.size() * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        bool done = true;
+        int worked = 0;
+        for (int b = 0; b < P.B; ++b) { done = done && ctl[(size_t)b * WC_COUNT + WC_DONE] != 0; worked += ctl[(size_t)b * WC_COUNT + WC_STEPS]; }
+        // (every step of a running signal applies atoms or ends a round: a batch of steps without any is a fault, not a wait)
+        if (!done && worked == ctx->wide_worked)
+            return fail(ctx, HSCMP_ERR_HIP, "the loop of %s made no progress in %d steps", variant_of(plan).c_str(), kWideStepsPerPoll);
+        ctx->wide_worked = worked;
+        if (done) break;
+    }
+    return HSCMP_OK;
+}
+
 // Queue the loop of the plan: run_encode behind the initial correlation, hscmp_continue on the state an earlier launch left.
 template <typename R> static int launch_loop(hscmp_ctx* ctx, const EncodePlan& plan, const DevParams& P)
 {
@@ -782,6 +861,9 @@ template <typename R> static int launch_loop(hscmp_ctx* ctx, const EncodePlan& p
     case EncodePlan::kLoopLocompSparse: rc = launch_policy<R, LocompSparse<R>>(ctx, P, sparse_args<R>(ctx, plan, P.T), 1, false); break;
     case EncodePlan::kLoopLocompMfma:
         if constexpr (sizeof(R) == 4) rc = launch_locomp_mfma(ctx, P, plan.group, false);
+        break;
+    case EncodePlan::kLoopWide:
+        if constexpr (sizeof(R) == 4) return wide_loop(ctx, plan, P);
         break;
     }
     if (rc != 0) return fail(ctx, HSCMP_ERR_HIP, "the loop of %s could not be launched", variant_of(plan).c_str());
@@ -1838,5 +1920,27 @@ extern "C" int hscmp_table_read(hscmp_ctx* ctx, void* out_table, void* out_resid
     if (out_table) HIP_TRY(ctx, hipMemcpyAsync(out_table, ctx->arena[kArenaTable].p, (size_t)ctx->tab_T * ctx->dict.K * es, hipMemcpyDeviceToHost, ctx->stream));
     if (out_residual) HIP_TRY(ctx, hipMemcpyAsync(out_residual, ctx->arena[kArenaTabRes].p, (size_t)ctx->tab_T * ctx->dict.F * es, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return HSCMP_OK;
+}
+
+extern "C" int hscmp_wide_plan(int K, int W, int F, hscmp_dtype dtype, int has_weights, int B, int T, const hscmp_params* params, int32_t* out4)
+{
+    if (!params || !out4 || K <= 0 || W <= 0 || F <= 0 || B <= 0 || T <= 0) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_wide_plan: bad arguments");
+    if (dtype != HSCMP_F32 && dtype != HSCMP_F64) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_wide_plan: bad dtype %d", (int)dtype);
+    Knobs kn{};
+    kn.slot_hash_min = kSlotHashMin; kn.locomp_group_cap = kLocompGroupCap; kn.locomp_ahead = 7;
+    DevParams P;
+    const int rc = make_params_g(nullptr, kn, K, W, F, B, T, params, &P);
+    if (rc) return rc;
+    const WideShape ws = wide_shape(P, dtype == HSCMP_F32, has_weights != 0, false, false);
+    out4[0] = ws.can ? 1 : 0; out4[1] = ws.by_default ? 1 : 0; out4[2] = P.maxsel; out4[3] = (int32_t)ws.control_lds;
+    return HSCMP_OK;
+}
+
+extern "C" int hscmp_wide_counters(hscmp_ctx* ctx, int32_t* out4)
+{
+    if (!ctx || !out4) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_wide_counters: NULL argument");
+    const bool wide = ctx->have_batch && ctx->plan.loop == EncodePlan::kLoopWide;
+    out4[0] = wide ? ctx->wide_steps : 0; out4[1] = wide ? ctx->wide_polls : 0; out4[2] = wide ? ctx->wide_worked : 0; out4[3] = wide ? ctx->B : 0;
     return HSCMP_OK;
 }

@@ -751,6 +751,8 @@ template <int S4C, bool HAS_W> struct RpMfma {
         __builtin_amdgcn_wave_barrier();
     }
 
+    // (wide_subtract_kernel of hscmp_wide.h repeats this body for INTERIOR atoms with the taps from the image in global memory:
+    //  no edge record there.  A change to the arithmetic here belongs there too.)
     static __device__ __forceinline__ void subtract(const DevParams& P, const State<R>&, const Sig<R>& G, const Args& A, char* lds,
                                                     int p, int k, R c, int lane, int)
     {

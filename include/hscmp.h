@@ -169,7 +169,9 @@ int hscmp_table_read(hscmp_ctx* ctx, void* out_table, void* out_residual);
 int hscmp_encode_batch(hscmp_ctx* ctx, const void* x, int B, int T, const hscmp_params* params);
 
 /* Same, x_dev already resident in GPU memory (device pointer, same layout); asynchronous on the
- * context's stream. */
+ * context's stream -- except when the wide loop runs the encode (hscmp_last_variant ends in "_wide"): that loop queues its
+ * kernels a few steps at a time and reads the signals' control blocks in between, so the call returns with the loop finished
+ * and the stream idle (hscmp_continue is synchronous for every loop). */
 int hscmp_encode_batch_device(hscmp_ctx* ctx, const void* x_dev, int B, int T, const hscmp_params* params);
 
 /* A batch of signals of different lengths in one call: x [B][T][F] with T the longest length, lengths host int32 [B] with
@@ -344,6 +346,17 @@ int hscmp_copy_from_device(hscmp_ctx* ctx, const void* src_dev, uint64_t nbytes,
 
 /* Name of the kernel variant the last encode dispatched ("mfma_f32", "generic_f64", ...). */
 const char* hscmp_last_variant(hscmp_ctx* ctx);
+
+/* The wide loop (a blocked round's atoms spread over the whole chip, "..._loop_f32_wide"): what its shape rule says about
+ * an encode of B signals of length T with a [K][W][F] dictionary.  Host arithmetic only: no context, no device.
+ * out4 = { the loop can run the shape (0 / 1), the default dispatch chooses it (0 / 1; HSCMP_WIDE=1 / 0 forces / forbids),
+ * candidates per round (blocks + 1; 1 for nb_blocks == 1), LDS bytes of its control workgroup (0: no wide form) }.
+ * LoCOMP and ragged batches never take the wide loop, whatever this says. */
+int hscmp_wide_plan(int K, int W, int F, hscmp_dtype dtype, int has_weights, int B, int T, const hscmp_params* params, int32_t* out4);
+
+/* Host-side counters of the last encode or hscmp_continue if the wide loop ran it (zeros otherwise):
+ * out4 = { steps queued (four launches each), times the control blocks were read, (signal, step) pairs that found work, B }. */
+int hscmp_wide_counters(hscmp_ctx* ctx, int32_t* out4);
 
 #ifdef __cplusplus
 }
