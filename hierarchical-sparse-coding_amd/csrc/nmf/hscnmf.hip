@@ -12,7 +12,8 @@
 // the reference's stop decision per signal on the device; a finished signal's workgroups return at once.
 // hscnmf_learn (the dictionary learner) adds, per iteration, the ratio, partial and update kernels of section 12;
 // hscnmf_learn_corpus (one dictionary from many signals of different lengths) runs the same kernel bodies over a ragged
-// geometry and sums the update over the signals, section 18.
+// geometry and sums the update over the signals, section 18; hscnmf_compute_ragged runs the coder over that geometry with
+// a stop flag per signal, in chunks of whole signals, section 23.
 #include "../../../include/hscnmf.h"
 #include "../common/hsc_lib.h"
 
@@ -954,11 +955,13 @@ constexpr int kMaxCorpusSignals = 1 << 22;
 // 2^24 - 1 workgroups.  The sample tiles (the row tiles are no more) and nmf_dsum_kernel's B * nchunk lie on such grids.
 constexpr long long kMaxCorpusGrid = (1LL << 32) / kThreads - 1;
 
-// the device memory of one hscnmf_learn_corpus call, freed (after a stream sync) when the call returns
+// the device memory of one hscnmf_learn_corpus (or hscnmf_compute_ragged) call, freed (after a stream sync) when the call
+// returns; `fn` names the entry point in the ERR_ALLOC message
 struct CorpusBuffers {
     hscnmf_ctx* ctx;
+    const char* fn;
     std::vector<void*> ptrs;
-    explicit CorpusBuffers(hscnmf_ctx* c) : ctx(c) {}
+    explicit CorpusBuffers(hscnmf_ctx* c, const char* f = "hscnmf_learn_corpus") : ctx(c), fn(f) {}
     ~CorpusBuffers()
     {
         (void)hipStreamSynchronize(ctx->stream);
@@ -969,7 +972,7 @@ struct CorpusBuffers {
         void* q = nullptr;
         hipError_t e = hipMalloc(&q, std::max<size_t>(bytes, 256));
         if (e != hipSuccess)
-            return fail(ctx, HSCNMF_ERR_ALLOC, "hscnmf_learn_corpus: hipMalloc of %zu bytes failed (%s)", bytes, hipGetErrorString(e));
+            return fail(ctx, HSCNMF_ERR_ALLOC, "%s: hipMalloc of %zu bytes failed (%s)", fn, bytes, hipGetErrorString(e));
         ptrs.push_back(q);
         *out = static_cast<U*>(q);
         return hsc::OK;
@@ -1145,4 +1148,318 @@ extern "C" int hscnmf_learn_corpus(hscnmf_ctx* ctx, int dtype, const void* x, co
     return learn_corpus_t<double>(ctx, (const double*)x, lengths, B, F, (const double*)D_init, K, W, (const double*)a_init, energy,
                                   *params, (double*)D_out, iterations, stop, snr, residual_scale, signal_snr,
                                   signal_residual_scale, timing_ms);
+}
+
+// ---- hscnmf_compute_ragged: the coder over B signals of different lengths, DESIGN.md section 23 ----------------------
+
+namespace {
+
+// the ragged geometry with the coder's stop state: one flag per signal (of the chunk)
+struct RaggedSignals : Ragged {
+    __device__ int flag(int b) const { return b; }
+};
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void nmf_step_signals_kernel(const T* __restrict__ Ain, T* __restrict__ Aout,
+                                                                    const T* __restrict__ X, const T* __restrict__ D,
+                                                                    const int* __restrict__ done, RaggedSignals g, int K, int W,
+                                                                    int F, int t, int PR, int slab)
+{
+    step_body(g, Ain, Aout, X, D, (size_t)0, done, K, W, F, t, PR, slab);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void nmf_residual_signals_kernel(const T* __restrict__ Abuf, const T* __restrict__ X,
+                                                                        const T* __restrict__ D, const int* __restrict__ done,
+                                                                        T* __restrict__ resid, double* __restrict__ part,
+                                                                        RaggedSignals g, int K, int W, int F, int PR, int slab)
+{
+    residual_body(g, Abuf, X, D, (size_t)0, done, resid, part, K, W, F, PR, slab);
+}
+
+// one workgroup (64 threads) per signal: nmf_decide_kernel on the signal's own sample-tile partials (64 threads striding
+// its tiles, then the tree: the same order), writing that signal's state alone
+__global__ __launch_bounds__(64) void nmf_decide_signals_kernel(const double* __restrict__ part,
+                                                                const SignalInfo* __restrict__ sig,
+                                                                const double* __restrict__ energy, int* __restrict__ done,
+                                                                int* __restrict__ iters, int* __restrict__ stop,
+                                                                double* __restrict__ snr, double* __restrict__ rscale,
+                                                                int it1, hscnmf_params p)
+{
+    const int b = blockIdx.x;
+    if (done[b]) return;
+    __shared__ double smx[64], sss[64];
+    const int ntiles = (sig[b].T + kRows - 1) / kRows;
+    const double* pb = part + (size_t)sig[b].st0 * 2;
+    double mx = 0.0, ss = 0.0;
+    for (int i = threadIdx.x; i < ntiles; i += 64) {
+        mx = fmax(mx, pb[(size_t)i * 2]);
+        ss = ss + pb[(size_t)i * 2 + 1];
+    }
+    smx[threadIdx.x] = mx;
+    sss[threadIdx.x] = ss;
+    __syncthreads();
+    for (int w = 32; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            smx[threadIdx.x] = fmax(smx[threadIdx.x], smx[threadIdx.x + w]);
+            sss[threadIdx.x] = sss[threadIdx.x] + sss[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double rs = smx[0], s = 10.0 * log10(energy[b] / sss[0]);
+        int code = HSCNMF_STOP_RUNNING;
+        if (it1 >= p.max_iterations) code = HSCNMF_STOP_MAX_ITERATIONS;
+        else if (p.has_residual_scale && rs <= p.tolerance_residual_scale) code = HSCNMF_STOP_RESIDUAL_SCALE;
+        else if (p.has_snr && s >= p.tolerance_snr) code = HSCNMF_STOP_SNR;
+        iters[b] = it1;
+        snr[b] = s;
+        rscale[b] = rs;
+        stop[b] = code;
+        if (code != HSCNMF_STOP_RUNNING) done[b] = 1;
+    }
+}
+
+// a chunk: the signals first .. first + count - 1, their samples, coefficient rows, row tiles and sample tiles, and the
+// device bytes they need
+struct RaggedChunk {
+    int first, count;
+    long long rows, arows, nrt, nst;
+    size_t bytes;
+};
+
+// The device buffers of a chunk, in the order they lie in the chunk's one allocation: the A pair, X, R, the residual
+// partials, (energy, snr, scale), (done, iterations, stop), the signal table, the two tile tables.  Each is rounded up to
+// 256 bytes (and is at least that); returns their sum.
+constexpr int kRaggedBuffers = 9;
+size_t ragged_sizes(size_t item, long long rows, long long arows, long long nrt, long long nst, long long nb, int F, int K,
+                    size_t (&s)[kRaggedBuffers])
+{
+    s[0] = s[1] = (size_t)arows * K * item;
+    s[2] = s[3] = (size_t)rows * F * item;
+    s[4] = (size_t)nst * 2 * sizeof(double);
+    s[5] = (size_t)nb * 3 * sizeof(double);
+    s[6] = (size_t)nb * 3 * sizeof(int);
+    s[7] = (size_t)nb * sizeof(SignalInfo);
+    s[8] = (size_t)(nrt + nst) * sizeof(int2);
+    size_t total = 0;
+    for (size_t& v : s) {
+        v = (std::max<size_t>(v, 256) + 255) / 256 * 256;
+        total += v;
+    }
+    return total;
+}
+
+// the argument checks hscnmf_ragged_plan and hscnmf_compute_ragged share (nothing is allocated before them)
+int ragged_check(hsc::CtxBase* ctx, const char* fn, int dtype, const int64_t* lengths, int B, int F, int K, int W)
+{
+    if (!lengths) return fail(ctx, HSCNMF_ERR_INVALID, "%s: NULL argument", fn);
+    if (dtype != HSCNMF_F32 && dtype != HSCNMF_F64) return fail(ctx, HSCNMF_ERR_INVALID, "%s: unknown dtype %d", fn, dtype);
+    if (B < 1 || K < 1 || F < 1) return fail(ctx, HSCNMF_ERR_INVALID, "%s: B = %d, K = %d, F = %d", fn, B, K, F);
+    if (W < 2) return fail(ctx, HSCNMF_ERR_INVALID, "%s: filter width %d (the reference needs W >= 2)", fn, W);
+    for (int b = 0; b < B; ++b)
+        if (lengths[b] < W)
+            return fail(ctx, HSCNMF_ERR_INVALID, "%s: signal %d: length %lld is shorter than the filter width %d", fn, b,
+                        (long long)lengths[b], W);
+    if ((int64_t)W * F > (1 << 24)) return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "%s: shape out of range", fn);
+    int PR = 0, slab = 0;
+    size_t lds = 0;
+    if (!(dtype == HSCNMF_F32 ? lds_plan<float>(W, F, PR, slab, lds) : lds_plan<double>(W, F, PR, slab, lds)))
+        return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "%s: W = %d, F = %d needs more than %d bytes of LDS per workgroup", fn, W, F,
+                    kLdsBytes);
+    for (int b = 0; b < B; ++b)
+        if ((lengths[b] - W + 1) * K > ((int64_t)1 << 31) / 8 || (lengths[b] + kRows - 1) / kRows > kMaxCorpusGrid)
+            return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "%s: signal %d: shape out of range", fn, b);
+    return hsc::OK;
+}
+
+// Consecutive signals into chunks: a chunk takes signals while its bytes stay within `budget`, its sample tiles within
+// kMaxCorpusGrid and its signals within kMaxCorpusSignals, and always takes at least one.
+void ragged_chunks(size_t item, const int64_t* lengths, int B, int F, int K, int W, size_t budget, std::vector<RaggedChunk>& out)
+{
+    size_t s[kRaggedBuffers];
+    out.clear();
+    for (int b = 0; b < B;) {
+        RaggedChunk c{b, 0, 0, 0, 0, 0, 0};
+        for (; b < B; ++b) {
+            const long long Tb = lengths[b], Lb = Tb - W + 1;
+            const long long rows = c.rows + Tb, arows = c.arows + Lb;
+            const long long nrt = c.nrt + (Lb + kRows - 1) / kRows, nst = c.nst + (Tb + kRows - 1) / kRows;
+            const size_t bytes = ragged_sizes(item, rows, arows, nrt, nst, c.count + 1, F, K, s);
+            if (c.count > 0 && (bytes > budget || nst > kMaxCorpusGrid || c.count + 1 > kMaxCorpusSignals)) break;
+            c = RaggedChunk{c.first, c.count + 1, rows, arows, nrt, nst, bytes};
+        }
+        out.push_back(c);
+    }
+}
+
+}  // namespace
+
+extern "C" int hscnmf_ragged_plan(int dtype, const int64_t* lengths, int B, int F, int K, int W, uint64_t budget_bytes,
+                                  int32_t* chunk_first, int32_t* n_chunks, uint64_t* max_chunk_bytes)
+{
+    const char* fn = "hscnmf_ragged_plan";
+    if (!n_chunks || !max_chunk_bytes) return fail(nullptr, HSCNMF_ERR_INVALID, "%s: NULL argument", fn);
+    if (int rc = ragged_check(nullptr, fn, dtype, lengths, B, F, K, W)) return rc;
+    if (budget_bytes < 1) return fail(nullptr, HSCNMF_ERR_INVALID, "%s: budget_bytes is 0", fn);
+    std::vector<RaggedChunk> chunks;
+    ragged_chunks(dtype == HSCNMF_F32 ? sizeof(float) : sizeof(double), lengths, B, F, K, W, (size_t)budget_bytes, chunks);
+    uint64_t most = 0;
+    for (size_t i = 0; i < chunks.size(); ++i) {
+        if (chunk_first) chunk_first[i] = chunks[i].first;
+        most = std::max<uint64_t>(most, chunks[i].bytes);
+    }
+    if (chunk_first) chunk_first[chunks.size()] = B;
+    *n_chunks = (int32_t)chunks.size();
+    *max_chunk_bytes = most;
+    return HSCNMF_OK;
+}
+
+// compute_t over the ragged geometry: per chunk of whole signals the upload, per iteration the W steps over the row
+// tiles, the residual over the sample tiles and the decision per signal, then the download.  One allocation holds the
+// largest chunk; D is uploaded once.  The launches and their order per signal are compute_t's.
+template <typename T>
+static int compute_ragged_t(hscnmf_ctx* ctx, const T* x, const int64_t* lengths, int B, int F, const T* D, int K, int W,
+                            const T* a_init, const double* energy, const hscnmf_params& p, T* coef, T* resid, int32_t* iters,
+                            int32_t* stop, double* snr, double* rscale, double* timing)
+{
+    const char* fn = "hscnmf_compute_ragged";
+    const int off = (W - 1) / 2;
+    int PR = 0, slab = 0;
+    size_t lds = 0;
+    lds_plan<T>(W, F, PR, slab, lds);                                // (ragged_check has accepted W and F)
+    HSC_TRY(hipSetDevice(ctx->device));
+    size_t freeb = 0, totalb = 0;
+    HSC_TRY(hipMemGetInfo(&freeb, &totalb));
+    const size_t budget = p.memory_budget ? (size_t)p.memory_budget : std::max<size_t>(freeb / 10 * 6, 1);
+    std::vector<RaggedChunk> chunks;
+    ragged_chunks(sizeof(T), lengths, B, F, K, W, budget, chunks);
+    size_t arena = 0;
+    for (const RaggedChunk& c : chunks) arena = std::max(arena, c.bytes);
+    // (the host tables are declared before `buf`, whose destructor synchronises the stream: they outlive their copies)
+    std::vector<SignalInfo> sig;
+    std::vector<int2> tiles;
+    std::vector<int> hdone;
+    CorpusBuffers buf(ctx, fn);
+    unsigned char* base = nullptr;
+    T* dD = nullptr;
+    if (int rc = buf.get(&base, arena)) return rc;
+    if (int rc = buf.get(&dD, (size_t)K * W * F * sizeof(T))) return rc;
+    hipStream_t st = ctx->stream;
+    HSC_TRY(hipMemcpyAsync(dD, D, (size_t)K * W * F * sizeof(T), hipMemcpyHostToDevice, st));
+    double tm[5] = {0, 0, 0, 0, 0};
+    long long x0 = 0, a0 = 0;                                        // the chunk's first sample and coefficient row in the stacks
+    for (const RaggedChunk& c : chunks) {
+        const int nb = c.count;
+        size_t s[kRaggedBuffers];
+        ragged_sizes(sizeof(T), c.rows, c.arows, c.nrt, c.nst, nb, F, K, s);
+        unsigned char* q = base;
+        void* at[kRaggedBuffers];
+        for (int i = 0; i < kRaggedBuffers; ++i) {
+            at[i] = q;
+            q += s[i];
+        }
+        T* dA[2] = {(T*)at[0], (T*)at[1]};
+        T *dX = (T*)at[2], *dR = (T*)at[3];
+        double *dPart = (double*)at[4], *dEn = (double*)at[5], *dSnr = dEn + nb, *dRs = dEn + 2 * (size_t)nb;
+        int *dDone = (int*)at[6], *dIt = dDone + nb, *dStop = dDone + 2 * (size_t)nb;
+        SignalInfo* dSig = (SignalInfo*)at[7];
+        int2* dTiles = (int2*)at[8];
+        // the chunk's tables, with offsets into the chunk's own stacks
+        sig.resize((size_t)nb);
+        tiles.resize((size_t)(c.nrt + c.nst));
+        long long rows = 0, arows = 0, nrt = 0, nst = 0;
+        for (int b = 0; b < nb; ++b) {
+            const long long Tb = lengths[c.first + b], Lb = Tb - W + 1;
+            const long long nr = (Lb + kRows - 1) / kRows, ns = (Tb + kRows - 1) / kRows;
+            sig[b] = SignalInfo{rows, arows, nrt, nst, (int)Tb, (int)Lb};
+            for (long long i = 0; i < nr; ++i) tiles[(size_t)(nrt + i)] = make_int2(b, (int)i);
+            for (long long i = 0; i < ns; ++i) tiles[(size_t)(c.nrt + nst + i)] = make_int2(b, (int)i);
+            rows += Tb;
+            arows += Lb;
+            nrt += nr;
+            nst += ns;
+        }
+        RaggedSignals grow, gsmp;
+        grow.sig = gsmp.sig = dSig;
+        grow.tiles = dTiles;
+        gsmp.tiles = dTiles + c.nrt;
+
+        HSC_TRY(hipEventRecord(ctx->ev[0], st));
+        HSC_TRY(hipMemcpyAsync(dX, x + (size_t)x0 * F, (size_t)c.rows * F * sizeof(T), hipMemcpyHostToDevice, st));
+        HSC_TRY(hipMemcpyAsync(dA[0], a_init + (size_t)a0 * K, (size_t)c.arows * K * sizeof(T), hipMemcpyHostToDevice, st));
+        HSC_TRY(hipMemcpyAsync(dEn, energy + c.first, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, st));
+        HSC_TRY(hipMemcpyAsync(dSig, sig.data(), (size_t)nb * sizeof(SignalInfo), hipMemcpyHostToDevice, st));
+        HSC_TRY(hipMemcpyAsync(dTiles, tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+        HSC_TRY(hipMemsetAsync(dDone, 0, (size_t)nb * 3 * sizeof(int), st));
+        HSC_TRY(hipEventRecord(ctx->ev[1], st));
+        int it = 0;
+        for (; it < p.max_iterations; ++it) {
+            for (int t = 0; t < W; ++t) {
+                const int g = it * W + t;
+                hipLaunchKernelGGL(nmf_step_signals_kernel<T>, dim3((unsigned)c.nrt), dim3(kThreads), lds, st, dA[g & 1],
+                                   dA[(g + 1) & 1], dX, dD, dDone, grow, K, W, F, t, PR, slab);
+            }
+            hipLaunchKernelGGL(nmf_residual_signals_kernel<T>, dim3((unsigned)c.nst), dim3(kThreads), lds, st,
+                               dA[((it + 1) * W) & 1], dX, dD, dDone, dR, dPart, gsmp, K, W, F, PR, slab);
+            hipLaunchKernelGGL(nmf_decide_signals_kernel, dim3(nb), dim3(64), 0, st, dPart, dSig, dEn, dDone, dIt, dStop, dSnr,
+                               dRs, it + 1, p);
+            HSC_TRY(hipGetLastError());
+            // the flags are read once per iteration, only with a tolerance and another iteration to go
+            if ((p.has_residual_scale || p.has_snr) && it + 1 < p.max_iterations) {
+                hdone.resize((size_t)nb);
+                HSC_TRY(hipMemcpyAsync(hdone.data(), dDone, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
+                HSC_TRY(hipStreamSynchronize(st));
+                if (std::all_of(hdone.begin(), hdone.end(), [](int v) { return v != 0; })) { ++it; break; }
+            }
+        }
+        HSC_TRY(hipEventRecord(ctx->ev[2], st));
+        HSC_TRY(hipMemcpyAsync(iters + c.first, dIt, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
+        HSC_TRY(hipMemcpyAsync(stop + c.first, dStop, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
+        HSC_TRY(hipMemcpyAsync(snr + c.first, dSnr, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st));
+        HSC_TRY(hipMemcpyAsync(rscale + c.first, dRs, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st));
+        HSC_TRY(hipMemcpyAsync(resid + (size_t)x0 * F, dR, (size_t)c.rows * F * sizeof(T), hipMemcpyDeviceToHost, st));
+        HSC_TRY(hipStreamSynchronize(st));
+        const int bad = no_result(iters, c.first, nb, it);
+        if (bad >= 0) return fail(ctx, HSCNMF_ERR_INVALID, "%s: signal %d has no result", fn, bad);
+        for (int b = 0; b < nb; ++b) {
+            // a signal that stopped after n iterations holds its coefficients in buffer (n * W) mod 2
+            const int n = iters[c.first + b], Tb = sig[b].T, Lb = sig[b].L;
+            T* dst = coef + (size_t)(x0 + sig[b].x0) * K;
+            std::memset(dst, 0, (size_t)off * K * sizeof(T));
+            std::memset(dst + (size_t)(off + Lb) * K, 0, (size_t)(Tb - off - Lb) * K * sizeof(T));
+            HSC_TRY(hipMemcpyAsync(dst + (size_t)off * K, dA[((size_t)n * W) & 1] + (size_t)sig[b].a0 * K,
+                                   (size_t)Lb * K * sizeof(T), hipMemcpyDeviceToHost, st));
+        }
+        HSC_TRY(hipEventRecord(ctx->ev[3], st));
+        HSC_TRY(hipStreamSynchronize(st));
+        if (int rc = hsc::add_times(ctx, 3, tm)) return rc;
+        tm[3] += 1;
+        tm[4] += it;
+        x0 += c.rows;
+        a0 += c.arows;
+    }
+    if (timing) std::memcpy(timing, tm, sizeof(tm));
+    return HSCNMF_OK;
+}
+
+extern "C" int hscnmf_compute_ragged(hscnmf_ctx* ctx, int dtype, const void* x, const int64_t* lengths, int B, int F,
+                                     const void* D, int K, int W, const void* a_init, const double* energy,
+                                     const hscnmf_params* params, void* coefficients, void* residual, int32_t* iterations,
+                                     int32_t* stop, double* snr, double* residual_scale, double* timing_ms)
+{
+    const char* fn = "hscnmf_compute_ragged";
+    if (!ctx) return fail(nullptr, HSCNMF_ERR_INVALID, "%s: ctx is NULL", fn);
+    if (!x || !lengths || !D || !a_init || !energy || !params || !coefficients || !residual || !iterations || !stop || !snr ||
+        !residual_scale)
+        return fail(ctx, HSCNMF_ERR_INVALID, "%s: NULL argument", fn);
+    if (params->max_iterations < 1) return fail(ctx, HSCNMF_ERR_INVALID, "%s: max_iterations = %d", fn, params->max_iterations);
+    if (int rc = ragged_check(ctx, fn, dtype, lengths, B, F, K, W)) return rc;
+    if (dtype == HSCNMF_F32)
+        return compute_ragged_t<float>(ctx, (const float*)x, lengths, B, F, (const float*)D, K, W, (const float*)a_init, energy,
+                                       *params, (float*)coefficients, (float*)residual, iterations, stop, snr, residual_scale,
+                                       timing_ms);
+    return compute_ragged_t<double>(ctx, (const double*)x, lengths, B, F, (const double*)D, K, W, (const double*)a_init, energy,
+                                    *params, (double*)coefficients, (double*)residual, iterations, stop, snr, residual_scale,
+                                    timing_ms);
 }

@@ -11,8 +11,9 @@ Reference behaviour kept:
   * the coefficients returned are the centred [T,K] array (rows (W-1)//2 .. (W-1)//2+T-W, zero elsewhere),
     the residual is squeezed to [T] for a [K,W] dictionary or a [T] signal.
 
-Added: computeCoefficientsBatch (signals [B,T(,F)] sharing D), ConvolutionalNMFLearner.trainBatch (one dictionary
-per signal) and trainCorpus (ONE dictionary from many signals, ragged corpora included).
+Added: computeCoefficientsBatch (signals [B,T(,F)] sharing D), computeCoefficientsRaggedBatch (signals of different
+lengths sharing D), ConvolutionalNMFLearner.trainBatch (one dictionary per signal) and trainCorpus
+(ONE dictionary from many signals, ragged corpora included).
 There is no CPU path: without libhscnmf.so or a visible GPU the calls raise hsc_amd._native.HscmpError.
 """
 import ctypes
@@ -28,7 +29,8 @@ logger = logging.getLogger(__name__)
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'nmf', 'libhscnmf.so')
 EXPORTS = ['hscnmf_version', 'hscnmf_create', 'hscnmf_destroy', 'hscnmf_last_error', 'hscnmf_compute', 'hscnmf_learn',
-           'hscnmf_learn_corpus']
+           'hscnmf_learn_corpus', 'hscnmf_compute_ragged']
+PLAN_EXPORTS = ['hscnmf_ragged_plan']     # include/hscnmf_plan.h: host arithmetic, no context
 STOP_NAMES = {0: 'running', 1: 'max_iterations', 2: 'residual_scale', 3: 'snr'}
 
 
@@ -48,8 +50,11 @@ def load_library():
         vp, ci = ctypes.c_void_p, ctypes.c_int
         head = [vp, ci, vp, ci, ci, ci, vp, ci, ci, vp, vp, ctypes.POINTER(HscnmfParams)]
         corpus = [vp, ci, vp, vp, ci, ci, vp, ci, ci, vp, vp, ctypes.POINTER(HscnmfParams)] + [vp] * 8
+        ragged = [vp, ci, vp, vp, ci, ci, vp, ci, ci, vp, vp, ctypes.POINTER(HscnmfParams)] + [vp] * 7
+        plan = [ci, vp, ci, ci, ci, ci, ctypes.c_uint64, vp, vp, vp]
         _lib = _native.load_satellite(LIB_PATH, 'hscnmf', {'hscnmf_compute': head + [vp] * 7, 'hscnmf_learn': head + [vp] * 6,
-                                                           'hscnmf_learn_corpus': corpus})
+                                                           'hscnmf_learn_corpus': corpus, 'hscnmf_compute_ragged': ragged,
+                                                           'hscnmf_ragged_plan': plan})
     return _lib
 
 
@@ -86,6 +91,47 @@ def _params(nbMaxIterations, toleranceResidualScale, toleranceSnr, memoryBudget)
     params.tolerance_snr = 0.0 if toleranceSnr is None else float(toleranceSnr)
     params.memory_budget = 0 if memoryBudget is None else int(memoryBudget)
     return params
+
+
+def ragged_plan(dtype, lengths, F, K, W, budget):
+    """The chunks computeCoefficientsRaggedBatch forms for signals of `lengths` under `budget` device bytes per chunk
+    (hscnmf_ragged_plan of include/hscnmf_plan.h: host arithmetic, no device).  Returns (chunk_first int32 [n_chunks + 1], the bytes of the largest
+    chunk): chunk c is the signals chunk_first[c] .. chunk_first[c + 1] - 1.  A refusal raises HscmpError with its code."""
+    lib = load_library()
+    lens = np.ascontiguousarray(np.asarray(lengths).reshape(-1), dtype=np.int64)
+    first = np.zeros((lens.shape[0] + 1,), dtype=np.int32)
+    n = np.zeros((1,), dtype=np.int32)
+    most = np.zeros((1,), dtype=np.uint64)
+    budget = int(budget)
+    if budget < 0 or budget >= 1 << 64:
+        raise ValueError('ragged_plan: the budget must be in [0, 2^64) bytes (got %d)' % budget)
+    p = _native._ptr
+    rc = lib.hscnmf_ragged_plan(_native.dtype_code(dtype), p(lens), int(lens.shape[0]), int(F), int(K), int(W), budget, p(first),
+                                p(n), p(most))
+    if rc != 0:
+        ex = _native.HscmpError('hscnmf_ragged_plan failed (%d): %s' % (rc, lib.hscnmf_last_error(None).decode()))
+        ex.code = int(rc)
+        raise ex
+    return first[:int(n[0]) + 1].copy(), int(most[0])
+
+
+def _call_compute_ragged(device, dt, x, lengths, D3, a0, energy, params):
+    """hscnmf_compute_ragged on the stack x [rows,F], lengths [B] int64, D3 [K,W,F], the stacked coefficients a0 [sum L_b,K]
+    (all of dtype dt).  Returns (coefficients [rows,K], residual [rows,F], NMFStats per signal)."""
+    B, F = lengths.shape[0], x.shape[1]
+    K, W = D3.shape[0], D3.shape[1]
+    ctx = _context(device)
+    coef = np.empty((x.shape[0], K), dtype=dt)
+    resid = np.empty((x.shape[0], F), dtype=dt)
+    iters = np.zeros((B,), dtype=np.int32)
+    stop = np.zeros((B,), dtype=np.int32)
+    snr = np.zeros((B,), dtype=np.float64)
+    rscale = np.zeros((B,), dtype=np.float64)
+    timing = np.zeros((5,), dtype=np.float64)
+    p = _native._ptr
+    ctx.call('compute_ragged', _native.dtype_code(dt), p(x), p(lengths), B, F, p(D3), K, W, p(a0), p(energy), ctypes.byref(params),
+             p(coef), p(resid), p(iters), p(stop), p(snr), p(rscale), p(timing))
+    return coef, resid, NMFStats(iters, stop, snr, rscale, timing)
 
 
 class NMFStats(object):
@@ -157,6 +203,68 @@ class ConvolutionalNMF(SparseApproximator):
             logger.debug('signal %d: SNR of %f dB after %d iterations, stop: %s' % (
                 b, snr[b], iters[b], STOP_NAMES.get(int(stop[b]))))
         return coef, resid, stats
+
+    def _prepare_ragged(self, sequences, D, lengths, initialCoefficients):
+        """The checks and draws of computeCoefficientsRaggedBatch, before any device call.  Returns (dt, x [rows,F],
+        lengths [B] int64, D3 [K,W,F], a0 [sum L_b,K], energy [B], the signals as given)."""
+        from .kmeans import corpus_signals
+        who = 'ConvolutionalNMF'
+        seqs = corpus_signals(sequences, lengths, who)
+        D = np.asarray(D)
+        if D.ndim not in (2, 3):
+            raise ValueError('%s: the dictionary must be [K,W] or [K,W,F] (got %d dimensions)' % (who, D.ndim))
+        K, W = D.shape[0], D.shape[1]
+        B = len(seqs)
+        F = 1 if seqs[0].ndim == 1 else seqs[0].shape[1]
+        if K < 1 or F < 1 or D.size != K * W * F:
+            raise ValueError('%s: a dictionary %s does not go with signals of %d features' % (who, D.shape, F))
+        for b, q in enumerate(seqs):
+            try:
+                check_shapes(q.shape[0], W)
+            except Exception as e:
+                raise type(e)('signal %d: %s' % (b, e))
+        if initialCoefficients is not None and len(initialCoefficients) != B:
+            raise ValueError('%s: %d initial coefficient arrays for %d signals' % (who, len(initialCoefficients), B))
+        lens = np.array([q.shape[0] for q in seqs], dtype=np.int64)
+        dt = _compute_dtype(seqs[0].dtype, D.dtype)
+        a0s = []
+        for b in range(B):                                # signal by signal, in corpus order (modeling.py:684)
+            if initialCoefficients is None:
+                a = draw_initial_coefficients(int(lens[b]), K, seqs[0].dtype)
+            else:
+                a = np.asarray(initialCoefficients[b])
+                if a.shape != (lens[b], K):
+                    raise ValueError('%s: the initial coefficients of signal %d must be [%d,%d] (got %s)' % (who, b, lens[b], K, a.shape))
+            a0s.append(np.asarray(a[:int(lens[b]) - W + 1], dtype=dt))      # rows past L_b never reach a reconstruction
+        x = np.ascontiguousarray(np.concatenate(seqs).reshape((-1, F)), dtype=dt)   # the signals' own samples, no padding
+        D3 = np.ascontiguousarray(D.reshape((K, W, F)), dtype=dt)
+        a0 = np.ascontiguousarray(np.concatenate(a0s), dtype=dt)
+        ends = np.cumsum(lens)
+        energy = np.array([np.sum(np.square(x[e - n:e])) for e, n in zip(ends, lens)], dtype=np.float64)   # modeling.py:681
+        return dt, x, lens, D3, a0, energy, seqs
+
+    def computeCoefficientsRaggedBatch(self, sequences, D, nbMaxIterations=None, toleranceResidualScale=None, toleranceSnr=None,
+                                       initialCoefficients=None, lengths=None):
+        """computeCoefficients for B signals of different lengths sharing D [K,W] or [K,W,F], in one call: `sequences` a
+        list / tuple of [T_b] or [T_b,F] arrays, a [B,T(,F)] array, or a padded array with `lengths` (its padding is never
+        read and may hold NaN); one dtype, one F.  Every signal gets, bit for bit, what computeCoefficientsBatch gives it
+        as a batch of one, and stops on its own; the signals are coded in chunks of whole signals within memoryBudget.
+        Without initialCoefficients (a list of [T_b,K] arrays) the draws are draw_initial_coefficients(T_b, K, dtype) per
+        signal in corpus order: under one numpy seed, a loop of computeCoefficients over the signals.
+        Returns (coefficients: a list of [T_b,K] arrays, residuals: a list of [T_b] or [T_b,F] arrays, NMFStats per signal)."""
+        dt, x, lens, D3, a0, energy, seqs = self._prepare_ragged(sequences, D, lengths, initialCoefficients)
+        params = _params(nbMaxIterations, toleranceResidualScale, toleranceSnr, self.memoryBudget)
+        coef, resid, stats = _call_compute_ragged(self.device, dt, x, lens, D3, a0, energy, params)
+        if seqs[0].ndim == 1 or np.ndim(D) == 2:
+            resid = np.squeeze(resid, axis=1)                                                  # modeling.py:744-745
+        if np.issubdtype(seqs[0].dtype, np.floating) and resid.dtype != seqs[0].dtype:
+            coef, resid = coef.astype(seqs[0].dtype), resid.astype(seqs[0].dtype)
+        ends = np.cumsum(lens)
+        self.lastStats = stats
+        for b in range(len(lens)):
+            logger.debug('signal %d: SNR of %f dB after %d iterations, stop: %s' % (
+                b, stats.snr[b], stats.iterations[b], STOP_NAMES.get(int(stats.stop[b]))))
+        return ([coef[e - n:e] for e, n in zip(ends, lens)], [resid[e - n:e] for e, n in zip(ends, lens)], stats)
 
     def computeCoefficients(self, sequence, D, nbMaxIterations=None, toleranceResidualScale=None, toleranceSnr=None):
         """hsc/modeling.py:667-747.  Returns (coefficients [T,K] dense, residual [T] or [T,F])."""

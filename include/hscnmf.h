@@ -1,7 +1,8 @@
 /* hscnmf.h -- C ABI of libhscnmf.so: batched convolutional NMF coefficients (the reference's
  * ConvolutionalNMF.computeCoefficients, hsc/modeling.py:662-747) and the convolutional NMF dictionary
  * learner (ConvolutionalDictionaryLearner(algorithm='nmf'), hsc/modeling.py:330-417), for one signal per dictionary
- * (hscnmf_learn) or one dictionary over a corpus of signals (hscnmf_learn_corpus), on MI355X / gfx950.
+ * (hscnmf_learn) or one dictionary over a corpus of signals (hscnmf_learn_corpus), and the coefficients of a corpus of
+ * signals of different lengths in one call (hscnmf_compute_ragged), on MI355X / gfx950.
  *
  * One context per host thread (contexts are not thread safe).  Every entry point returns
  * HSCNMF_OK (0) or a negative status; hscnmf_last_error() describes the last failure.
@@ -11,6 +12,8 @@
 #define HSCNMF_H
 
 #include <stdint.h>
+
+#include "hscnmf_plan.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -39,11 +42,13 @@ typedef struct {
     int32_t reserved;
     double tolerance_residual_scale;
     double tolerance_snr;
-    uint64_t memory_budget;           /* device bytes for one chunk of signals (learners), for the whole corpus in
-                                         hscnmf_learn_corpus; 0: 60% of the free memory */
+    uint64_t memory_budget;           /* device bytes for one chunk of signals (learners; whole signals of different
+                                         lengths in hscnmf_compute_ragged), for the whole corpus in hscnmf_learn_corpus;
+                                         0: 60% of the free memory */
 } hscnmf_params;
 
-int hscnmf_version(void);                          /* 2: hscnmf_learn (hscnmf_learn_corpus was added without a new version) */
+int hscnmf_version(void);                          /* 2: hscnmf_learn (hscnmf_learn_corpus, hscnmf_compute_ragged and
+                                                      hscnmf_ragged_plan were added without a new version) */
 int hscnmf_create(hscnmf_ctx** out, int device_id);
 void hscnmf_destroy(hscnmf_ctx* ctx);
 const char* hscnmf_last_error(hscnmf_ctx* ctx);   /* ctx may be NULL (errors of hscnmf_create) */
@@ -114,6 +119,38 @@ int hscnmf_learn_corpus(hscnmf_ctx* ctx, int dtype, const void* x, const int64_t
                         int K, int W, const void* a_init, const double* energy, const hscnmf_params* params, void* D_out,
                         int32_t* iterations, int32_t* stop, double* snr, double* residual_scale, double* signal_snr,
                         double* signal_residual_scale, double* timing_ms);
+
+/* hscnmf_compute for B signals of different lengths sharing one dictionary.  With L_b = T_b-W+1 and W' = (W-1)/2, all
+ * pointers host memory, C order:
+ *   x        [rows][F]      the signals stacked without padding, rows = sum_b T_b
+ *   lengths  [B] int64      T_b
+ *   D        [K][W][F]      the one dictionary
+ *   a_init   [sum_b L_b][K] the signals' initial coefficients stacked (rows 0 .. T_b-W of each signal only)
+ *   energy   [B]            sum of squares of each signal (float64)
+ * outputs:
+ *   coefficients [rows][K]  per signal the reference's coefficientsCentered: rows W' .. W'+L_b-1 of the signal's own block
+ *                           hold its coefficients, its other rows are set to zero
+ *   residual     [rows][F]
+ *   iterations, stop, snr, residual_scale [B]; timing_ms [5] (may be NULL): as for hscnmf_compute, summed over chunks
+ * Signal b gets, bit for bit, what hscnmf_compute gives it as a batch of one on x_b and its rows of a_init: coefficients,
+ * residual, iteration count, stop reason, SNR and residual scale, whatever the other signals are, whatever their order
+ * and wherever the chunk boundaries fall.  Every signal has its own stop state; the workgroups of a stopped signal return
+ * at its flag.
+ * Chunks: a chunk is a run of consecutive signals whose device bytes (the coefficient pair, x, the residual, the residual
+ * partials, the per-signal state and the tile tables; D is uploaded once beside them) stay within params->memory_budget
+ * (0: 60% of the free memory), whose tiles of 128 samples number at most 2^24 - 1 and whose signals at most 4 194 304; a
+ * chunk always holds at least one signal.  hscnmf_ragged_plan (hscnmf_plan.h) gives the chunks of a budget.
+ * Refused before anything is allocated, the message naming the signal where there is one: HSCNMF_ERR_INVALID for a NULL
+ * argument, an unknown dtype, B, K or F < 1, W < 2, max_iterations < 1 or a T_b < W; HSCNMF_ERR_UNSUPPORTED for a W, F
+ * whose workgroup does not fit the LDS, W*F > 2^24, or a signal with L_b * K > 2^28 or more than 2^24 - 1 tiles.  A failed
+ * allocation (HSCNMF_ERR_ALLOC) leaves nothing allocated. */
+int hscnmf_compute_ragged(hscnmf_ctx* ctx, int dtype, const void* x, const int64_t* lengths, int B, int F,
+                          const void* D, int K, int W, const void* a_init, const double* energy,
+                          const hscnmf_params* params, void* coefficients, void* residual,
+                          int32_t* iterations, int32_t* stop, double* snr, double* residual_scale, double* timing_ms);
+
+/* hscnmf_ragged_plan, the chunks hscnmf_compute_ragged forms under a budget (host arithmetic, no context), is declared
+ * in hscnmf_plan.h, which this header includes: the entry points declared here all take a context. */
 
 #ifdef __cplusplus
 }
