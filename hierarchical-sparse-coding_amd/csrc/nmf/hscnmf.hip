@@ -10,10 +10,13 @@
 // reading A from one buffer of a ping-pong pair and writing the other.  After the W steps of an iteration
 // nmf_residual_kernel reconstructs once more (residual, per-tile max|r| and sum r^2) and nmf_decide_kernel takes
 // the reference's stop decision per signal on the device; a finished signal's workgroups return at once.
-// hscnmf_learn (the dictionary learner) adds, per iteration, the ratio, partial and update kernels of section 12;
-// hscnmf_learn_corpus (one dictionary from many signals of different lengths) runs the same kernel bodies over a ragged
-// geometry and sums the update over the signals, section 18; hscnmf_compute_ragged runs the coder over that geometry with
-// a stop flag per signal, in chunks of whole signals, section 23.
+// Every kernel that works on a tile is a template on a geometry (Uniform, Ragged<one flag per signal?>): where the tile's
+// signal lies, its lengths, its stop flag and its dictionary.  hscnmf_learn (the dictionary learner) adds, per iteration,
+// the ratio, partial and update kernels of section 12; hscnmf_learn_corpus (one dictionary from many signals of different
+// lengths) runs the ragged geometry with one flag and sums the update over the signals, section 18;
+// hscnmf_compute_ragged runs the coder over the ragged geometry with a flag per signal, in chunks of whole signals,
+// section 23.  On the host the entry points share one argument ladder (check_args), one owner of a call's device memory
+// (DeviceBuffers), the step launches and the stop poll; the two coders share their chunk (Coder::chunk).
 #include "../../../include/hscnmf.h"
 #include "../common/hsc_lib.h"
 
@@ -142,11 +145,12 @@ __device__ void tile_recon(const T* __restrict__ A, int L, int K, const T* __res
     }
 }
 
-// Where a workgroup's signal and tile lie.  Uniform: B signals of one length, the signal on blockIdx.y and the tile on
-// blockIdx.x (hscnmf_compute, hscnmf_learn).  Ragged: signals of different lengths stacked without padding
-// (hscnmf_learn_corpus), a 1-D grid with one (signal, tile) pair per workgroup and one stop flag for the corpus.
+// Where a workgroup's signal and tile lie, and what belongs to the signal.  Uniform: B signals of one length, the signal
+// on blockIdx.y and the tile on blockIdx.x, a stop flag per signal and a dictionary per signal dstride values apart
+// (hscnmf_compute: 0, one dictionary for the batch; hscnmf_learn: K*W*F).
 struct Uniform {
     int L, Tn;
+    size_t dstride;
     __device__ int signal() const { return blockIdx.y; }
     __device__ int tile() const { return blockIdx.x; }
     __device__ int flag(int b) const { return b; }
@@ -154,7 +158,9 @@ struct Uniform {
     __device__ int samples(int) const { return Tn; }
     __device__ size_t row0(int b) const { return (size_t)b * L; }           // first coefficient row of signal b
     __device__ size_t sample0(int b) const { return (size_t)b * Tn; }       // first sample of signal b
+    __device__ size_t dict0(int b) const { return (size_t)b * dstride; }    // first value of signal b's dictionary
     __device__ size_t slot(int b) const { return (size_t)b * gridDim.x + blockIdx.x; }   // the workgroup's partials
+    __device__ size_t part0(int b) const { return (size_t)b * ((Tn + kRows - 1) / kRows); }   // signal b's first sample tile
 };
 
 // one signal of a corpus: its first sample and coefficient row in the stacks, its first row tile and sample tile in the
@@ -164,28 +170,34 @@ struct SignalInfo {
     int T, L;
 };
 
+// Ragged: signals of different lengths stacked without padding, a 1-D grid with one (signal, tile) pair per workgroup, one
+// dictionary, and one stop flag for the corpus (hscnmf_learn_corpus) or one per signal (hscnmf_compute_ragged).
+template <bool PerSignal>
 struct Ragged {
     const SignalInfo* __restrict__ sig;
     const int2* __restrict__ tiles;                                         // (signal, tile) of workgroup blockIdx.x
     __device__ int signal() const { return tiles[blockIdx.x].x; }
     __device__ int tile() const { return tiles[blockIdx.x].y; }
-    __device__ int flag(int) const { return 0; }
+    __device__ int flag(int b) const { return PerSignal ? b : 0; }
     __device__ int rows(int b) const { return sig[b].L; }
     __device__ int samples(int b) const { return sig[b].T; }
     __device__ size_t row0(int b) const { return (size_t)sig[b].a0; }
     __device__ size_t sample0(int b) const { return (size_t)sig[b].x0; }
+    __device__ size_t dict0(int) const { return 0; }
     __device__ size_t slot(int) const { return blockIdx.x; }
+    __device__ size_t part0(int b) const { return (size_t)sig[b].st0; }
 };
 
 template <typename T, typename G>
-__device__ __forceinline__ void step_body(const G g, const T* __restrict__ Ain, T* __restrict__ Aout,
-                                          const T* __restrict__ X, const T* __restrict__ D, size_t dstride,
-                                          const int* __restrict__ done, int K, int W, int F, int t, int PR, int slab)
+__global__ __launch_bounds__(kThreads) void nmf_step_kernel(const T* __restrict__ Ain, T* __restrict__ Aout,
+                                                            const T* __restrict__ X, const T* __restrict__ D,
+                                                            const int* __restrict__ done, G g, int K, int W, int F, int t,
+                                                            int PR, int slab)
 {
     const int b = g.signal();
+    const int L = g.rows(b), Tn = g.samples(b);       // (named before the flag: the table's address loads beside the tiles')
     if (done[g.flag(b)]) return;
-    const int L = g.rows(b), Tn = g.samples(b);
-    D += (size_t)b * dstride;                                        // 0: one dictionary for the batch (the coder)
+    D += g.dict0(b);
     extern __shared__ __align__(16) unsigned char smem[];
     T* rec = reinterpret_cast<T*>(smem);
     T* Pl = rec + kRows * F;
@@ -214,34 +226,16 @@ __device__ __forceinline__ void step_body(const G g, const T* __restrict__ Ain, 
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kThreads) void nmf_step_kernel(const T* __restrict__ Ain, T* __restrict__ Aout,
-                                                            const T* __restrict__ X, const T* __restrict__ D,
-                                                            size_t dstride, const int* __restrict__ done, int L, int Tn,
-                                                            int K, int W, int F, int t, int PR, int slab)
-{
-    step_body(Uniform{L, Tn}, Ain, Aout, X, D, dstride, done, K, W, F, t, PR, slab);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void nmf_step_ragged_kernel(const T* __restrict__ Ain, T* __restrict__ Aout,
-                                                                   const T* __restrict__ X, const T* __restrict__ D,
-                                                                   const int* __restrict__ done, Ragged g, int K, int W,
-                                                                   int F, int t, int PR, int slab)
-{
-    step_body(g, Ain, Aout, X, D, (size_t)0, done, K, W, F, t, PR, slab);
-}
-
 template <typename T, typename G>
-__device__ __forceinline__ void residual_body(const G g, const T* __restrict__ Abuf, const T* __restrict__ X,
-                                              const T* __restrict__ D, size_t dstride, const int* __restrict__ done,
-                                              T* __restrict__ resid, double* __restrict__ part, int K, int W, int F,
-                                              int PR, int slab)
+__global__ __launch_bounds__(kThreads) void nmf_residual_kernel(const T* __restrict__ Abuf, const T* __restrict__ X,
+                                                                const T* __restrict__ D, const int* __restrict__ done,
+                                                                T* __restrict__ resid, double* __restrict__ part, G g, int K,
+                                                                int W, int F, int PR, int slab)
 {
     const int b = g.signal();
+    const int L = g.rows(b), Tn = g.samples(b);       // (named before the flag: the table's address loads beside the tiles')
     if (done[g.flag(b)]) return;
-    const int L = g.rows(b), Tn = g.samples(b);
-    D += (size_t)b * dstride;
+    D += g.dict0(b);
     extern __shared__ __align__(16) unsigned char smem[];
     T* rec = reinterpret_cast<T*>(smem);
     T* Pl = rec + kRows * F;
@@ -275,39 +269,16 @@ __device__ __forceinline__ void residual_body(const G g, const T* __restrict__ A
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kThreads) void nmf_residual_kernel(const T* __restrict__ Abuf, const T* __restrict__ X,
-                                                                const T* __restrict__ D, size_t dstride,
-                                                                const int* __restrict__ done, T* __restrict__ resid,
-                                                                double* __restrict__ part, int L, int Tn, int K, int W, int F,
-                                                                int PR, int slab)
+// A signal's max|r| and sum r^2 from its ntiles sample-tile partials pb, by a workgroup of 64 threads: the threads stride
+// the tiles, then the tree; thread 0 hands the two to `then(max, sum)`.
+template <typename Then>
+__device__ __forceinline__ void signal_reduce(const double* __restrict__ pb, int ntiles, Then then)
 {
-    residual_body(Uniform{L, Tn}, Abuf, X, D, dstride, done, resid, part, K, W, F, PR, slab);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void nmf_residual_ragged_kernel(const T* __restrict__ Abuf, const T* __restrict__ X,
-                                                                       const T* __restrict__ D, const int* __restrict__ done,
-                                                                       T* __restrict__ resid, double* __restrict__ part,
-                                                                       Ragged g, int K, int W, int F, int PR, int slab)
-{
-    residual_body(g, Abuf, X, D, (size_t)0, done, resid, part, K, W, F, PR, slab);
-}
-
-// one workgroup (64 threads) per signal: the stop rules of hsc/modeling.py:729-740, in that order
-__global__ __launch_bounds__(64) void nmf_decide_kernel(const double* __restrict__ part, int ntiles,
-                                                        const double* __restrict__ energy, int* __restrict__ done,
-                                                        int* __restrict__ iters, int* __restrict__ stop,
-                                                        double* __restrict__ snr, double* __restrict__ rscale,
-                                                        int it1, hscnmf_params p)
-{
-    const int b = blockIdx.x;
-    if (done[b]) return;
     __shared__ double smx[64], sss[64];
     double mx = 0.0, ss = 0.0;
     for (int i = threadIdx.x; i < ntiles; i += 64) {
-        mx = fmax(mx, part[((size_t)b * ntiles + i) * 2]);
-        ss = ss + part[((size_t)b * ntiles + i) * 2 + 1];
+        mx = fmax(mx, pb[(size_t)i * 2]);
+        ss = ss + pb[(size_t)i * 2 + 1];
     }
     smx[threadIdx.x] = mx;
     sss[threadIdx.x] = ss;
@@ -319,60 +290,62 @@ __global__ __launch_bounds__(64) void nmf_decide_kernel(const double* __restrict
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0) {
-        const double rs = smx[0], s = 10.0 * log10(energy[b] / sss[0]);
-        int code = HSCNMF_STOP_RUNNING;
-        if (it1 >= p.max_iterations) code = HSCNMF_STOP_MAX_ITERATIONS;
-        else if (p.has_residual_scale && rs <= p.tolerance_residual_scale) code = HSCNMF_STOP_RESIDUAL_SCALE;
-        else if (p.has_snr && s >= p.tolerance_snr) code = HSCNMF_STOP_SNR;
+    if (threadIdx.x == 0) then(smx[0], sss[0]);
+}
+
+// the stop rules of hsc/modeling.py:729-740, in that order, after it1 iterations
+__device__ __forceinline__ int stop_code(int it1, double residual_scale, double snr, const hscnmf_params& p)
+{
+    int code = HSCNMF_STOP_RUNNING;
+    if (it1 >= p.max_iterations) code = HSCNMF_STOP_MAX_ITERATIONS;
+    else if (p.has_residual_scale && residual_scale <= p.tolerance_residual_scale) code = HSCNMF_STOP_RESIDUAL_SCALE;
+    else if (p.has_snr && snr >= p.tolerance_snr) code = HSCNMF_STOP_SNR;
+    return code;
+}
+
+// one workgroup (64 threads) per signal with a stop flag of its own: the signal's statistics and its stop decision
+template <typename G>
+__global__ __launch_bounds__(64) void nmf_decide_kernel(const double* __restrict__ part, G g,
+                                                        const double* __restrict__ energy, int* __restrict__ done,
+                                                        int* __restrict__ iters, int* __restrict__ stop,
+                                                        double* __restrict__ snr, double* __restrict__ rscale,
+                                                        int it1, hscnmf_params p)
+{
+    const int b = blockIdx.x;
+    if (done[b]) return;
+    signal_reduce(part + g.part0(b) * 2, (g.samples(b) + kRows - 1) / kRows, [&](double rs, double ss) {
+        const double s = 10.0 * log10(energy[b] / ss);
+        const int code = stop_code(it1, rs, s, p);
         iters[b] = it1;
         snr[b] = s;
         rscale[b] = rs;
         stop[b] = code;
         if (code != HSCNMF_STOP_RUNNING) done[b] = 1;
-    }
+    });
 }
 
 // ---- the dictionary update of the learner (hsc/modeling.py:383-395), DESIGN.md section 12 ----------------------------
 
 // R[n][f] = X[n][f] / |recon[n][f]| for the samples n0 .. n0+kRows-1 of the tile (the updated A, the old D)
 template <typename T, typename G>
-__device__ __forceinline__ void ratio_body(const G g, const T* __restrict__ Abuf, const T* __restrict__ X,
-                                           const T* __restrict__ D, size_t dstride, const int* __restrict__ done,
-                                           T* __restrict__ R, int K, int W, int F, int PR, int slab)
+__global__ __launch_bounds__(kThreads) void nmf_ratio_kernel(const T* __restrict__ Abuf, const T* __restrict__ X,
+                                                             const T* __restrict__ D, const int* __restrict__ done,
+                                                             T* __restrict__ R, G g, int K, int W, int F, int PR, int slab)
 {
     const int b = g.signal();
+    const int L = g.rows(b), Tn = g.samples(b);       // (named before the flag: the table's address loads beside the tiles')
     if (done[g.flag(b)]) return;
-    const int L = g.rows(b), Tn = g.samples(b);
     extern __shared__ __align__(16) unsigned char smem[];
     T* rec = reinterpret_cast<T*>(smem);
     T* Pl = rec + kRows * F;
     const int n0 = g.tile() * kRows;
-    tile_recon(Abuf + g.row0(b) * K, L, K, D + (size_t)b * dstride, W, F, n0, PR, slab, rec, Pl);
+    tile_recon(Abuf + g.row0(b) * K, L, K, D + g.dict0(b), W, F, n0, PR, slab, rec, Pl);
     for (int e = threadIdx.x; e < kRows * F; e += kThreads) {
         const int n = n0 + e / F;
         if (n >= Tn) break;
         const size_t o = (g.sample0(b) + n0) * F + e;
         R[o] = X[o] / fabs(rec[e]);
     }
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void nmf_ratio_kernel(const T* __restrict__ Abuf, const T* __restrict__ X,
-                                                             const T* __restrict__ D, size_t dstride,
-                                                             const int* __restrict__ done, T* __restrict__ R, int L, int Tn,
-                                                             int K, int W, int F, int PR, int slab)
-{
-    ratio_body(Uniform{L, Tn}, Abuf, X, D, dstride, done, R, K, W, F, PR, slab);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void nmf_ratio_ragged_kernel(const T* __restrict__ Abuf, const T* __restrict__ X,
-                                                                    const T* __restrict__ D, const int* __restrict__ done,
-                                                                    T* __restrict__ R, Ragged g, int K, int W, int F, int PR,
-                                                                    int slab)
-{
-    ratio_body(g, Abuf, X, D, (size_t)0, done, R, K, W, F, PR, slab);
 }
 
 // One RB x CB block of C[k][c] = sum_{sl < rows} A[s0+sl][k] Rl[sl*F + c] (c = t*F+f: the Hankel matrix of the R tile,
@@ -426,13 +399,14 @@ __device__ __forceinline__ void dpart_block(const double* __restrict__ A, int ro
 // (c = t*F+f < NW) and part[slot][k][NW] = sum_s A[s][k] (ascending s), for the update kernel to sum; slot: the
 // signal's tiles in ascending order, signal after signal.
 template <typename T, typename G>
-__device__ __forceinline__ void dpart_body(const G g, const T* __restrict__ Abuf, const T* __restrict__ R,
-                                           const int* __restrict__ done, T* __restrict__ part, int K, int W, int F)
+__global__ __launch_bounds__(kThreads) void nmf_dpart_kernel(const T* __restrict__ Abuf, const T* __restrict__ R,
+                                                             const int* __restrict__ done, T* __restrict__ part, G g, int K,
+                                                             int W, int F)
 {
     constexpr int RB = Tile<T>::RB, CB = Tile<T>::CB;
     const int b = g.signal();
+    const int L = g.rows(b), Tn = g.samples(b);       // (named before the flag: the table's address loads beside the tiles')
     if (done[g.flag(b)]) return;
-    const int L = g.rows(b), Tn = g.samples(b);
     extern __shared__ __align__(16) unsigned char smem[];
     T* Rl = reinterpret_cast<T*>(smem);                              // R samples s0 .. s0+kRows+W-2 (0 past T)
     const int s0 = g.tile() * kRows, NW = W * F, ld = NW + 1, nr = (kRows + W - 1) * F;
@@ -452,24 +426,9 @@ __device__ __forceinline__ void dpart_body(const G g, const T* __restrict__ Abuf
         dpart_block(A, rows, K, Rl, F, NW, (it % nkb) * RB, (it / nkb) * CB, out, ld);
 }
 
-template <typename T>
-__global__ __launch_bounds__(kThreads) void nmf_dpart_kernel(const T* __restrict__ Abuf, const T* __restrict__ R,
-                                                             const int* __restrict__ done, T* __restrict__ part, int L,
-                                                             int Tn, int K, int W, int F)
-{
-    dpart_body(Uniform{L, Tn}, Abuf, R, done, part, K, W, F);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void nmf_dpart_ragged_kernel(const T* __restrict__ Abuf, const T* __restrict__ R,
-                                                                    const int* __restrict__ done, T* __restrict__ part,
-                                                                    Ragged g, int K, int W, int F)
-{
-    dpart_body(g, Abuf, R, done, part, K, W, F);
-}
-
 // One workgroup per (atom k, learner b): N and den summed over the tiles in ascending order, D[k] *= N / den, then
-// D[k] /= ||D[k]|| when the norm is > 0 (hsc/utils.py:67-74).  IEEE division and sqrt; no atomics.
+// D[k] /= ||D[k]|| when the norm is > 0 (hsc/utils.py:67-74).  IEEE division and sqrt; no atomics.  The corpus learner is
+// the grid [K, 1] over nmf_dsum_kernel's sums: one learner whose "tiles" are the signals, in ascending order.
 template <typename T>
 __global__ __launch_bounds__(kThreads) void nmf_dupdate_kernel(const T* __restrict__ part, int ntiles,
                                                                const int* __restrict__ done, T* __restrict__ D, int K, int NW)
@@ -527,45 +486,6 @@ __global__ __launch_bounds__(kThreads) void nmf_dsum_kernel(const T* __restrict_
     S[(size_t)b * tstride + e] = acc;
 }
 
-// One workgroup per atom k: N and den summed over the signals in ascending order, then nmf_dupdate_kernel's update and
-// normalisation of the one dictionary.  IEEE division and sqrt; no atomics.
-template <typename T>
-__global__ __launch_bounds__(kThreads) void nmf_dupdate_corpus_kernel(const T* __restrict__ S, int B,
-                                                                      const int* __restrict__ done, T* __restrict__ D,
-                                                                      int K, int NW)
-{
-    const int k = blockIdx.x;
-    if (done[0]) return;
-    extern __shared__ __align__(16) unsigned char smem[];
-    T* red = reinterpret_cast<T*>(smem);                             // [kThreads] sums of squares, then [NW + 1] sums
-    T* sum = red + kThreads;
-    const int ld = NW + 1;
-    const size_t tstride = (size_t)K * ld;
-    const T* p = S + (size_t)k * ld;
-    for (int c = threadIdx.x; c < ld; c += kThreads) {
-        T acc = T(0);
-        for (int b = 0; b < B; ++b) acc = acc + p[(size_t)b * tstride + c];
-        sum[c] = acc;
-    }
-    __syncthreads();
-    T* d = D + (size_t)k * NW;
-    const T den = sum[NW];
-    T ss = T(0);
-    for (int c = threadIdx.x; c < NW; c += kThreads) {
-        const T v = d[c] * (sum[c] / den);
-        sum[c] = v;
-        ss = ss + v * v;
-    }
-    red[threadIdx.x] = ss;
-    __syncthreads();
-    for (int w = kThreads / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + w];
-        __syncthreads();
-    }
-    const T nrm = sqrt(red[0]);
-    for (int c = threadIdx.x; c < NW; c += kThreads) d[c] = nrm > T(0) ? sum[c] / nrm : sum[c];
-}
-
 // one workgroup (64 threads) per signal: max|r| and sum r^2 of the signal as nmf_decide_kernel forms them, and the
 // signal's own SNR and residual scale
 __global__ __launch_bounds__(64) void nmf_signal_stats_kernel(const double* __restrict__ part,
@@ -576,34 +496,16 @@ __global__ __launch_bounds__(64) void nmf_signal_stats_kernel(const double* __re
 {
     const int b = blockIdx.x;
     if (done[0]) return;
-    __shared__ double smx[64], sss[64];
-    const int ntiles = (sig[b].T + kRows - 1) / kRows;
-    const double* pb = part + (size_t)sig[b].st0 * 2;
-    double mx = 0.0, ss = 0.0;
-    for (int i = threadIdx.x; i < ntiles; i += 64) {
-        mx = fmax(mx, pb[(size_t)i * 2]);
-        ss = ss + pb[(size_t)i * 2 + 1];
-    }
-    smx[threadIdx.x] = mx;
-    sss[threadIdx.x] = ss;
-    __syncthreads();
-    for (int w = 32; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            smx[threadIdx.x] = fmax(smx[threadIdx.x], smx[threadIdx.x + w]);
-            sss[threadIdx.x] = sss[threadIdx.x] + sss[threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        sigmx[b] = smx[0];
-        sigss[b] = sss[0];
-        snr[b] = 10.0 * log10(energy[b] / sss[0]);
-        rscale[b] = smx[0];
-    }
+    signal_reduce(part + (size_t)sig[b].st0 * 2, (sig[b].T + kRows - 1) / kRows, [&](double mx, double ss) {
+        sigmx[b] = mx;
+        sigss[b] = ss;
+        snr[b] = 10.0 * log10(energy[b] / ss);
+        rscale[b] = mx;
+    });
 }
 
 // One workgroup: the signals' statistics combined in ascending signal order (staged through LDS kThreads at a time, summed
-// by one thread), then the stop rules of nmf_decide_kernel on the corpus.  state: done, iterations, stop; out: snr, scale.
+// by one thread), then the stop rules on the corpus.  state: done, iterations, stop; out: snr, scale.
 __global__ __launch_bounds__(kThreads) void nmf_decide_corpus_kernel(const double* __restrict__ sigmx,
                                                                      const double* __restrict__ sigss,
                                                                      const double* __restrict__ energy, int B,
@@ -631,10 +533,7 @@ __global__ __launch_bounds__(kThreads) void nmf_decide_corpus_kernel(const doubl
     }
     if (threadIdx.x == 0) {
         const double s = 10.0 * log10(en / ss);
-        int code = HSCNMF_STOP_RUNNING;
-        if (it1 >= p.max_iterations) code = HSCNMF_STOP_MAX_ITERATIONS;
-        else if (p.has_residual_scale && mx <= p.tolerance_residual_scale) code = HSCNMF_STOP_RESIDUAL_SCALE;
-        else if (p.has_snr && s >= p.tolerance_snr) code = HSCNMF_STOP_SNR;
+        const int code = stop_code(it1, mx, s, p);
         state[1] = it1;
         state[2] = code;
         out[0] = s;
@@ -680,289 +579,68 @@ static bool lds_plan(int W, int F, int& PR, int& slab, size_t& bytes)
 
 namespace {
 
-// What hscnmf_compute and hscnmf_learn share: the chunk of Bc signals the memory budget allows, its device buffers
-// (allocated per call; the destructor frees them after a stream sync), the per-chunk upload and download around the
-// iterations, and the timings summed over chunks (timing_ms of include/hscnmf.h).
-template <typename T>
-struct Chunks {
-    hscnmf_ctx* ctx;
-    int Tn, F, K, W, L, ntt;
-    size_t dsz;                       // D values per signal when every signal has a D of its own (learn), else 0
-    int Bc = 0;
-    T *dA[2] = {nullptr, nullptr}, *dX = nullptr, *dR = nullptr, *dD = nullptr, *dPD = nullptr;
-    double *dPart = nullptr, *dEn = nullptr, *dSnr = nullptr, *dRs = nullptr;
-    int *dDone = nullptr, *dIt = nullptr, *dStop = nullptr;
-    std::vector<int> hdone;
-    double tm[5] = {0, 0, 0, 0, 0};
-
-    Chunks(hscnmf_ctx* c, int Tn_, int F_, int K_, int W_, size_t dsz_)
-        : ctx(c), Tn(Tn_), F(F_), K(K_), W(W_), L(Tn_ - W_ + 1), ntt((Tn_ + kRows - 1) / kRows), dsz(dsz_) {}
-
-    ~Chunks()
-    {
-        (void)hipStreamSynchronize(ctx->stream);
-        void* ptrs[] = {dA[0], dA[1], dX, dR, dD, dPD, dPart, dEn, dSnr, dRs, dDone, dIt, dStop};
-        for (void* q : ptrs) if (q) (void)hipFree(q);
-    }
-
-    // chunk size and buffers: per signal the A pair, X, R, the stop state and (learn) its D and psz partial values
-    int alloc(const hscnmf_params& p, int B, size_t psz)
-    {
-        HSC_TRY(hipSetDevice(ctx->device));
-        size_t freeb = 0, totalb = 0;
-        HSC_TRY(hipMemGetInfo(&freeb, &totalb));
-        const size_t per = (2 * (size_t)L * K + 2 * (size_t)Tn * F + dsz + psz) * sizeof(T) + (size_t)ntt * 2 * sizeof(double) +
-                           3 * sizeof(double) + 3 * sizeof(int);
-        const size_t budget = p.memory_budget ? (size_t)p.memory_budget : freeb / 10 * 6;
-        Bc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)B, budget / per, (size_t)65535}));
-        HSC_TRY(hipMalloc(&dA[0], (size_t)Bc * L * K * sizeof(T)));
-        HSC_TRY(hipMalloc(&dA[1], (size_t)Bc * L * K * sizeof(T)));
-        HSC_TRY(hipMalloc(&dX, (size_t)Bc * Tn * F * sizeof(T)));
-        HSC_TRY(hipMalloc(&dR, (size_t)Bc * Tn * F * sizeof(T)));
-        HSC_TRY(hipMalloc(&dD, (dsz ? (size_t)Bc * dsz : (size_t)K * W * F) * sizeof(T)));
-        if (psz) HSC_TRY(hipMalloc(&dPD, (size_t)Bc * psz * sizeof(T)));
-        HSC_TRY(hipMalloc(&dPart, (size_t)Bc * ntt * 2 * sizeof(double)));
-        HSC_TRY(hipMalloc(&dEn, (size_t)Bc * sizeof(double)));
-        HSC_TRY(hipMalloc(&dSnr, (size_t)Bc * sizeof(double)));
-        HSC_TRY(hipMalloc(&dRs, (size_t)Bc * sizeof(double)));
-        HSC_TRY(hipMalloc(&dDone, (size_t)Bc * sizeof(int)));
-        HSC_TRY(hipMalloc(&dIt, (size_t)Bc * sizeof(int)));
-        HSC_TRY(hipMalloc(&dStop, (size_t)Bc * sizeof(int)));
-        hdone.resize(Bc);
-        return hsc::OK;
-    }
-
-    // signals c0 .. c0 + nb - 1 between events 0 and 1: X, rows 0 .. L-1 of the initial coefficients, (learn) the
-    // initial dictionaries D_init, the energies; done, iterations and stop zeroed
-    int upload(int c0, int nb, const T* x, const T* a_init, const T* D_init, const double* energy)
-    {
-        hipStream_t st = ctx->stream;
-        HSC_TRY(hipEventRecord(ctx->ev[0], st));
-        HSC_TRY(hipMemcpyAsync(dX, x + (size_t)c0 * Tn * F, (size_t)nb * Tn * F * sizeof(T), hipMemcpyHostToDevice, st));
-        HSC_TRY(hipMemcpy2DAsync(dA[0], (size_t)L * K * sizeof(T), a_init + (size_t)c0 * Tn * K, (size_t)Tn * K * sizeof(T),
-                                 (size_t)L * K * sizeof(T), nb, hipMemcpyHostToDevice, st));
-        if (dsz) HSC_TRY(hipMemcpyAsync(dD, D_init + (size_t)c0 * dsz, (size_t)nb * dsz * sizeof(T), hipMemcpyHostToDevice, st));
-        HSC_TRY(hipMemcpyAsync(dEn, energy + c0, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, st));
-        HSC_TRY(hipMemsetAsync(dDone, 0, (size_t)nb * sizeof(int), st));
-        HSC_TRY(hipMemsetAsync(dIt, 0, (size_t)nb * sizeof(int), st));
-        HSC_TRY(hipMemsetAsync(dStop, 0, (size_t)nb * sizeof(int), st));
-        HSC_TRY(hipEventRecord(ctx->ev[1], st));
-        return hsc::OK;
-    }
-
-    // after iteration `it`: 1 when every signal of the chunk has stopped, else 0 (or a negative status).  The flags are
-    // read once per iteration, only with a tolerance and another iteration to go.
-    int all_stopped(const hscnmf_params& p, int it, int nb)
-    {
-        if (!(p.has_residual_scale || p.has_snr) || it + 1 >= p.max_iterations) return 0;
-        HSC_TRY(hipMemcpyAsync(hdone.data(), dDone, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HSC_TRY(hipStreamSynchronize(ctx->stream));
-        return std::all_of(hdone.begin(), hdone.begin() + nb, [](int v) { return v != 0; }) ? 1 : 0;
-    }
-
-    // event 2 (the iterations end), then the chunk's iterations, stop reasons, SNR and residual scales
-    int download_stats(int c0, int nb, int32_t* iters, int32_t* stop, double* snr, double* rscale)
-    {
-        hipStream_t st = ctx->stream;
-        HSC_TRY(hipEventRecord(ctx->ev[2], st));
-        HSC_TRY(hipMemcpyAsync(iters + c0, dIt, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
-        HSC_TRY(hipMemcpyAsync(stop + c0, dStop, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
-        HSC_TRY(hipMemcpyAsync(snr + c0, dSnr, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st));
-        HSC_TRY(hipMemcpyAsync(rscale + c0, dRs, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st));
-        return hsc::OK;
-    }
-
-    // once event 3 has completed: the chunk's upload, iteration and download times and the `it` iterations it ran
-    int add_times(int it)
-    {
-        if (int rc = hsc::add_times(ctx, 3, tm)) return rc;
-        tm[3] += 1;
-        tm[4] += it;
-        return hsc::OK;
-    }
-};
-
-// the first signal of c0 .. c0 + nb - 1 without a result (its iteration count outside [1, it]), or -1
-int no_result(const int32_t* iters, int c0, int nb, int it)
-{
-    for (int b = c0; b < c0 + nb; ++b)
-        if (iters[b] < 1 || iters[b] > it) return b;
-    return -1;
-}
-
-}  // namespace
-
-template <typename T>
-static int compute_t(hscnmf_ctx* ctx, const T* x, int B, int Tn, int F, const T* D, int K, int W, const T* a_init,
-                     const double* energy, const hscnmf_params& p, T* coef, T* resid, int32_t* iters, int32_t* stop,
-                     double* snr, double* rscale, double* timing)
-{
-    const int L = Tn - W + 1, ntl = (L + kRows - 1) / kRows, ntt = (Tn + kRows - 1) / kRows, off = (W - 1) / 2;
-    int PR = 0, slab = 0;
-    size_t lds = 0;
-    if (!lds_plan<T>(W, F, PR, slab, lds))
-        return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_compute: W = %d, F = %d needs more than %d bytes of LDS per workgroup",
-                    W, F, kLdsBytes);
-    Chunks<T> c(ctx, Tn, F, K, W, 0);
-    if (int rc = c.alloc(p, B, 0)) return rc;
-    HSC_TRY(hipMemcpyAsync(c.dD, D, (size_t)K * W * F * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    for (int c0 = 0; c0 < B; c0 += c.Bc) {
-        const int nb = std::min(c.Bc, B - c0);
-        if (int rc = c.upload(c0, nb, x, a_init, nullptr, energy)) return rc;
-        int it = 0;
-        for (; it < p.max_iterations; ++it) {
-            for (int t = 0; t < W; ++t) {
-                const int g = it * W + t;
-                hipLaunchKernelGGL(nmf_step_kernel<T>, dim3(ntl, nb), dim3(kThreads), lds, ctx->stream, c.dA[g & 1],
-                                   c.dA[(g + 1) & 1], c.dX, c.dD, (size_t)0, c.dDone, L, Tn, K, W, F, t, PR, slab);
-            }
-            hipLaunchKernelGGL(nmf_residual_kernel<T>, dim3(ntt, nb), dim3(kThreads), lds, ctx->stream,
-                               c.dA[((it + 1) * W) & 1], c.dX, c.dD, (size_t)0, c.dDone, c.dR, c.dPart, L, Tn, K, W, F, PR, slab);
-            hipLaunchKernelGGL(nmf_decide_kernel, dim3(nb), dim3(64), 0, ctx->stream, c.dPart, ntt, c.dEn, c.dDone, c.dIt,
-                               c.dStop, c.dSnr, c.dRs, it + 1, p);
-            HSC_TRY(hipGetLastError());
-            const int stopped = c.all_stopped(p, it, nb);
-            if (stopped < 0) return stopped;
-            if (stopped) { ++it; break; }
-        }
-        if (int rc = c.download_stats(c0, nb, iters, stop, snr, rscale)) return rc;
-        HSC_TRY(hipMemcpyAsync(resid + (size_t)c0 * Tn * F, c.dR, (size_t)nb * Tn * F * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        HSC_TRY(hipStreamSynchronize(ctx->stream));
-        const int bad = no_result(iters, c0, nb, it);
-        if (bad >= 0) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_compute: signal %d has no result", bad);
-        for (int b = 0; b < nb; ++b) {
-            // a signal that stopped after n iterations holds its coefficients in buffer (n * W) mod 2
-            const int n = iters[c0 + b];
-            T* dst = coef + (size_t)(c0 + b) * Tn * K;
-            std::memset(dst, 0, (size_t)off * K * sizeof(T));
-            std::memset(dst + (size_t)(off + L) * K, 0, (size_t)(Tn - off - L) * K * sizeof(T));
-            HSC_TRY(hipMemcpyAsync(dst + (size_t)off * K, c.dA[((size_t)n * W) & 1] + (size_t)b * L * K, (size_t)L * K * sizeof(T),
-                                   hipMemcpyDeviceToHost, ctx->stream));
-        }
-        HSC_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-        HSC_TRY(hipStreamSynchronize(ctx->stream));
-        if (int rc = c.add_times(it)) return rc;
-    }
-    if (timing) std::memcpy(timing, c.tm, sizeof(c.tm));
-    return HSCNMF_OK;
-}
-
-extern "C" int hscnmf_compute(hscnmf_ctx* ctx, int dtype, const void* x, int B, int T, int F, const void* D, int K, int W,
-                              const void* a_init, const double* energy, const hscnmf_params* params, void* coefficients,
-                              void* residual, int32_t* iterations, int32_t* stop, double* snr, double* residual_scale,
-                              double* timing_ms)
-{
-    if (!ctx) return fail(nullptr, HSCNMF_ERR_INVALID, "hscnmf_compute: ctx is NULL");
-    if (!x || !D || !a_init || !energy || !params || !coefficients || !residual || !iterations || !stop || !snr || !residual_scale)
-        return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_compute: NULL argument");
-    if (dtype != HSCNMF_F32 && dtype != HSCNMF_F64) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_compute: unknown dtype %d", dtype);
-    if (B < 1 || K < 1 || F < 1) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_compute: B = %d, K = %d, F = %d", B, K, F);
-    if (W < 2) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_compute: filter width %d (the reference needs W >= 2)", W);
-    if (T < W) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_compute: signal length %d is shorter than the filter width %d", T, W);
-    if (params->max_iterations < 1) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_compute: max_iterations = %d", params->max_iterations);
-    if ((int64_t)W * F > (1 << 24) || (int64_t)(T - W + 1) * K > ((int64_t)1 << 31) / 8)
-        return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_compute: shape out of range");
-    if (dtype == HSCNMF_F32)
-        return compute_t<float>(ctx, (const float*)x, B, T, F, (const float*)D, K, W, (const float*)a_init, energy, *params,
-                                (float*)coefficients, (float*)residual, iterations, stop, snr, residual_scale, timing_ms);
-    return compute_t<double>(ctx, (const double*)x, B, T, F, (const double*)D, K, W, (const double*)a_init, energy, *params,
-                             (double*)coefficients, (double*)residual, iterations, stop, snr, residual_scale, timing_ms);
-}
-
-// The learner (hsc/modeling.py:330-417): per chunk of learners, each iteration is the W steps, R = X/|recon| (updated A,
-// old D) into the residual buffer, the tile partials, the dictionary update, then the residual and the stop decision with
-// the new D.  Every learner owns its D ([B][K][W][F], stride K*W*F); a finished learner's D stays as it was.
-template <typename T>
-static int learn_t(hscnmf_ctx* ctx, const T* x, int B, int Tn, int F, const T* D_init, int K, int W, const T* a_init,
-                   const double* energy, const hscnmf_params& p, T* D_out, int32_t* iters, int32_t* stop, double* snr,
-                   double* rscale, double* timing)
-{
-    const int L = Tn - W + 1, ntl = (L + kRows - 1) / kRows, ntt = (Tn + kRows - 1) / kRows, NW = W * F;
-    const size_t dsz = (size_t)K * NW, psz = (size_t)ntl * K * (NW + 1);
-    const size_t lds_part = (size_t)(kRows + W - 1) * F * sizeof(T), lds_upd = (size_t)(kThreads + NW + 1) * sizeof(T);
-    int PR = 0, slab = 0;
-    size_t lds = 0;
-    if (!lds_plan<T>(W, F, PR, slab, lds) || lds_part > (size_t)kLdsBytes || lds_upd > (size_t)kLdsBytes)
-        return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_learn: W = %d, F = %d needs more than %d bytes of LDS per workgroup",
-                    W, F, kLdsBytes);
-    Chunks<T> c(ctx, Tn, F, K, W, dsz);
-    if (int rc = c.alloc(p, B, psz)) return rc;
-    for (int c0 = 0; c0 < B; c0 += c.Bc) {
-        const int nb = std::min(c.Bc, B - c0);
-        if (int rc = c.upload(c0, nb, x, a_init, D_init, energy)) return rc;
-        int it = 0;
-        for (; it < p.max_iterations; ++it) {
-            for (int t = 0; t < W; ++t) {
-                const int g = it * W + t;
-                hipLaunchKernelGGL(nmf_step_kernel<T>, dim3(ntl, nb), dim3(kThreads), lds, ctx->stream, c.dA[g & 1],
-                                   c.dA[(g + 1) & 1], c.dX, c.dD, dsz, c.dDone, L, Tn, K, W, F, t, PR, slab);
-            }
-            const T* dAn = c.dA[((it + 1) * W) & 1];
-            hipLaunchKernelGGL(nmf_ratio_kernel<T>, dim3(ntt, nb), dim3(kThreads), lds, ctx->stream, dAn, c.dX, c.dD, dsz,
-                               c.dDone, c.dR, L, Tn, K, W, F, PR, slab);
-            hipLaunchKernelGGL(nmf_dpart_kernel<T>, dim3(ntl, nb), dim3(kThreads), lds_part, ctx->stream, dAn, c.dR, c.dDone,
-                               c.dPD, L, Tn, K, W, F);
-            hipLaunchKernelGGL(nmf_dupdate_kernel<T>, dim3(K, nb), dim3(kThreads), lds_upd, ctx->stream, c.dPD, ntl, c.dDone,
-                               c.dD, K, NW);
-            hipLaunchKernelGGL(nmf_residual_kernel<T>, dim3(ntt, nb), dim3(kThreads), lds, ctx->stream, dAn, c.dX, c.dD, dsz,
-                               c.dDone, c.dR, c.dPart, L, Tn, K, W, F, PR, slab);
-            hipLaunchKernelGGL(nmf_decide_kernel, dim3(nb), dim3(64), 0, ctx->stream, c.dPart, ntt, c.dEn, c.dDone, c.dIt,
-                               c.dStop, c.dSnr, c.dRs, it + 1, p);
-            HSC_TRY(hipGetLastError());
-            const int stopped = c.all_stopped(p, it, nb);
-            if (stopped < 0) return stopped;
-            if (stopped) { ++it; break; }
-        }
-        if (int rc = c.download_stats(c0, nb, iters, stop, snr, rscale)) return rc;
-        HSC_TRY(hipMemcpyAsync(D_out + (size_t)c0 * dsz, c.dD, (size_t)nb * dsz * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        HSC_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-        HSC_TRY(hipStreamSynchronize(ctx->stream));
-        const int bad = no_result(iters, c0, nb, it);
-        if (bad >= 0) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: learner %d has no result", bad);
-        if (int rc = c.add_times(it)) return rc;
-    }
-    if (timing) std::memcpy(timing, c.tm, sizeof(c.tm));
-    return HSCNMF_OK;
-}
-
-extern "C" int hscnmf_learn(hscnmf_ctx* ctx, int dtype, const void* x, int B, int T, int F, const void* D_init, int K, int W,
-                            const void* a_init, const double* energy, const hscnmf_params* params, void* D_out,
-                            int32_t* iterations, int32_t* stop, double* snr, double* residual_scale, double* timing_ms)
-{
-    if (!ctx) return fail(nullptr, HSCNMF_ERR_INVALID, "hscnmf_learn: ctx is NULL");
-    if (!x || !D_init || !a_init || !energy || !params || !D_out || !iterations || !stop || !snr || !residual_scale)
-        return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: NULL argument");
-    if (dtype != HSCNMF_F32 && dtype != HSCNMF_F64) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: unknown dtype %d", dtype);
-    if (B < 1 || K < 1 || F < 1) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: B = %d, K = %d, F = %d", B, K, F);
-    if (W < 2) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: filter width %d (the reference needs W >= 2)", W);
-    if (T < W) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: signal length %d is shorter than the filter width %d", T, W);
-    if (params->max_iterations < 1) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: max_iterations = %d", params->max_iterations);
-    if ((int64_t)W * F > (1 << 24) || (int64_t)(T - W + 1) * K > ((int64_t)1 << 31) / 8 || K > 65535)
-        return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_learn: shape out of range");
-    if (dtype == HSCNMF_F32)
-        return learn_t<float>(ctx, (const float*)x, B, T, F, (const float*)D_init, K, W, (const float*)a_init, energy, *params,
-                              (float*)D_out, iterations, stop, snr, residual_scale, timing_ms);
-    return learn_t<double>(ctx, (const double*)x, B, T, F, (const double*)D_init, K, W, (const double*)a_init, energy, *params,
-                           (double*)D_out, iterations, stop, snr, residual_scale, timing_ms);
-}
-
-// ---- hscnmf_learn_corpus: one dictionary from B signals of different lengths, DESIGN.md section 18 --------------------
-
-namespace {
-
 constexpr int kMaxCorpusSignals = 1 << 22;
 // HIP refuses a launch with gridDim.x * blockDim.x >= 2^32: with workgroups of kThreads = 256 a 1-D grid has at most
 // 2^24 - 1 workgroups.  The sample tiles (the row tiles are no more) and nmf_dsum_kernel's B * nchunk lie on such grids.
 constexpr long long kMaxCorpusGrid = (1LL << 32) / kThreads - 1;
 
-// the device memory of one hscnmf_learn_corpus (or hscnmf_compute_ragged) call, freed (after a stream sync) when the call
-// returns; `fn` names the entry point in the ERR_ALLOC message
-struct CorpusBuffers {
+// what the launches of a call share: the shape, lds_plan's answer and the LDS of nmf_dpart_kernel and nmf_dupdate_kernel
+struct Plan {
+    int K, W, F, PR, slab;
+    size_t lds, lds_part, lds_upd;
+};
+
+// the calls check_args serves: hscnmf_compute, hscnmf_learn, hscnmf_learn_corpus, and hscnmf_compute_ragged with its plan
+enum class Call { Coder, Learner, CorpusLearner, RaggedCoder };
+
+// The argument checks of the five entry points (after their own NULL checks), in one ladder; nothing is allocated before
+// them.  lengths: B of them, or the one length of a uniform batch (Coder, Learner).  params: where max_iterations is
+// checked here (NULL: not here).  Two refusals have a place of their own per kind of call.  Fills in `pl`.
+int check_args(hsc::CtxBase* ctx, const char* fn, Call call, int dtype, const int64_t* lengths, int B, int F, int K, int W,
+               const hscnmf_params* params, Plan& pl)
+{
+    const bool uniform = call == Call::Coder || call == Call::Learner, learner = call == Call::Learner || call == Call::CorpusLearner;
+    const bool bad_iterations = params && params->max_iterations < 1;
+    auto no_iterations = [&] { return fail(ctx, HSCNMF_ERR_INVALID, "%s: max_iterations = %d", fn, params->max_iterations); };
+    auto no_lds = [&] {
+        return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "%s: W = %d, F = %d needs more than %d bytes of LDS per workgroup", fn, W, F, kLdsBytes);
+    };
+    if (!lengths) return fail(ctx, HSCNMF_ERR_INVALID, "%s: NULL argument", fn);
+    if (dtype != HSCNMF_F32 && dtype != HSCNMF_F64) return fail(ctx, HSCNMF_ERR_INVALID, "%s: unknown dtype %d", fn, dtype);
+    if (B < 1 || K < 1 || F < 1) return fail(ctx, HSCNMF_ERR_INVALID, "%s: B = %d, K = %d, F = %d", fn, B, K, F);
+    if (W < 2) return fail(ctx, HSCNMF_ERR_INVALID, "%s: filter width %d (the reference needs W >= 2)", fn, W);
+    if (bad_iterations && call == Call::CorpusLearner) return no_iterations();      // a corpus: before its lengths
+    if (uniform && lengths[0] < W)
+        return fail(ctx, HSCNMF_ERR_INVALID, "%s: signal length %d is shorter than the filter width %d", fn, (int)lengths[0], W);
+    for (int b = 0; !uniform && b < B; ++b)
+        if (lengths[b] < W)
+            return fail(ctx, HSCNMF_ERR_INVALID, "%s: signal %d: length %lld is shorter than the filter width %d", fn, b,
+                        (long long)lengths[b], W);
+    if (bad_iterations) return no_iterations();                                     // a uniform batch: after its length
+    if (call == Call::CorpusLearner && B > kMaxCorpusSignals)
+        return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "%s: %d signals (at most %d)", fn, B, kMaxCorpusSignals);
+    const int64_t max_lk = ((int64_t)1 << 31) / 8;
+    if ((int64_t)W * F > (1 << 24) || (learner && K > 65535) || (uniform && (lengths[0] - W + 1) * K > max_lk))
+        return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "%s: shape out of range", fn);
+    const size_t item = dtype == HSCNMF_F32 ? sizeof(float) : sizeof(double);
+    pl = Plan{K, W, F, 0, 0, 0, (size_t)(kRows + W - 1) * F * item, (size_t)(kThreads + W * F + 1) * item};
+    bool fits = dtype == HSCNMF_F32 ? lds_plan<float>(W, F, pl.PR, pl.slab, pl.lds) : lds_plan<double>(W, F, pl.PR, pl.slab, pl.lds);
+    if (learner) fits = fits && pl.lds_part <= (size_t)kLdsBytes && pl.lds_upd <= (size_t)kLdsBytes;
+    if (!fits && call == Call::RaggedCoder) return no_lds();                        // the ragged coder: before the signals' shapes
+    for (int b = 0; !uniform && b < B; ++b)
+        if ((lengths[b] - W + 1) * K > max_lk || (call == Call::RaggedCoder && (lengths[b] + kRows - 1) / kRows > kMaxCorpusGrid))
+            return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "%s: signal %d: shape out of range", fn, b);
+    return fits ? hsc::OK : no_lds();                                               // the others: after them
+}
+
+// the device memory of one call, freed (after a stream sync) when the call returns; `fn` names the entry point in the
+// ERR_ALLOC message.  Host memory that an asynchronous copy of the call touches is declared before it.
+struct DeviceBuffers {
     hscnmf_ctx* ctx;
     const char* fn;
     std::vector<void*> ptrs;
-    explicit CorpusBuffers(hscnmf_ctx* c, const char* f = "hscnmf_learn_corpus") : ctx(c), fn(f) {}
-    ~CorpusBuffers()
+    DeviceBuffers(hscnmf_ctx* c, const char* f) : ctx(c), fn(f) {}
+    ~DeviceBuffers()
     {
         (void)hipStreamSynchronize(ctx->stream);
         for (void* q : ptrs) (void)hipFree(q);
@@ -979,24 +657,324 @@ struct CorpusBuffers {
     }
 };
 
+// the device pointers of a chunk of n signals with a stop flag each: the coefficient pair, x, the residual (the learners'
+// R before it), the dictionaries, the residual partials, stat = [3][n] energy, SNR, residual scale and state = [3][n]
+// done, iterations, stop
+template <typename T>
+struct Dev {
+    T *A[2], *X, *R, *D;
+    double *part, *stat;
+    int* state;
+};
+
+// where a call's per-signal results go on the host
+struct Stats {
+    int32_t *iters, *stop;
+    double *snr, *rscale;
+};
+
+// a host-to-device copy of `bytes`; with spitch, `rows` rows of `bytes` that lie spitch bytes apart on the host
+struct Upload {
+    void* dst = nullptr;
+    const void* src = nullptr;
+    size_t bytes = 0, spitch = 0, rows = 0;
+};
+
+// between events 0 and 1: the copies (those of no bytes skipped) and the call's stop state (`zeroed` bytes at `state`) zeroed
+int upload(hscnmf_ctx* ctx, std::initializer_list<Upload> ups, void* state, size_t zeroed)
+{
+    hipStream_t st = ctx->stream;
+    HSC_TRY(hipEventRecord(ctx->ev[0], st));
+    for (const Upload& u : ups) {
+        if (!u.bytes) continue;
+        if (u.spitch) HSC_TRY(hipMemcpy2DAsync(u.dst, u.bytes, u.src, u.spitch, u.bytes, u.rows, hipMemcpyHostToDevice, st));
+        else HSC_TRY(hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, st));
+    }
+    HSC_TRY(hipMemsetAsync(state, 0, zeroed, st));
+    HSC_TRY(hipEventRecord(ctx->ev[1], st));
+    return hsc::OK;
+}
+
+// the W steps of iteration `it` over the row tiles; the updated coefficients end in A[((it + 1) * W) & 1]
+template <typename T, typename G>
+void launch_steps(hipStream_t st, const G& g, dim3 grid, const Plan& pl, T* const* A, const T* X, const T* D, const int* done,
+                  int it)
+{
+    for (int t = 0; t < pl.W; ++t) {
+        const int s = it * pl.W + t;
+        hipLaunchKernelGGL((nmf_step_kernel<T, G>), grid, dim3(kThreads), pl.lds, st, A[s & 1], A[(s + 1) & 1], X, D, done, g, pl.K,
+                           pl.W, pl.F, t, pl.PR, pl.slab);
+    }
+}
+
+// the residual of iteration `it` over the sample tiles (with the dictionary as it is now), then the n signals' decisions
+template <typename T, typename G>
+void launch_residual_decide(hipStream_t st, const G& g, dim3 grid, const Plan& pl, const Dev<T>& d, int n, int it,
+                            const hscnmf_params& p)
+{
+    hipLaunchKernelGGL((nmf_residual_kernel<T, G>), grid, dim3(kThreads), pl.lds, st, d.A[((it + 1) * pl.W) & 1], d.X, d.D, d.state,
+                       d.R, d.part, g, pl.K, pl.W, pl.F, pl.PR, pl.slab);
+    hipLaunchKernelGGL(nmf_decide_kernel<G>, dim3(n), dim3(64), 0, st, d.part, g, d.stat, d.state, d.state + n,
+                       d.state + 2 * (size_t)n, d.stat + n, d.stat + 2 * (size_t)n, it + 1, p);
+}
+
+// after iteration `it`: 1 when all n flags at `done` are set, else 0 (or a negative status).  The flags are read once per
+// iteration, only with a tolerance and another iteration to go.
+int all_stopped(hscnmf_ctx* ctx, const hscnmf_params& p, int it, const int* done, int n, std::vector<int>& hdone)
+{
+    if (!(p.has_residual_scale || p.has_snr) || it + 1 >= p.max_iterations) return 0;
+    hdone.resize((size_t)n);
+    HSC_TRY(hipMemcpyAsync(hdone.data(), done, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HSC_TRY(hipStreamSynchronize(ctx->stream));
+    return std::all_of(hdone.begin(), hdone.end(), [](int v) { return v != 0; }) ? 1 : 0;
+}
+
+// event 2 (the iterations end), then the n signals' iterations, stop reasons, SNR and residual scales to `out` from `first`
+template <typename T>
+int download_stats(hscnmf_ctx* ctx, const Dev<T>& d, int first, int n, const Stats& out)
+{
+    hipStream_t st = ctx->stream;
+    HSC_TRY(hipEventRecord(ctx->ev[2], st));
+    HSC_TRY(hipMemcpyAsync(out.iters + first, d.state + n, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipMemcpyAsync(out.stop + first, d.state + 2 * (size_t)n, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipMemcpyAsync(out.snr + first, d.stat + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipMemcpyAsync(out.rscale + first, d.stat + 2 * (size_t)n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+    return hsc::OK;
+}
+
+// the first signal of c0 .. c0 + nb - 1 without a result (its iteration count outside [1, it]), or -1
+int no_result(const int32_t* iters, int c0, int nb, int it)
+{
+    for (int b = c0; b < c0 + nb; ++b)
+        if (iters[b] < 1 || iters[b] > it) return b;
+    return -1;
+}
+
+// once event 3 has completed: a chunk's upload, iteration and download times and the `it` iterations it ran, added to
+// tm (timing_ms of include/hscnmf.h)
+int add_chunk_times(hscnmf_ctx* ctx, double* tm, int it)
+{
+    if (int rc = hsc::add_times(ctx, 3, tm)) return rc;
+    tm[3] += 1;
+    tm[4] += it;
+    return hsc::OK;
+}
+
+// The chunk size Bc of hscnmf_compute and hscnmf_learn and the chunk's buffers.  Per signal: the A pair, X, R, the stop
+// state and (learn) its dsz dictionary values and psz partial values in PD.
+template <typename T>
+int uniform_alloc(DeviceBuffers& buf, const hscnmf_params& p, const Plan& pl, int B, int Tn, size_t dsz, size_t psz, Dev<T>& d,
+                  T** PD, int& Bc)
+{
+    hscnmf_ctx* ctx = buf.ctx;
+    const size_t L = Tn - pl.W + 1, ntt = (Tn + kRows - 1) / kRows, K = pl.K, F = pl.F;
+    HSC_TRY(hipSetDevice(ctx->device));
+    size_t freeb = 0, totalb = 0;
+    HSC_TRY(hipMemGetInfo(&freeb, &totalb));
+    const size_t per = (2 * L * K + 2 * (size_t)Tn * F + dsz + psz) * sizeof(T) + ntt * 2 * sizeof(double) + 3 * sizeof(double) +
+                       3 * sizeof(int);
+    const size_t budget = p.memory_budget ? (size_t)p.memory_budget : freeb / 10 * 6;
+    Bc = (int)std::max<size_t>(1, std::min<size_t>({(size_t)B, budget / per, (size_t)65535}));
+    const size_t n = Bc;
+    if (int rc = buf.get(&d.A[0], n * L * K * sizeof(T))) return rc;
+    if (int rc = buf.get(&d.A[1], n * L * K * sizeof(T))) return rc;
+    if (int rc = buf.get(&d.X, n * Tn * F * sizeof(T))) return rc;
+    if (int rc = buf.get(&d.R, n * Tn * F * sizeof(T))) return rc;
+    if (int rc = buf.get(&d.D, (dsz ? n * dsz : K * pl.W * F) * sizeof(T))) return rc;
+    if (psz) if (int rc = buf.get(PD, n * psz * sizeof(T))) return rc;
+    if (int rc = buf.get(&d.part, n * ntt * 2 * sizeof(double))) return rc;
+    if (int rc = buf.get(&d.stat, n * 3 * sizeof(double))) return rc;
+    return buf.get(&d.state, n * 3 * sizeof(int));
+}
+
+// What hscnmf_compute and hscnmf_compute_ragged share: the host side of the call, the timings summed over its chunks and
+// the chunk itself.
+template <typename T>
+struct Coder {
+    hscnmf_ctx* ctx;
+    const char* fn;
+    const hscnmf_params& p;
+    const Plan& pl;
+    const T* x;
+    const double* energy;
+    T *coef, *resid;
+    Stats out;
+    std::vector<int> hdone;
+    double tm[5];
+
+    // One chunk: the signals first .. first + nb - 1 of the call, described by sig[0 .. nb) (T, L, and x0 / a0: the first
+    // sample / coefficient row in the chunk's stacks), their samples stacked in x, resid and coef from sample hx0 on.
+    // Upload (x, a_init as the caller lays it out, the energies, the caller's tables), per iteration the W steps on
+    // `grow`, the residual and the decisions on `gsmp`, the once-per-iteration poll; then the statistics, the residual
+    // and every signal's coefficients, centred in its T rows.
+    template <typename G>
+    int chunk(const G& grow, dim3 rgrid, const G& gsmp, dim3 sgrid, const Dev<T>& d, int first, int nb, const SignalInfo* sig,
+              size_t hx0, const Upload& a_init, const Upload& table0 = Upload{}, const Upload& table1 = Upload{})
+    {
+        const int K = pl.K, W = pl.W, F = pl.F, off = (W - 1) / 2;
+        const size_t xbytes = (size_t)(sig[nb - 1].x0 + sig[nb - 1].T) * F * sizeof(T);
+        hipStream_t st = ctx->stream;
+        if (int rc = upload(ctx, {Upload{d.X, x + hx0 * F, xbytes}, a_init, Upload{d.stat, energy + first, (size_t)nb * sizeof(double)},
+                                  table0, table1}, d.state, (size_t)nb * 3 * sizeof(int)))
+            return rc;
+        int it = 0;
+        for (; it < p.max_iterations; ++it) {
+            launch_steps(st, grow, rgrid, pl, d.A, d.X, d.D, d.state, it);
+            launch_residual_decide(st, gsmp, sgrid, pl, d, nb, it, p);
+            HSC_TRY(hipGetLastError());
+            const int stopped = all_stopped(ctx, p, it, d.state, nb, hdone);
+            if (stopped < 0) return stopped;
+            if (stopped) { ++it; break; }
+        }
+        if (int rc = download_stats(ctx, d, first, nb, out)) return rc;
+        HSC_TRY(hipMemcpyAsync(resid + hx0 * F, d.R, xbytes, hipMemcpyDeviceToHost, st));
+        HSC_TRY(hipStreamSynchronize(st));
+        const int bad = no_result(out.iters, first, nb, it);
+        if (bad >= 0) return fail(ctx, HSCNMF_ERR_INVALID, "%s: signal %d has no result", fn, bad);
+        for (int b = 0; b < nb; ++b) {
+            // a signal that stopped after n iterations holds its coefficients in buffer (n * W) mod 2
+            const int n = out.iters[first + b], Tb = sig[b].T, Lb = sig[b].L;
+            T* dst = coef + (hx0 + (size_t)sig[b].x0) * K;
+            std::memset(dst, 0, (size_t)off * K * sizeof(T));
+            std::memset(dst + (size_t)(off + Lb) * K, 0, (size_t)(Tb - off - Lb) * K * sizeof(T));
+            HSC_TRY(hipMemcpyAsync(dst + (size_t)off * K, d.A[((size_t)n * W) & 1] + (size_t)sig[b].a0 * K, (size_t)Lb * K * sizeof(T),
+                                   hipMemcpyDeviceToHost, st));
+        }
+        HSC_TRY(hipEventRecord(ctx->ev[3], st));
+        HSC_TRY(hipStreamSynchronize(st));
+        return add_chunk_times(ctx, tm, it);
+    }
+};
+
 }  // namespace
 
-// As learn_t with ONE dictionary and the ragged geometry: per iteration the W steps, R = X/|recon|, the tile partials,
-// their sums per signal (nmf_dsum_kernel) and over the signals (nmf_dupdate_corpus_kernel), the residual with the new D,
-// the signals' statistics and the corpus decision.  No synchronisation inside an iteration; the whole corpus is resident.
+// hscnmf_compute: chunks of Bc signals of one length on the uniform geometry, a_init [B][T][K] uploaded as its rows 0 .. L-1
 template <typename T>
-static int learn_corpus_t(hscnmf_ctx* ctx, const T* x, const int64_t* lengths, int B, int F, const T* D_init, int K, int W,
-                          const T* a_init, const double* energy, const hscnmf_params& p, T* D_out, int32_t* iters,
-                          int32_t* stop, double* snr, double* rscale, double* sig_snr, double* sig_rscale, double* timing)
+static int compute_t(hscnmf_ctx* ctx, const Plan& pl, const T* x, int B, int Tn, const T* D, const T* a_init, const double* energy,
+                     const hscnmf_params& p, T* coef, T* resid, const Stats& out, double* timing)
 {
-    const int NW = W * F, ld = NW + 1;
+    const int K = pl.K, W = pl.W, F = pl.F, L = Tn - W + 1, ntl = (L + kRows - 1) / kRows, ntt = (Tn + kRows - 1) / kRows;
+    std::vector<SignalInfo> sig;
+    Coder<T> c{ctx, "hscnmf_compute", p, pl, x, energy, coef, resid, out, {}, {0, 0, 0, 0, 0}};
+    DeviceBuffers buf(ctx, c.fn);
+    Dev<T> d;
+    int Bc = 0;
+    if (int rc = uniform_alloc<T>(buf, p, pl, B, Tn, 0, 0, d, nullptr, Bc)) return rc;
+    HSC_TRY(hipMemcpyAsync(d.D, D, (size_t)K * W * F * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    for (int b = 0; b < Bc; ++b) sig.push_back(SignalInfo{(long long)b * Tn, (long long)b * L, 0, 0, Tn, L});
+    const Uniform g{L, Tn, 0};
+    for (int c0 = 0; c0 < B; c0 += Bc) {
+        const int nb = std::min(Bc, B - c0);
+        const Upload a{d.A[0], a_init + (size_t)c0 * Tn * K, (size_t)L * K * sizeof(T), (size_t)Tn * K * sizeof(T), (size_t)nb};
+        if (int rc = c.chunk(g, dim3(ntl, nb), g, dim3(ntt, nb), d, c0, nb, sig.data(), (size_t)c0 * Tn, a)) return rc;
+    }
+    if (timing) std::memcpy(timing, c.tm, sizeof(c.tm));
+    return HSCNMF_OK;
+}
+
+extern "C" int hscnmf_compute(hscnmf_ctx* ctx, int dtype, const void* x, int B, int T, int F, const void* D, int K, int W,
+                              const void* a_init, const double* energy, const hscnmf_params* params, void* coefficients,
+                              void* residual, int32_t* iterations, int32_t* stop, double* snr, double* residual_scale,
+                              double* timing_ms)
+{
+    const char* fn = "hscnmf_compute";
+    if (!ctx) return fail(nullptr, HSCNMF_ERR_INVALID, "%s: ctx is NULL", fn);
+    if (!x || !D || !a_init || !energy || !params || !coefficients || !residual || !iterations || !stop || !snr || !residual_scale)
+        return fail(ctx, HSCNMF_ERR_INVALID, "%s: NULL argument", fn);
+    const int64_t length = T;
+    const Stats out{iterations, stop, snr, residual_scale};
+    Plan pl;
+    if (int rc = check_args(ctx, fn, Call::Coder, dtype, &length, B, F, K, W, params, pl)) return rc;
+    if (dtype == HSCNMF_F32)
+        return compute_t<float>(ctx, pl, (const float*)x, B, T, (const float*)D, (const float*)a_init, energy, *params,
+                                (float*)coefficients, (float*)residual, out, timing_ms);
+    return compute_t<double>(ctx, pl, (const double*)x, B, T, (const double*)D, (const double*)a_init, energy, *params,
+                             (double*)coefficients, (double*)residual, out, timing_ms);
+}
+
+// The learner (hsc/modeling.py:330-417): per chunk of learners, each iteration is the W steps, R = X/|recon| (updated A,
+// old D) into the residual buffer, the tile partials, the dictionary update, then the residual and the stop decision with
+// the new D.  Every learner owns its D ([B][K][W][F], stride K*W*F); a finished learner's D stays as it was.
+template <typename T>
+static int learn_t(hscnmf_ctx* ctx, const Plan& pl, const T* x, int B, int Tn, const T* D_init, const T* a_init,
+                   const double* energy, const hscnmf_params& p, T* D_out, const Stats& out, double* timing)
+{
+    const int K = pl.K, W = pl.W, F = pl.F, L = Tn - W + 1, ntl = (L + kRows - 1) / kRows, ntt = (Tn + kRows - 1) / kRows, NW = W * F;
+    const size_t dsz = (size_t)K * NW, psz = (size_t)ntl * K * (NW + 1);
+    std::vector<int> hdone;
+    double tm[5] = {0, 0, 0, 0, 0};
+    DeviceBuffers buf(ctx, "hscnmf_learn");
+    Dev<T> d;
+    T* dPD = nullptr;
+    int Bc = 0;
+    if (int rc = uniform_alloc(buf, p, pl, B, Tn, dsz, psz, d, &dPD, Bc)) return rc;
+    const Uniform g{L, Tn, dsz};
+    hipStream_t st = ctx->stream;
+    for (int c0 = 0; c0 < B; c0 += Bc) {
+        const int nb = std::min(Bc, B - c0);
+        const Upload a{d.A[0], a_init + (size_t)c0 * Tn * K, (size_t)L * K * sizeof(T), (size_t)Tn * K * sizeof(T), (size_t)nb};
+        if (int rc = upload(ctx, {Upload{d.X, x + (size_t)c0 * Tn * F, (size_t)nb * Tn * F * sizeof(T)}, a,
+                                  Upload{d.D, D_init + (size_t)c0 * dsz, (size_t)nb * dsz * sizeof(T)},
+                                  Upload{d.stat, energy + c0, (size_t)nb * sizeof(double)}}, d.state, (size_t)nb * 3 * sizeof(int)))
+            return rc;
+        int it = 0;
+        for (; it < p.max_iterations; ++it) {
+            launch_steps(st, g, dim3(ntl, nb), pl, d.A, d.X, d.D, d.state, it);
+            const T* dAn = d.A[((it + 1) * W) & 1];
+            hipLaunchKernelGGL((nmf_ratio_kernel<T, Uniform>), dim3(ntt, nb), dim3(kThreads), pl.lds, st, dAn, d.X, d.D, d.state, d.R, g,
+                               K, W, F, pl.PR, pl.slab);
+            hipLaunchKernelGGL((nmf_dpart_kernel<T, Uniform>), dim3(ntl, nb), dim3(kThreads), pl.lds_part, st, dAn, d.R, d.state, dPD, g,
+                               K, W, F);
+            hipLaunchKernelGGL(nmf_dupdate_kernel<T>, dim3(K, nb), dim3(kThreads), pl.lds_upd, st, dPD, ntl, d.state, d.D, K, NW);
+            launch_residual_decide(st, g, dim3(ntt, nb), pl, d, nb, it, p);
+            HSC_TRY(hipGetLastError());
+            const int stopped = all_stopped(ctx, p, it, d.state, nb, hdone);
+            if (stopped < 0) return stopped;
+            if (stopped) { ++it; break; }
+        }
+        if (int rc = download_stats(ctx, d, c0, nb, out)) return rc;
+        HSC_TRY(hipMemcpyAsync(D_out + (size_t)c0 * dsz, d.D, (size_t)nb * dsz * sizeof(T), hipMemcpyDeviceToHost, st));
+        HSC_TRY(hipEventRecord(ctx->ev[3], st));
+        HSC_TRY(hipStreamSynchronize(st));
+        const int bad = no_result(out.iters, c0, nb, it);
+        if (bad >= 0) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn: learner %d has no result", bad);
+        if (int rc = add_chunk_times(ctx, tm, it)) return rc;
+    }
+    if (timing) std::memcpy(timing, tm, sizeof(tm));
+    return HSCNMF_OK;
+}
+
+extern "C" int hscnmf_learn(hscnmf_ctx* ctx, int dtype, const void* x, int B, int T, int F, const void* D_init, int K, int W,
+                            const void* a_init, const double* energy, const hscnmf_params* params, void* D_out,
+                            int32_t* iterations, int32_t* stop, double* snr, double* residual_scale, double* timing_ms)
+{
+    const char* fn = "hscnmf_learn";
+    if (!ctx) return fail(nullptr, HSCNMF_ERR_INVALID, "%s: ctx is NULL", fn);
+    if (!x || !D_init || !a_init || !energy || !params || !D_out || !iterations || !stop || !snr || !residual_scale)
+        return fail(ctx, HSCNMF_ERR_INVALID, "%s: NULL argument", fn);
+    const int64_t length = T;
+    const Stats out{iterations, stop, snr, residual_scale};
+    Plan pl;
+    if (int rc = check_args(ctx, fn, Call::Learner, dtype, &length, B, F, K, W, params, pl)) return rc;
+    if (dtype == HSCNMF_F32)
+        return learn_t<float>(ctx, pl, (const float*)x, B, T, (const float*)D_init, (const float*)a_init, energy, *params,
+                              (float*)D_out, out, timing_ms);
+    return learn_t<double>(ctx, pl, (const double*)x, B, T, (const double*)D_init, (const double*)a_init, energy, *params,
+                           (double*)D_out, out, timing_ms);
+}
+
+// ---- hscnmf_learn_corpus: one dictionary from B signals of different lengths, DESIGN.md section 18 --------------------
+
+// As learn_t with ONE dictionary and the ragged geometry: per iteration the W steps, R = X/|recon|, the tile partials,
+// their sums per signal (nmf_dsum_kernel) and over the signals (nmf_dupdate_kernel), the residual with the new D, the
+// signals' statistics and the corpus decision.  No synchronisation inside an iteration; the whole corpus is resident.
+template <typename T>
+static int learn_corpus_t(hscnmf_ctx* ctx, const Plan& pl, const T* x, const int64_t* lengths, int B, const T* D_init,
+                          const T* a_init, const double* energy, const hscnmf_params& p, T* D_out, const Stats& out,
+                          double* sig_snr, double* sig_rscale, double* timing)
+{
+    const int K = pl.K, W = pl.W, F = pl.F, NW = W * F, ld = NW + 1;
     const size_t dsz = (size_t)K * NW, tstride = (size_t)K * ld;
-    const size_t lds_part = (size_t)(kRows + W - 1) * F * sizeof(T), lds_upd = (size_t)(kThreads + NW + 1) * sizeof(T);
-    int PR = 0, slab = 0;
-    size_t lds = 0;
-    if (!lds_plan<T>(W, F, PR, slab, lds) || lds_part > (size_t)kLdsBytes || lds_upd > (size_t)kLdsBytes)
-        return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_learn_corpus: W = %d, F = %d needs more than %d bytes of LDS per workgroup",
-                    W, F, kLdsBytes);
     // the per-signal table and the flat tile tables
     std::vector<SignalInfo> sig((size_t)B);
     long long rows = 0, arows = 0, nrt = 0, nst = 0;
@@ -1036,70 +1014,49 @@ static int learn_corpus_t(hscnmf_ctx* ctx, const T* x, const int64_t* lengths, i
     if (need > budget)
         return fail(ctx, HSCNMF_ERR_ALLOC, "hscnmf_learn_corpus: the corpus needs %zu bytes of device memory, the budget is %zu bytes "
                     "(a corpus is resident as a whole: there is no chunking)", need, budget);
-    CorpusBuffers buf(ctx);
-    T *dA[2], *dX, *dR, *dD, *dPD, *dS;
-    double *dPart, *dStat, *dOut;
-    SignalInfo* dSig;
-    int2* dTiles;
-    int* dState;
-    if (int rc = buf.get(&dA[0], sizes[0])) return rc;
-    if (int rc = buf.get(&dA[1], sizes[1])) return rc;
-    if (int rc = buf.get(&dX, sizes[2])) return rc;
-    if (int rc = buf.get(&dR, sizes[3])) return rc;
-    if (int rc = buf.get(&dD, sizes[4])) return rc;
-    if (int rc = buf.get(&dPD, sizes[5])) return rc;
-    if (int rc = buf.get(&dS, sizes[6])) return rc;
-    if (int rc = buf.get(&dPart, sizes[7])) return rc;
-    if (int rc = buf.get(&dStat, sizes[8])) return rc;
-    if (int rc = buf.get(&dSig, sizes[9])) return rc;
-    if (int rc = buf.get(&dTiles, sizes[10])) return rc;
-    if (int rc = buf.get(&dOut, sizes[11])) return rc;
-    dState = reinterpret_cast<int*>(dOut + 2);
+    std::vector<int> hdone;
+    int hstate[3] = {0, 0, 0};
+    double hout[2] = {0.0, 0.0};
+    DeviceBuffers buf(ctx, "hscnmf_learn_corpus");
+    void* at[std::size(sizes)];
+    for (size_t i = 0; i < std::size(sizes); ++i)
+        if (int rc = buf.get(&at[i], sizes[i])) return rc;
+    T *dA[2] = {(T*)at[0], (T*)at[1]}, *dX = (T*)at[2], *dR = (T*)at[3], *dD = (T*)at[4], *dPD = (T*)at[5], *dS = (T*)at[6];
+    double *dPart = (double*)at[7], *dStat = (double*)at[8], *dOut = (double*)at[11];
+    SignalInfo* dSig = (SignalInfo*)at[9];
+    int2* dTiles = (int2*)at[10];
+    int* dState = reinterpret_cast<int*>(dOut + 2);
     double *dEn = dStat, *dMx = dStat + B, *dSs = dStat + 2 * (size_t)B, *dSnr = dStat + 3 * (size_t)B, *dRs = dStat + 4 * (size_t)B;
-    const Ragged grow{dSig, dTiles}, gsmp{dSig, dTiles + nrt};
+    using G = Ragged<false>;
+    const G grow{dSig, dTiles}, gsmp{dSig, dTiles + nrt};
+    const dim3 rgrid((unsigned)nrt), sgrid((unsigned)nst);
 
     hipStream_t st = ctx->stream;
-    HSC_TRY(hipEventRecord(ctx->ev[0], st));
-    HSC_TRY(hipMemcpyAsync(dX, x, sizes[2], hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(dA[0], a_init, sizes[0], hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(dD, D_init, sizes[4], hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(dEn, energy, (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(dSig, sig.data(), sizes[9], hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(dTiles, rtiles.data(), (size_t)nrt * sizeof(int2), hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(dTiles + nrt, stiles.data(), (size_t)nst * sizeof(int2), hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemsetAsync(dOut, 0, sizes[11], st));
-    HSC_TRY(hipEventRecord(ctx->ev[1], st));
-    // (the host tables are declared before `buf`, whose destructor synchronises the stream: they outlive their copies)
-    int it = 0, hdone = 0;
+    if (int rc = upload(ctx, {Upload{dX, x, sizes[2]}, Upload{dA[0], a_init, sizes[0]}, Upload{dD, D_init, sizes[4]},
+                              Upload{dEn, energy, (size_t)B * sizeof(double)}, Upload{dSig, sig.data(), sizes[9]},
+                              Upload{dTiles, rtiles.data(), (size_t)nrt * sizeof(int2)},
+                              Upload{dTiles + nrt, stiles.data(), (size_t)nst * sizeof(int2)}}, dOut, sizes[11]))
+        return rc;
+    int it = 0;
     for (; it < p.max_iterations; ++it) {
-        for (int t = 0; t < W; ++t) {
-            const int g = it * W + t;
-            hipLaunchKernelGGL(nmf_step_ragged_kernel<T>, dim3((unsigned)nrt), dim3(kThreads), lds, st, dA[g & 1], dA[(g + 1) & 1],
-                               dX, dD, dState, grow, K, W, F, t, PR, slab);
-        }
+        launch_steps(st, grow, rgrid, pl, dA, dX, dD, dState, it);
         const T* dAn = dA[((it + 1) * W) & 1];
-        hipLaunchKernelGGL(nmf_ratio_ragged_kernel<T>, dim3((unsigned)nst), dim3(kThreads), lds, st, dAn, dX, dD, dState, dR, gsmp,
-                           K, W, F, PR, slab);
-        hipLaunchKernelGGL(nmf_dpart_ragged_kernel<T>, dim3((unsigned)nrt), dim3(kThreads), lds_part, st, dAn, dR, dState, dPD, grow,
-                           K, W, F);
+        hipLaunchKernelGGL((nmf_ratio_kernel<T, G>), sgrid, dim3(kThreads), pl.lds, st, dAn, dX, dD, dState, dR, gsmp, K, W, F, pl.PR,
+                           pl.slab);
+        hipLaunchKernelGGL((nmf_dpart_kernel<T, G>), rgrid, dim3(kThreads), pl.lds_part, st, dAn, dR, dState, dPD, grow, K, W, F);
         hipLaunchKernelGGL(nmf_dsum_kernel<T>, dim3((unsigned)((size_t)B * nchunk)), dim3(kThreads), 0, st, dPD, dSig, dState, dS,
                            (unsigned)nchunk, tstride);
-        hipLaunchKernelGGL(nmf_dupdate_corpus_kernel<T>, dim3(K), dim3(kThreads), lds_upd, st, dS, B, dState, dD, K, NW);
-        hipLaunchKernelGGL(nmf_residual_ragged_kernel<T>, dim3((unsigned)nst), dim3(kThreads), lds, st, dAn, dX, dD, dState, dR, dPart,
-                           gsmp, K, W, F, PR, slab);
+        hipLaunchKernelGGL(nmf_dupdate_kernel<T>, dim3(K, 1), dim3(kThreads), pl.lds_upd, st, dS, B, dState, dD, K, NW);
+        hipLaunchKernelGGL((nmf_residual_kernel<T, G>), sgrid, dim3(kThreads), pl.lds, st, dAn, dX, dD, dState, dR, dPart, gsmp, K, W,
+                           F, pl.PR, pl.slab);
         hipLaunchKernelGGL(nmf_signal_stats_kernel, dim3(B), dim3(64), 0, st, dPart, dSig, dEn, dState, dMx, dSs, dSnr, dRs);
         hipLaunchKernelGGL(nmf_decide_corpus_kernel, dim3(1), dim3(kThreads), 0, st, dMx, dSs, dEn, B, dState, dOut, it + 1, p);
         HSC_TRY(hipGetLastError());
-        // the flag is read once per iteration, only with a tolerance and another iteration to go
-        if ((p.has_residual_scale || p.has_snr) && it + 1 < p.max_iterations) {
-            HSC_TRY(hipMemcpyAsync(&hdone, dState, sizeof(int), hipMemcpyDeviceToHost, st));
-            HSC_TRY(hipStreamSynchronize(st));
-            if (hdone) { ++it; break; }
-        }
+        const int stopped = all_stopped(ctx, p, it, dState, 1, hdone);
+        if (stopped < 0) return stopped;
+        if (stopped) { ++it; break; }
     }
     HSC_TRY(hipEventRecord(ctx->ev[2], st));
-    int hstate[3] = {0, 0, 0};
-    double hout[2] = {0.0, 0.0};
     HSC_TRY(hipMemcpyAsync(hstate, dState, sizeof(hstate), hipMemcpyDeviceToHost, st));
     HSC_TRY(hipMemcpyAsync(hout, dOut, sizeof(hout), hipMemcpyDeviceToHost, st));
     HSC_TRY(hipMemcpyAsync(sig_snr, dSnr, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1108,12 +1065,12 @@ static int learn_corpus_t(hscnmf_ctx* ctx, const T* x, const int64_t* lengths, i
     HSC_TRY(hipEventRecord(ctx->ev[3], st));
     HSC_TRY(hipStreamSynchronize(st));
     if (hstate[1] != it) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn_corpus: the corpus has no result");
-    *iters = hstate[1];
-    *stop = hstate[2];
-    *snr = hout[0];
-    *rscale = hout[1];
-    double tm[5] = {0, 0, 0, 1, (double)it};
-    if (int rc = hsc::add_times(ctx, 3, tm)) return rc;
+    *out.iters = hstate[1];
+    *out.stop = hstate[2];
+    *out.snr = hout[0];
+    *out.rscale = hout[1];
+    double tm[5] = {0, 0, 0, 0, 0};
+    if (int rc = add_chunk_times(ctx, tm, it)) return rc;
     if (timing) std::memcpy(timing, tm, sizeof(tm));
     return HSCNMF_OK;
 }
@@ -1123,102 +1080,24 @@ extern "C" int hscnmf_learn_corpus(hscnmf_ctx* ctx, int dtype, const void* x, co
                                    const hscnmf_params* params, void* D_out, int32_t* iterations, int32_t* stop, double* snr,
                                    double* residual_scale, double* signal_snr, double* signal_residual_scale, double* timing_ms)
 {
-    if (!ctx) return fail(nullptr, HSCNMF_ERR_INVALID, "hscnmf_learn_corpus: ctx is NULL");
+    const char* fn = "hscnmf_learn_corpus";
+    if (!ctx) return fail(nullptr, HSCNMF_ERR_INVALID, "%s: ctx is NULL", fn);
     if (!x || !lengths || !D_init || !a_init || !energy || !params || !D_out || !iterations || !stop || !snr || !residual_scale ||
         !signal_snr || !signal_residual_scale)
-        return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn_corpus: NULL argument");
-    if (dtype != HSCNMF_F32 && dtype != HSCNMF_F64) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn_corpus: unknown dtype %d", dtype);
-    if (B < 1 || K < 1 || F < 1) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn_corpus: B = %d, K = %d, F = %d", B, K, F);
-    if (W < 2) return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn_corpus: filter width %d (the reference needs W >= 2)", W);
-    if (params->max_iterations < 1)
-        return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn_corpus: max_iterations = %d", params->max_iterations);
-    for (int b = 0; b < B; ++b)
-        if (lengths[b] < W)
-            return fail(ctx, HSCNMF_ERR_INVALID, "hscnmf_learn_corpus: signal %d: length %lld is shorter than the filter width %d", b,
-                        (long long)lengths[b], W);
-    if (B > kMaxCorpusSignals) return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_learn_corpus: %d signals (at most %d)", B, kMaxCorpusSignals);
-    if ((int64_t)W * F > (1 << 24) || K > 65535) return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_learn_corpus: shape out of range");
-    for (int b = 0; b < B; ++b)
-        if ((lengths[b] - W + 1) * K > ((int64_t)1 << 31) / 8)
-            return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "hscnmf_learn_corpus: signal %d: shape out of range", b);
+        return fail(ctx, HSCNMF_ERR_INVALID, "%s: NULL argument", fn);
+    const Stats out{iterations, stop, snr, residual_scale};
+    Plan pl;
+    if (int rc = check_args(ctx, fn, Call::CorpusLearner, dtype, lengths, B, F, K, W, params, pl)) return rc;
     if (dtype == HSCNMF_F32)
-        return learn_corpus_t<float>(ctx, (const float*)x, lengths, B, F, (const float*)D_init, K, W, (const float*)a_init, energy,
-                                     *params, (float*)D_out, iterations, stop, snr, residual_scale, signal_snr,
-                                     signal_residual_scale, timing_ms);
-    return learn_corpus_t<double>(ctx, (const double*)x, lengths, B, F, (const double*)D_init, K, W, (const double*)a_init, energy,
-                                  *params, (double*)D_out, iterations, stop, snr, residual_scale, signal_snr,
-                                  signal_residual_scale, timing_ms);
+        return learn_corpus_t<float>(ctx, pl, (const float*)x, lengths, B, (const float*)D_init, (const float*)a_init, energy,
+                                     *params, (float*)D_out, out, signal_snr, signal_residual_scale, timing_ms);
+    return learn_corpus_t<double>(ctx, pl, (const double*)x, lengths, B, (const double*)D_init, (const double*)a_init, energy,
+                                  *params, (double*)D_out, out, signal_snr, signal_residual_scale, timing_ms);
 }
 
 // ---- hscnmf_compute_ragged: the coder over B signals of different lengths, DESIGN.md section 23 ----------------------
 
 namespace {
-
-// the ragged geometry with the coder's stop state: one flag per signal (of the chunk)
-struct RaggedSignals : Ragged {
-    __device__ int flag(int b) const { return b; }
-};
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void nmf_step_signals_kernel(const T* __restrict__ Ain, T* __restrict__ Aout,
-                                                                    const T* __restrict__ X, const T* __restrict__ D,
-                                                                    const int* __restrict__ done, RaggedSignals g, int K, int W,
-                                                                    int F, int t, int PR, int slab)
-{
-    step_body(g, Ain, Aout, X, D, (size_t)0, done, K, W, F, t, PR, slab);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void nmf_residual_signals_kernel(const T* __restrict__ Abuf, const T* __restrict__ X,
-                                                                        const T* __restrict__ D, const int* __restrict__ done,
-                                                                        T* __restrict__ resid, double* __restrict__ part,
-                                                                        RaggedSignals g, int K, int W, int F, int PR, int slab)
-{
-    residual_body(g, Abuf, X, D, (size_t)0, done, resid, part, K, W, F, PR, slab);
-}
-
-// one workgroup (64 threads) per signal: nmf_decide_kernel on the signal's own sample-tile partials (64 threads striding
-// its tiles, then the tree: the same order), writing that signal's state alone
-__global__ __launch_bounds__(64) void nmf_decide_signals_kernel(const double* __restrict__ part,
-                                                                const SignalInfo* __restrict__ sig,
-                                                                const double* __restrict__ energy, int* __restrict__ done,
-                                                                int* __restrict__ iters, int* __restrict__ stop,
-                                                                double* __restrict__ snr, double* __restrict__ rscale,
-                                                                int it1, hscnmf_params p)
-{
-    const int b = blockIdx.x;
-    if (done[b]) return;
-    __shared__ double smx[64], sss[64];
-    const int ntiles = (sig[b].T + kRows - 1) / kRows;
-    const double* pb = part + (size_t)sig[b].st0 * 2;
-    double mx = 0.0, ss = 0.0;
-    for (int i = threadIdx.x; i < ntiles; i += 64) {
-        mx = fmax(mx, pb[(size_t)i * 2]);
-        ss = ss + pb[(size_t)i * 2 + 1];
-    }
-    smx[threadIdx.x] = mx;
-    sss[threadIdx.x] = ss;
-    __syncthreads();
-    for (int w = 32; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            smx[threadIdx.x] = fmax(smx[threadIdx.x], smx[threadIdx.x + w]);
-            sss[threadIdx.x] = sss[threadIdx.x] + sss[threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const double rs = smx[0], s = 10.0 * log10(energy[b] / sss[0]);
-        int code = HSCNMF_STOP_RUNNING;
-        if (it1 >= p.max_iterations) code = HSCNMF_STOP_MAX_ITERATIONS;
-        else if (p.has_residual_scale && rs <= p.tolerance_residual_scale) code = HSCNMF_STOP_RESIDUAL_SCALE;
-        else if (p.has_snr && s >= p.tolerance_snr) code = HSCNMF_STOP_SNR;
-        iters[b] = it1;
-        snr[b] = s;
-        rscale[b] = rs;
-        stop[b] = code;
-        if (code != HSCNMF_STOP_RUNNING) done[b] = 1;
-    }
-}
 
 // a chunk: the signals first .. first + count - 1, their samples, coefficient rows, row tiles and sample tiles, and the
 // device bytes they need
@@ -1250,29 +1129,6 @@ size_t ragged_sizes(size_t item, long long rows, long long arows, long long nrt,
     return total;
 }
 
-// the argument checks hscnmf_ragged_plan and hscnmf_compute_ragged share (nothing is allocated before them)
-int ragged_check(hsc::CtxBase* ctx, const char* fn, int dtype, const int64_t* lengths, int B, int F, int K, int W)
-{
-    if (!lengths) return fail(ctx, HSCNMF_ERR_INVALID, "%s: NULL argument", fn);
-    if (dtype != HSCNMF_F32 && dtype != HSCNMF_F64) return fail(ctx, HSCNMF_ERR_INVALID, "%s: unknown dtype %d", fn, dtype);
-    if (B < 1 || K < 1 || F < 1) return fail(ctx, HSCNMF_ERR_INVALID, "%s: B = %d, K = %d, F = %d", fn, B, K, F);
-    if (W < 2) return fail(ctx, HSCNMF_ERR_INVALID, "%s: filter width %d (the reference needs W >= 2)", fn, W);
-    for (int b = 0; b < B; ++b)
-        if (lengths[b] < W)
-            return fail(ctx, HSCNMF_ERR_INVALID, "%s: signal %d: length %lld is shorter than the filter width %d", fn, b,
-                        (long long)lengths[b], W);
-    if ((int64_t)W * F > (1 << 24)) return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "%s: shape out of range", fn);
-    int PR = 0, slab = 0;
-    size_t lds = 0;
-    if (!(dtype == HSCNMF_F32 ? lds_plan<float>(W, F, PR, slab, lds) : lds_plan<double>(W, F, PR, slab, lds)))
-        return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "%s: W = %d, F = %d needs more than %d bytes of LDS per workgroup", fn, W, F,
-                    kLdsBytes);
-    for (int b = 0; b < B; ++b)
-        if ((lengths[b] - W + 1) * K > ((int64_t)1 << 31) / 8 || (lengths[b] + kRows - 1) / kRows > kMaxCorpusGrid)
-            return fail(ctx, HSCNMF_ERR_UNSUPPORTED, "%s: signal %d: shape out of range", fn, b);
-    return hsc::OK;
-}
-
 // Consecutive signals into chunks: a chunk takes signals while its bytes stay within `budget`, its sample tiles within
 // kMaxCorpusGrid and its signals within kMaxCorpusSignals, and always takes at least one.
 void ragged_chunks(size_t item, const int64_t* lengths, int B, int F, int K, int W, size_t budget, std::vector<RaggedChunk>& out)
@@ -1300,7 +1156,8 @@ extern "C" int hscnmf_ragged_plan(int dtype, const int64_t* lengths, int B, int 
 {
     const char* fn = "hscnmf_ragged_plan";
     if (!n_chunks || !max_chunk_bytes) return fail(nullptr, HSCNMF_ERR_INVALID, "%s: NULL argument", fn);
-    if (int rc = ragged_check(nullptr, fn, dtype, lengths, B, F, K, W)) return rc;
+    Plan pl;
+    if (int rc = check_args(nullptr, fn, Call::RaggedCoder, dtype, lengths, B, F, K, W, nullptr, pl)) return rc;
     if (budget_bytes < 1) return fail(nullptr, HSCNMF_ERR_INVALID, "%s: budget_bytes is 0", fn);
     std::vector<RaggedChunk> chunks;
     ragged_chunks(dtype == HSCNMF_F32 ? sizeof(float) : sizeof(double), lengths, B, F, K, W, (size_t)budget_bytes, chunks);
@@ -1315,19 +1172,14 @@ extern "C" int hscnmf_ragged_plan(int dtype, const int64_t* lengths, int B, int 
     return HSCNMF_OK;
 }
 
-// compute_t over the ragged geometry: per chunk of whole signals the upload, per iteration the W steps over the row
-// tiles, the residual over the sample tiles and the decision per signal, then the download.  One allocation holds the
-// largest chunk; D is uploaded once.  The launches and their order per signal are compute_t's.
+// hscnmf_compute_ragged: chunks of whole signals (ragged_chunks) on the ragged geometry with a stop flag per signal.  One
+// allocation holds the largest chunk; D is uploaded once.  The launches and their order per signal are compute_t's.
 template <typename T>
-static int compute_ragged_t(hscnmf_ctx* ctx, const T* x, const int64_t* lengths, int B, int F, const T* D, int K, int W,
-                            const T* a_init, const double* energy, const hscnmf_params& p, T* coef, T* resid, int32_t* iters,
-                            int32_t* stop, double* snr, double* rscale, double* timing)
+static int compute_ragged_t(hscnmf_ctx* ctx, const Plan& pl, const T* x, const int64_t* lengths, int B, const T* D,
+                            const T* a_init, const double* energy, const hscnmf_params& p, T* coef, T* resid, const Stats& out,
+                            double* timing)
 {
-    const char* fn = "hscnmf_compute_ragged";
-    const int off = (W - 1) / 2;
-    int PR = 0, slab = 0;
-    size_t lds = 0;
-    lds_plan<T>(W, F, PR, slab, lds);                                // (ragged_check has accepted W and F)
+    const int K = pl.K, W = pl.W, F = pl.F;
     HSC_TRY(hipSetDevice(ctx->device));
     size_t freeb = 0, totalb = 0;
     HSC_TRY(hipMemGetInfo(&freeb, &totalb));
@@ -1336,18 +1188,15 @@ static int compute_ragged_t(hscnmf_ctx* ctx, const T* x, const int64_t* lengths,
     ragged_chunks(sizeof(T), lengths, B, F, K, W, budget, chunks);
     size_t arena = 0;
     for (const RaggedChunk& c : chunks) arena = std::max(arena, c.bytes);
-    // (the host tables are declared before `buf`, whose destructor synchronises the stream: they outlive their copies)
     std::vector<SignalInfo> sig;
     std::vector<int2> tiles;
-    std::vector<int> hdone;
-    CorpusBuffers buf(ctx, fn);
+    Coder<T> coder{ctx, "hscnmf_compute_ragged", p, pl, x, energy, coef, resid, out, {}, {0, 0, 0, 0, 0}};
+    DeviceBuffers buf(ctx, coder.fn);
     unsigned char* base = nullptr;
     T* dD = nullptr;
     if (int rc = buf.get(&base, arena)) return rc;
     if (int rc = buf.get(&dD, (size_t)K * W * F * sizeof(T))) return rc;
-    hipStream_t st = ctx->stream;
-    HSC_TRY(hipMemcpyAsync(dD, D, (size_t)K * W * F * sizeof(T), hipMemcpyHostToDevice, st));
-    double tm[5] = {0, 0, 0, 0, 0};
+    HSC_TRY(hipMemcpyAsync(dD, D, (size_t)K * W * F * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
     long long x0 = 0, a0 = 0;                                        // the chunk's first sample and coefficient row in the stacks
     for (const RaggedChunk& c : chunks) {
         const int nb = c.count;
@@ -1359,10 +1208,7 @@ static int compute_ragged_t(hscnmf_ctx* ctx, const T* x, const int64_t* lengths,
             at[i] = q;
             q += s[i];
         }
-        T* dA[2] = {(T*)at[0], (T*)at[1]};
-        T *dX = (T*)at[2], *dR = (T*)at[3];
-        double *dPart = (double*)at[4], *dEn = (double*)at[5], *dSnr = dEn + nb, *dRs = dEn + 2 * (size_t)nb;
-        int *dDone = (int*)at[6], *dIt = dDone + nb, *dStop = dDone + 2 * (size_t)nb;
+        const Dev<T> d{{(T*)at[0], (T*)at[1]}, (T*)at[2], (T*)at[3], dD, (double*)at[4], (double*)at[5], (int*)at[6]};
         SignalInfo* dSig = (SignalInfo*)at[7];
         int2* dTiles = (int2*)at[8];
         // the chunk's tables, with offsets into the chunk's own stacks
@@ -1380,66 +1226,16 @@ static int compute_ragged_t(hscnmf_ctx* ctx, const T* x, const int64_t* lengths,
             nrt += nr;
             nst += ns;
         }
-        RaggedSignals grow, gsmp;
-        grow.sig = gsmp.sig = dSig;
-        grow.tiles = dTiles;
-        gsmp.tiles = dTiles + c.nrt;
-
-        HSC_TRY(hipEventRecord(ctx->ev[0], st));
-        HSC_TRY(hipMemcpyAsync(dX, x + (size_t)x0 * F, (size_t)c.rows * F * sizeof(T), hipMemcpyHostToDevice, st));
-        HSC_TRY(hipMemcpyAsync(dA[0], a_init + (size_t)a0 * K, (size_t)c.arows * K * sizeof(T), hipMemcpyHostToDevice, st));
-        HSC_TRY(hipMemcpyAsync(dEn, energy + c.first, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, st));
-        HSC_TRY(hipMemcpyAsync(dSig, sig.data(), (size_t)nb * sizeof(SignalInfo), hipMemcpyHostToDevice, st));
-        HSC_TRY(hipMemcpyAsync(dTiles, tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-        HSC_TRY(hipMemsetAsync(dDone, 0, (size_t)nb * 3 * sizeof(int), st));
-        HSC_TRY(hipEventRecord(ctx->ev[1], st));
-        int it = 0;
-        for (; it < p.max_iterations; ++it) {
-            for (int t = 0; t < W; ++t) {
-                const int g = it * W + t;
-                hipLaunchKernelGGL(nmf_step_signals_kernel<T>, dim3((unsigned)c.nrt), dim3(kThreads), lds, st, dA[g & 1],
-                                   dA[(g + 1) & 1], dX, dD, dDone, grow, K, W, F, t, PR, slab);
-            }
-            hipLaunchKernelGGL(nmf_residual_signals_kernel<T>, dim3((unsigned)c.nst), dim3(kThreads), lds, st,
-                               dA[((it + 1) * W) & 1], dX, dD, dDone, dR, dPart, gsmp, K, W, F, PR, slab);
-            hipLaunchKernelGGL(nmf_decide_signals_kernel, dim3(nb), dim3(64), 0, st, dPart, dSig, dEn, dDone, dIt, dStop, dSnr,
-                               dRs, it + 1, p);
-            HSC_TRY(hipGetLastError());
-            // the flags are read once per iteration, only with a tolerance and another iteration to go
-            if ((p.has_residual_scale || p.has_snr) && it + 1 < p.max_iterations) {
-                hdone.resize((size_t)nb);
-                HSC_TRY(hipMemcpyAsync(hdone.data(), dDone, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
-                HSC_TRY(hipStreamSynchronize(st));
-                if (std::all_of(hdone.begin(), hdone.end(), [](int v) { return v != 0; })) { ++it; break; }
-            }
-        }
-        HSC_TRY(hipEventRecord(ctx->ev[2], st));
-        HSC_TRY(hipMemcpyAsync(iters + c.first, dIt, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
-        HSC_TRY(hipMemcpyAsync(stop + c.first, dStop, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
-        HSC_TRY(hipMemcpyAsync(snr + c.first, dSnr, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st));
-        HSC_TRY(hipMemcpyAsync(rscale + c.first, dRs, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, st));
-        HSC_TRY(hipMemcpyAsync(resid + (size_t)x0 * F, dR, (size_t)c.rows * F * sizeof(T), hipMemcpyDeviceToHost, st));
-        HSC_TRY(hipStreamSynchronize(st));
-        const int bad = no_result(iters, c.first, nb, it);
-        if (bad >= 0) return fail(ctx, HSCNMF_ERR_INVALID, "%s: signal %d has no result", fn, bad);
-        for (int b = 0; b < nb; ++b) {
-            // a signal that stopped after n iterations holds its coefficients in buffer (n * W) mod 2
-            const int n = iters[c.first + b], Tb = sig[b].T, Lb = sig[b].L;
-            T* dst = coef + (size_t)(x0 + sig[b].x0) * K;
-            std::memset(dst, 0, (size_t)off * K * sizeof(T));
-            std::memset(dst + (size_t)(off + Lb) * K, 0, (size_t)(Tb - off - Lb) * K * sizeof(T));
-            HSC_TRY(hipMemcpyAsync(dst + (size_t)off * K, dA[((size_t)n * W) & 1] + (size_t)sig[b].a0 * K,
-                                   (size_t)Lb * K * sizeof(T), hipMemcpyDeviceToHost, st));
-        }
-        HSC_TRY(hipEventRecord(ctx->ev[3], st));
-        HSC_TRY(hipStreamSynchronize(st));
-        if (int rc = hsc::add_times(ctx, 3, tm)) return rc;
-        tm[3] += 1;
-        tm[4] += it;
+        const Ragged<true> grow{dSig, dTiles}, gsmp{dSig, dTiles + c.nrt};
+        if (int rc = coder.chunk(grow, dim3((unsigned)c.nrt), gsmp, dim3((unsigned)c.nst), d, c.first, nb, sig.data(), (size_t)x0,
+                                 Upload{d.A[0], a_init + (size_t)a0 * K, (size_t)c.arows * K * sizeof(T)},
+                                 Upload{dSig, sig.data(), (size_t)nb * sizeof(SignalInfo)},
+                                 Upload{dTiles, tiles.data(), tiles.size() * sizeof(int2)}))
+            return rc;
         x0 += c.rows;
         a0 += c.arows;
     }
-    if (timing) std::memcpy(timing, tm, sizeof(tm));
+    if (timing) std::memcpy(timing, coder.tm, sizeof(coder.tm));
     return HSCNMF_OK;
 }
 
@@ -1454,12 +1250,12 @@ extern "C" int hscnmf_compute_ragged(hscnmf_ctx* ctx, int dtype, const void* x, 
         !residual_scale)
         return fail(ctx, HSCNMF_ERR_INVALID, "%s: NULL argument", fn);
     if (params->max_iterations < 1) return fail(ctx, HSCNMF_ERR_INVALID, "%s: max_iterations = %d", fn, params->max_iterations);
-    if (int rc = ragged_check(ctx, fn, dtype, lengths, B, F, K, W)) return rc;
+    const Stats out{iterations, stop, snr, residual_scale};
+    Plan pl;
+    if (int rc = check_args(ctx, fn, Call::RaggedCoder, dtype, lengths, B, F, K, W, nullptr, pl)) return rc;
     if (dtype == HSCNMF_F32)
-        return compute_ragged_t<float>(ctx, (const float*)x, lengths, B, F, (const float*)D, K, W, (const float*)a_init, energy,
-                                       *params, (float*)coefficients, (float*)residual, iterations, stop, snr, residual_scale,
-                                       timing_ms);
-    return compute_ragged_t<double>(ctx, (const double*)x, lengths, B, F, (const double*)D, K, W, (const double*)a_init, energy,
-                                    *params, (double*)coefficients, (double*)residual, iterations, stop, snr, residual_scale,
-                                    timing_ms);
+        return compute_ragged_t<float>(ctx, pl, (const float*)x, lengths, B, (const float*)D, (const float*)a_init, energy,
+                                       *params, (float*)coefficients, (float*)residual, out, timing_ms);
+    return compute_ragged_t<double>(ctx, pl, (const double*)x, lengths, B, (const double*)D, (const double*)a_init, energy,
+                                    *params, (double*)coefficients, (double*)residual, out, timing_ms);
 }

@@ -65,7 +65,8 @@ const char* hscnmf_last_error(hscnmf_ctx* ctx);   /* ctx may be NULL (errors of 
  *   iterations   [B] int32, stop [B] int32 (HSCNMF_STOP_*), snr [B] float64, residual_scale [B] float64
  *   timing_ms    [5] float64 (may be NULL): upload, iterations, download (ms from HIP events, summed over chunks),
  *                number of chunks, number of iterations run (summed over chunks)
- * Requires W >= 2 and T >= W. */
+ * Requires W >= 2 and T >= W.  A failed device allocation answers HSCNMF_ERR_ALLOC, here as in every other entry point,
+ * the message naming the entry point and the bytes; the call's device memory is freed when it returns. */
 int hscnmf_compute(hscnmf_ctx* ctx, int dtype, const void* x, int B, int T, int F, const void* D, int K, int W,
                    const void* a_init, const double* energy, const hscnmf_params* params,
                    void* coefficients, void* residual, int32_t* iterations, int32_t* stop, double* snr,

@@ -163,7 +163,7 @@ def test_coder_matches_restatement(dtype, K, W, F, T, iters):
 @pytest.mark.gpu
 @pytest.mark.parametrize('dtype', [np.float64, np.float32])
 def test_coder_chunked_batch_matches_restatement(dtype):
-    """Five signals in chunks of two (the memory budget of Chunks::alloc for two signals): uploads at an offset, a
+    """Five signals in chunks of two (the memory budget of uniform_alloc for two signals): uploads at an offset, a
     chunk of two signals on blockIdx.y, and a last chunk of one."""
     from hsc_amd.modeling import ConvolutionalNMF
     B, K, W, F, T, iters = 5, 9, 33, 2, 300, 2
