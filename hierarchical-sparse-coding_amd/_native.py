@@ -25,9 +25,9 @@ METHOD_CMP, METHOD_LOCOMP = 0, 1
 
 # every symbol include/hscmp.h declares (checked by tests/test_abi.py)
 EXPORTS = ['hscmp_version', 'hscmp_create', 'hscmp_destroy', 'hscmp_last_error', 'hscmp_set_stream', 'hscmp_set_method',
-           'hscmp_synchronize', 'hscmp_set_dictionary', 'hscmp_convolve1d', 'hscmp_select_best_atoms',
+           'hscmp_synchronize', 'hscmp_set_dictionary', 'hscmp_set_dictionaries', 'hscmp_convolve1d', 'hscmp_select_best_atoms',
            'hscmp_update_inner_products', 'hscmp_table_open', 'hscmp_table_select', 'hscmp_table_update', 'hscmp_table_read', 'hscmp_assign_windows', 'hscmp_host_overlap_add', 'hscmp_host_slots_to_csc', 'hscmp_hierarchy_epilogue', 'hscmp_encode_batch',
-           'hscmp_encode_batch_device', 'hscmp_encode_batch_ragged', 'hscmp_encode_batch_ragged_device', 'hscmp_encode_batch_from_level', 'hscmp_load_level', 'hscmp_load_level_ragged', 'hscmp_continue', 'hscmp_grow_events', 'hscmp_mem_info', 'hscmp_copy_from_device', 'hscmp_stop_signal', 'hscmp_fetch_events',
+           'hscmp_encode_batch_device', 'hscmp_encode_batch_ragged', 'hscmp_encode_batch_ragged_device', 'hscmp_encode_batch_multi', 'hscmp_encode_batch_from_level', 'hscmp_load_level', 'hscmp_load_level_ragged', 'hscmp_continue', 'hscmp_grow_events', 'hscmp_mem_info', 'hscmp_copy_from_device', 'hscmp_stop_signal', 'hscmp_fetch_events',
            'hscmp_fetch_stats', 'hscmp_fetch_residual', 'hscmp_fetch_energies', 'hscmp_fetch_slots',
            'hscmp_get_device_view', 'hscmp_last_kernel_ms', 'hscmp_last_variant', 'hscmp_wide_plan', 'hscmp_wide_counters']
 
@@ -93,6 +93,7 @@ def load_library():
     lib.hscmp_set_method.argtypes = [vp, ci]
     lib.hscmp_synchronize.argtypes = [vp]
     lib.hscmp_set_dictionary.argtypes = [vp, vp, ci, ci, ci, ci, vp]
+    lib.hscmp_set_dictionaries.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp]
     lib.hscmp_convolve1d.argtypes = [vp, vp, ci, ci, vp]
     lib.hscmp_select_best_atoms.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ctypes.c_double, vp, vp, vp, vp, ci,
                                             ctypes.POINTER(ctypes.c_int32)]
@@ -109,6 +110,7 @@ def load_library():
     lib.hscmp_encode_batch_device.argtypes = [vp, vp, ci, ci, ctypes.POINTER(HscmpParams)]
     lib.hscmp_encode_batch_ragged.argtypes = [vp, vp, ci, ci, vp, ctypes.POINTER(HscmpParams)]
     lib.hscmp_encode_batch_ragged_device.argtypes = [vp, vp, ci, ci, vp, ctypes.POINTER(HscmpParams)]
+    lib.hscmp_encode_batch_multi.argtypes = [vp, vp, ci, ci, vp, ctypes.POINTER(HscmpParams)]
     lib.hscmp_encode_batch_from_level.argtypes = [vp, vp, ci, ci, ctypes.c_double, ctypes.POINTER(HscmpParams)]
     lib.hscmp_load_level.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp]
     lib.hscmp_load_level_ragged.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp]
@@ -350,6 +352,23 @@ class Engine(object):
         #  handle that outlived that must fail loudly instead of reading a table of another dictionary)
         self._table_generation = getattr(self, '_table_generation', 0) + 1
 
+    def set_dictionaries(self, Ds, weights=None):
+        """A set of G dictionaries (hscmp_set_dictionaries) for encode_batch_multi: Ds [G,K,W] or [G,K,W,F] float32/float64
+        (or a sequence of G arrays of one shape and dtype); weights [G,K] or None.  Always uploaded: the set replaces the
+        engine's dictionary, and only encode_batch_multi encodes with it until set_dictionary puts a plain one back."""
+        D4 = stack_dictionaries(Ds)
+        G, K, W, F = D4.shape
+        code = dtype_code(D4.dtype)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=D4.dtype)
+        if w is not None and w.shape != (G, K):
+            raise ValueError('weights must be [G,K] = (%d, %d): one entry per atom of every dictionary (got %s)' % (G, K, w.shape))
+        # (a failed call leaves the context without a dictionary and without a batch: say the same here first)
+        self._dict_key = self._src_key = None
+        self.dtype = self.K = self.W = self.F = self.G = self._batch = None
+        self._check(self._lib.hscmp_set_dictionaries(self._h, _ptr(D4), G, K, W, F, code, _ptr(w)), 'hscmp_set_dictionaries')
+        self.dtype, self.K, self.W, self.F, self.G = D4.dtype, K, W, F, G
+        self._table_generation = getattr(self, '_table_generation', 0) + 1
+
     def convolve1d(self, x, same):
         x2 = np.ascontiguousarray(x.reshape((x.shape[0], -1)), dtype=self.dtype)
         assert x2.shape[1] == self.F
@@ -471,6 +490,18 @@ class Engine(object):
         self._check(self._lib.hscmp_encode_batch_ragged_device(self._h, ctypes.c_void_p(x_dev_ptr), int(B), int(T), _ptr(lens),
                                                                ctypes.byref(params)), 'hscmp_encode_batch_ragged_device')
         self._batch = (int(B), int(T), int(params.max_events))
+
+    def encode_batch_multi(self, x, dict_of, params):
+        """x [B,T,F] host array of the dictionary dtype, dict_of int [B]: signal b is encoded with dictionary dict_of[b] of the
+        set (set_dictionaries), as encode_batch would encode it alone with that dictionary."""
+        x3 = np.ascontiguousarray(x, dtype=self.dtype)
+        assert x3.ndim == 3 and x3.shape[2] == self.F
+        B, T = x3.shape[0], x3.shape[1]
+        of = np.ascontiguousarray(dict_of, dtype=np.int32)
+        assert of.shape == (B,)
+        self._batch = None                       # (a failure leaves the context without one)
+        self._check(self._lib.hscmp_encode_batch_multi(self._h, _ptr(x3), B, T, _ptr(of), ctypes.byref(params)), 'hscmp_encode_batch_multi')
+        self._batch = (B, T, int(params.max_events))
 
     def encode_batch_from_level(self, prev, first, count, minCoefficients, params):
         """Hierarchical level chaining on the device (modeling.py:1489): the coefficient slots of signals
@@ -641,6 +672,33 @@ class Engine(object):
         return self._lib.hscmp_last_variant(self._h).decode()
 
 
+def stack_dictionaries(Ds):
+    """The G dictionaries of a set as one C-ordered [G,K,W,F] array: `Ds` [G,K,W] / [G,K,W,F], or a sequence of G arrays
+    [K,W] / [K,W,F] that must agree in shape and dtype (ValueError otherwise)."""
+    if isinstance(Ds, (list, tuple)):
+        parts = [np.asarray(d) for d in Ds]
+        if len(parts) == 0:
+            raise ValueError('a set of dictionaries needs at least one dictionary')
+        for g, d in enumerate(parts):
+            if d.shape != parts[0].shape:
+                raise ValueError('dictionary %d has shape %s, dictionary 0 has %s: the dictionaries of a set share one shape' % (
+                    g, d.shape, parts[0].shape))
+            if d.dtype != parts[0].dtype:
+                raise ValueError('dictionary %d has dtype %s, dictionary 0 has %s: the dictionaries of a set share one dtype' % (
+                    g, d.dtype, parts[0].dtype))
+        if parts[0].ndim not in (2, 3):
+            raise ValueError('a dictionary must be [K,W] or [K,W,F] (got %d dimensions)' % parts[0].ndim)
+        Ds = np.stack(parts)
+    else:
+        Ds = np.asarray(Ds)
+        if Ds.ndim not in (3, 4):
+            raise ValueError('the dictionaries must be [G,K,W] or [G,K,W,F] (got %d dimensions)' % Ds.ndim)
+    if Ds.shape[0] == 0:
+        raise ValueError('a set of dictionaries needs at least one dictionary')
+    dtype_code(Ds.dtype)
+    return np.ascontiguousarray(Ds.reshape((Ds.shape[0], Ds.shape[1], Ds.shape[2], -1)))
+
+
 def pack_level(matrices, T, K):
     """The arguments of hscmp_load_level from B scipy.sparse matrices [T, K]: (offsets int64 [B + 1], rows int32, cols int32,
     data float64, cap) -- every matrix as canonical CSC (tocsc, duplicates summed, explicit zeros dropped, row indices
@@ -714,6 +772,15 @@ def default_engine(device=0):
     program gets its own -- the coders of hsc_amd.modeling can then run side by side in a thread pool (the ctypes calls
     release the interpreter lock; the contexts use separate HIP streams).  The dictionary is re-uploaded when it changes."""
     table = _engines.__dict__.setdefault('by_device', {})
+    if device not in table:
+        table[device] = Engine(device)
+    return table[device]
+
+
+def multi_engine(device=0):
+    """The engine of this (thread, device) that holds SETS of dictionaries (Engine.set_dictionaries / encode_batch_multi): one of
+    its own, so that a set never takes the place of a dictionary that default_engine or engine_for keep resident."""
+    table = _engines.__dict__.setdefault('multi', {})
     if device not in table:
         table[device] = Engine(device)
     return table[device]

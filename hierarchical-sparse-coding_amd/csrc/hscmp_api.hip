@@ -156,12 +156,16 @@ struct EncodePlan {
     bool init_only = false;   // HSCMP_INIT_ONLY (tests): stop behind the initial correlation
     bool bound_loop = false;  // the four-signal loop re-correlates as upper bounds (MfmaRecorr BOUND)
     bool ragged = false;      // signals of different lengths: the RAGGED instances of the loops read each signal's geometry
+    bool multi = false;       // a dictionary per signal out of a set: the MULTI instances of the generic pair read it through dict_of
     Knobs knobs{};            // the encode's snapshot: the launches read pairing, row bitmaps and LDS pad from it
 };
 
 // The dictionary and everything derived from it: replaced as a whole by hscmp_set_dictionary (dtype < 0: none set).
 struct Dictionary {
     int K = 0, W = 0, F = 0, dtype = -1;
+    int G = 0;                // 0: one dictionary (hscmp_set_dictionary); >= 1: a set of G (hscmp_set_dictionaries): D, Dc and w hold G of
+                              // them at strides K*W*F, K*W*F and K, none of the images below is built, and only
+                              // hscmp_encode_batch_multi encodes with it
     DevBuf D;
     DevBuf w;                 // empty when no weights
     DevBuf Dfrag;             // MFMA fragment-ordered copy (F == 1)
@@ -184,6 +188,7 @@ struct Workspace {
     DevBuf head;              // [B][T] slot chains by position (round-parallel loop)
     DevBuf lgram;             // [B][kLgramDoubles] LoCOMP: Gram matrices beyond the LDS copy
     DevBuf geom;              // [B][kGeomWords] of a ragged batch
+    DevBuf dict_of;           // [B] the dictionary of every signal (hscmp_encode_batch_multi)
     DevBuf wide;              // control blocks and candidate arrays of the wide loop (hscmp_wide.h: wide_scratch_bytes)
 };
 
@@ -257,6 +262,12 @@ static int fail(hscmp_ctx* ctx, int code, const char* fmt, ...)
     if (ctx) ctx->err = buf; else g_err = buf;
     return code;
 }
+
+// A context that holds a set of dictionaries (hscmp_set_dictionaries) encodes through hscmp_encode_batch_multi alone: every other
+// entry point that reads the dictionary answers this before it queues anything.
+#define NOT_A_SET(ctx, who)                                                                     \
+    if ((ctx)->dict.G > 0)                                                                      \
+        return fail(ctx, HSCMP_ERR_STATE, "%s: the context holds a set of %d dictionaries (hscmp_set_dictionaries): only hscmp_encode_batch_multi encodes with it", who, (ctx)->dict.G);
 
 #define HIP_TRY(ctx, expr)                                                                      \
     do {                                                                                        \
@@ -468,6 +479,47 @@ extern "C" int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W,
     return HSCMP_OK;
 }
 
+// A set of G dictionaries of one shape: what the generic kernels read -- D, the chain-ordered copy Dc
+// (F > 1) and the weights -- dictionary after dictionary at a fixed stride, and none of the images of hscmp_set_dictionary.
+extern "C" int hscmp_set_dictionaries(hscmp_ctx* ctx, const void* D, int G, int K, int W, int F, hscmp_dtype dtype, const void* weights)
+{
+    if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_set_dictionaries: ctx is NULL");
+    if (!D || G <= 0 || K <= 0 || W <= 0 || F <= 0)
+        return fail(ctx, HSCMP_ERR_INVALID, "hscmp_set_dictionaries: bad shape G=%d K=%d W=%d F=%d", G, K, W, F);
+    if (dtype != HSCMP_F32 && dtype != HSCMP_F64) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_set_dictionaries: bad dtype %d", (int)dtype);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    (void)read_knobs();                         // (arms HSCMP_ALLOC_FAIL_AT)
+    // as hscmp_set_dictionary: the old dictionary, the batch and the table first; the set is built aside and moved in whole
+    drop_batch(ctx, true);
+    ctx->dict = Dictionary{};
+    Dictionary d;
+    d.K = K; d.W = W; d.F = F; d.dtype = dtype; d.G = G;
+    const size_t es = esize(dtype), n1 = (size_t)K * W * F, nD = (size_t)G * n1 * es;
+    int rc;
+    if ((rc = upload(ctx, d.D, D, nD))) return rc;
+    // all-ones weights count as no weights only when EVERY dictionary's are: one weighted dictionary makes the set weighted
+    // (|c * 1| == |c| bit for bit, so the all-ones dictionaries of a weighted set select as they would alone)
+    if (weights) {
+        bool all_one = true;
+        for (size_t i = 0; i < (size_t)G * K && all_one; ++i)
+            all_one = dtype == HSCMP_F32 ? ((const float*)weights)[i] == 1.0f : ((const double*)weights)[i] == 1.0;
+        if (all_one) weights = nullptr;
+    }
+    if (weights && (rc = upload(ctx, d.w, weights, (size_t)G * K * es))) return rc;
+    if (F > 1) {
+        // Dc[g][k][f][w] = D[g][k][w][f]: consecutive addresses along the pinned chain (f outer, w inner)
+        std::vector<char> dc(nD);
+        for (size_t gk = 0; gk < (size_t)G * K; ++gk)
+            for (int w = 0; w < W; ++w)
+                for (int f = 0; f < F; ++f)
+                    memcpy(&dc[((gk * F + f) * W + w) * es], (const char*)D + ((gk * W + w) * F + f) * es, es);
+        if ((rc = upload(ctx, d.Dc, dc.data(), nD))) return rc;
+    }
+    ctx->dict = std::move(d);
+    return HSCMP_OK;
+}
+
 // geometry given explicitly (the row-level selection runs on a caller's table of any K, W: the context's dictionary is
 // not involved and is not touched)
 static int make_params_g(hscmp_ctx* ctx, const Knobs& kn, int K, int W, int F, int B, int T, const hscmp_params* p, DevParams* out)
@@ -573,8 +625,8 @@ static int ensure_workspace(hscmp_ctx* ctx, const DevParams& P, bool need_x, boo
     return ensure_workspace_g(ctx, P, need_x, esize(ctx->dict.dtype), ctx->dict.F > 1, row_lists, geom_bytes);
 }
 
-// ragged: of the batch being encoded or resumed (its plan says so), not of the one the context may still hold
-template <typename R> static State<R> make_state(hscmp_ctx* c, bool ragged)
+// ragged, multi: of the batch being encoded or resumed (its plan says so), not of the one the context may still hold
+template <typename R> static State<R> make_state(hscmp_ctx* c, bool ragged, bool multi = false)
 {
     State<R> S;
     S.D = c->dict.D.as<const R>(); S.weights = c->dict.w.as<const R>();
@@ -586,6 +638,7 @@ template <typename R> static State<R> make_state(hscmp_ctx* c, bool ragged)
     S.sel_t = c->ws.sel_t.as<int>(); S.sel_k = c->ws.sel_k.as<int>(); S.sel_c = c->ws.sel_c.as<R>();
     S.stats = c->ws.stats.as<int>(); S.energy = c->ws.energy.as<R>(); S.edge = c->ws.edge.as<unsigned long long>();
     S.geom = ragged ? c->ws.geom.as<int>() : nullptr;
+    S.dict_of = multi ? c->ws.dict_of.as<int>() : nullptr;
     return S;
 }
 
@@ -613,13 +666,13 @@ template <typename Pol> static size_t policy_lds_bytes(const DevParams& P0, cons
 
 // The loop of policy Pol (iterate_kernel), `signals_per_wg` signals per workgroup.  dry: only tell whether its LDS fits (kLdsLoop),
 // queue nothing.  0: launched (or fits); -1: it cannot run this shape.
-template <typename R, typename Pol, bool RAGGED = false>
+template <typename R, typename Pol, bool RAGGED = false, bool MULTI = false>
 static int launch_policy(hscmp_ctx* ctx, const DevParams& P0, const typename Pol::Args& A, int signals_per_wg, bool dry)
 {
     DevParams P = P0;
     set_segments(P, Pol::kMaxSegments);
-    return launch_tile_kernel(iterate_kernel<R, Pol, RAGGED>, dim3((P.B + signals_per_wg - 1) / signals_per_wg), dim3(signals_per_wg * kThreads),
-                              Pol::total_lds_bytes(P, A), kLdsLoop, 0, dry, ctx->stream, P, make_state<R>(ctx, RAGGED), A);
+    return launch_tile_kernel(iterate_kernel<R, Pol, RAGGED, MULTI>, dim3((P.B + signals_per_wg - 1) / signals_per_wg), dim3(signals_per_wg * kThreads),
+                              Pol::total_lds_bytes(P, A), kLdsLoop, 0, dry, ctx->stream, P, make_state<R>(ctx, RAGGED, MULTI), A);
 }
 
 // LoCOMP with the re-correlations on the matrix cores (LocompMfma: single-feature float32 with a dictionary image), `group`
@@ -757,6 +810,7 @@ static std::string variant_of(const EncodePlan& plan)
     else if (plan.rp) v += "_rp";
     else if (plan.loop == EncodePlan::kLoopMfma && plan.group > 1) v += "_x" + std::to_string(plan.group);
     if (plan.ragged) v += "_ragged";
+    if (plan.multi) v += "_multi";
     return v;
 }
 
@@ -789,8 +843,12 @@ template <typename R> static int launch_init(hscmp_ctx* ctx, const EncodePlan& p
     }
     case EncodePlan::kInitOwn: break;
     case EncodePlan::kInitGeneric:
-        hipLaunchKernelGGL((corr_init_generic_kernel<R, false>), dim3((P.T + kThreads - 1) / kThreads, P.B), dim3(kThreads), 0, ctx->stream,
-                           P, S, ctx->ws.resid.as<const R>(), P.off, P.T, (R*)nullptr);
+        if (plan.multi)
+            hipLaunchKernelGGL((corr_init_generic_kernel<R, false, true>), dim3((P.T + kThreads - 1) / kThreads, P.B), dim3(kThreads), 0, ctx->stream,
+                               P, make_state<R>(ctx, false, true), ctx->ws.resid.as<const R>(), P.off, P.T, (R*)nullptr);
+        else
+            hipLaunchKernelGGL((corr_init_generic_kernel<R, false>), dim3((P.T + kThreads - 1) / kThreads, P.B), dim3(kThreads), 0, ctx->stream,
+                               P, S, ctx->ws.resid.as<const R>(), P.off, P.T, (R*)nullptr);
         break;
     }
     if (rc != 0) return fail(ctx, HSCMP_ERR_HIP, "the initial correlation of %s could not be launched", variant_of(plan).c_str());
@@ -855,9 +913,13 @@ template <typename R> static int launch_loop(hscmp_ctx* ctx, const EncodePlan& p
                              : launch_policy<R, SparseRecorr<R, false>>(ctx, P, sparse_args<R>(ctx, plan, P.T), 1, false);
         break;
     case EncodePlan::kLoopGeneric:
-        rc = plan.ragged ? launch_policy<R, GenericRecorr<R>, true>(ctx, P, {}, 1, false) : launch_policy<R, GenericRecorr<R>>(ctx, P, {}, 1, false);
+        rc = plan.multi    ? launch_policy<R, GenericRecorr<R>, false, true>(ctx, P, {}, 1, false)
+             : plan.ragged ? launch_policy<R, GenericRecorr<R>, true>(ctx, P, {}, 1, false)
+                           : launch_policy<R, GenericRecorr<R>>(ctx, P, {}, 1, false);
         break;
-    case EncodePlan::kLoopLocomp: rc = launch_policy<R, LocompRecorr<R>>(ctx, P, {}, 1, false); break;
+    case EncodePlan::kLoopLocomp:
+        rc = plan.multi ? launch_policy<R, LocompRecorr<R>, false, true>(ctx, P, {}, 1, false) : launch_policy<R, LocompRecorr<R>>(ctx, P, {}, 1, false);
+        break;
     case EncodePlan::kLoopLocompSparse: rc = launch_policy<R, LocompSparse<R>>(ctx, P, sparse_args<R>(ctx, plan, P.T), 1, false); break;
     case EncodePlan::kLoopLocompMfma:
         if constexpr (sizeof(R) == 4) rc = launch_locomp_mfma(ctx, P, plan.group, false);
@@ -956,6 +1018,7 @@ static int encode_common(hscmp_ctx* ctx, const void* x, bool host, int B, int T,
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "%s: ctx is NULL", who);
     if (ctx->dict.dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "%s: no dictionary set", who);
+    NOT_A_SET(ctx, who);
     if (!x || !params || B <= 0 || T <= 0) return fail(ctx, HSCMP_ERR_INVALID, "%s: bad arguments (B=%d T=%d)", who, B, T);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const Knobs kn = read_knobs();
@@ -1000,9 +1063,62 @@ extern "C" int hscmp_encode_batch_device(hscmp_ctx* ctx, const void* x_dev, int 
     return encode_common(ctx, x_dev, false, B, T, params);
 }
 
+// A batch encoded with a dictionary per signal out of the context's set: the generic pair alone -- prepare,
+// the generic initial correlation and the generic loop (CMP) or the dense LoCOMP loop, in their MULTI instances -- so there is
+// nothing to choose and the plan is written down here.  Signal b comes out as hscmp_encode_batch would return it alone on a context
+// whose dictionary is dictionary dict_of[b].
+template <typename R> static int multi_loop_fits(hscmp_ctx* ctx, const EncodePlan& plan, const DevParams& P)
+{
+    return plan.loop == EncodePlan::kLoopLocomp ? launch_policy<R, LocompRecorr<R>, false, true>(ctx, P, {}, 1, true)
+                                                : launch_policy<R, GenericRecorr<R>, false, true>(ctx, P, {}, 1, true);
+}
+
+extern "C" int hscmp_encode_batch_multi(hscmp_ctx* ctx, const void* x, int B, int T, const int32_t* dict_of, const hscmp_params* params)
+{
+    const char* who = "hscmp_encode_batch_multi";
+    if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "%s: ctx is NULL", who);
+    if (ctx->dict.dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "%s: no dictionary set", who);
+    if (ctx->dict.G <= 0)
+        return fail(ctx, HSCMP_ERR_STATE, "%s: the context holds one dictionary (hscmp_set_dictionary), not a set (hscmp_set_dictionaries)", who);
+    if (!x || !params || !dict_of || B <= 0 || T <= 0) return fail(ctx, HSCMP_ERR_INVALID, "%s: bad arguments (B=%d T=%d)", who, B, T);
+    for (int b = 0; b < B; ++b)
+        if (dict_of[b] < 0 || dict_of[b] >= ctx->dict.G)
+            return fail(ctx, HSCMP_ERR_INVALID, "%s: signal %d asks for dictionary %d outside [0, G=%d)", who, b, (int)dict_of[b], ctx->dict.G);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const Knobs kn = read_knobs();
+    DevParams P;
+    int rc = make_params(ctx, kn, B, T, params, &P);
+    if (rc) return rc;
+    const bool f64 = ctx->dict.dtype == HSCMP_F64;
+    EncodePlan plan;
+    plan.knobs = kn;
+    plan.f64 = f64;
+    plan.multi = true;
+    plan.init = EncodePlan::kInitGeneric;
+    plan.loop = ctx->method == HSCMP_METHOD_LOCOMP ? EncodePlan::kLoopLocomp : EncodePlan::kLoopGeneric;
+    if ((f64 ? multi_loop_fits<double>(ctx, plan, P) : multi_loop_fits<float>(ctx, plan, P)) != 0)
+        return fail(ctx, HSCMP_ERR_UNSUPPORTED, "%s: the loop of %s does not fit this shape", who, variant_of(plan).c_str());
+    drop_batch(ctx);
+    // (no sparsity-aware kernel runs: none of their buffers is asked for)
+    if ((rc = ensure_workspace_g(ctx, P, true, esize(ctx->dict.dtype), false, false))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));         // (the previous batch's kernels may still read the old dict_of)
+    const size_t dbytes = (size_t)B * sizeof(int);
+    const hipError_t e = ctx->ws.dict_of.replace(dbytes);
+    if (e != hipSuccess) return alloc_failed(ctx, dbytes, e);
+    HIP_TRY(ctx, hipMemcpy(ctx->ws.dict_of.p, dict_of, dbytes, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ws.x.p, x, (size_t)B * T * ctx->dict.F * esize(ctx->dict.dtype), hipMemcpyHostToDevice, ctx->stream));
+    ctx->listed_rows = 0;                       // the residual buffer is overwritten with a dense input
+    rc = f64 ? run_encode<double>(ctx, plan, P, ctx->ws.x.p) : run_encode<float>(ctx, plan, P, ctx->ws.x.p);
+    if (rc) return rc;
+    commit_batch(ctx, plan, P, *params, ctx->ws.x.p, std::vector<int>());     // (plan.multi and ws.dict_of stay: hscmp_continue resumes with them)
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return HSCMP_OK;
+}
+
 static int encode_ragged(hscmp_ctx* ctx, const void* x, bool host, int B, int T, const int32_t* lengths, const hscmp_params* params, const char* who)
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "%s: ctx is NULL", who);
+    NOT_A_SET(ctx, who);
     if (B < 1) return fail(ctx, HSCMP_ERR_INVALID, "%s: B=%d, at least one signal is needed", who, B);
     if (!lengths) return fail(ctx, HSCMP_ERR_INVALID, "%s: lengths is NULL", who);
     if (ctx->method == HSCMP_METHOD_LOCOMP) return fail(ctx, HSCMP_ERR_UNSUPPORTED, "%s: the LoCOMP loop has no ragged form", who);
@@ -1023,6 +1139,8 @@ extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, in
                                              const hscmp_params* params)
 {
     if (!ctx || !prev) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: NULL context");
+    NOT_A_SET(ctx, "hscmp_encode_batch_from_level");
+    if (prev->dict.G > 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_encode_batch_from_level: the previous level holds a set of dictionaries (hscmp_set_dictionaries)");
     if (ctx->dict.dtype != HSCMP_F64) return fail(ctx, HSCMP_ERR_STATE, "hscmp_encode_batch_from_level: the level dictionary must be float64");
     if (!prev->have_batch) return fail(ctx, HSCMP_ERR_STATE, "hscmp_encode_batch_from_level: the previous level has no results");
     if (ctx->device != prev->device) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: contexts on different GPUs");
@@ -1104,6 +1222,7 @@ static int load_level_common(hscmp_ctx* ctx, const void* x, int B, int T, const 
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "%s: ctx is NULL", who);
     if (ctx->dict.dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "%s: no dictionary set", who);
+    NOT_A_SET(ctx, who);
     if (B <= 0 || T <= 0 || !offsets) return fail(ctx, HSCMP_ERR_INVALID, "%s: bad arguments (B=%d T=%d)", who, B, T);
     if (lengths)
         for (int b = 0; b < B; ++b)
@@ -1446,6 +1565,7 @@ extern "C" int hscmp_convolve1d(hscmp_ctx* ctx, const void* x, int T, int same, 
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_convolve1d: ctx is NULL");
     if (ctx->dict.dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_convolve1d: no dictionary set");
+    NOT_A_SET(ctx, "hscmp_convolve1d");
     if (!x || !out || T <= 0) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_convolve1d: bad arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     (void)read_knobs();
@@ -1480,6 +1600,7 @@ extern "C" int hscmp_assign_windows(hscmp_ctx* ctx, const void* windows, int N, 
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_assign_windows: ctx is NULL");
     if (ctx->dict.dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_assign_windows: no dictionary set");
+    NOT_A_SET(ctx, "hscmp_assign_windows");
     if (!windows || !out_t || !out_k || N <= 0) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_assign_windows: bad arguments");
     if (L < ctx->dict.W) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_assign_windows: windows of %d samples are shorter than the filters (W=%d)", L, ctx->dict.W);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1566,6 +1687,8 @@ extern "C" int hscmp_hierarchy_epilogue(hscmp_ctx* last, hscmp_ctx* level0, int 
                                         double* out_residual_energy)
 {
     if (!last || !level0) return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: NULL context");
+    NOT_A_SET(last, "hscmp_hierarchy_epilogue");
+    if (level0->dict.G > 0) return fail(last, HSCMP_ERR_STATE, "hscmp_hierarchy_epilogue: level 0 holds a set of dictionaries (hscmp_set_dictionaries)");
     if (!last->have_batch || !level0->have_batch) return fail(last, HSCMP_ERR_STATE, "hscmp_hierarchy_epilogue: no batch encoded");
     NOT_LOADED(last, "hscmp_hierarchy_epilogue (last level)");
     if (last->device != level0->device) return fail(last, HSCMP_ERR_INVALID, "hscmp_hierarchy_epilogue: contexts on different GPUs");
@@ -1811,6 +1934,7 @@ extern "C" int hscmp_update_inner_products(hscmp_ctx* ctx, void* ip, const void*
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_update_inner_products: ctx is NULL");
     if (ctx->dict.dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_update_inner_products: no dictionary set");
+    NOT_A_SET(ctx, "hscmp_update_inner_products");
     if (!ip || !residual || T <= 0) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_update_inner_products: bad arguments");
     if (p < 0 || p >= T) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_update_inner_products: atom centre %d outside the signal [0, %d)", p, T);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1856,6 +1980,7 @@ extern "C" int hscmp_table_open(hscmp_ctx* ctx, const void* x, int T)
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_table_open: ctx is NULL");
     if (ctx->dict.dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_table_open: no dictionary set");
+    NOT_A_SET(ctx, "hscmp_table_open");
     if (!x || T <= 0) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_table_open: bad arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     (void)read_knobs();
@@ -1867,6 +1992,7 @@ extern "C" int hscmp_table_select(hscmp_ctx* ctx, int nb_blocks, int offset, dou
                                   int32_t* out_t, int32_t* out_k, void* out_c, int max_out, int32_t* n_out)
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_table_select: ctx is NULL");
+    NOT_A_SET(ctx, "hscmp_table_select");
     if (ctx->tab_T <= 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_table_select: no table open (hscmp_table_open)");
     if (!out_t || !out_k || !out_c || !n_out) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_table_select: bad arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1887,6 +2013,7 @@ extern "C" int hscmp_table_select(hscmp_ctx* ctx, int nb_blocks, int offset, dou
 extern "C" int hscmp_table_update(hscmp_ctx* ctx, const void* residual_samples, int start, int count, const int32_t* centres, int ncentres)
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_table_update: ctx is NULL");
+    NOT_A_SET(ctx, "hscmp_table_update");
     if (ctx->tab_T <= 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_table_update: no table open (hscmp_table_open)");
     const int T = ctx->tab_T;
     if (count < 0 || start < 0 || start + count > T || (count > 0 && !residual_samples) || ncentres < 0 || (ncentres > 0 && !centres))
@@ -1914,6 +2041,7 @@ extern "C" int hscmp_table_update(hscmp_ctx* ctx, const void* residual_samples, 
 extern "C" int hscmp_table_read(hscmp_ctx* ctx, void* out_table, void* out_residual)
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "hscmp_table_read: ctx is NULL");
+    NOT_A_SET(ctx, "hscmp_table_read");
     if (ctx->tab_T <= 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_table_read: no table open (hscmp_table_open)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t es = esize(ctx->dict.dtype);

@@ -333,6 +333,7 @@ template <typename R> struct State {
     int* head;          // [B][T] round-parallel loop: most recent coefficient slot at position t (-1: none), chained through hval
     double* lgram;      // [B][lgram_doubles(lg_cap)] LoCOMP: what a group keeps beyond its LDS copy (nullptr: other methods)
     const int* geom;    // [B][kGeomWords] ragged batches: the signal's own length and block geometry; nullptr: uniform
+    const int* dict_of; // [B] a set of dictionaries: the dictionary of signal b; nullptr: one dictionary
 };
 
 // Ragged batches: every per-signal array keeps the stride of the longest length P.T, and a signal's rows t >= T_b are dead --
@@ -351,6 +352,24 @@ template <bool RAGGED, typename R> __device__ __forceinline__ DevParams signal_p
         Q.bs = __builtin_amdgcn_readfirstlane(g[1]);
         Q.nbk = __builtin_amdgcn_readfirstlane(g[2]);
         Q.nseg = (Q.T + P.seg - 1) >> P.seg_shift;
+        return Q;
+    }
+}
+// A set of dictionaries (hscmp_set_dictionaries): D, Dc and the weights of dictionary g lie g strides behind
+// those of dictionary 0 (K*W*F and K elements), and signal b takes dictionary dict_of[b].  The kernels that work on one signal read
+// the dictionary through signal_state: MULTI = false returns S itself (the copy folds away, as in signal_params), so the loops of
+// a context with one dictionary compile to the code they were before.
+template <bool MULTI, typename R> __device__ __forceinline__ State<R> signal_state(const DevParams& P, const State<R>& S, int b)
+{
+    if constexpr (!MULTI) {
+        return S;
+    } else {
+        State<R> Q = S;
+        const int64_t g = __builtin_amdgcn_readfirstlane(S.dict_of[b]);
+        const int64_t n = (int64_t)P.K * P.W * P.F;
+        Q.D = S.D + g * n;
+        Q.Dc = S.Dc + g * n;
+        if (S.weights) Q.weights = S.weights + g * P.K;
         return Q;
     }
 }

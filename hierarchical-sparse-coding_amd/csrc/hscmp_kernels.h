@@ -269,11 +269,13 @@ __global__ __launch_bounds__(kThreads) void prepare_from_slots_sorted_kernel(Dev
 //   grid = (ceil(Tout/kThreads), B), block = kThreads
 //   TABLE = false: write per-position best (best_c, best_k);  TABLE = true: write out[Tout][K]
 // ------------------------------------------------------------------------------------------------
-template <typename R, bool TABLE>
-__global__ __launch_bounds__(kThreads) void corr_init_generic_kernel(DevParams P, State<R> S, const R* __restrict__ src,
+//   MULTI: signal b against dictionary dict_of[b] of a set (signal_state)
+template <typename R, bool TABLE, bool MULTI = false>
+__global__ __launch_bounds__(kThreads) void corr_init_generic_kernel(DevParams P, State<R> SB, const R* __restrict__ src,
                                                                       int lead, int Tout, R* __restrict__ table)
 {
     const int b = blockIdx.y;
+    const State<R> S = signal_state<MULTI>(P, SB, b);
     const int t = blockIdx.x * kThreads + threadIdx.x;
     if (t >= Tout) return;
     if (!TABLE && t >= signal_length(P, S, b)) return;      // (a dead row of a ragged batch: left as it is)
@@ -1095,21 +1097,24 @@ __device__ __forceinline__ void locomp_precompute(const DevParams& P, const Stat
                                                   const int* ord_t, const int* ord_k, const R* ord_c, int first, int count, LocompPre<R>& pre,
                                                   LocompRows& rows, SY& sy);
 
-template <typename R, typename Recorr, bool RAGGED = false>
-__global__ __launch_bounds__(kThreads * Recorr::kGroup, Recorr::kMinWavesPerSimd) void iterate_kernel(DevParams PB, State<R> S, typename Recorr::Args A)
+template <typename R, typename Recorr, bool RAGGED = false, bool MULTI = false>
+__global__ __launch_bounds__(kThreads * Recorr::kGroup, Recorr::kMinWavesPerSimd) void iterate_kernel(DevParams PB, State<R> SB, typename Recorr::Args A)
 {
+    static_assert(!MULTI || Recorr::kGroup == 1, "a dictionary per signal: one signal per workgroup");
     // all LDS comes from ONE dynamic array (16-byte aligned base): per signal the control block first, then the
     // policy's region (dictionary image, residual window); a policy with kGroup > 1 keeps what the signals share
     // in front of the per-signal regions
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using SH = typename Recorr::Shared;
     constexpr int GS = Recorr::kGroup;
-    Recorr::prologue_shared(PB, S, A, smem);             // (kGroup > 1: the shared image, behind a hardware barrier)
+    Recorr::prologue_shared(PB, SB, A, smem);            // (kGroup > 1: the shared image, behind a hardware barrier)
     // (wave-uniform by construction; readfirstlane tells the compiler, so the per-signal pointers live in SGPRs)
     const int b = GS == 1 ? (int)blockIdx.x : (int)blockIdx.x * GS + gsig();
     if (GS > 1 && b >= PB.B) return;                     // (a ragged last workgroup; no hardware barrier from here on)
     // PB: the batch (strides, LDS layout); P: this signal (its own length and blocks in a ragged batch)
-    const DevParams P = signal_params<RAGGED>(PB, S, b);
+    const DevParams P = signal_params<RAGGED>(PB, SB, b);
+    // SB: the batch; S: this signal's view of it (its own dictionary and weights out of a set)
+    const State<R> S = signal_state<MULTI>(PB, SB, b);
     char* sbase = smem + Recorr::signal_lds_offset(PB, A);
     SH& sh = *reinterpret_cast<SH*>(sbase);
     char* plds = sbase + ((sizeof(SH) + 15) / 16) * 16;

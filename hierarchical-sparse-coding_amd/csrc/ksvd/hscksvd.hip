@@ -10,6 +10,8 @@
 //   plan 2: per atom, in stream order, ksvd_gather_kernel and ksvd_gram_kernel on grids over the occurrences / the
 //           Gram entries (and ksvd_centre_kernel for the PCA branch), then ksvd_tail_kernel on one workgroup.  No
 //           kernel waits for another workgroup: the order of the atoms is the order of the launches.
+// hscksvd_update_batch (B independent problems of one shape): ONE launch of ksvd_sweep_batch_kernel,
+// workgroup b running plan 1 on problem b over its own scratch; nothing is shared between two workgroups.
 // Per atom k with m occurrences:
 //   1. gather: one wave per patch (plan 1: wave w builds the patches i = w, w + 16, ...).  Lane l < W*F owns sample
 //      (s, f) = (l / F, l % F) at stacked row tau = g_i - (W-1)/2 + s, live when lo <= tau < hi.  For every other
@@ -318,9 +320,9 @@ __device__ __forceinline__ void atom_tail(const SweepArgs& a, int k, int o0, int
     __syncthreads();
 }
 
-__global__ __launch_bounds__(kThreads) void ksvd_sweep_kernel(SweepArgs a)
+// ---- plan 1: all atoms of one problem, one after the other, on the calling workgroup
+__device__ __forceinline__ void sweep_atoms(const SweepArgs& a, TailLds& lds)
 {
-    __shared__ TailLds lds;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = a.W * a.F;
     for (int k = 0; k < a.K; ++k) {
@@ -334,6 +336,33 @@ __global__ __launch_bounds__(kThreads) void ksvd_sweep_kernel(SweepArgs a)
         if (a.use_pca && m >= 2) centre_patches(a.P, m, n, lds.u, tid, kThreads);
         atom_tail<false>(a, k, o0, m, lds, tid);
     }
+}
+
+__global__ __launch_bounds__(kThreads) void ksvd_sweep_kernel(SweepArgs a)
+{
+    __shared__ TailLds lds;
+    sweep_atoms(a, lds);
+}
+
+// ---- hscksvd_update_batch: workgroup b runs plan 1 on problem b.  `a` describes problem 0; problem b's dictionary, column
+// pointers, occurrence pointers and stats lie b strides behind, its entries (rows, values, occurrence ids and spans: all relative
+// to its first entry) entry_off[b] behind, its patches patch_off[b] patches behind.  Nothing is shared between two workgroups.
+__global__ __launch_bounds__(kThreads) void ksvd_sweep_batch_kernel(SweepArgs a, const long long* __restrict__ entry_off,
+                                                                    const long long* __restrict__ patch_off)
+{
+    __shared__ TailLds lds;
+    const int b = blockIdx.x, n = a.W * a.F;
+    const long long e0 = entry_off[b];
+    a.D += (size_t)b * a.K * n;
+    a.indptr += (size_t)b * (a.K + 1);
+    a.occ_ptr += (size_t)b * (a.K + 1);
+    a.stats += (size_t)b * a.K * kStats;
+    a.rows += e0;
+    a.vals += e0;
+    a.occ += e0;
+    a.occ_span += e0;
+    a.P += (size_t)patch_off[b] * n;
+    sweep_atoms(a, lds);
 }
 
 // ---- plan 2: the phases of ONE atom as kernels of their own (the stats of an atom without occurrences are zeroed by the host)
@@ -512,6 +541,118 @@ extern "C" int hscksvd_update(hscksvd_ctx* ctx, int T, int K, int W, int F, doub
     const int32_t row_offsets[2] = {0, T};
     return run_update(ctx, "hscksvd_update", 1, row_offsets, K, W, F, D, indptr, indices, data, use_pca, kPlanOne,
                       out_atom_stats, timing_ms);
+}
+
+extern "C" int hscksvd_update_batch(hscksvd_ctx* ctx, int B, int T, int K, int W, int F, double* D, const int64_t* entry_offsets,
+                                    const int32_t* indptr, const int32_t* indices, double* data, int use_pca, double* out_atom_stats,
+                                    double* timing_ms)
+{
+    const char* fn = "hscksvd_update_batch";
+    if (!ctx) return fail(nullptr, HSCKSVD_ERR_INVALID, "%s: ctx is NULL", fn);
+    if (B < 1 || T < 1 || K < 1 || W < 1 || F < 1)
+        return fail(ctx, HSCKSVD_ERR_INVALID, "%s: bad shape B = %d, T = %d, K = %d, W = %d, F = %d", fn, B, T, K, W, F);
+    if (W * F > kMaxN) return fail(ctx, HSCKSVD_ERR_UNSUPPORTED, "%s: W * F = %d exceeds the limit of %d", fn, W * F, kMaxN);
+    if (use_pca && F != 1) return fail(ctx, HSCKSVD_ERR_UNSUPPORTED, "%s: the PCA branch needs F = 1 (got F = %d)", fn, F);
+    if (!D || !indptr || !entry_offsets) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: D, indptr or entry_offsets is NULL", fn);
+    if (entry_offsets[0] != 0) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: entry_offsets[0] = %lld, expected 0", fn, (long long)entry_offsets[0]);
+    for (int b = 0; b < B; ++b)
+        if (entry_offsets[b + 1] < entry_offsets[b]) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: entry_offsets decreases at problem %d", fn, b);
+    const long long nnz = entry_offsets[B];
+    if (nnz >= (1ll << 31)) return fail(ctx, HSCKSVD_ERR_UNSUPPORTED, "%s: %lld stored entries in all, the limit is 2^31 - 1", fn, nnz);
+    if (nnz > 0 && (!indices || !data)) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: indices or data is NULL", fn);
+    const int n = W * F;
+
+    // per problem: hscksvd_update's checks, then its occurrences (entry ids relative to the problem's first entry, at the
+    // problem's own place in the entry arrays) and the room its patches need
+    std::vector<int> occ_ptr((size_t)B * (K + 1), 0), occ((size_t)nnz, 0);
+    std::vector<int2> occ_span((size_t)nnz, make_int2(0, T));
+    std::vector<long long> eoff((size_t)B), poff((size_t)B);
+    long long patches = 0, occurrences = 0;
+    for (int b = 0; b < B; ++b) {
+        const int32_t* ip = indptr + (size_t)b * (K + 1);
+        const long long e0 = entry_offsets[b];
+        const int32_t* idx = indices + e0;
+        const double* val = data + e0;
+        if (ip[0] != 0) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: problem %d: indptr[0] = %d, expected 0", fn, b, ip[0]);
+        for (int k = 0; k < K; ++k)
+            if (ip[k + 1] < ip[k]) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: problem %d: indptr decreases at column %d", fn, b, k);
+        if (ip[K] != entry_offsets[b + 1] - e0)
+            return fail(ctx, HSCKSVD_ERR_INVALID, "%s: problem %d: indptr[K] = %d, but entry_offsets gives it %lld entries", fn, b, ip[K],
+                        (long long)(entry_offsets[b + 1] - e0));
+        int* op = occ_ptr.data() + (size_t)b * (K + 1);
+        int count = 0, max_m = 0;
+        for (int k = 0; k < K; ++k) {
+            for (int e = ip[k]; e < ip[k + 1]; ++e) {
+                if (idx[e] < 0 || idx[e] >= T)
+                    return fail(ctx, HSCKSVD_ERR_INVALID, "%s: problem %d: row %d of entry %d is outside [0, %d)", fn, b, idx[e], e, T);
+                if (e > ip[k] && idx[e] <= idx[e - 1])
+                    return fail(ctx, HSCKSVD_ERR_INVALID, "%s: problem %d: the rows of column %d are not strictly ascending", fn, b, k);
+                if (val[e] != 0.0) occ[(size_t)e0 + count++] = e;
+            }
+            op[k + 1] = count;
+            max_m = std::max(max_m, op[k + 1] - op[k]);
+        }
+        eoff[b] = e0;
+        poff[b] = patches;
+        patches += max_m;
+        occurrences += count;
+    }
+    std::vector<double> stats((size_t)B * K * kStats, 0.0);
+    if (timing_ms) timing_ms[0] = timing_ms[1] = timing_ms[2] = 0.0;
+    if (occurrences == 0) {
+        if (out_atom_stats) std::memcpy(out_atom_stats, stats.data(), stats.size() * sizeof(double));
+        return HSCKSVD_OK;                                              // no atom of any problem occurs: nothing changes
+    }
+
+    HSC_TRY(hipSetDevice(ctx->device));
+    const size_t bD = (size_t)B * K * n * sizeof(double), bI = (size_t)B * (K + 1) * sizeof(int), bR = (size_t)nnz * sizeof(int),
+                 bV = (size_t)nnz * sizeof(double), bS = (size_t)B * K * kStats * sizeof(double),
+                 bP = (size_t)patches * n * sizeof(double), bB = (size_t)nnz * sizeof(int2), bO = (size_t)B * sizeof(long long);
+    const size_t bytes[9] = {bD, bI, bR, bV, bR, bI + bS + 16, bP, bB, 2 * bO};     // (slot 8: the two offset arrays)
+    if (int rc = ctx->buf.ensure(ctx, bytes, fn)) return rc;
+    int* d_occ_ptr = (int*)ctx->buf[5];
+    double* d_stats = (double*)((char*)ctx->buf[5] + (bI + 15) / 16 * 16);
+    long long* d_eoff = (long long*)ctx->buf[8];
+    long long* d_poff = d_eoff + B;
+    hipStream_t st = ctx->stream;
+    HSC_TRY(hipEventRecord(ctx->ev[0], st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[0], D, bD, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[1], indptr, bI, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[2], indices, bR, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[3], data, bV, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[4], occ.data(), bR, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(d_occ_ptr, occ_ptr.data(), bI, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[7], occ_span.data(), bB, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(d_eoff, eoff.data(), bO, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(d_poff, poff.data(), bO, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipEventRecord(ctx->ev[1], st));
+    SweepArgs args;
+    args.K = K;
+    args.W = W;
+    args.F = F;
+    args.use_pca = use_pca ? 1 : 0;
+    args.D = (double*)ctx->buf[0];
+    args.indptr = (const int*)ctx->buf[1];
+    args.rows = (const int*)ctx->buf[2];
+    args.vals = (double*)ctx->buf[3];
+    args.occ = (const int*)ctx->buf[4];
+    args.occ_ptr = d_occ_ptr;
+    args.occ_span = (const int2*)ctx->buf[7];
+    args.P = (double*)ctx->buf[6];
+    args.G = nullptr;                                                   // (plan 2's: never read here)
+    args.stats = d_stats;
+    hipLaunchKernelGGL(ksvd_sweep_batch_kernel, dim3(B), dim3(kThreads), 0, st, args, d_eoff, d_poff);
+    HSC_TRY(hipGetLastError());
+    HSC_TRY(hipEventRecord(ctx->ev[2], st));
+    HSC_TRY(hipMemcpyAsync(D, ctx->buf[0], bD, hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipMemcpyAsync(data, ctx->buf[3], bV, hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipMemcpyAsync(stats.data(), d_stats, bS, hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipEventRecord(ctx->ev[3], st));
+    HSC_TRY(hipStreamSynchronize(st));
+    if (timing_ms)
+        if (int rc = hsc::add_times(ctx, 3, timing_ms)) return rc;          // (zeroed above)
+    if (out_atom_stats) std::memcpy(out_atom_stats, stats.data(), stats.size() * sizeof(double));
+    return HSCKSVD_OK;
 }
 
 extern "C" int hscksvd_update_corpus(hscksvd_ctx* ctx, int B, const int32_t* row_offsets, int K, int W, int F, double* D,

@@ -19,6 +19,11 @@ A corpus (B signals, one dictionary): update_corpus / ConvolutionalKSVDLearner.t
 computeCoefficientsBatch call per iteration (ragged batches included) and update the dictionary from every signal's
 occurrences with hscksvd_update_corpus; no atom reaches into a neighbouring signal.  DESIGN.md section 16.
 
+Independent learners (B signals, B dictionaries: restarts, or a dictionary per signal): update_batch /
+ConvolutionalKSVDLearner.trainBatch encode the running learners' signals against their own dictionaries in one
+computeCoefficientsMultiBatch call per iteration and update the dictionaries with one hscksvd_update_batch launch, a workgroup
+per learner; learner b is bit for bit `train` on signal b.  DESIGN.md section 24.
+
 There is no CPU path: without libhscksvd.so or a visible GPU the calls raise hsc_amd._native.HscmpError.
 ConvolutionalDictionaryLearner(algorithm='ksvd') keeps its host sweep and is not routed here.
 """
@@ -36,7 +41,7 @@ logger = logging.getLogger(__name__)
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'ksvd', 'libhscksvd.so')
 EXPORTS = ['hscksvd_version', 'hscksvd_create', 'hscksvd_destroy', 'hscksvd_last_error', 'hscksvd_update',
-           'hscksvd_update_corpus']
+           'hscksvd_update_corpus', 'hscksvd_update_batch']
 MAX_ATOM_SIZE = 64                       # W * F, include/hscksvd.h HSCKSVD_MAX_ATOM_SIZE
 WIDE_FROM_OCCURRENCES = 64               # include/hscksvd.h HSCKSVD_WIDE_FROM_OCCURRENCES: what plan 'auto' decides on
 PLANS = {'auto': 0, 'one': 1, 'wide': 2}
@@ -53,7 +58,8 @@ def load_library():
         vp, ci = ctypes.c_void_p, ctypes.c_int
         _lib = _native.load_satellite(LIB_PATH, 'hscksvd', {
             'hscksvd_update': [vp, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, vp],
-            'hscksvd_update_corpus': [vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp, vp]})
+            'hscksvd_update_corpus': [vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, vp, vp],
+            'hscksvd_update_batch': [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp]})
     return _lib
 
 
@@ -157,6 +163,53 @@ def update_corpus(D, coefficients, usePCA=False, device=0, plan='auto'):
     return D3.reshape(D.shape), cscs, stats, timing
 
 
+def update_batch(Ds, coefficients, usePCA=False, device=0):
+    """B independent sweeps of the K-SVD dictionary update in one launch (hscksvd_update_batch): Ds [B,K,W] or [B,K,W,F] (or a
+    list of B dictionaries of one shape) and a list of B sparse [T,K] coefficient matrices, problem b being
+    update(Ds[b], coefficients[b]) bit for bit.  Returns (Ds float64 of the stacked shape, list of B csc_matrix [T,K]
+    float64 with the updated values, stats [B,K,4] float64: n_k, lambda1, lambda2, Jacobi sweeps, timing_ms [3]: upload,
+    sweep, download).  The inputs are not modified."""
+    if isinstance(Ds, (list, tuple)):
+        parts = [np.asarray(d) for d in Ds]
+        if len(parts) == 0 or any(d.shape != parts[0].shape for d in parts):
+            raise ValueError('K-SVD: update_batch needs at least one dictionary, all of one shape')
+        Ds = np.stack(parts)
+    Ds = np.asarray(Ds)
+    if Ds.ndim != 3 and Ds.ndim != 4:
+        raise ValueError('K-SVD: the dictionaries must be [B,K,W] or [B,K,W,F] (got %d dimensions)' % Ds.ndim)
+    B, K, W = Ds.shape[0], Ds.shape[1], Ds.shape[2]
+    D4 = np.array(Ds.reshape((B, K, W, -1)), dtype=np.float64, order='C')
+    F = D4.shape[3]
+    coefficients = list(coefficients)
+    if len(coefficients) != B or B == 0:
+        raise ValueError('K-SVD: %d coefficient matrices for %d dictionaries' % (len(coefficients), B))
+    T = coefficients[0].shape[0]
+    for c in coefficients:
+        if c.shape != (T, K):
+            raise ValueError('K-SVD: update_batch needs coefficient matrices of one shape [T,K] = (%d, %d) (got %s)' % (T, K, c.shape))
+    check_update_shapes(T, W, F, usePCA)
+    cscs = []
+    for c in coefficients:
+        c = scipy.sparse.csc_matrix(c, dtype=np.float64, copy=True)
+        if not c.has_sorted_indices:
+            c.sort_indices()
+        cscs.append(c)
+    offsets = np.concatenate([[0], np.cumsum([c.nnz for c in cscs], dtype=np.int64)]).astype(np.int64)
+    if offsets[-1] >= 2 ** 31:
+        raise NotImplementedError('K-SVD on the GPU: %d stored coefficients in all, the limit is 2^31 - 1' % offsets[-1])
+    indptr = np.ascontiguousarray(np.stack([c.indptr for c in cscs]), dtype=np.int32)
+    indices = np.ascontiguousarray(np.concatenate([c.indices for c in cscs]), dtype=np.int32)
+    data = np.ascontiguousarray(np.concatenate([c.data for c in cscs]), dtype=np.float64)
+    stats = np.zeros((B, K, ATOM_STATS), dtype=np.float64)
+    timing = np.zeros((3,), dtype=np.float64)
+    ctx = _context(device)
+    p = _native._ptr
+    ctx.call('update_batch', B, T, K, W, F, p(D4), p(offsets), p(indptr), p(indices), p(data), 1 if usePCA else 0, p(stats), p(timing))
+    for b, c in enumerate(cscs):
+        c.data[:] = data[offsets[b]:offsets[b + 1]]
+    return D4.reshape(Ds.shape), cscs, stats, timing
+
+
 def _corpus_signals(sequences, lengths):
     """The signals of a corpus as a list of [T_b] or [T_b,F] views: `sequences` [B,T] / [B,T,F], a list / tuple of
     arrays, or a padded array with `lengths` [B] (the forms of computeCoefficientsBatch)."""
@@ -250,6 +303,67 @@ class ConvolutionalKSVDLearner(object):
             n += 1
         self.lastStats = stats
         return D
+
+    def trainBatch(self, sequences, method='locomp', maxIterations=100, tolerance=0.0, nbNonzeroCoefs=None, toleranceSnr=40.0,
+                   usePCA=False, rngs=None):
+        """B independent learners, learner b on sequences[b] ([B,T] or [B,T,F]): restarts, or a dictionary per signal.
+        rngs: a list of B generators (learner b then reproduces train() with rngs[b], bit for bit), or one generator / None
+        (the learner's own rng, else numpy's global generator) shared by all: the initial dictionaries are then drawn in batch
+        order.
+        Each iteration is ONE computeCoefficientsMultiBatch over the learners still running (every signal against its own
+        dictionary) and ONE update_batch over them (a workgroup per learner).  Each learner stops on its own
+        (n < maxIterations and alpha > tolerance); a stopped learner is neither encoded nor updated.  DESIGN.md section 24.
+        Returns (D float64 [B,K,W] or [B,K,W,F], per-learner lastStats lists: train's records plus variant, the encode's kernel
+        variant; encode_ms and update_ms are the batch's wall clock, shared by the learners that ran in it)."""
+        from .learning import ConvolutionalDictionaryLearner
+        from .modeling import is_ragged
+        self._check_method(method)
+        if is_ragged(sequences):
+            raise NotImplementedError('ConvolutionalKSVDLearner.trainBatch has no ragged form (signals of different lengths): '
+                                      'pass a [B,T] or [B,T,F] array')
+        sequences = np.asarray(sequences)
+        if sequences.ndim != 2 and sequences.ndim != 3:
+            raise ValueError('K-SVD: the batch must be [B,T] or [B,T,F] (got %d dimensions)' % sequences.ndim)
+        B = sequences.shape[0]
+        if B == 0:
+            raise ValueError('K-SVD: a batch needs at least one learner')
+        check_update_shapes(sequences.shape[1], self.windowSize, 1 if sequences.ndim == 2 else sequences.shape[2], usePCA)
+        if isinstance(rngs, (list, tuple)):
+            if len(rngs) != B:
+                raise ValueError('K-SVD: %d generators for %d learners' % (len(rngs), B))
+            rngs = list(rngs)
+        else:
+            rngs = [self.rng if rngs is None else rngs] * B
+        load_library()                                       # no CPU path: fail before the first encode
+        D = np.stack([np.asarray(ConvolutionalDictionaryLearner(self.k, self.windowSize, rng=rngs[b])._init_D(sequences[b], initMethod='noise'),
+                                 dtype=np.float64) for b in range(B)])
+        coder = self._coder(method)
+        stats = [[] for _ in range(B)]
+        n = 0
+        # (train's loop test before its first iteration: n = 0, alpha = tolerance + 1)
+        running = np.arange(B) if (0 < maxIterations and tolerance + 1.0 > tolerance) else np.arange(0)
+        while running.size > 0:
+            t0 = time.perf_counter()
+            res = coder.computeCoefficientsMultiBatch(sequences[running], D[running], nbNonzeroCoefs=nbNonzeroCoefs,
+                                                      toleranceSnr=toleranceSnr)
+            t1 = time.perf_counter()
+            newD, coefficients, atoms, timing = update_batch(D[running], res.coefficients, usePCA, self.device)
+            t2 = time.perf_counter()
+            keep = []
+            for i, b in enumerate(running):
+                alpha = np.sqrt(np.sum(np.square(newD[i] - D[b])))
+                D[b] = newD[i]
+                stats[b].append(dict(alpha=float(alpha), nnz=int(coefficients[i].nnz), encode_ms=1e3 * (t1 - t0),
+                                     update_ms=1e3 * (t2 - t1), sweep_ms=float(timing[1]), n_k=atoms[i, :, 0].astype(np.int64),
+                                     eigenvalues=atoms[i, :, 1:3].copy(), variant=res.variant))
+                logger.debug('K-SVD learner %d iteration %d: tolerance = %f, sparsity = %f' % (
+                    b, n, alpha, float(coefficients[i].nnz) / np.prod(coefficients[i].shape)))
+                if n + 1 < maxIterations and alpha > tolerance:
+                    keep.append(b)
+            running = np.asarray(keep, dtype=np.int64)
+            n += 1
+        self.lastStats = stats
+        return D, stats
 
     def trainCorpus(self, sequences, method='locomp', maxIterations=100, tolerance=0.0, nbNonzeroCoefs=None,
                     toleranceSnr=40.0, usePCA=False, lengths=None):

@@ -115,20 +115,39 @@ class LoCOMP(ConvolutionalMatchingPursuit):
                                                            minCoefficients, weights, None, maxEvents)
         again = np.where(res.stats[:, _native.STAT_STOP] == _native.STOP_GROUP)[0]
         for b in again:
-            coef, residual = self._computeCoefficientsHost(np.asarray(sequences[b]), D, nbNonzeroCoefs, toleranceResidualScale, toleranceSnr,
-                                                           nbBlocks, minCoefficients, weights, None)
-            res.coefficients[b] = coef
-            res.residuals[b] = residual
-            # what describes the signal now is the host loop's run, not the device run that was given up: counters the host loop
-            # can answer are refreshed, the others cleared, the stop reason says who finished the signal
-            if res.stats is not None:
-                res.stats[b, :] = 0
-                res.stats[b, _native.STAT_NNZ] = coef.nnz
-                res.stats[b, _native.STAT_STOP] = _native.STOP_HOST
-            if res.energies is not None:
-                res.energies[b, 1] = float(np.sum(np.square(np.asarray(residual, dtype=np.float64))))
-            if res.events is not None:
-                res.events[b] = (np.zeros((0,), np.int32), np.zeros((0,), np.int32), np.zeros((0,), res.events[b][2].dtype))
+            self._retake_on_host(res, b, np.asarray(sequences[b]), D, nbNonzeroCoefs, toleranceResidualScale, toleranceSnr,
+                                 nbBlocks, minCoefficients, weights)
+        return res
+
+    def _retake_on_host(self, res, b, sequence, D, nbNonzeroCoefs, toleranceResidualScale, toleranceSnr, nbBlocks, minCoefficients, weights):
+        """Signal b of a device batch (stop reason 'group') again through the host loop, its entries of `res` replaced."""
+        coef, residual = self._computeCoefficientsHost(sequence, D, nbNonzeroCoefs, toleranceResidualScale, toleranceSnr,
+                                                       nbBlocks, minCoefficients, weights, None)
+        res.coefficients[b] = coef
+        res.residuals[b] = residual
+        # what describes the signal now is the host loop's run, not the device run that was given up: counters the host loop
+        # can answer are refreshed, the others cleared, the stop reason says who finished the signal
+        if res.stats is not None:
+            res.stats[b, :] = 0
+            res.stats[b, _native.STAT_NNZ] = coef.nnz
+            res.stats[b, _native.STAT_STOP] = _native.STOP_HOST
+        if res.energies is not None:
+            res.energies[b, 1] = float(np.sum(np.square(np.asarray(residual, dtype=np.float64))))
+        if res.events is not None:
+            res.events[b] = (np.zeros((0,), np.int32), np.zeros((0,), np.int32), np.zeros((0,), res.events[b][2].dtype))
+
+    def computeCoefficientsMultiBatch(self, sequences, dictionaries, dictionaryOf=None, nbNonzeroCoefs=None, toleranceResidualScale=None,
+                                      toleranceSnr=None, nbBlocks=1, minCoefficients=1e-16, weights=None, maxEvents=None):
+        """The base class's batch with a dictionary per signal, through the LoCOMP device loop (the dense policy).  A signal with a
+        neighbourhood beyond the kernel's capacity (stop reason 'group') is taken again by the host loop with ITS OWN dictionary
+        and weights, as computeCoefficientsBatch does."""
+        res = super(LoCOMP, self).computeCoefficientsMultiBatch(sequences, dictionaries, dictionaryOf, nbNonzeroCoefs, toleranceResidualScale,
+                                                                toleranceSnr, nbBlocks, minCoefficients, weights, maxEvents)
+        again = np.where(res.stats[:, _native.STAT_STOP] == _native.STOP_GROUP)[0]
+        for b in again:
+            g = int(b) if dictionaryOf is None else int(np.asarray(dictionaryOf)[b])
+            self._retake_on_host(res, b, np.asarray(sequences[b]), np.asarray(dictionaries[g]), nbNonzeroCoefs, toleranceResidualScale,
+                                 toleranceSnr, nbBlocks, minCoefficients, None if weights is None else np.asarray(weights)[g])
         return res
 
     def _batch_on_host(self, sequences, D, *args):

@@ -389,33 +389,12 @@ class ConvolutionalMatchingPursuit(SparseApproximator):
         finally:
             if method != _native.METHOD_CMP:
                 eng.set_method(_native.METHOD_CMP)                   # (engines are shared; a resumed batch keeps its own loop)
-        kernel_ms = list(eng.last_kernel_ms())
-        while True:
-            if per_round:
+        callback = None
+        if per_round:
+            def callback():
                 self._run_with_callback(eng, seqs if ragged else sequences, D, K, T, minCoefficients, stopCondition, lens)
-            stats = eng.fetch_stats()
-            if not np.any(stats[:, _native.STAT_STOP] == _native.STOP_CAPACITY):
-                break
-            # the event list was too short for this stop rule: enlarge it and resume where the loop stopped
-            # (a round is only started when all its atoms fit, so the trace equals an uninterrupted run)
-            bound = _native.max_event_capacity(T)
-            if maxEvents >= bound:
-                raise _native.HscmpError('the pursuit does not converge: more than %d selections per signal without meeting a stop '
-                                         'rule (the same atoms are re-selected; the reference would not terminate)' % maxEvents)
-            maxEvents = min(4 * maxEvents, bound)          # enlarge the event lists and resume (exact, see hscmp_grow_events)
-            eng.grow_events(maxEvents)
-            eng.continue_rounds(1 if per_round else 0)
-            kernel_ms[2] += eng.last_kernel_ms()[2]
-
-        ev_t, ev_k, ev_c = eng.fetch_events()
-        st, sk, sa = eng.fetch_slots()
-        residuals = eng.fetch_residual()
-        energies = eng.fetch_energies()
-        coefficients, events = [], []
-        for b in range(B):
-            ne, ns = int(stats[b, _native.STAT_EVENTS]), int(stats[b, _native.STAT_SLOTS])
-            coefficients.append(_slots_to_csc(st[b], sk[b], sa[b], ns, (T if lens is None else int(lens[b]), K), minCoefficients))
-            events.append((ev_t[b, :ne].copy(), ev_k[b, :ne].copy(), ev_c[b, :ne].copy()))
+        stats, kernel_ms = self._run_to_the_end(eng, T, maxEvents, callback)
+        coefficients, events, residuals, energies = self._fetch_batch(eng, stats, T, K, lens, minCoefficients)
         cast = residuals.dtype != src_dtype and np.issubdtype(src_dtype, np.floating)
         if ragged:
             # per-signal residuals of the signal's own length, shaped like computeCoefficients' (modeling.py:1183-1186)
@@ -437,6 +416,104 @@ class ConvolutionalMatchingPursuit(SparseApproximator):
             logger.debug('signal %d: %d selections in %d rounds, nnz %d, duplicates %d, stop: %s' % (
                 b, stats[b, _native.STAT_ITERATIONS], stats[b, _native.STAT_ROUNDS], stats[b, _native.STAT_NNZ],
                 stats[b, _native.STAT_DUPLICATES], _native.STOP_NAMES.get(int(stats[b, _native.STAT_STOP]))))
+        return res
+
+    def _run_to_the_end(self, eng, T, maxEvents, callback=None):
+        """Behind an encode of `eng`: run the callback rounds (`callback`, or None) and, while a signal stopped on the capacity of
+        its event list, enlarge the lists and resume.  Returns (stats, kernel_ms of the encode plus the resumed launches)."""
+        kernel_ms = list(eng.last_kernel_ms())
+        while True:
+            if callback is not None:
+                callback()
+            stats = eng.fetch_stats()
+            if not np.any(stats[:, _native.STAT_STOP] == _native.STOP_CAPACITY):
+                return stats, kernel_ms
+            # the event list was too short for this stop rule: enlarge it and resume where the loop stopped
+            # (a round is only started when all its atoms fit, so the trace equals an uninterrupted run)
+            bound = _native.max_event_capacity(T)
+            if maxEvents >= bound:
+                raise _native.HscmpError('the pursuit does not converge: more than %d selections per signal without meeting a stop '
+                                         'rule (the same atoms are re-selected; the reference would not terminate)' % maxEvents)
+            maxEvents = min(4 * maxEvents, bound)          # enlarge the event lists and resume (exact, see hscmp_grow_events)
+            eng.grow_events(maxEvents)
+            eng.continue_rounds(1 if callback is not None else 0)
+            kernel_ms[2] += eng.last_kernel_ms()[2]
+
+    def _fetch_batch(self, eng, stats, T, K, lens, minCoefficients):
+        """The finished batch of `eng`: (per-signal csc [T,K] -- [lens[b],K] in a ragged batch --, per-signal events, residuals
+        [B,T,F] as the engine keeps them, energies [B,2])."""
+        ev_t, ev_k, ev_c = eng.fetch_events()
+        st, sk, sa = eng.fetch_slots()
+        residuals = eng.fetch_residual()
+        energies = eng.fetch_energies()
+        coefficients, events = [], []
+        for b in range(stats.shape[0]):
+            ne, ns = int(stats[b, _native.STAT_EVENTS]), int(stats[b, _native.STAT_SLOTS])
+            coefficients.append(_slots_to_csc(st[b], sk[b], sa[b], ns, (T if lens is None else int(lens[b]), K), minCoefficients))
+            events.append((ev_t[b, :ne].copy(), ev_k[b, :ne].copy(), ev_c[b, :ne].copy()))
+        return coefficients, events, residuals, energies
+
+    def computeCoefficientsMultiBatch(self, sequences, dictionaries, dictionaryOf=None, nbNonzeroCoefs=None,
+                                      toleranceResidualScale=None, toleranceSnr=None, nbBlocks=1, minCoefficients=1e-16,
+                                      weights=None, maxEvents=None):
+        """computeCoefficientsBatch with a dictionary per signal (DESIGN.md section 24): `sequences` [B,T] or [B,T,F];
+        `dictionaries` [G,K,W] or [G,K,W,F], or a list of G arrays of one shape and dtype; `dictionaryOf` int [B] names signal b's
+        dictionary (None: G == B and signal b takes dictionary b); `weights` None or [G,K].  Signal b gets exactly what
+        computeCoefficients gives it alone with dictionaries[dictionaryOf[b]] and weights[dictionaryOf[b]]; one call encodes
+        them side by side (hscmp_encode_batch_multi, the generic kernels).  Returns a BatchResult."""
+        method = getattr(self, '_method', _native.METHOD_CMP)
+        if is_ragged(sequences):
+            raise NotImplementedError('computeCoefficientsMultiBatch has no ragged form (signals of different lengths): pass a '
+                                      '[B,T] or [B,T,F] array')
+        Ds = _native.stack_dictionaries(dictionaries)
+        sequences = np.asarray(sequences)
+        if sequences.ndim != 2 and sequences.ndim != 3:
+            raise ValueError('computeCoefficientsMultiBatch: the signals must be [B,T] or [B,T,F] (got %d dimensions)' % sequences.ndim)
+        G, K, W, F = Ds.shape
+        B, T = sequences.shape[0], sequences.shape[1]
+        if (1 if sequences.ndim == 2 else sequences.shape[2]) != F:
+            raise ValueError('computeCoefficientsMultiBatch: the signals have %d features, the dictionaries %d' % (
+                1 if sequences.ndim == 2 else sequences.shape[2], F))
+        if dictionaryOf is None:
+            if G != B:
+                raise ValueError('computeCoefficientsMultiBatch: dictionaryOf=None needs one dictionary per signal (%d dictionaries, '
+                                 '%d signals)' % (G, B))
+            of = np.arange(B, dtype=np.int32)
+        else:
+            of = np.asarray(dictionaryOf)
+            if of.shape != (B,):
+                raise ValueError('computeCoefficientsMultiBatch: dictionaryOf must have one entry per signal (%d), got shape %s' % (B, of.shape))
+            if np.any(of < 0) or np.any(of >= G):
+                b = int(np.argmax((of < 0) | (of >= G)))
+                raise ValueError('computeCoefficientsMultiBatch: signal %d asks for dictionary %d outside [0, %d)' % (b, int(of[b]), G))
+            of = of.astype(np.int32)
+        if weights is not None and np.shape(weights) != (G, K):
+            raise ValueError('computeCoefficientsMultiBatch: weights must be [G,K] = (%d, %d), got %s' % (G, K, np.shape(weights)))
+        dictionaries_nd = np.ndim(dictionaries[0]) + 1 if isinstance(dictionaries, (list, tuple)) else np.ndim(dictionaries)
+        dt = _compute_dtype(sequences.dtype, Ds.dtype)
+        eps = float(np.finfo(Ds.dtype).eps)
+        x = np.ascontiguousarray(sequences.reshape((B, T, -1)), dtype=dt)
+        if maxEvents is None:
+            maxEvents = 2 * int(nbNonzeroCoefs) + 64 if nbNonzeroCoefs is not None else 4096
+        params = _native.make_params(nbNonzeroCoefs, toleranceResidualScale, toleranceSnr, nbBlocks, minCoefficients, eps, maxEvents, 0)
+
+        eng = _native.multi_engine(self.device)
+        eng.set_dictionaries(np.asarray(Ds, dtype=dt), None if weights is None else np.asarray(weights, dtype=dt))
+        if method != _native.METHOD_CMP:
+            eng.set_method(method)
+        try:
+            eng.encode_batch_multi(x, of, params)
+        finally:
+            if method != _native.METHOD_CMP:
+                eng.set_method(_native.METHOD_CMP)                   # (engines are shared; a resumed batch keeps its own loop)
+        stats, kernel_ms = self._run_to_the_end(eng, T, maxEvents)
+        coefficients, events, residuals, energies = self._fetch_batch(eng, stats, T, K, None, minCoefficients)
+        if sequences.ndim == 2 or dictionaries_nd == 3:
+            residuals = np.squeeze(residuals, axis=2)                      # modeling.py:1183-1184
+        if residuals.dtype != sequences.dtype and np.issubdtype(sequences.dtype, np.floating):
+            residuals = residuals.astype(sequences.dtype)
+        res = BatchResult(coefficients, residuals, events, stats, energies, eng.last_variant(), kernel_ms, None)
+        self.lastResult = res
         return res
 
     def _run_with_callback(self, eng, sequences, D, K, T, minCoefficients, stopCondition, lengths=None):

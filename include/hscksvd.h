@@ -97,6 +97,25 @@ int hscksvd_update_corpus(hscksvd_ctx* ctx, int B, const int32_t* row_offsets, i
                           const int32_t* indptr, const int32_t* indices, double* data, int use_pca, int plan,
                           double* out_atom_stats, double* timing_ms);
 
+/* B independent sweeps in ONE launch: B dictionaries of one shape, each with the coefficient matrix
+ * [T][K] of its own signal.  Problem b is
+ *   hscksvd_update(T, K, W, F, D[b], indptr[b], indices + entry_offsets[b], data + entry_offsets[b], use_pca, ...)
+ * bit for bit -- D, data and stats -- and inherits every rule fixed above (sign, ties, the zero Gram matrix, m = 1, the PCA
+ * branch) and the limits with their messages (W * F <= HSCKSVD_MAX_ATOM_SIZE, PCA needs F = 1).
+ *   D             [B][K][W][F]  in / out
+ *   entry_offsets [B+1]         entry_offsets[0] = 0, non-decreasing: problem b's stored entries are
+ *                               [entry_offsets[b], entry_offsets[b+1]) of indices / data
+ *   indptr        [B][K+1]      CSC column pointers of problem b, RELATIVE to its first entry (indptr[b][0] = 0,
+ *                               indptr[b][K] = entry_offsets[b+1] - entry_offsets[b])
+ *   indices, data               the problems' entries one after the other; rows in [0, T), strictly ascending per column
+ *   out_atom_stats [B][K][HSCKSVD_ATOM_STATS] (may be NULL); timing_ms [3] (may be NULL): upload, the launch, download
+ * One workgroup per problem runs the one-workgroup sweep (plan 1) over its own scratch: the grid is B, nothing is shared
+ * between two problems, there are no atomics and every sum runs in the single sweep's order.  A problem without a stored
+ * non-zero entry keeps its dictionary (stats 0).  All entries together must stay below 2^31. */
+int hscksvd_update_batch(hscksvd_ctx* ctx, int B, int T, int K, int W, int F, double* D, const int64_t* entry_offsets,
+                         const int32_t* indptr, const int32_t* indices, double* data, int use_pca, double* out_atom_stats,
+                         double* timing_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,19 @@ int hscmp_synchronize(hscmp_ctx* ctx);
 int hscmp_set_dictionary(hscmp_ctx* ctx, const void* D, int K, int W, int F, hscmp_dtype dtype,
                          const void* weights);
 
+/* A SET of G dictionaries of one shape, D [G][K][W][F] with optional weights [G][K] (host pointers; G = 1 is allowed), for
+ * hscmp_encode_batch_multi: a batch in which every signal names its own dictionary.  Replaces the
+ * context's dictionary as hscmp_set_dictionary does (the old dictionary, the batch and the resident table go first; a failure
+ * leaves "no dictionary set").  Weights that are all exactly 1 count as no weights only when EVERY dictionary's are: one weighted
+ * dictionary makes the whole set weighted.  The context keeps, per dictionary and at a fixed stride, what the generic kernels
+ * read (D, its chain-ordered copy for F > 1, the weights) and builds no matrix-core, bound or sparse-list image.
+ * While the context holds a set, every other entry point that encodes with the dictionary -- hscmp_encode_batch, _device,
+ * _ragged(_device), _from_level (as either level), hscmp_load_level(_ragged), hscmp_hierarchy_epilogue, hscmp_table_*,
+ * hscmp_assign_windows, hscmp_convolve1d, hscmp_update_inner_products -- answers HSCMP_ERR_STATE, before it queues anything;
+ * hscmp_set_dictionary puts a plain dictionary back. */
+int hscmp_set_dictionaries(hscmp_ctx* ctx, const void* D, int G, int K, int W, int F, hscmp_dtype dtype,
+                           const void* weights);
+
 /* modeling.py:149-188 convolve1d(sequence, filters, padding): x [T][F] host -> out [Tout][K]
  * host; same != 0: zero-padded 'same' (Tout = T), else 'valid' (Tout = T-W+1).  Uses the
  * dictionary of the context. */
@@ -185,6 +198,18 @@ int hscmp_encode_batch_device(hscmp_ctx* ctx, const void* x_dev, int B, int T, c
  * hscmp_last_variant ends in "_ragged".  The _device form takes x in GPU memory and is asynchronous on the context's stream. */
 int hscmp_encode_batch_ragged(hscmp_ctx* ctx, const void* x, int B, int T, const int32_t* lengths, const hscmp_params* params);
 int hscmp_encode_batch_ragged_device(hscmp_ctx* ctx, const void* x_dev, int B, int T, const int32_t* lengths, const hscmp_params* params);
+
+/* A batch x [B][T][F] (host) encoded with a dictionary per signal: dict_of host int32 [B], each in [0, G), names signal b's
+ * dictionary in the set of hscmp_set_dictionaries.  Signal b comes out exactly as hscmp_encode_batch would return it alone
+ * on a context whose dictionary (and weights) is dictionary dict_of[b] of the set: events, coefficient slots, stats, residual
+ * and both energies -- bit for bit under HSCMP_METHOD_CMP whatever kernels that single encode picks, and under
+ * HSCMP_METHOD_LOCOMP bit for bit against the single encode on the dense LoCOMP loop (float32: HSCMP_LOCOMP_NO_MFMA=1).
+ * The generic kernels run it (any dtype, F >= 1, single arg-max and blocked rounds, with and without weights);
+ * hscmp_last_variant ends in "_multi".  hscmp_continue, hscmp_grow_events, hscmp_stop_signal and the fetches work on the batch
+ * as on any other; the context keeps dict_of until the next encode.  Synchronous, like hscmp_encode_batch.
+ * HSCMP_ERR_STATE on a context that holds a plain dictionary (or none); HSCMP_ERR_INVALID for a dict_of[b] outside [0, G)
+ * (hscmp_last_error names the signal); both before anything is queued. */
+int hscmp_encode_batch_multi(hscmp_ctx* ctx, const void* x, int B, int T, const int32_t* dict_of, const hscmp_params* params);
 
 /* Level chaining of the hierarchical encoder (modeling.py:1489, `input = levelCoefficients.todense()`),
  * entirely on the device: the accumulated coefficients of signals [first, first+count) of `prev`
