@@ -1,17 +1,22 @@
 // hscksvd.hip -- libhscksvd.so: the dictionary update of the convolutional K-SVD learner (hsc/modeling.py:591-633)
 // on gfx950, C ABI in include/hscksvd.h.  DESIGN.md section 13.
 //
-// The coefficient matrix is the vertical stack of the signals' [T_b][K] matrices (hscksvd_update: one signal); every
-// occurrence carries the stacked rows [lo, hi) of its own signal, and nothing of another signal enters its patch.
-// The atoms depend on each other in order (atom k reads the new atoms and coefficients of every k' < k).  Two plans
-// run the same device functions, so they return the same bits:
-//   plan 1: ONE launch of ksvd_sweep_kernel on ONE workgroup of 1024 threads; the atoms run one after the other
-//           inside the kernel, separated by workgroup barriers, and never wait for the host.
-//   plan 2: per atom, in stream order, ksvd_gather_kernel and ksvd_gram_kernel on grids over the occurrences / the
-//           Gram entries (and ksvd_centre_kernel for the PCA branch), then ksvd_tail_kernel on one workgroup.  No
+// A call works on P >= 1 problems of one (K, W, F), and one host driver (run_update) checks, lays out, uploads, launches and
+// downloads them.  Problem p has its own dictionary, column pointers, occurrence pointers and stats at stride p, its own
+// entries (rows, values, occurrence ids and spans, the ids relative to its first entry) from entry_off[p] on and its own
+// patch scratch from patch_off[p] on.  Its coefficient matrix is the vertical stack of its signals' [T_b][K] matrices;
+// every occurrence carries the stacked rows [lo, hi) of its own signal, and nothing of another signal enters its patch.
+//   hscksvd_update:         P = 1, one signal [0, T)
+//   hscksvd_update_corpus:  P = 1, B signals from row_offsets
+//   hscksvd_update_batch:   P = B, one signal [0, T) each
+// The atoms of a problem depend on each other in order (atom k reads the new atoms and coefficients of every k' < k).
+// Two plans run the same device functions, so they return the same bits:
+//   plan 1: ONE launch of ksvd_sweep_kernel, workgroup p of 1024 threads on problem p; the atoms run one after the other
+//           inside the kernel, separated by workgroup barriers, and never wait for the host.  Nothing is shared between
+//           two workgroups.
+//   plan 2 (P = 1): per atom, in stream order, ksvd_gather_kernel and ksvd_gram_kernel on grids over the occurrences /
+//           the Gram entries (and ksvd_centre_kernel for the PCA branch), then ksvd_tail_kernel on one workgroup.  No
 //           kernel waits for another workgroup: the order of the atoms is the order of the launches.
-// hscksvd_update_batch (B independent problems of one shape): ONE launch of ksvd_sweep_batch_kernel,
-// workgroup b running plan 1 on problem b over its own scratch; nothing is shared between two workgroups.
 // Per atom k with m occurrences:
 //   1. gather: one wave per patch (plan 1: wave w builds the patches i = w, w + 16, ...).  Lane l < W*F owns sample
 //      (s, f) = (l / F, l % F) at stacked row tau = g_i - (W-1)/2 + s, live when lo <= tau < hi.  For every other
@@ -338,30 +343,24 @@ __device__ __forceinline__ void sweep_atoms(const SweepArgs& a, TailLds& lds)
     }
 }
 
-__global__ __launch_bounds__(kThreads) void ksvd_sweep_kernel(SweepArgs a)
+// Workgroup p runs plan 1 on problem p.  `a` describes problem 0; problem p's dictionary, column pointers, occurrence pointers
+// and stats lie p strides behind, its entries (rows, values, occurrence ids and spans: all relative to its first entry)
+// entry_off[p] behind, its patches patch_off[p] patches behind.  Nothing is shared between two workgroups.
+__global__ __launch_bounds__(kThreads) void ksvd_sweep_kernel(SweepArgs a, const long long* __restrict__ entry_off,
+                                                              const long long* __restrict__ patch_off)
 {
     __shared__ TailLds lds;
-    sweep_atoms(a, lds);
-}
-
-// ---- hscksvd_update_batch: workgroup b runs plan 1 on problem b.  `a` describes problem 0; problem b's dictionary, column
-// pointers, occurrence pointers and stats lie b strides behind, its entries (rows, values, occurrence ids and spans: all relative
-// to its first entry) entry_off[b] behind, its patches patch_off[b] patches behind.  Nothing is shared between two workgroups.
-__global__ __launch_bounds__(kThreads) void ksvd_sweep_batch_kernel(SweepArgs a, const long long* __restrict__ entry_off,
-                                                                    const long long* __restrict__ patch_off)
-{
-    __shared__ TailLds lds;
-    const int b = blockIdx.x, n = a.W * a.F;
-    const long long e0 = entry_off[b];
-    a.D += (size_t)b * a.K * n;
-    a.indptr += (size_t)b * (a.K + 1);
-    a.occ_ptr += (size_t)b * (a.K + 1);
-    a.stats += (size_t)b * a.K * kStats;
+    const int p = blockIdx.x, n = a.W * a.F;
+    const long long e0 = entry_off[p];
+    a.D += (size_t)p * a.K * n;
+    a.indptr += (size_t)p * (a.K + 1);
+    a.occ_ptr += (size_t)p * (a.K + 1);
+    a.stats += (size_t)p * a.K * kStats;
     a.rows += e0;
     a.vals += e0;
     a.occ += e0;
     a.occ_span += e0;
-    a.P += (size_t)patch_off[b] * n;
+    a.P += (size_t)patch_off[p] * n;
     sweep_atoms(a, lds);
 }
 
@@ -403,7 +402,7 @@ static_assert(HSCKSVD_OK == hsc::OK && HSCKSVD_ERR_INVALID == hsc::ERR_INVALID &
 
 struct HSC_HIDDEN hscksvd_ctx : hsc::CtxBase {
     hipEvent_t ev[4] = {};
-    hsc::Buffers<9> buf;               // D, indptr, rows, vals, occ, occ_ptr + stats, P, occ_span, G
+    hsc::Buffers<10> buf;              // D, indptr, rows, vals, occ, occ_ptr + stats, P, occ_span, G, entry_off + patch_off
 };
 
 using hsc::fail;
@@ -420,73 +419,98 @@ namespace {
 
 enum { kPlanAuto = 0, kPlanOne = 1, kPlanWide = 2 };
 
-// The sweep behind both entry points (`fn` heads the messages): the stack of B signals, signal b the rows
-// [row_offsets[b], row_offsets[b + 1]).
-int run_update(hscksvd_ctx* ctx, const char* fn, int B, const int32_t* row_offsets, int K, int W, int F, double* D,
-               const int32_t* indptr, const int32_t* indices, double* data, int use_pca, int plan, double* out_atom_stats,
-               double* timing_ms)
+// The sweep behind the three entry points (`fn` heads the messages) over P problems of one (K, W, F).  Problem p has its own
+// dictionary, indptr [K+1] and stats [K][kStats] at stride p, and its entries (indices, data) from entry_offsets[p] on.  `batch`
+// (hscksvd_update_batch): entry_offsets [P+1] is the caller's argument, checked here, and the messages name the problem;
+// otherwise P = 1 and the entries are [0, indptr[K]).  The rows of every problem are the stack of S signals, signal s the rows
+// [row_offsets[s], row_offsets[s + 1]).  Plans 0 and 2 take P = 1 only.
+int run_update(hscksvd_ctx* ctx, const char* fn, bool batch, int P, const int64_t* entry_offsets, int S, const int32_t* row_offsets,
+               int K, int W, int F, double* D, const int32_t* indptr, const int32_t* indices, double* data, int use_pca, int plan,
+               double* out_atom_stats, double* timing_ms)
 {
     if (W * F > kMaxN) return fail(ctx, HSCKSVD_ERR_UNSUPPORTED, "%s: W * F = %d exceeds the limit of %d", fn, W * F, kMaxN);
     if (use_pca && F != 1) return fail(ctx, HSCKSVD_ERR_UNSUPPORTED, "%s: the PCA branch needs F = 1 (got F = %d)", fn, F);
-    if (!D || !indptr) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: D or indptr is NULL", fn);
-    if (indptr[0] != 0) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: indptr[0] = %d, expected 0", fn, indptr[0]);
-    for (int k = 0; k < K; ++k)
-        if (indptr[k + 1] < indptr[k]) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: indptr decreases at column %d", fn, k);
-    const int nnz = indptr[K], T = row_offsets[B];
-    if (nnz > 0 && (!indices || !data)) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: indices or data is NULL", fn);
-    for (int k = 0; k < K; ++k)
-        for (int e = indptr[k]; e < indptr[k + 1]; ++e) {
-            if (indices[e] < 0 || indices[e] >= T)
-                return fail(ctx, HSCKSVD_ERR_INVALID, "%s: row %d of entry %d is outside [0, %d)", fn, indices[e], e, T);
-            if (e > indptr[k] && indices[e] <= indices[e - 1])
-                return fail(ctx, HSCKSVD_ERR_INVALID, "%s: the rows of column %d are not strictly ascending", fn, k);
-        }
-    const int n = W * F, n2 = n + (n & 1);
+    const bool no_entries = !indices || !data;
+    if (batch) {
+        if (!D || !indptr || !entry_offsets) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: D, indptr or entry_offsets is NULL", fn);
+        if (entry_offsets[0] != 0) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: entry_offsets[0] = %lld, expected 0", fn, (long long)entry_offsets[0]);
+        for (int p = 0; p < P; ++p)
+            if (entry_offsets[p + 1] < entry_offsets[p]) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: entry_offsets decreases at problem %d", fn, p);
+        if (entry_offsets[P] >= (1ll << 31))
+            return fail(ctx, HSCKSVD_ERR_UNSUPPORTED, "%s: %lld stored entries in all, the limit is 2^31 - 1", fn, (long long)entry_offsets[P]);
+        if (entry_offsets[P] > 0 && no_entries) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: indices or data is NULL", fn);
+    } else if (!D || !indptr) {
+        return fail(ctx, HSCKSVD_ERR_INVALID, "%s: D or indptr is NULL", fn);
+    }
+    const int n = W * F, n2 = n + (n & 1), T = row_offsets[S];
+    char name[32] = "";
+    auto who = [&](int p) {                                             // "problem p: " in the batch's messages
+        if (batch) snprintf(name, sizeof(name), "problem %d: ", p);
+        return name;
+    };
 
-    // occurrences: column k's entries whose value is not 0.0 (they keep their values until atom k's turn), each with
-    // the rows of its signal
-    std::vector<int> occ_ptr((size_t)K + 1, 0), occ;
+    // Per problem the checks of its columns and rows and, in the same walk, its occurrences: column k's entries whose value is
+    // not 0.0 (they keep their values until atom k's turn), each with the rows of its signal.  They lie at the problem's own
+    // place in the entry arrays, their ids relative to its first entry; its patches get the room of its most frequent atom.
+    std::vector<int> occ_ptr((size_t)P * (K + 1), 0), occ;
     std::vector<int2> occ_span;
-    occ.reserve(nnz);
-    occ_span.reserve(nnz);
-    int max_m = 0;
-    for (int k = 0; k < K; ++k) {
-        for (int e = indptr[k]; e < indptr[k + 1]; ++e)
-            if (data[e] != 0.0) {
-                const int32_t* hi = std::upper_bound(row_offsets, row_offsets + B + 1, indices[e]);
-                occ.push_back(e);
-                occ_span.push_back(make_int2(hi[-1], hi[0]));
+    std::vector<long long> off(2 * (size_t)P);                          // entry_off [P], then patch_off [P]
+    long long nnz = 0, patches = 0, occurrences = 0;
+    int widest = 0;
+    for (int p = 0; p < P; ++p) {
+        const int32_t* ip = indptr + (size_t)p * (K + 1);
+        if (ip[0] != 0) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: %sindptr[0] = %d, expected 0", fn, who(p), ip[0]);
+        for (int k = 0; k < K; ++k)
+            if (ip[k + 1] < ip[k]) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: %sindptr decreases at column %d", fn, who(p), k);
+        const long long e0 = batch ? entry_offsets[p] : 0, count = batch ? entry_offsets[p + 1] - e0 : ip[K];
+        if (ip[K] != count)
+            return fail(ctx, HSCKSVD_ERR_INVALID, "%s: %sindptr[K] = %d, but entry_offsets gives it %lld entries", fn, who(p), ip[K], count);
+        if (count > 0 && no_entries) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: indices or data is NULL", fn);
+        const int32_t* idx = indices + e0;
+        const double* val = data + e0;
+        int* op = occ_ptr.data() + (size_t)p * (K + 1);
+        int max_m = 0;
+        occ.resize((size_t)e0, 0);
+        occ_span.resize((size_t)e0, make_int2(0, 0));
+        for (int k = 0; k < K; ++k) {
+            for (int e = ip[k]; e < ip[k + 1]; ++e) {
+                if (idx[e] < 0 || idx[e] >= T)
+                    return fail(ctx, HSCKSVD_ERR_INVALID, "%s: %srow %d of entry %d is outside [0, %d)", fn, who(p), idx[e], e, T);
+                if (e > ip[k] && idx[e] <= idx[e - 1])
+                    return fail(ctx, HSCKSVD_ERR_INVALID, "%s: %sthe rows of column %d are not strictly ascending", fn, who(p), k);
+                if (val[e] != 0.0) {
+                    const int32_t* hi = std::upper_bound(row_offsets, row_offsets + S + 1, idx[e]);
+                    occ.push_back(e);
+                    occ_span.push_back(make_int2(hi[-1], hi[0]));
+                }
             }
-        occ_ptr[k + 1] = (int)occ.size();
-        max_m = std::max(max_m, occ_ptr[k + 1] - occ_ptr[k]);
+            op[k + 1] = (int)(occ.size() - (size_t)e0);
+            max_m = std::max(max_m, op[k + 1] - op[k]);
+        }
+        off[p] = e0;
+        off[(size_t)P + p] = patches;
+        patches += max_m;
+        occurrences += op[K];
+        widest = std::max(widest, max_m);
+        nnz = e0 + count;
     }
-    std::vector<double> stats((size_t)K * kStats, 0.0);
+    occ.resize((size_t)nnz, 0);
+    occ_span.resize((size_t)nnz, make_int2(0, 0));
+    std::vector<double> stats((size_t)P * K * kStats, 0.0);
     if (timing_ms) timing_ms[0] = timing_ms[1] = timing_ms[2] = 0.0;
-    if (occ.empty()) {
+    if (occurrences == 0) {
         if (out_atom_stats) std::memcpy(out_atom_stats, stats.data(), stats.size() * sizeof(double));
-        return HSCKSVD_OK;                                              // no atom occurs: nothing changes
+        return HSCKSVD_OK;                                              // no atom of any problem occurs: nothing changes
     }
-    if (plan == kPlanAuto) plan = max_m >= HSCKSVD_WIDE_FROM_OCCURRENCES ? kPlanWide : kPlanOne;
+    if (plan == kPlanAuto) plan = widest >= HSCKSVD_WIDE_FROM_OCCURRENCES ? kPlanWide : kPlanOne;
 
     HSC_TRY(hipSetDevice(ctx->device));
-    const size_t bD = (size_t)K * n * sizeof(double), bI = (size_t)(K + 1) * sizeof(int),
-                 bR = (size_t)nnz * sizeof(int), bV = (size_t)nnz * sizeof(double), bO = occ.size() * sizeof(int),
-                 bS = (size_t)K * kStats * sizeof(double), bP = (size_t)max_m * n * sizeof(double),
-                 bB = occ.size() * sizeof(int2), bG = (size_t)n2 * n2 * sizeof(double);
-    const size_t bytes[9] = {bD, bI, bR, bV, bO, bI + bS + 16, bP, bB, bG};
+    const size_t bD = (size_t)P * K * n * sizeof(double), bI = (size_t)P * (K + 1) * sizeof(int), bR = (size_t)nnz * sizeof(int),
+                 bV = (size_t)nnz * sizeof(double), bS = (size_t)P * K * kStats * sizeof(double),
+                 bP = (size_t)patches * n * sizeof(double), bB = (size_t)nnz * sizeof(int2), bG = (size_t)n2 * n2 * sizeof(double),
+                 bF = off.size() * sizeof(long long);
+    const size_t bytes[10] = {bD, bI, bR, bV, bR, bI + bS + 16, bP, bB, bG, bF};
     if (int rc = ctx->buf.ensure(ctx, bytes, fn)) return rc;
-    int* d_occ_ptr = (int*)ctx->buf[5];
-    double* d_stats = (double*)((char*)ctx->buf[5] + (bI + 15) / 16 * 16);
-    hipStream_t st = ctx->stream;
-    HSC_TRY(hipEventRecord(ctx->ev[0], st));
-    HSC_TRY(hipMemcpyAsync(ctx->buf[0], D, bD, hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(ctx->buf[1], indptr, bI, hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(ctx->buf[2], indices, bR, hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(ctx->buf[3], data, bV, hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(ctx->buf[4], occ.data(), bO, hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(d_occ_ptr, occ_ptr.data(), bI, hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(ctx->buf[7], occ_span.data(), bB, hipMemcpyHostToDevice, st));
-    HSC_TRY(hipEventRecord(ctx->ev[1], st));
     SweepArgs args;
     args.K = K;
     args.W = W;
@@ -497,15 +521,27 @@ int run_update(hscksvd_ctx* ctx, const char* fn, int B, const int32_t* row_offse
     args.rows = (const int*)ctx->buf[2];
     args.vals = (double*)ctx->buf[3];
     args.occ = (const int*)ctx->buf[4];
-    args.occ_ptr = d_occ_ptr;
-    args.occ_span = (const int2*)ctx->buf[7];
+    args.occ_ptr = (const int*)ctx->buf[5];
+    args.stats = (double*)((char*)ctx->buf[5] + (bI + 15) / 16 * 16);
     args.P = (double*)ctx->buf[6];
+    args.occ_span = (const int2*)ctx->buf[7];
     args.G = (double*)ctx->buf[8];
-    args.stats = d_stats;
+    const long long* d_off = (const long long*)ctx->buf[9];
+    hipStream_t st = ctx->stream;
+    HSC_TRY(hipEventRecord(ctx->ev[0], st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[0], D, bD, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[1], indptr, bI, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[2], indices, bR, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[3], data, bV, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[4], occ.data(), bR, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[5], occ_ptr.data(), bI, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[7], occ_span.data(), bB, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipMemcpyAsync(ctx->buf[9], off.data(), bF, hipMemcpyHostToDevice, st));
+    HSC_TRY(hipEventRecord(ctx->ev[1], st));
     if (plan == kPlanOne) {
-        hipLaunchKernelGGL(ksvd_sweep_kernel, dim3(1), dim3(kThreads), 0, st, args);
-    } else {
-        HSC_TRY(hipMemsetAsync(d_stats, 0, bS, st));
+        hipLaunchKernelGGL(ksvd_sweep_kernel, dim3(P), dim3(kThreads), 0, st, args, d_off, d_off + P);
+    } else {                                                            // (P = 1: `args` is the problem)
+        HSC_TRY(hipMemsetAsync(args.stats, 0, bS, st));
         const int waves = kGridThreads / 64;
         for (int k = 0; k < K; ++k) {
             const int m = occ_ptr[k + 1] - occ_ptr[k];
@@ -521,7 +557,7 @@ int run_update(hscksvd_ctx* ctx, const char* fn, int B, const int32_t* row_offse
     HSC_TRY(hipEventRecord(ctx->ev[2], st));
     HSC_TRY(hipMemcpyAsync(D, ctx->buf[0], bD, hipMemcpyDeviceToHost, st));
     HSC_TRY(hipMemcpyAsync(data, ctx->buf[3], bV, hipMemcpyDeviceToHost, st));
-    HSC_TRY(hipMemcpyAsync(stats.data(), d_stats, bS, hipMemcpyDeviceToHost, st));
+    HSC_TRY(hipMemcpyAsync(stats.data(), args.stats, bS, hipMemcpyDeviceToHost, st));
     HSC_TRY(hipEventRecord(ctx->ev[3], st));
     HSC_TRY(hipStreamSynchronize(st));
     if (timing_ms)
@@ -539,8 +575,8 @@ extern "C" int hscksvd_update(hscksvd_ctx* ctx, int T, int K, int W, int F, doub
     if (T < 1 || K < 1 || W < 1 || F < 1)
         return fail(ctx, HSCKSVD_ERR_INVALID, "hscksvd_update: bad shape T = %d, K = %d, W = %d, F = %d", T, K, W, F);
     const int32_t row_offsets[2] = {0, T};
-    return run_update(ctx, "hscksvd_update", 1, row_offsets, K, W, F, D, indptr, indices, data, use_pca, kPlanOne,
-                      out_atom_stats, timing_ms);
+    return run_update(ctx, "hscksvd_update", false, 1, nullptr, 1, row_offsets, K, W, F, D, indptr, indices, data, use_pca,
+                      kPlanOne, out_atom_stats, timing_ms);
 }
 
 extern "C" int hscksvd_update_batch(hscksvd_ctx* ctx, int B, int T, int K, int W, int F, double* D, const int64_t* entry_offsets,
@@ -551,108 +587,9 @@ extern "C" int hscksvd_update_batch(hscksvd_ctx* ctx, int B, int T, int K, int W
     if (!ctx) return fail(nullptr, HSCKSVD_ERR_INVALID, "%s: ctx is NULL", fn);
     if (B < 1 || T < 1 || K < 1 || W < 1 || F < 1)
         return fail(ctx, HSCKSVD_ERR_INVALID, "%s: bad shape B = %d, T = %d, K = %d, W = %d, F = %d", fn, B, T, K, W, F);
-    if (W * F > kMaxN) return fail(ctx, HSCKSVD_ERR_UNSUPPORTED, "%s: W * F = %d exceeds the limit of %d", fn, W * F, kMaxN);
-    if (use_pca && F != 1) return fail(ctx, HSCKSVD_ERR_UNSUPPORTED, "%s: the PCA branch needs F = 1 (got F = %d)", fn, F);
-    if (!D || !indptr || !entry_offsets) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: D, indptr or entry_offsets is NULL", fn);
-    if (entry_offsets[0] != 0) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: entry_offsets[0] = %lld, expected 0", fn, (long long)entry_offsets[0]);
-    for (int b = 0; b < B; ++b)
-        if (entry_offsets[b + 1] < entry_offsets[b]) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: entry_offsets decreases at problem %d", fn, b);
-    const long long nnz = entry_offsets[B];
-    if (nnz >= (1ll << 31)) return fail(ctx, HSCKSVD_ERR_UNSUPPORTED, "%s: %lld stored entries in all, the limit is 2^31 - 1", fn, nnz);
-    if (nnz > 0 && (!indices || !data)) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: indices or data is NULL", fn);
-    const int n = W * F;
-
-    // per problem: hscksvd_update's checks, then its occurrences (entry ids relative to the problem's first entry, at the
-    // problem's own place in the entry arrays) and the room its patches need
-    std::vector<int> occ_ptr((size_t)B * (K + 1), 0), occ((size_t)nnz, 0);
-    std::vector<int2> occ_span((size_t)nnz, make_int2(0, T));
-    std::vector<long long> eoff((size_t)B), poff((size_t)B);
-    long long patches = 0, occurrences = 0;
-    for (int b = 0; b < B; ++b) {
-        const int32_t* ip = indptr + (size_t)b * (K + 1);
-        const long long e0 = entry_offsets[b];
-        const int32_t* idx = indices + e0;
-        const double* val = data + e0;
-        if (ip[0] != 0) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: problem %d: indptr[0] = %d, expected 0", fn, b, ip[0]);
-        for (int k = 0; k < K; ++k)
-            if (ip[k + 1] < ip[k]) return fail(ctx, HSCKSVD_ERR_INVALID, "%s: problem %d: indptr decreases at column %d", fn, b, k);
-        if (ip[K] != entry_offsets[b + 1] - e0)
-            return fail(ctx, HSCKSVD_ERR_INVALID, "%s: problem %d: indptr[K] = %d, but entry_offsets gives it %lld entries", fn, b, ip[K],
-                        (long long)(entry_offsets[b + 1] - e0));
-        int* op = occ_ptr.data() + (size_t)b * (K + 1);
-        int count = 0, max_m = 0;
-        for (int k = 0; k < K; ++k) {
-            for (int e = ip[k]; e < ip[k + 1]; ++e) {
-                if (idx[e] < 0 || idx[e] >= T)
-                    return fail(ctx, HSCKSVD_ERR_INVALID, "%s: problem %d: row %d of entry %d is outside [0, %d)", fn, b, idx[e], e, T);
-                if (e > ip[k] && idx[e] <= idx[e - 1])
-                    return fail(ctx, HSCKSVD_ERR_INVALID, "%s: problem %d: the rows of column %d are not strictly ascending", fn, b, k);
-                if (val[e] != 0.0) occ[(size_t)e0 + count++] = e;
-            }
-            op[k + 1] = count;
-            max_m = std::max(max_m, op[k + 1] - op[k]);
-        }
-        eoff[b] = e0;
-        poff[b] = patches;
-        patches += max_m;
-        occurrences += count;
-    }
-    std::vector<double> stats((size_t)B * K * kStats, 0.0);
-    if (timing_ms) timing_ms[0] = timing_ms[1] = timing_ms[2] = 0.0;
-    if (occurrences == 0) {
-        if (out_atom_stats) std::memcpy(out_atom_stats, stats.data(), stats.size() * sizeof(double));
-        return HSCKSVD_OK;                                              // no atom of any problem occurs: nothing changes
-    }
-
-    HSC_TRY(hipSetDevice(ctx->device));
-    const size_t bD = (size_t)B * K * n * sizeof(double), bI = (size_t)B * (K + 1) * sizeof(int), bR = (size_t)nnz * sizeof(int),
-                 bV = (size_t)nnz * sizeof(double), bS = (size_t)B * K * kStats * sizeof(double),
-                 bP = (size_t)patches * n * sizeof(double), bB = (size_t)nnz * sizeof(int2), bO = (size_t)B * sizeof(long long);
-    const size_t bytes[9] = {bD, bI, bR, bV, bR, bI + bS + 16, bP, bB, 2 * bO};     // (slot 8: the two offset arrays)
-    if (int rc = ctx->buf.ensure(ctx, bytes, fn)) return rc;
-    int* d_occ_ptr = (int*)ctx->buf[5];
-    double* d_stats = (double*)((char*)ctx->buf[5] + (bI + 15) / 16 * 16);
-    long long* d_eoff = (long long*)ctx->buf[8];
-    long long* d_poff = d_eoff + B;
-    hipStream_t st = ctx->stream;
-    HSC_TRY(hipEventRecord(ctx->ev[0], st));
-    HSC_TRY(hipMemcpyAsync(ctx->buf[0], D, bD, hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(ctx->buf[1], indptr, bI, hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(ctx->buf[2], indices, bR, hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(ctx->buf[3], data, bV, hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(ctx->buf[4], occ.data(), bR, hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(d_occ_ptr, occ_ptr.data(), bI, hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(ctx->buf[7], occ_span.data(), bB, hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(d_eoff, eoff.data(), bO, hipMemcpyHostToDevice, st));
-    HSC_TRY(hipMemcpyAsync(d_poff, poff.data(), bO, hipMemcpyHostToDevice, st));
-    HSC_TRY(hipEventRecord(ctx->ev[1], st));
-    SweepArgs args;
-    args.K = K;
-    args.W = W;
-    args.F = F;
-    args.use_pca = use_pca ? 1 : 0;
-    args.D = (double*)ctx->buf[0];
-    args.indptr = (const int*)ctx->buf[1];
-    args.rows = (const int*)ctx->buf[2];
-    args.vals = (double*)ctx->buf[3];
-    args.occ = (const int*)ctx->buf[4];
-    args.occ_ptr = d_occ_ptr;
-    args.occ_span = (const int2*)ctx->buf[7];
-    args.P = (double*)ctx->buf[6];
-    args.G = nullptr;                                                   // (plan 2's: never read here)
-    args.stats = d_stats;
-    hipLaunchKernelGGL(ksvd_sweep_batch_kernel, dim3(B), dim3(kThreads), 0, st, args, d_eoff, d_poff);
-    HSC_TRY(hipGetLastError());
-    HSC_TRY(hipEventRecord(ctx->ev[2], st));
-    HSC_TRY(hipMemcpyAsync(D, ctx->buf[0], bD, hipMemcpyDeviceToHost, st));
-    HSC_TRY(hipMemcpyAsync(data, ctx->buf[3], bV, hipMemcpyDeviceToHost, st));
-    HSC_TRY(hipMemcpyAsync(stats.data(), d_stats, bS, hipMemcpyDeviceToHost, st));
-    HSC_TRY(hipEventRecord(ctx->ev[3], st));
-    HSC_TRY(hipStreamSynchronize(st));
-    if (timing_ms)
-        if (int rc = hsc::add_times(ctx, 3, timing_ms)) return rc;          // (zeroed above)
-    if (out_atom_stats) std::memcpy(out_atom_stats, stats.data(), stats.size() * sizeof(double));
-    return HSCKSVD_OK;
+    const int32_t row_offsets[2] = {0, T};
+    return run_update(ctx, fn, true, B, entry_offsets, 1, row_offsets, K, W, F, D, indptr, indices, data, use_pca, kPlanOne,
+                      out_atom_stats, timing_ms);
 }
 
 extern "C" int hscksvd_update_corpus(hscksvd_ctx* ctx, int B, const int32_t* row_offsets, int K, int W, int F, double* D,
@@ -671,5 +608,7 @@ extern "C" int hscksvd_update_corpus(hscksvd_ctx* ctx, int B, const int32_t* row
     }
     if (plan != kPlanAuto && plan != kPlanOne && plan != kPlanWide)
         return fail(ctx, HSCKSVD_ERR_UNSUPPORTED, "%s: unknown plan %d (0 auto, 1 one workgroup, 2 wide)", fn, plan);
-    return run_update(ctx, fn, B, row_offsets, K, W, F, D, indptr, indices, data, use_pca, plan, out_atom_stats, timing_ms);
+    return run_update(ctx, fn, false, 1, nullptr, B, row_offsets, K, W, F, D, indptr, indices, data, use_pca, plan, out_atom_stats,
+                      timing_ms);
 }
+

@@ -84,6 +84,34 @@ def check_update_shapes(T, W, F, usePCA):
                          'W * F eigenvector to a [W, F] atom' % F)
 
 
+def _dictionary_copy(D, ndim):
+    """D [..,K,W] or [..,K,W,F] as the float64 C-ordered copy of `ndim` dimensions (F explicit) that the library updates."""
+    return np.array(D.reshape(D.shape[:ndim - 1] + (-1,)), dtype=np.float64, order='C')
+
+
+def _coefficient_copy(c):
+    """A sparse [T,K] matrix as a float64 CSC copy with sorted rows: what the library's indptr / indices / data describe."""
+    c = scipy.sparse.csc_matrix(c, dtype=np.float64, copy=True)
+    if not c.has_sorted_indices:
+        c.sort_indices()
+    return c
+
+
+def _sweep(device, entry, lead, D, offsets, indptr, indices, data, usePCA, plan=()):
+    """The call the three updates end in: hscksvd_<entry>(*lead, K, W, F, D, *offsets, indptr, indices, data, usePCA, *plan,
+    stats, timing), D from _dictionary_copy and updated in place.  Returns (the updated data, stats D.shape[:-2] + [4], timing_ms)."""
+    K, W, F = D.shape[-3:]
+    indptr = np.ascontiguousarray(indptr, dtype=np.int32)
+    indices = np.ascontiguousarray(indices, dtype=np.int32)
+    data = np.ascontiguousarray(data, dtype=np.float64)
+    stats = np.zeros(D.shape[:-2] + (ATOM_STATS,), dtype=np.float64)
+    timing = np.zeros((3,), dtype=np.float64)
+    p = _native._ptr
+    _context(device).call(entry, *lead, K, W, F, p(D), *offsets, p(indptr), p(indices), p(data), 1 if usePCA else 0, *plan,
+                          p(stats), p(timing))
+    return data, stats, timing
+
+
 def update(D, coefficients, usePCA=False, device=0):
     """One sweep of the K-SVD dictionary update (hscksvd_update) on D [K,W] or [K,W,F] and the [T,K] sparse
     coefficients the coder returned.  Returns (D float64 of D's shape, csc_matrix [T,K] float64 with the updated
@@ -91,25 +119,15 @@ def update(D, coefficients, usePCA=False, device=0):
     The inputs are not modified."""
     D = np.asarray(D)
     assert D.ndim == 2 or D.ndim == 3
-    K, W = D.shape[0], D.shape[1]
-    D3 = np.array(D.reshape((K, W, -1)), dtype=np.float64, order='C')
-    F = D3.shape[2]
+    D3 = _dictionary_copy(D, 3)
+    K, W, F = D3.shape
     T = coefficients.shape[0]
     assert coefficients.shape[1] == K
     check_update_shapes(T, W, F, usePCA)
-    csc = scipy.sparse.csc_matrix(coefficients, dtype=np.float64, copy=True)
-    if not csc.has_sorted_indices:
-        csc.sort_indices()
-    indptr = np.ascontiguousarray(csc.indptr, dtype=np.int32)
-    indices = np.ascontiguousarray(csc.indices, dtype=np.int32)
-    data = np.ascontiguousarray(csc.data, dtype=np.float64)
-    stats = np.zeros((K, ATOM_STATS), dtype=np.float64)
-    timing = np.zeros((3,), dtype=np.float64)
-    ctx = _context(device)
-    p = _native._ptr
-    ctx.call('update', T, K, W, F, p(D3), p(indptr), p(indices), p(data), 1 if usePCA else 0, p(stats), p(timing))
-    out = scipy.sparse.csc_matrix((data, indices, indptr), shape=csc.shape)
-    return D3.reshape(D.shape), out, stats, timing
+    csc = _coefficient_copy(coefficients)
+    data, stats, timing = _sweep(device, 'update', (T,), D3, (), csc.indptr, csc.indices, csc.data, usePCA)
+    csc.data[:] = data
+    return D3.reshape(D.shape), csc, stats, timing
 
 
 def update_corpus(D, coefficients, usePCA=False, device=0, plan='auto'):
@@ -121,9 +139,8 @@ def update_corpus(D, coefficients, usePCA=False, device=0, plan='auto'):
     The inputs are not modified."""
     D = np.asarray(D)
     assert D.ndim == 2 or D.ndim == 3
-    K, W = D.shape[0], D.shape[1]
-    D3 = np.array(D.reshape((K, W, -1)), dtype=np.float64, order='C')
-    F = D3.shape[2]
+    D3 = _dictionary_copy(D, 3)
+    K, W, F = D3.shape
     if plan not in PLANS:
         raise ValueError("K-SVD: plan must be 'auto', 'one' or 'wide' (got %r)" % (plan,))
     coefficients = list(coefficients)
@@ -135,25 +152,15 @@ def update_corpus(D, coefficients, usePCA=False, device=0, plan='auto'):
     offsets = np.concatenate([[0], np.cumsum([c.shape[0] for c in coefficients], dtype=np.int64)])
     if offsets[-1] >= 2 ** 31:
         raise NotImplementedError('K-SVD on the GPU: the corpus has %d samples in all, the limit is 2^31 - 1' % offsets[-1])
-    cscs = []
-    for c in coefficients:
-        c = scipy.sparse.csc_matrix(c, dtype=np.float64, copy=True)
-        if not c.has_sorted_indices:
-            c.sort_indices()
-        cscs.append(c)
+    cscs = [_coefficient_copy(c) for c in coefficients]
     # the stack in CSC: column, then signal, then time -- a stable sort by column of the signals' entries in signal order
     cols = np.concatenate([np.repeat(np.arange(K), np.diff(c.indptr)) for c in cscs])
     order = np.argsort(cols, kind='stable')
-    indptr = np.concatenate([[0], np.cumsum(np.bincount(cols, minlength=K))]).astype(np.int32)
-    indices = np.concatenate([c.indices + off for c, off in zip(cscs, offsets[:-1])])[order].astype(np.int32)
-    data = np.ascontiguousarray(np.concatenate([c.data for c in cscs])[order], dtype=np.float64)
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(cols, minlength=K))])
+    indices = np.concatenate([c.indices + off for c, off in zip(cscs, offsets[:-1])])[order]
     row_offsets = offsets.astype(np.int32)
-    stats = np.zeros((K, ATOM_STATS), dtype=np.float64)
-    timing = np.zeros((3,), dtype=np.float64)
-    ctx = _context(device)
-    p = _native._ptr
-    ctx.call('update_corpus', len(cscs), p(row_offsets), K, W, F, p(D3), p(indptr), p(indices), p(data),
-             1 if usePCA else 0, PLANS[plan], p(stats), p(timing))
+    data, stats, timing = _sweep(device, 'update_corpus', (len(cscs), _native._ptr(row_offsets)), D3, (), indptr, indices,
+                                 np.concatenate([c.data for c in cscs])[order], usePCA, (PLANS[plan],))
     back = np.empty_like(data)
     back[order] = data
     first = 0
@@ -177,9 +184,8 @@ def update_batch(Ds, coefficients, usePCA=False, device=0):
     Ds = np.asarray(Ds)
     if Ds.ndim != 3 and Ds.ndim != 4:
         raise ValueError('K-SVD: the dictionaries must be [B,K,W] or [B,K,W,F] (got %d dimensions)' % Ds.ndim)
-    B, K, W = Ds.shape[0], Ds.shape[1], Ds.shape[2]
-    D4 = np.array(Ds.reshape((B, K, W, -1)), dtype=np.float64, order='C')
-    F = D4.shape[3]
+    D4 = _dictionary_copy(Ds, 4)
+    B, K, W, F = D4.shape
     coefficients = list(coefficients)
     if len(coefficients) != B or B == 0:
         raise ValueError('K-SVD: %d coefficient matrices for %d dictionaries' % (len(coefficients), B))
@@ -188,23 +194,12 @@ def update_batch(Ds, coefficients, usePCA=False, device=0):
         if c.shape != (T, K):
             raise ValueError('K-SVD: update_batch needs coefficient matrices of one shape [T,K] = (%d, %d) (got %s)' % (T, K, c.shape))
     check_update_shapes(T, W, F, usePCA)
-    cscs = []
-    for c in coefficients:
-        c = scipy.sparse.csc_matrix(c, dtype=np.float64, copy=True)
-        if not c.has_sorted_indices:
-            c.sort_indices()
-        cscs.append(c)
+    cscs = [_coefficient_copy(c) for c in coefficients]
     offsets = np.concatenate([[0], np.cumsum([c.nnz for c in cscs], dtype=np.int64)]).astype(np.int64)
     if offsets[-1] >= 2 ** 31:
         raise NotImplementedError('K-SVD on the GPU: %d stored coefficients in all, the limit is 2^31 - 1' % offsets[-1])
-    indptr = np.ascontiguousarray(np.stack([c.indptr for c in cscs]), dtype=np.int32)
-    indices = np.ascontiguousarray(np.concatenate([c.indices for c in cscs]), dtype=np.int32)
-    data = np.ascontiguousarray(np.concatenate([c.data for c in cscs]), dtype=np.float64)
-    stats = np.zeros((B, K, ATOM_STATS), dtype=np.float64)
-    timing = np.zeros((3,), dtype=np.float64)
-    ctx = _context(device)
-    p = _native._ptr
-    ctx.call('update_batch', B, T, K, W, F, p(D4), p(offsets), p(indptr), p(indices), p(data), 1 if usePCA else 0, p(stats), p(timing))
+    data, stats, timing = _sweep(device, 'update_batch', (B, T), D4, (_native._ptr(offsets),), np.stack([c.indptr for c in cscs]),
+                                 np.concatenate([c.indices for c in cscs]), np.concatenate([c.data for c in cscs]), usePCA)
     for b, c in enumerate(cscs):
         c.data[:] = data[offsets[b]:offsets[b + 1]]
     return D4.reshape(Ds.shape), cscs, stats, timing
@@ -274,16 +269,27 @@ class ConvolutionalKSVDLearner(object):
         F = 1 if data.ndim == 1 else data.shape[1]
         check_update_shapes(data.shape[0], self.windowSize, F, usePCA)
 
+    def _initial_D(self, data, rng):
+        """The reference's initial dictionary ('noise') for data [T] or [T,F], drawn from `rng` (None: numpy's global generator)."""
+        from .learning import ConvolutionalDictionaryLearner
+        D = ConvolutionalDictionaryLearner(self.k, self.windowSize, rng=rng)._init_D(data, initMethod='noise')
+        return np.asarray(D, dtype=np.float64)
+
+    @staticmethod
+    def _record(alpha, nnz, t0, t1, t2, timing, atoms, **more):
+        """One iteration's lastStats record: encode from t0 to t1, update to t2 (seconds), the update's timing and atoms [K,4];
+        `more`: trainCorpus' plan, the batch encodes' variant."""
+        return dict(alpha=float(alpha), nnz=int(nnz), encode_ms=1e3 * (t1 - t0), update_ms=1e3 * (t2 - t1),
+                    sweep_ms=float(timing[1]), n_k=atoms[:, 0].astype(np.int64), eigenvalues=atoms[:, 1:3].copy(), **more)
+
     def train(self, data, method='locomp', maxIterations=100, tolerance=0.0, nbNonzeroCoefs=None, toleranceSnr=40.0,
               usePCA=False):
         """hsc/modeling.py:528-641 (`_train_ksvd`).  data [T] or [T,F]; returns D float64 [K,W] or [K,W,F]."""
-        from .learning import ConvolutionalDictionaryLearner
         from .modeling import ConvolutionalSparseCoder
         data = np.asarray(data)
         self._check(data, method, usePCA)
         load_library()                                       # no CPU path: fail before the first encode
-        D = ConvolutionalDictionaryLearner(self.k, self.windowSize, rng=self.rng)._init_D(data, initMethod='noise')
-        D = np.asarray(D, dtype=np.float64)
+        D = self._initial_D(data, self.rng)
         stats = []
         n, alpha = 0, tolerance + 1.0
         while n < maxIterations and alpha > tolerance:
@@ -295,9 +301,7 @@ class ConvolutionalKSVDLearner(object):
             D, coefficients, atoms, timing = update(oldD, coefficients, usePCA, self.device)
             t2 = time.perf_counter()
             alpha = np.sqrt(np.sum(np.square(D - oldD)))
-            stats.append(dict(alpha=float(alpha), nnz=int(coefficients.nnz), encode_ms=1e3 * (t1 - t0),
-                              update_ms=1e3 * (t2 - t1), sweep_ms=float(timing[1]), n_k=atoms[:, 0].astype(np.int64),
-                              eigenvalues=atoms[:, 1:3].copy()))
+            stats.append(self._record(alpha, coefficients.nnz, t0, t1, t2, timing, atoms))
             logger.debug('K-SVD iteration %d: tolerance = %f, sparsity = %f' % (
                 n, alpha, float(coefficients.nnz) / np.prod(coefficients.shape)))
             n += 1
@@ -315,7 +319,6 @@ class ConvolutionalKSVDLearner(object):
         (n < maxIterations and alpha > tolerance); a stopped learner is neither encoded nor updated.  DESIGN.md section 24.
         Returns (D float64 [B,K,W] or [B,K,W,F], per-learner lastStats lists: train's records plus variant, the encode's kernel
         variant; encode_ms and update_ms are the batch's wall clock, shared by the learners that ran in it)."""
-        from .learning import ConvolutionalDictionaryLearner
         from .modeling import is_ragged
         self._check_method(method)
         if is_ragged(sequences):
@@ -335,8 +338,7 @@ class ConvolutionalKSVDLearner(object):
         else:
             rngs = [self.rng if rngs is None else rngs] * B
         load_library()                                       # no CPU path: fail before the first encode
-        D = np.stack([np.asarray(ConvolutionalDictionaryLearner(self.k, self.windowSize, rng=rngs[b])._init_D(sequences[b], initMethod='noise'),
-                                 dtype=np.float64) for b in range(B)])
+        D = np.stack([self._initial_D(sequences[b], rngs[b]) for b in range(B)])
         coder = self._coder(method)
         stats = [[] for _ in range(B)]
         n = 0
@@ -353,9 +355,7 @@ class ConvolutionalKSVDLearner(object):
             for i, b in enumerate(running):
                 alpha = np.sqrt(np.sum(np.square(newD[i] - D[b])))
                 D[b] = newD[i]
-                stats[b].append(dict(alpha=float(alpha), nnz=int(coefficients[i].nnz), encode_ms=1e3 * (t1 - t0),
-                                     update_ms=1e3 * (t2 - t1), sweep_ms=float(timing[1]), n_k=atoms[i, :, 0].astype(np.int64),
-                                     eigenvalues=atoms[i, :, 1:3].copy(), variant=res.variant))
+                stats[b].append(self._record(alpha, coefficients[i].nnz, t0, t1, t2, timing, atoms[i], variant=res.variant))
                 logger.debug('K-SVD learner %d iteration %d: tolerance = %f, sparsity = %f' % (
                     b, n, alpha, float(coefficients[i].nnz) / np.prod(coefficients[i].shape)))
                 if n + 1 < maxIterations and alpha > tolerance:
@@ -375,7 +375,6 @@ class ConvolutionalKSVDLearner(object):
         result on that signal, bit for bit.  Returns D float64 [K,W] or [K,W,F].
         lastStats: `train`'s records (nnz: the stored coefficients of all signals) plus plan (1: one workgroup, 2: wide)
         and variant (the encode's kernel variant)."""
-        from .learning import ConvolutionalDictionaryLearner
         from .modeling import ConvolutionalSparseCoder, is_ragged, reject_ragged
         self._check_method(method)
         if method == 'locomp':
@@ -388,8 +387,7 @@ class ConvolutionalKSVDLearner(object):
         load_library()                                       # no CPU path: fail before the first encode
         if not is_ragged(sequences, lengths):
             sequences = np.asarray(sequences)
-        D = ConvolutionalDictionaryLearner(self.k, self.windowSize, rng=self.rng)._init_D(np.concatenate(seqs), initMethod='noise')
-        D = np.asarray(D, dtype=np.float64)
+        D = self._initial_D(np.concatenate(seqs), self.rng)
         stats = []
         n, alpha = 0, tolerance + 1.0
         while n < maxIterations and alpha > tolerance:
@@ -402,9 +400,8 @@ class ConvolutionalKSVDLearner(object):
             t2 = time.perf_counter()
             alpha = np.sqrt(np.sum(np.square(D - oldD)))
             nnz = sum(int(c.nnz) for c in coefficients)
-            stats.append(dict(alpha=float(alpha), nnz=nnz, encode_ms=1e3 * (t1 - t0), update_ms=1e3 * (t2 - t1),
-                              sweep_ms=float(timing[1]), n_k=atoms[:, 0].astype(np.int64), eigenvalues=atoms[:, 1:3].copy(),
-                              plan=2 if np.max(atoms[:, 0]) >= WIDE_FROM_OCCURRENCES else 1, variant=res.variant))
+            stats.append(self._record(alpha, nnz, t0, t1, t2, timing, atoms,
+                                      plan=2 if np.max(atoms[:, 0]) >= WIDE_FROM_OCCURRENCES else 1, variant=res.variant))
             logger.debug('K-SVD corpus iteration %d: tolerance = %f, sparsity = %f' % (
                 n, alpha, float(nnz) / (sum(q.shape[0] for q in seqs) * self.k)))
             n += 1

@@ -3,7 +3,8 @@ of the dictionary-per-signal encode.
 
 update_batch: problem b equals ksvd.update on problem b bit for bit -- D, coefficient values and stats -- in both branches, for
 problems that are dense in occurrences, have an atom without occurrence, an atom with one occurrence, or no stored entry at
-all.  trainBatch: learner b equals train on sequences[b] with the same seed, bit for bit, every learner stops on its own, and
+all; and, as the three entry points share one driver, every problem also equals the float64 restatement
+(tests/ksvd_restatement.py) within ksvd.update's tolerances, problems of very different entry counts included.  trainBatch: learner b equals train on sequences[b] with the same seed, bit for bit, every learner stops on its own, and
 a shared generator draws the initial dictionaries in batch order."""
 import numpy as np
 import pytest
@@ -69,6 +70,38 @@ def test_update_batch_equals_update(F, usePCA):
     assert np.array_equal(lD, newD[:2])
 
 
+@pytest.mark.parametrize('F,usePCA', [(1, False), (2, False), (1, True)], ids=['F1_svd', 'F2_svd', 'F1_pca'])
+def test_update_batch_matches_restatement(F, usePCA):
+    """Every problem of the batch against the float64 restatement, at ksvd.update's tolerances: an anchor outside the library,
+    which test_update_batch_equals_update (one driver behind both sides) is not."""
+    from hsc_amd import ksvd
+    from tests.test_gpu_ksvd_limits import compare_with_restatement
+    Ds, Cs = _problems(F)
+    newD, newC, stats, _ = ksvd.update_batch(Ds, Cs, usePCA=usePCA)
+    for b in range(4):
+        st_ref = compare_with_restatement((newD[b], newC[b], stats[b]), Ds[b], Cs[b], usePCA)
+        assert np.any(st_ref[:, 3] == 1) == (b < 3)                              # (eigenvectors were taken)
+
+
+@pytest.mark.parametrize('usePCA', [False, True], ids=['svd', 'pca'])
+def test_update_batch_uneven_problems_match_restatement(usePCA):
+    """Problems of 103, 0 and 1 stored entries, the empty one in the middle, in both orders: an entry offset or a patch offset
+    that is wrong puts a problem's entries or patches into a neighbour's."""
+    from hsc_amd import ksvd
+    from tests.test_gpu_ksvd_limits import compare_with_restatement
+    rng = np.random.RandomState(5)
+    Ds = rng.randn(3, K, W)
+    Ds /= np.sqrt(np.sum(Ds ** 2, axis=2, keepdims=True))
+    Cs = [_coefficients(rng, [25, 30, 20, 28]), scipy.sparse.csc_matrix((T, K)), _coefficients(rng, [0, 1, 0, 0])]
+    assert [c.nnz for c in Cs] == [103, 0, 1]
+    for order in ([0, 1, 2], [2, 1, 0]):
+        newD, newC, stats, _ = ksvd.update_batch(Ds[order], [Cs[b] for b in order], usePCA=usePCA)
+        for i, b in enumerate(order):
+            compare_with_restatement((newD[i], newC[i], stats[i]), Ds[b], Cs[b], usePCA)
+        assert [int(np.sum(stats[i, :, 0])) for i in range(3)] == [Cs[b].nnz for b in order]
+        assert np.array_equal(newD[1], Ds[1]) and not np.array_equal(newD[order.index(0)], Ds[0])
+
+
 def test_update_batch_all_empty():
     from hsc_amd import ksvd
     Ds, _ = _problems(1)
@@ -92,6 +125,27 @@ def test_update_batch_library_refusals():
     with pytest.raises(_native.HscmpError, match='problem 0: indptr\\[K\\] = 3') as ei:
         ctx.call('update_batch', 1, 100, 2, 8, 1, p(D), p(off), p(ip), None, None, 0, None, None)
     assert ei.value.code == -1
+    # the same three inputs through hscksvd_update and hscksvd_update_corpus: the same texts under their own names, no problem
+    # named; they have no entry_offsets to disagree with, so the third is three entries without indices or data
+    rows = np.array([0, 100], dtype=np.int32)
+    for fn, lead, plan in (('update', (100,), ()), ('update_corpus', (1, p(rows)), (0,))):
+        refused = []
+        for W, F, pca in ((33, 2, 0), (8, 2, 1), (8, 1, 0)):
+            with pytest.raises(_native.HscmpError) as ei:
+                ctx.call(fn, *lead, 2, W, F, p(D), p(ip), None, None, pca, *plan, None, None)
+            assert 'problem' not in str(ei.value)
+            refused.append((ei.value.code, str(ei.value).split(': ', 1)[1]))     # ('<fn> failed (<rc>): <the library's text>')
+        assert refused == [(-5, 'hscksvd_%s: W * F = 66 exceeds the limit of 64' % fn),
+                           (-5, 'hscksvd_%s: the PCA branch needs F = 1 (got F = 2)' % fn),
+                           (-1, 'hscksvd_%s: indices or data is NULL' % fn)]
+    # and a refusal of the per-problem checks, which only the batch prefixes
+    ip[0, 0] = 5
+    with pytest.raises(_native.HscmpError, match='hscksvd_update_batch: problem 0: indptr\\[0\\] = 5, expected 0'):
+        ctx.call('update_batch', 1, 100, 2, 8, 1, p(D), p(off), p(ip), None, None, 0, None, None)
+    with pytest.raises(_native.HscmpError, match='hscksvd_update: indptr\\[0\\] = 5, expected 0'):
+        ctx.call('update', 100, 2, 8, 1, p(D), p(ip), None, None, 0, None, None)
+    with pytest.raises(_native.HscmpError, match='hscksvd_update_corpus: indptr\\[0\\] = 5, expected 0'):
+        ctx.call('update_corpus', 1, p(rows), 2, 8, 1, p(D), p(ip), None, None, 0, 0, None, None)
 
 
 # ---- trainBatch ------------------------------------------------------------------------------------------------------
