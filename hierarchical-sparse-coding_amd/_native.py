@@ -27,7 +27,7 @@ METHOD_CMP, METHOD_LOCOMP = 0, 1
 EXPORTS = ['hscmp_version', 'hscmp_create', 'hscmp_destroy', 'hscmp_last_error', 'hscmp_set_stream', 'hscmp_set_method',
            'hscmp_synchronize', 'hscmp_set_dictionary', 'hscmp_set_dictionaries', 'hscmp_convolve1d', 'hscmp_select_best_atoms',
            'hscmp_update_inner_products', 'hscmp_table_open', 'hscmp_table_select', 'hscmp_table_update', 'hscmp_table_read', 'hscmp_assign_windows', 'hscmp_host_overlap_add', 'hscmp_host_slots_to_csc', 'hscmp_hierarchy_epilogue', 'hscmp_encode_batch',
-           'hscmp_encode_batch_device', 'hscmp_encode_batch_ragged', 'hscmp_encode_batch_ragged_device', 'hscmp_encode_batch_multi', 'hscmp_encode_batch_from_level', 'hscmp_load_level', 'hscmp_load_level_ragged', 'hscmp_continue', 'hscmp_grow_events', 'hscmp_mem_info', 'hscmp_copy_from_device', 'hscmp_stop_signal', 'hscmp_fetch_events',
+           'hscmp_encode_batch_device', 'hscmp_encode_batch_ragged', 'hscmp_encode_batch_ragged_device', 'hscmp_encode_batch_rules', 'hscmp_encode_batch_rules_device', 'hscmp_encode_batch_multi', 'hscmp_encode_batch_from_level', 'hscmp_load_level', 'hscmp_load_level_ragged', 'hscmp_continue', 'hscmp_grow_events', 'hscmp_mem_info', 'hscmp_copy_from_device', 'hscmp_stop_signal', 'hscmp_fetch_events',
            'hscmp_fetch_stats', 'hscmp_fetch_residual', 'hscmp_fetch_energies', 'hscmp_fetch_slots',
            'hscmp_get_device_view', 'hscmp_last_kernel_ms', 'hscmp_last_variant', 'hscmp_wide_plan', 'hscmp_wide_counters']
 
@@ -41,6 +41,13 @@ class HscmpParams(ctypes.Structure):
                 ('eps', ctypes.c_double),
                 ('max_events', ctypes.c_int32),
                 ('max_rounds', ctypes.c_int32)]
+
+
+class HscmpSignalRules(ctypes.Structure):
+    """hscmp_signal_rules: host pointers, each NULL or [B] (make_rules fills it and keeps the arrays alive)."""
+    _fields_ = [('nb_nonzero_coefs', ctypes.c_void_p),
+                ('tolerance_snr', ctypes.c_void_p),
+                ('tolerance_residual_scale', ctypes.c_void_p)]
 
 
 class HscmpDeviceView(ctypes.Structure):
@@ -110,6 +117,8 @@ def load_library():
     lib.hscmp_encode_batch_device.argtypes = [vp, vp, ci, ci, ctypes.POINTER(HscmpParams)]
     lib.hscmp_encode_batch_ragged.argtypes = [vp, vp, ci, ci, vp, ctypes.POINTER(HscmpParams)]
     lib.hscmp_encode_batch_ragged_device.argtypes = [vp, vp, ci, ci, vp, ctypes.POINTER(HscmpParams)]
+    lib.hscmp_encode_batch_rules.argtypes = [vp, vp, ci, ci, vp, ctypes.POINTER(HscmpSignalRules), ctypes.POINTER(HscmpParams)]
+    lib.hscmp_encode_batch_rules_device.argtypes = [vp, vp, ci, ci, vp, ctypes.POINTER(HscmpSignalRules), ctypes.POINTER(HscmpParams)]
     lib.hscmp_encode_batch_multi.argtypes = [vp, vp, ci, ci, vp, ctypes.POINTER(HscmpParams)]
     lib.hscmp_encode_batch_from_level.argtypes = [vp, vp, ci, ci, ctypes.c_double, ctypes.POINTER(HscmpParams)]
     lib.hscmp_load_level.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp]
@@ -225,6 +234,43 @@ def make_params(nbNonzeroCoefs=None, toleranceResidualScale=None, toleranceSnr=N
         tolerance_residual_scale=nan if toleranceResidualScale is None else float(toleranceResidualScale),
         null_coeff_thres=nan if minCoefficients is None else float(minCoefficients),
         eps=float(eps), max_events=int(maxEvents), max_rounds=int(maxRounds))
+
+
+def is_per_signal(v):
+    """A stop rule given per signal: anything with a length (list, tuple, array), not a scalar or None."""
+    return v is not None and np.ndim(v) > 0
+
+
+def make_rules(B, nbNonzeroCoefs=None, toleranceResidualScale=None, toleranceSnr=None):
+    """The hscmp_signal_rules of a batch of B signals: every argument that is a length-B sequence becomes that rule's array
+    (int32 / float64) and replaces that scalar of hscmp_params; a scalar or None beside it stays make_params' business.
+    None when all three are scalars or None: the batch has one set of rules and takes the plain entry points.
+    The struct keeps its arrays alive (`arrays`: name -> ndarray).  ValueError, naming the argument and the signal, for a wrong
+    length, NaN, a negative value or a non-integral nbNonzeroCoefs."""
+    given = (('nbNonzeroCoefs', nbNonzeroCoefs, 'nb_nonzero_coefs'), ('toleranceSnr', toleranceSnr, 'tolerance_snr'),
+             ('toleranceResidualScale', toleranceResidualScale, 'tolerance_residual_scale'))
+    if not any(is_per_signal(v) for _, v, _ in given):
+        return None
+    B = int(B)
+    rules = HscmpSignalRules()
+    rules.arrays = {}
+    for name, v, field in given:
+        if not is_per_signal(v):
+            continue
+        a = np.asarray(v, dtype=np.float64)
+        if a.shape != (B,):
+            raise ValueError('%s must be a scalar or have one entry per signal (%d), got shape %s' % (name, B, a.shape))
+        for b in range(B):
+            if np.isnan(a[b]):
+                raise ValueError('%s: signal %d: the value is NaN' % (name, b))
+            if a[b] < 0:
+                raise ValueError('%s: signal %d: the value %r is negative' % (name, b, float(a[b])))
+            if field == 'nb_nonzero_coefs' and (a[b] != np.floor(a[b]) or a[b] > np.iinfo(np.int32).max):
+                raise ValueError('%s: signal %d: the value %r is not an integer' % (name, b, float(a[b])))
+        a = np.ascontiguousarray(a, dtype=np.int32 if field == 'nb_nonzero_coefs' else np.float64)
+        rules.arrays[field] = a
+        setattr(rules, field, a.ctypes.data)
+    return rules
 
 
 class DeviceTable(object):
@@ -489,6 +535,27 @@ class Engine(object):
         assert lens.shape == (int(B),)
         self._check(self._lib.hscmp_encode_batch_ragged_device(self._h, ctypes.c_void_p(x_dev_ptr), int(B), int(T), _ptr(lens),
                                                                ctypes.byref(params)), 'hscmp_encode_batch_ragged_device')
+        self._batch = (int(B), int(T), int(params.max_events))
+
+    def encode_batch_rules(self, x, lengths, rules, params):
+        """encode_batch_ragged with stop rules per signal: `rules` from make_rules (its arrays replace the three scalars of
+        `params`), lengths int [B] or None (every signal has T samples).  The engine then holds a ragged batch."""
+        x3 = np.ascontiguousarray(x, dtype=self.dtype)
+        assert x3.ndim == 3 and x3.shape[2] == self.F
+        B, T = x3.shape[0], x3.shape[1]
+        lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+        assert lens is None or lens.shape == (B,)
+        self._check(self._lib.hscmp_encode_batch_rules(self._h, _ptr(x3), B, T, _ptr(lens), None if rules is None else ctypes.byref(rules),
+                                                       ctypes.byref(params)), 'hscmp_encode_batch_rules')
+        self._batch = (B, T, int(params.max_events))
+
+    def encode_batch_rules_device(self, x_dev_ptr, B, T, lengths, rules, params):
+        """x_dev_ptr: device address of [B,T,F] in the dictionary dtype; lengths host int [B] or None; asynchronous."""
+        lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+        assert lens is None or lens.shape == (int(B),)
+        self._check(self._lib.hscmp_encode_batch_rules_device(self._h, ctypes.c_void_p(x_dev_ptr), int(B), int(T), _ptr(lens),
+                                                              None if rules is None else ctypes.byref(rules), ctypes.byref(params)),
+                    'hscmp_encode_batch_rules_device')
         self._batch = (int(B), int(T), int(params.max_events))
 
     def encode_batch_multi(self, x, dict_of, params):

@@ -157,6 +157,7 @@ struct EncodePlan {
     bool bound_loop = false;  // the four-signal loop re-correlates as upper bounds (MfmaRecorr BOUND)
     bool ragged = false;      // signals of different lengths: the RAGGED instances of the loops read each signal's geometry
     bool multi = false;       // a dictionary per signal out of a set: the MULTI instances of the generic pair read it through dict_of
+    bool rules = false;       // stop rules per signal: a ragged batch whose RAGGED instances read ws.rules too
     Knobs knobs{};            // the encode's snapshot: the launches read pairing, row bitmaps and LDS pad from it
 };
 
@@ -189,6 +190,7 @@ struct Workspace {
     DevBuf lgram;             // [B][kLgramDoubles] LoCOMP: Gram matrices beyond the LDS copy
     DevBuf geom;              // [B][kGeomWords] of a ragged batch
     DevBuf dict_of;           // [B] the dictionary of every signal (hscmp_encode_batch_multi)
+    DevBuf rules;             // [B] SignalRule of a batch with stop rules per signal (hscmp_encode_batch_rules)
     DevBuf wide;              // control blocks and candidate arrays of the wide loop (hscmp_wide.h: wide_scratch_bytes)
 };
 
@@ -201,7 +203,7 @@ enum { kArenaEpiRep, kArenaEpiOffsets, kArenaEpiN, kArenaEpiColptr, kArenaEpiInd
 //  - a call that may replace the dictionary or a workspace buffer first drops what depends on it (drop_batch), in front of its
 //    first allocation; a failed hscmp_set_dictionary leaves no dictionary, a failed encode no batch, and every entry point
 //    answers either with HSCMP_ERR_STATE before it queues anything;
-//  - have_batch, ragged, geom, P, plan, B / T / cap / maxsel, last and last_x_dev are written together (commit_batch), after the
+//  - have_batch, ragged, geom, rules, P, plan, B / T / cap / maxsel, last and last_x_dev are written together (commit_batch), after the
 //    last launch of the encode has been queued without error;
 //  - listed_rows, rowflag_valid and rl_filled describe buffer contents, not the batch: they follow the writes to those buffers.
 struct hscmp_ctx {
@@ -230,6 +232,9 @@ struct hscmp_ctx {
     // next encode of any kind; the batch's P.T is the longest length and every per-signal array keeps that stride
     bool ragged = false;
     std::vector<int> geom;
+    // stop rules per signal (hscmp_encode_batch_rules): the table on the host and in ws.rules, from the encode's drop_batch until the
+    // next one (hscmp_continue resumes with it); empty: the rules of P apply to every signal
+    std::vector<SignalRule> rules;
     hscmp_params last{};
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool timed = false;
@@ -246,7 +251,7 @@ struct hscmp_ctx {
 // table and the listed rows belong to as well).
 static void drop_batch(hscmp_ctx* ctx, bool dictionary = false)
 {
-    ctx->have_batch = false; ctx->loaded = false; ctx->ragged = false; ctx->geom.clear();
+    ctx->have_batch = false; ctx->loaded = false; ctx->ragged = false; ctx->geom.clear(); ctx->rules.clear();
     if (dictionary) { ctx->tab_T = 0; ctx->listed_rows = 0; }
 }
 
@@ -582,9 +587,11 @@ static int sparse_init_split(int B, int T, int W)
 
 // Every workspace buffer holds what a batch of shape P needs afterwards (0 bytes: not needed, left as it is).  A buffer that is too
 // small is replaced, after one wait for the stream (the previous batch's kernels may still read it): on HSCMP_ERR_ALLOC some
-// buffers are gone, which is why the callers drop the batch first.  geom_bytes: the per-signal geometry of a ragged batch.
+// buffers are gone, which is why the callers drop the batch first.  geom_bytes: the per-signal geometry of a ragged batch;
+// rules_bytes: its table of stop rules per signal.
 // (element size and feature layout given explicitly: see make_params_g)
-static int ensure_workspace_g(hscmp_ctx* ctx, const DevParams& P, bool need_x, size_t es, bool multi_feature, bool row_lists, size_t geom_bytes = 0)
+static int ensure_workspace_g(hscmp_ctx* ctx, const DevParams& P, bool need_x, size_t es, bool multi_feature, bool row_lists, size_t geom_bytes = 0,
+                              size_t rules_bytes = 0)
 {
     const size_t B = P.B, TF = (size_t)P.T * P.F, T = P.T, cap = P.cap, ms = P.maxsel;
     const bool locomp = ctx->method == HSCMP_METHOD_LOCOMP;
@@ -601,7 +608,7 @@ static int ensure_workspace_g(hscmp_ctx* ctx, const DevParams& P, bool need_x, s
         {w.hkey, B * ((size_t)P.hmask + 1) * sizeof(unsigned long long)}, {w.hval, B * ((size_t)P.hmask + 1) * sizeof(int)},
         {w.head, (P.blocked || locomp) ? B * T * sizeof(int) : 0},
         {w.lgram, locomp ? B * lgram_doubles(P.lg_cap) * sizeof(double) : 0},
-        {w.geom, geom_bytes},
+        {w.geom, geom_bytes}, {w.rules, rules_bytes},
         // every shape the wide loop could take, whatever HSCMP_WIDE and the batch size will make plan_encode choose behind this
         // call (52 bytes per block of a round: wide_scratch_bytes)
         {w.wide, es == 4 && !multi_feature && !locomp && geom_bytes == 0 && wide_params_ok(P) ? wide_scratch_bytes(P.B, P.maxsel) : 0},
@@ -620,9 +627,9 @@ static int ensure_workspace_g(hscmp_ctx* ctx, const DevParams& P, bool need_x, s
     }
     return HSCMP_OK;
 }
-static int ensure_workspace(hscmp_ctx* ctx, const DevParams& P, bool need_x, bool row_lists, size_t geom_bytes = 0)
+static int ensure_workspace(hscmp_ctx* ctx, const DevParams& P, bool need_x, bool row_lists, size_t geom_bytes = 0, size_t rules_bytes = 0)
 {
-    return ensure_workspace_g(ctx, P, need_x, esize(ctx->dict.dtype), ctx->dict.F > 1, row_lists, geom_bytes);
+    return ensure_workspace_g(ctx, P, need_x, esize(ctx->dict.dtype), ctx->dict.F > 1, row_lists, geom_bytes, rules_bytes);
 }
 
 // ragged, multi: of the batch being encoded or resumed (its plan says so), not of the one the context may still hold
@@ -639,6 +646,7 @@ template <typename R> static State<R> make_state(hscmp_ctx* c, bool ragged, bool
     S.stats = c->ws.stats.as<int>(); S.energy = c->ws.energy.as<R>(); S.edge = c->ws.edge.as<unsigned long long>();
     S.geom = ragged ? c->ws.geom.as<int>() : nullptr;
     S.dict_of = multi ? c->ws.dict_of.as<int>() : nullptr;
+    S.rules = ragged && !c->rules.empty() ? c->ws.rules.p : nullptr;      // (the context's table is this batch's: drop_batch clears it)
     return S;
 }
 
@@ -810,6 +818,7 @@ static std::string variant_of(const EncodePlan& plan)
     else if (plan.rp) v += "_rp";
     else if (plan.loop == EncodePlan::kLoopMfma && plan.group > 1) v += "_x" + std::to_string(plan.group);
     if (plan.ragged) v += "_ragged";
+    if (plan.rules) v += "_rules";
     if (plan.multi) v += "_multi";
     return v;
 }
@@ -1012,9 +1021,10 @@ static int ragged_geometry(hscmp_ctx* ctx, const char* who, int B, int T, const 
     return HSCMP_OK;
 }
 
-// lengths: NULL for a uniform batch, else host int32 [B] (hscmp_encode_batch_ragged*)
+// lengths: NULL for a uniform batch, else host int32 [B] (hscmp_encode_batch_ragged*); rules: NULL, or the [B] table of a ragged
+// batch with stop rules per signal (hscmp_encode_batch_rules*: params then says which rules exist, the table their values)
 static int encode_common(hscmp_ctx* ctx, const void* x, bool host, int B, int T, const hscmp_params* params, const int32_t* lengths = nullptr,
-                         const char* who = "hscmp_encode_batch")
+                         const char* who = "hscmp_encode_batch", std::vector<SignalRule>* rules = nullptr)
 {
     if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "%s: ctx is NULL", who);
     if (ctx->dict.dtype < 0) return fail(ctx, HSCMP_ERR_STATE, "%s: no dictionary set", who);
@@ -1030,15 +1040,19 @@ static int encode_common(hscmp_ctx* ctx, const void* x, bool host, int B, int T,
     if (lengths && (rc = ragged_geometry(ctx, who, B, T, lengths, params, P, geom, &min_T))) return rc;
     const bool row_lists = use_row_lists(ctx, kn);
     drop_batch(ctx);
-    if ((rc = ensure_workspace(ctx, P, host, row_lists, geom.size() * sizeof(int)))) return rc;
-    const EncodePlan plan = ctx->dict.dtype == HSCMP_F32 ? plan_encode<float>(ctx, kn, P, row_lists, min_T, lengths != nullptr)
-                                                         : plan_encode<double>(ctx, kn, P, row_lists, min_T, lengths != nullptr);
+    if (rules) ctx->rules = std::move(*rules);      // (from here on make_state hands the table to the RAGGED instances)
+    if ((rc = ensure_workspace(ctx, P, host, row_lists, geom.size() * sizeof(int), ctx->rules.size() * sizeof(SignalRule)))) return rc;
+    EncodePlan plan = ctx->dict.dtype == HSCMP_F32 ? plan_encode<float>(ctx, kn, P, row_lists, min_T, lengths != nullptr)
+                                                   : plan_encode<double>(ctx, kn, P, row_lists, min_T, lengths != nullptr);
+    plan.rules = !ctx->rules.empty();
     // (every CMP plan has its ragged form, DESIGN.md sections 15 and 21; the LoCOMP loops have none -- encode_ragged refuses them first)
     if (plan.ragged && plan.loop != EncodePlan::kLoopMfma && plan.loop != EncodePlan::kLoopGeneric && plan.loop != EncodePlan::kLoopSparse)
         return fail(ctx, HSCMP_ERR_UNSUPPORTED, "%s: %s has no ragged form (the LoCOMP loops)", who, variant_of(plan).c_str());
     if (lengths) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the previous batch's kernels may still read the old geometry)
         HIP_TRY(ctx, hipMemcpyAsync(ctx->ws.geom.p, geom.data(), geom.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        if (plan.rules)     // (behind the same wait; the context keeps the host table, so the upload may still read it)
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->ws.rules.p, ctx->rules.data(), ctx->rules.size() * sizeof(SignalRule), hipMemcpyHostToDevice, ctx->stream));
     }
     const void* xd = x;
     if (host) {
@@ -1133,6 +1147,68 @@ extern "C" int hscmp_encode_batch_ragged(hscmp_ctx* ctx, const void* x, int B, i
 extern "C" int hscmp_encode_batch_ragged_device(hscmp_ctx* ctx, const void* x_dev, int B, int T, const int32_t* lengths, const hscmp_params* params)
 {
     return encode_ragged(ctx, x_dev, false, B, T, lengths, params, "hscmp_encode_batch_ragged_device");
+}
+
+// Stop rules per signal: a ragged batch (a uniform one: every length T) plus a [B] table of the rules' values.
+// A rule with an array exists for every signal and its scalar in `params` is not read; a rule without one stays what `params`
+// says, for every signal.  Everything is checked before anything is queued, so a refusal leaves the previous batch as it was.
+static int encode_rules(hscmp_ctx* ctx, const void* x, bool host, int B, int T, const int32_t* lengths, const hscmp_signal_rules* rules,
+                        const hscmp_params* params, const char* who)
+{
+    if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "%s: ctx is NULL", who);
+    NOT_A_SET(ctx, who);
+    if (!rules || (!rules->nb_nonzero_coefs && !rules->tolerance_snr && !rules->tolerance_residual_scale))
+        return fail(ctx, HSCMP_ERR_INVALID, "%s: no rule has an array: use hscmp_encode_batch_ragged", who);
+    if (ctx->method == HSCMP_METHOD_LOCOMP) return fail(ctx, HSCMP_ERR_UNSUPPORTED, "%s: the LoCOMP loop has no per-signal stop rules", who);
+    if (B < 1 || T < 1 || !params) return fail(ctx, HSCMP_ERR_INVALID, "%s: bad arguments (B=%d T=%d)", who, B, T);
+    hscmp_params pe = *params;
+    // (the rules without an array: make_params_g's expressions on the scalars)
+    const SignalRule scalars{std::isnan(pe.tolerance_snr) ? 0.0 : std::pow(10.0, pe.tolerance_snr / 10.0),
+                             std::isnan(pe.tolerance_residual_scale) ? 0.0 : pe.tolerance_residual_scale,
+                             pe.nb_nonzero_coefs < 0 ? -1 : pe.nb_nonzero_coefs, 0};
+    std::vector<SignalRule> table((size_t)B, scalars);
+    if (rules->nb_nonzero_coefs) {
+        pe.nb_nonzero_coefs = 0;        // (present; P.l0 becomes the largest, which no kernel reads behind signal_params)
+        for (int b = 0; b < B; ++b) {
+            const int32_t l0 = rules->nb_nonzero_coefs[b];
+            if (l0 < 0) return fail(ctx, HSCMP_ERR_INVALID, "%s: signal %d: nb_nonzero_coefs is %d, it must be >= 0", who, b, (int)l0);
+            table[(size_t)b].l0 = l0;
+            pe.nb_nonzero_coefs = std::max(pe.nb_nonzero_coefs, l0);
+        }
+    }
+    if (rules->tolerance_snr) {
+        for (int b = 0; b < B; ++b) {
+            const double v = rules->tolerance_snr[b];
+            if (std::isnan(v) || v < 0.0) return fail(ctx, HSCMP_ERR_INVALID, "%s: signal %d: tolerance_snr is %g, it must be >= 0", who, b, v);
+            table[(size_t)b].snr_ratio = std::pow(10.0, v / 10.0);          // (make_params_g's expression: the same bits)
+        }
+        pe.tolerance_snr = rules->tolerance_snr[0];
+    }
+    if (rules->tolerance_residual_scale) {
+        for (int b = 0; b < B; ++b) {
+            const double v = rules->tolerance_residual_scale[b];
+            if (std::isnan(v) || v < 0.0)
+                return fail(ctx, HSCMP_ERR_INVALID, "%s: signal %d: tolerance_residual_scale is %g, it must be >= 0", who, b, v);
+            table[(size_t)b].tol_scale = v;
+        }
+        pe.tolerance_residual_scale = rules->tolerance_residual_scale[0];
+    }
+    const std::vector<int32_t> all_T(lengths ? (size_t)0 : (size_t)B, T);
+    const int rc = encode_common(ctx, x, host, B, T, &pe, lengths ? lengths : all_T.data(), who, &table);
+    if (rc && !ctx->have_batch) ctx->rules.clear();     // (a refusal in front of drop_batch leaves the previous batch and ITS table)
+    return rc;
+}
+
+extern "C" int hscmp_encode_batch_rules(hscmp_ctx* ctx, const void* x, int B, int T, const int32_t* lengths, const hscmp_signal_rules* rules,
+                                        const hscmp_params* params)
+{
+    return encode_rules(ctx, x, true, B, T, lengths, rules, params, "hscmp_encode_batch_rules");
+}
+
+extern "C" int hscmp_encode_batch_rules_device(hscmp_ctx* ctx, const void* x_dev, int B, int T, const int32_t* lengths, const hscmp_signal_rules* rules,
+                                               const hscmp_params* params)
+{
+    return encode_rules(ctx, x_dev, false, B, T, lengths, rules, params, "hscmp_encode_batch_rules_device");
 }
 
 extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, int first, int count, double min_coefficients,

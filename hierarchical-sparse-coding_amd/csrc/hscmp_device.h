@@ -334,6 +334,7 @@ template <typename R> struct State {
     double* lgram;      // [B][lgram_doubles(lg_cap)] LoCOMP: what a group keeps beyond its LDS copy (nullptr: other methods)
     const int* geom;    // [B][kGeomWords] ragged batches: the signal's own length and block geometry; nullptr: uniform
     const int* dict_of; // [B] a set of dictionaries: the dictionary of signal b; nullptr: one dictionary
+    const void* rules;  // [B] SignalRule, a ragged batch with stop rules per signal; nullptr: the batch's rules apply
 };
 
 // Ragged batches: every per-signal array keeps the stride of the longest length P.T, and a signal's rows t >= T_b are dead --
@@ -341,6 +342,17 @@ template <typename R> struct State {
 // signal take its own geometry (length, segment count, block size and count) in place of the batch's, through signal_params:
 // RAGGED = false returns P itself (the copy folds away), so the loops of a uniform batch compile to the code they were before.
 constexpr int kGeomWords = 3;   // T_b, bs_b, nbk_b
+// Stop rules per signal (hscmp_encode_batch_rules): the VALUES of the three rules for signal b.  Which rules
+// exist (has_snr, has_scale, l0 >= 0) stays the batch's, so the plan is one for the batch.  signal_params reads the table as 32-bit
+// words through readfirstlane, like the geometry, so the values stay in SGPRs (a double is two halves).
+struct SignalRule { double snr_ratio; double tol_scale; int l0; int pad; };
+constexpr int kRuleWords = sizeof(SignalRule) / sizeof(int);
+static_assert(kRuleWords == 6, "SignalRule is read as six 32-bit words");
+__device__ __forceinline__ double uniform_double(const int* w)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane(w[0]), hi = (unsigned)__builtin_amdgcn_readfirstlane(w[1]);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
 template <bool RAGGED, typename R> __device__ __forceinline__ DevParams signal_params(const DevParams& P, const State<R>& S, int b)
 {
     if constexpr (!RAGGED) {
@@ -352,6 +364,12 @@ template <bool RAGGED, typename R> __device__ __forceinline__ DevParams signal_p
         Q.bs = __builtin_amdgcn_readfirstlane(g[1]);
         Q.nbk = __builtin_amdgcn_readfirstlane(g[2]);
         Q.nseg = (Q.T + P.seg - 1) >> P.seg_shift;
+        if (S.rules) {
+            const int* r = (const int*)S.rules + kRuleWords * b;
+            Q.snr_ratio = uniform_double(r);
+            Q.tol_scale = uniform_double(r + 2);
+            Q.l0 = __builtin_amdgcn_readfirstlane(r[4]);
+        }
         return Q;
     }
 }

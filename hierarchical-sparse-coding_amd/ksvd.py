@@ -371,6 +371,8 @@ class ConvolutionalKSVDLearner(object):
         [T_b(,F)] arrays, or a padded array with `lengths`; method='cmp' only, and within what the engine's ragged encode takes:
         DESIGN.md section 15), as computeCoefficientsBatch takes them.
         Each iteration is one encodeBatch of the whole corpus (the stop rules apply per signal) and one update_corpus.
+        With method='cmp', `nbNonzeroCoefs` and `toleranceSnr` may be sequences with one value per signal (an L0 that follows
+        the signal's length, say): encodeBatch then gives every signal its own stop rules in the same call.
         D is drawn as `train` draws it, with low / high over the whole corpus; a corpus of one signal gives `train`'s
         result on that signal, bit for bit.  Returns D float64 [K,W] or [K,W,F].
         lastStats: `train`'s records (nnz: the stored coefficients of all signals) plus plan (1: one workgroup, 2: wide)

@@ -108,6 +108,7 @@ class LoCOMP(ConvolutionalMatchingPursuit):
         taken again by the host loop below; so is every call with a stopCondition (its argument there is the coefficient matrix,
         :1397) or with verbose plots.  Returns a BatchResult like the base class."""
         reject_ragged(sequences, lengths, 'LoCOMP.computeCoefficientsBatch (the LoCOMP device loop)')
+        self._reject_per_signal_rules(nbNonzeroCoefs, toleranceResidualScale, toleranceSnr)      # (the device loop and the host loop alike)
         if stopCondition is not None or self.verbose or self.refit == 'host' or os.environ.get('HSCMP_LOCOMP_HOST') == '1':
             return self._batch_on_host(sequences, D, nbNonzeroCoefs, toleranceResidualScale, toleranceSnr, nbBlocks, minCoefficients, weights,
                                        stopCondition)
@@ -141,6 +142,7 @@ class LoCOMP(ConvolutionalMatchingPursuit):
         """The base class's batch with a dictionary per signal, through the LoCOMP device loop (the dense policy).  A signal with a
         neighbourhood beyond the kernel's capacity (stop reason 'group') is taken again by the host loop with ITS OWN dictionary
         and weights, as computeCoefficientsBatch does."""
+        self._reject_per_signal_rules(nbNonzeroCoefs, toleranceResidualScale, toleranceSnr)
         res = super(LoCOMP, self).computeCoefficientsMultiBatch(sequences, dictionaries, dictionaryOf, nbNonzeroCoefs, toleranceResidualScale,
                                                                 toleranceSnr, nbBlocks, minCoefficients, weights, maxEvents)
         again = np.where(res.stats[:, _native.STAT_STOP] == _native.STOP_GROUP)[0]
@@ -149,6 +151,11 @@ class LoCOMP(ConvolutionalMatchingPursuit):
             self._retake_on_host(res, b, np.asarray(sequences[b]), np.asarray(dictionaries[g]), nbNonzeroCoefs, toleranceResidualScale,
                                  toleranceSnr, nbBlocks, minCoefficients, None if weights is None else np.asarray(weights)[g])
         return res
+
+    @staticmethod
+    def _reject_per_signal_rules(*rules):
+        if any(_native.is_per_signal(v) for v in rules):
+            raise NotImplementedError('the LoCOMP loop has no per-signal stop rules')
 
     def _batch_on_host(self, sequences, D, *args):
         from .modeling import BatchResult

@@ -241,6 +241,11 @@ def ragged_batch(sequences, lengths, dtype, W, F):
     return x, lens.astype(np.int32), seqs
 
 
+def _has_per_signal_rules(nbNonzeroCoefs, toleranceResidualScale, toleranceSnr):
+    """Is one of the three stop rules given per signal (a sequence), not as a scalar or None."""
+    return any(_native.is_per_signal(v) for v in (nbNonzeroCoefs, toleranceResidualScale, toleranceSnr))
+
+
 class BatchResult(object):
     """Per-signal outputs of computeCoefficientsBatch (everything the reference returns, plus the
     ordered selection trace the reference only logs)."""
@@ -345,10 +350,16 @@ class ConvolutionalMatchingPursuit(SparseApproximator):
         encoded concurrently, one persistent workgroup each.  Returns a BatchResult.
         Signals of different lengths (a ragged batch): `sequences` a list / tuple of arrays [T_b] or [T_b,F], or a padded array
         [B,T(,F)] with `lengths` [B]; every signal gets exactly what computeCoefficients gives it alone, the result holds
-        per-signal residuals [T_b(,F)] and coefficients [T_b,K]."""
+        per-signal residuals [T_b(,F)] and coefficients [T_b,K].
+        Stop rules per signal: any of `nbNonzeroCoefs`, `toleranceResidualScale`, `toleranceSnr` may be a length-B sequence, and
+        signal b then stops on its own value, exactly as computeCoefficients stops it alone with that scalar (uniform and ragged
+        batches alike; the result's variant ends in '_rules')."""
         assert D.ndim == 2 or D.ndim == 3
         ragged = is_ragged(sequences, lengths)
         method = getattr(self, '_method', _native.METHOD_CMP)       # (hsc_amd.locomp.LoCOMP: the loop with the group re-fit)
+        per_signal = _has_per_signal_rules(nbNonzeroCoefs, toleranceResidualScale, toleranceSnr)
+        if per_signal and method != _native.METHOD_CMP:
+            raise NotImplementedError('the LoCOMP loop has no per-signal stop rules')
         if ragged and method != _native.METHOD_CMP:
             raise NotImplementedError('the LoCOMP loop has no ragged form (signals of different lengths)')
         eps = float(np.finfo(D.dtype).eps) if np.issubdtype(D.dtype, np.floating) else float(np.finfo(np.float64).eps)
@@ -372,17 +383,22 @@ class ConvolutionalMatchingPursuit(SparseApproximator):
             lens, seqs = None, None
         if weights is not None:
             assert len(weights) == K
+        # (the rules given per signal go into the table, their scalars stay unset; checked before the engine is touched)
+        rules = _native.make_rules(B, nbNonzeroCoefs, toleranceResidualScale, toleranceSnr) if per_signal else None
         eng = _native.engine_for(self.device, D3, None if weights is None else np.asarray(weights, dtype=dt))
 
         if maxEvents is None:
-            maxEvents = 2 * int(nbNonzeroCoefs) + 64 if nbNonzeroCoefs is not None else 4096
+            maxEvents = 2 * int(np.max(nbNonzeroCoefs)) + 64 if nbNonzeroCoefs is not None else 4096
         per_round = stopCondition is not None
-        params = _native.make_params(nbNonzeroCoefs, toleranceResidualScale, toleranceSnr, nbBlocks,
+        scalars = [None if _native.is_per_signal(v) else v for v in (nbNonzeroCoefs, toleranceResidualScale, toleranceSnr)]
+        params = _native.make_params(scalars[0], scalars[1], scalars[2], nbBlocks,
                                      minCoefficients, eps, maxEvents, 1 if per_round else 0)
         if method != _native.METHOD_CMP:
             eng.set_method(method)
         try:
-            if ragged:
+            if rules is not None:
+                eng.encode_batch_rules(x, lens, rules, params)
+            elif ragged:
                 eng.encode_batch_ragged(x, lens, params)
             else:
                 eng.encode_batch(x, params)
@@ -462,6 +478,8 @@ class ConvolutionalMatchingPursuit(SparseApproximator):
         computeCoefficients gives it alone with dictionaries[dictionaryOf[b]] and weights[dictionaryOf[b]]; one call encodes
         them side by side (hscmp_encode_batch_multi, the generic kernels).  Returns a BatchResult."""
         method = getattr(self, '_method', _native.METHOD_CMP)
+        if _has_per_signal_rules(nbNonzeroCoefs, toleranceResidualScale, toleranceSnr):
+            raise NotImplementedError('computeCoefficientsMultiBatch has no per-signal stop rules')
         if is_ragged(sequences):
             raise NotImplementedError('computeCoefficientsMultiBatch has no ragged form (signals of different lengths): pass a '
                                       '[B,T] or [B,T,F] array')

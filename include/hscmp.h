@@ -199,6 +199,32 @@ int hscmp_encode_batch_device(hscmp_ctx* ctx, const void* x_dev, int B, int T, c
 int hscmp_encode_batch_ragged(hscmp_ctx* ctx, const void* x, int B, int T, const int32_t* lengths, const hscmp_params* params);
 int hscmp_encode_batch_ragged_device(hscmp_ctx* ctx, const void* x_dev, int B, int T, const int32_t* lengths, const hscmp_params* params);
 
+/* Stop rules per signal.  Host pointers, each NULL or [B]; a non-NULL array makes that rule present for
+ * every signal and replaces the scalar of hscmp_params, which is then not read (a NULL array: the scalar holds for every
+ * signal, as in hscmp_encode_batch_ragged). */
+typedef struct hscmp_signal_rules {
+    const int32_t* nb_nonzero_coefs;
+    const double*  tolerance_snr;
+    const double*  tolerance_residual_scale;
+} hscmp_signal_rules;
+
+/* hscmp_encode_batch_ragged with stop rules per signal: x [B][T][F], lengths host int32 [B] or NULL (every signal has T samples).
+ * Signal b comes out exactly as hscmp_encode_batch would return x[b][0:lengths[b]] alone with signal b's values in the scalar
+ * fields of `params`: events in selection order, coefficient slots, all eight stats (the stop reason among them), the residual
+ * and both energies, bit for bit whatever kernels that single encode picks.  Which rules exist is one property of the batch (it
+ * chooses the kernels); only their values differ.  The context then holds a ragged batch: it keeps the table, beside the lengths,
+ * for hscmp_continue, hscmp_grow_events, hscmp_stop_signal and the fetches until the next encode, and serves
+ * hscmp_encode_batch_from_level and hscmp_hierarchy_epilogue as the ragged batch of the same lengths would.
+ * hscmp_last_variant is the ragged variant's name plus "_rules".  Before anything is queued (the previous batch stays as it was):
+ * HSCMP_ERR_INVALID for rules == NULL or three NULL arrays (use hscmp_encode_batch_ragged), and for a NaN or negative tolerance
+ * or a negative nb_nonzero_coefs (hscmp_last_error names the signal and the rule); HSCMP_ERR_UNSUPPORTED under
+ * HSCMP_METHOD_LOCOMP; HSCMP_ERR_STATE on a context that holds a set of dictionaries; everything else as
+ * hscmp_encode_batch_ragged.  The _device form takes x in GPU memory and is asynchronous on the context's stream. */
+int hscmp_encode_batch_rules(hscmp_ctx* ctx, const void* x, int B, int T, const int32_t* lengths, const hscmp_signal_rules* rules,
+                             const hscmp_params* params);
+int hscmp_encode_batch_rules_device(hscmp_ctx* ctx, const void* x_dev, int B, int T, const int32_t* lengths,
+                                    const hscmp_signal_rules* rules, const hscmp_params* params);
+
 /* A batch x [B][T][F] (host) encoded with a dictionary per signal: dict_of host int32 [B], each in [0, G), names signal b's
  * dictionary in the set of hscmp_set_dictionaries.  Signal b comes out exactly as hscmp_encode_batch would return it alone
  * on a context whose dictionary (and weights) is dictionary dict_of[b] of the set: events, coefficient slots, stats, residual
