@@ -27,7 +27,7 @@ METHOD_CMP, METHOD_LOCOMP = 0, 1
 EXPORTS = ['hscmp_version', 'hscmp_create', 'hscmp_destroy', 'hscmp_last_error', 'hscmp_set_stream', 'hscmp_set_method',
            'hscmp_synchronize', 'hscmp_set_dictionary', 'hscmp_set_dictionaries', 'hscmp_convolve1d', 'hscmp_select_best_atoms',
            'hscmp_update_inner_products', 'hscmp_table_open', 'hscmp_table_select', 'hscmp_table_update', 'hscmp_table_read', 'hscmp_assign_windows', 'hscmp_host_overlap_add', 'hscmp_host_slots_to_csc', 'hscmp_hierarchy_epilogue', 'hscmp_encode_batch',
-           'hscmp_encode_batch_device', 'hscmp_encode_batch_ragged', 'hscmp_encode_batch_ragged_device', 'hscmp_encode_batch_rules', 'hscmp_encode_batch_rules_device', 'hscmp_encode_batch_multi', 'hscmp_encode_batch_from_level', 'hscmp_load_level', 'hscmp_load_level_ragged', 'hscmp_continue', 'hscmp_grow_events', 'hscmp_mem_info', 'hscmp_copy_from_device', 'hscmp_stop_signal', 'hscmp_fetch_events',
+           'hscmp_encode_batch_device', 'hscmp_encode_batch_ragged', 'hscmp_encode_batch_ragged_device', 'hscmp_encode_batch_rules', 'hscmp_encode_batch_rules_device', 'hscmp_encode_batch_multi', 'hscmp_encode_batch_from_level', 'hscmp_encode_batch_from_level_rules', 'hscmp_load_level', 'hscmp_load_level_ragged', 'hscmp_continue', 'hscmp_grow_events', 'hscmp_mem_info', 'hscmp_copy_from_device', 'hscmp_stop_signal', 'hscmp_fetch_events',
            'hscmp_fetch_stats', 'hscmp_fetch_residual', 'hscmp_fetch_energies', 'hscmp_fetch_slots',
            'hscmp_get_device_view', 'hscmp_last_kernel_ms', 'hscmp_last_variant', 'hscmp_wide_plan', 'hscmp_wide_counters']
 
@@ -121,6 +121,7 @@ def load_library():
     lib.hscmp_encode_batch_rules_device.argtypes = [vp, vp, ci, ci, vp, ctypes.POINTER(HscmpSignalRules), ctypes.POINTER(HscmpParams)]
     lib.hscmp_encode_batch_multi.argtypes = [vp, vp, ci, ci, vp, ctypes.POINTER(HscmpParams)]
     lib.hscmp_encode_batch_from_level.argtypes = [vp, vp, ci, ci, ctypes.c_double, ctypes.POINTER(HscmpParams)]
+    lib.hscmp_encode_batch_from_level_rules.argtypes = [vp, vp, ci, ci, ctypes.c_double, ctypes.POINTER(HscmpSignalRules), ctypes.POINTER(HscmpParams)]
     lib.hscmp_load_level.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp]
     lib.hscmp_load_level_ragged.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp]
     lib.hscmp_continue.argtypes = [vp, ci]
@@ -576,6 +577,15 @@ class Engine(object):
         minc = float('nan') if minCoefficients is None else float(minCoefficients)
         self._check(self._lib.hscmp_encode_batch_from_level(self._h, prev._h, int(first), int(count), ctypes.c_double(minc),
                                                             ctypes.byref(params)), 'hscmp_encode_batch_from_level')
+        self._batch = (int(count), prev._batch[1], int(params.max_events))
+
+    def encode_batch_from_level_rules(self, prev, first, count, minCoefficients, rules, params):
+        """encode_batch_from_level with stop rules per signal: `rules` from make_rules(count, ...), entry i for signal first + i of
+        `prev`.  The engine then holds a ragged batch (of prev's lengths, or `count` times T) and its table."""
+        minc = float('nan') if minCoefficients is None else float(minCoefficients)
+        self._check(self._lib.hscmp_encode_batch_from_level_rules(self._h, prev._h, int(first), int(count), ctypes.c_double(minc),
+                                                                  None if rules is None else ctypes.byref(rules), ctypes.byref(params)),
+                    'hscmp_encode_batch_from_level_rules')
         self._batch = (int(count), prev._batch[1], int(params.max_events))
 
     def load_level(self, x, T, matrices):

@@ -1149,24 +1149,24 @@ extern "C" int hscmp_encode_batch_ragged_device(hscmp_ctx* ctx, const void* x_de
     return encode_ragged(ctx, x_dev, false, B, T, lengths, params, "hscmp_encode_batch_ragged_device");
 }
 
-// Stop rules per signal (DESIGN.md section 25): a ragged batch (a uniform one: every length T) plus a [B] table of the rules' values.
-// A rule with an array exists for every signal and its scalar in `params` is not read; a rule without one stays what `params`
-// says, for every signal.  Everything is checked before anything is queued, so a refusal leaves the previous batch as it was.
-static int encode_rules(hscmp_ctx* ctx, const void* x, bool host, int B, int T, const int32_t* lengths, const hscmp_signal_rules* rules,
-                        const hscmp_params* params, const char* who)
+// The two refusals every call with a rules table starts with.  plain: the call that encodes the same batch without a table.
+static int rules_refused(hscmp_ctx* ctx, const char* who, const char* plain, const hscmp_signal_rules* rules)
 {
-    if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "%s: ctx is NULL", who);
-    NOT_A_SET(ctx, who);
     if (!rules || (!rules->nb_nonzero_coefs && !rules->tolerance_snr && !rules->tolerance_residual_scale))
-        return fail(ctx, HSCMP_ERR_INVALID, "%s: no rule has an array: use hscmp_encode_batch_ragged", who);
+        return fail(ctx, HSCMP_ERR_INVALID, "%s: no rule has an array: use %s", who, plain);
     if (ctx->method == HSCMP_METHOD_LOCOMP) return fail(ctx, HSCMP_ERR_UNSUPPORTED, "%s: the LoCOMP loop has no per-signal stop rules", who);
-    if (B < 1 || T < 1 || !params) return fail(ctx, HSCMP_ERR_INVALID, "%s: bad arguments (B=%d T=%d)", who, B, T);
-    hscmp_params pe = *params;
+    return HSCMP_OK;
+}
+
+// The [B] table of a rules batch from the caller's arrays (entry b: signal b of the batch being encoded), and in `pe` the params
+// that say which rules exist: the one place that owns the table's expressions and the messages about its values.
+static int rules_table(hscmp_ctx* ctx, const char* who, int B, const hscmp_signal_rules* rules, hscmp_params& pe, std::vector<SignalRule>& table)
+{
     // (the rules without an array: make_params_g's expressions on the scalars)
     const SignalRule scalars{std::isnan(pe.tolerance_snr) ? 0.0 : std::pow(10.0, pe.tolerance_snr / 10.0),
                              std::isnan(pe.tolerance_residual_scale) ? 0.0 : pe.tolerance_residual_scale,
                              pe.nb_nonzero_coefs < 0 ? -1 : pe.nb_nonzero_coefs, 0};
-    std::vector<SignalRule> table((size_t)B, scalars);
+    table.assign((size_t)B, scalars);
     if (rules->nb_nonzero_coefs) {
         pe.nb_nonzero_coefs = 0;        // (present; P.l0 becomes the largest, which no kernel reads behind signal_params)
         for (int b = 0; b < B; ++b) {
@@ -1193,8 +1193,25 @@ static int encode_rules(hscmp_ctx* ctx, const void* x, bool host, int B, int T, 
         }
         pe.tolerance_residual_scale = rules->tolerance_residual_scale[0];
     }
+    return HSCMP_OK;
+}
+
+// Stop rules per signal (DESIGN.md section 25): a ragged batch (a uniform one: every length T) plus a [B] table of the rules' values.
+// A rule with an array exists for every signal and its scalar in `params` is not read; a rule without one stays what `params`
+// says, for every signal.  Everything is checked before anything is queued, so a refusal leaves the previous batch as it was.
+static int encode_rules(hscmp_ctx* ctx, const void* x, bool host, int B, int T, const int32_t* lengths, const hscmp_signal_rules* rules,
+                        const hscmp_params* params, const char* who)
+{
+    if (!ctx) return fail(nullptr, HSCMP_ERR_INVALID, "%s: ctx is NULL", who);
+    NOT_A_SET(ctx, who);
+    int rc = rules_refused(ctx, who, "hscmp_encode_batch_ragged", rules);
+    if (rc) return rc;
+    if (B < 1 || T < 1 || !params) return fail(ctx, HSCMP_ERR_INVALID, "%s: bad arguments (B=%d T=%d)", who, B, T);
+    hscmp_params pe = *params;
+    std::vector<SignalRule> table;
+    if ((rc = rules_table(ctx, who, B, rules, pe, table))) return rc;
     const std::vector<int32_t> all_T(lengths ? (size_t)0 : (size_t)B, T);
-    const int rc = encode_common(ctx, x, host, B, T, &pe, lengths ? lengths : all_T.data(), who, &table);
+    rc = encode_common(ctx, x, host, B, T, &pe, lengths ? lengths : all_T.data(), who, &table);
     if (rc && !ctx->have_batch) ctx->rules.clear();     // (a refusal in front of drop_batch leaves the previous batch and ITS table)
     return rc;
 }
@@ -1211,42 +1228,57 @@ extern "C" int hscmp_encode_batch_rules_device(hscmp_ctx* ctx, const void* x_dev
     return encode_rules(ctx, x_dev, false, B, T, lengths, rules, params, "hscmp_encode_batch_rules_device");
 }
 
-extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, int first, int count, double min_coefficients,
-                                             const hscmp_params* params)
+// rules: NULL, or the caller's table for signals [first, first + count) of prev (hscmp_encode_batch_from_level_rules): the level is
+// then encoded as a ragged batch with the table, as encode_rules encodes a level 0 -- a uniform prev with every length T.
+static int from_level_common(hscmp_ctx* ctx, hscmp_ctx* prev, int first, int count, double min_coefficients, const hscmp_signal_rules* rules,
+                             bool with_rules, const hscmp_params* params_in, const char* who)
 {
-    if (!ctx || !prev) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: NULL context");
-    NOT_A_SET(ctx, "hscmp_encode_batch_from_level");
-    if (prev->dict.G > 0) return fail(ctx, HSCMP_ERR_STATE, "hscmp_encode_batch_from_level: the previous level holds a set of dictionaries (hscmp_set_dictionaries)");
-    if (ctx->dict.dtype != HSCMP_F64) return fail(ctx, HSCMP_ERR_STATE, "hscmp_encode_batch_from_level: the level dictionary must be float64");
-    if (!prev->have_batch) return fail(ctx, HSCMP_ERR_STATE, "hscmp_encode_batch_from_level: the previous level has no results");
-    if (ctx->device != prev->device) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: contexts on different GPUs");
-    if (ctx->dict.F != prev->dict.K) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: F=%d of this level != K=%d of the previous one", ctx->dict.F, prev->dict.K);
-    if (!params || first < 0 || count <= 0 || first + count > prev->B) return fail(ctx, HSCMP_ERR_INVALID, "hscmp_encode_batch_from_level: bad signal range");
-    const bool ragged = prev->ragged;
+    if (!ctx || !prev) return fail(ctx, HSCMP_ERR_INVALID, "%s: NULL context", who);
+    NOT_A_SET(ctx, who);
+    if (prev->dict.G > 0) return fail(ctx, HSCMP_ERR_STATE, "%s: the previous level holds a set of dictionaries (hscmp_set_dictionaries)", who);
+    if (ctx->dict.dtype != HSCMP_F64) return fail(ctx, HSCMP_ERR_STATE, "%s: the level dictionary must be float64", who);
+    if (!prev->have_batch) return fail(ctx, HSCMP_ERR_STATE, "%s: the previous level has no results", who);
+    if (ctx->device != prev->device) return fail(ctx, HSCMP_ERR_INVALID, "%s: contexts on different GPUs", who);
+    if (ctx->dict.F != prev->dict.K) return fail(ctx, HSCMP_ERR_INVALID, "%s: F=%d of this level != K=%d of the previous one", who, ctx->dict.F, prev->dict.K);
+    if (!params_in || first < 0 || count <= 0 || first + count > prev->B) return fail(ctx, HSCMP_ERR_INVALID, "%s: bad signal range", who);
+    int rc;
+    hscmp_params pe = *params_in;               // (with a table: which rules exist, as encode_rules hands them to encode_common)
+    const hscmp_params* const params = &pe;
+    std::vector<SignalRule> table;
+    if (with_rules) {
+        if ((rc = rules_refused(ctx, who, "hscmp_encode_batch_from_level", rules))) return rc;
+        if ((rc = rules_table(ctx, who, count, rules, pe, table))) return rc;
+    }
+    const bool ragged = prev->ragged || with_rules;
     if (ragged && ctx->method == HSCMP_METHOD_LOCOMP)
-        return fail(ctx, HSCMP_ERR_UNSUPPORTED, "hscmp_encode_batch_from_level: the previous level holds a ragged batch, and the LoCOMP loop has no ragged form");
+        return fail(ctx, HSCMP_ERR_UNSUPPORTED, "%s: the previous level holds a ragged batch, and the LoCOMP loop has no ragged form", who);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(prev->stream));           // the previous level's results are final
     const int T = prev->T;
     const Knobs kn = read_knobs();
     DevParams P;
-    int rc = make_params(ctx, kn, count, T, params, &P);
-    if (rc) return rc;
-    // a ragged previous level: the lengths are its signals', the block geometry this level's (its W and nbBlocks)
+    if ((rc = make_params(ctx, kn, count, T, params, &P))) return rc;
+    // a ragged previous level: the lengths are its signals', the block geometry this level's (its W and nbBlocks); a uniform one
+    // under a table: every length T
     int min_T = T;
     std::vector<int> geom;
     if (ragged) {
-        std::vector<int32_t> lens((size_t)count);
-        for (int i = 0; i < count; ++i) lens[(size_t)i] = prev->geom[(size_t)(first + i) * kGeomWords];
-        if ((rc = ragged_geometry(ctx, "hscmp_encode_batch_from_level", count, T, lens.data(), params, P, geom, &min_T))) return rc;
+        std::vector<int32_t> lens((size_t)count, T);
+        for (int i = 0; prev->ragged && i < count; ++i) lens[(size_t)i] = prev->geom[(size_t)(first + i) * kGeomWords];
+        if ((rc = ragged_geometry(ctx, who, count, T, lens.data(), params, P, geom, &min_T))) return rc;
     }
     const bool row_lists = use_row_lists(ctx, kn);
     drop_batch(ctx);                            // (this level's batch; prev is only read)
-    if ((rc = ensure_workspace(ctx, P, false, row_lists, geom.size() * sizeof(int)))) return rc;        // no input buffer: the slots are scattered straight into the residual
-    const EncodePlan plan = plan_encode<double>(ctx, kn, P, row_lists, min_T, ragged);
+    ctx->rules = std::move(table);              // (empty without a table; from here on make_state hands it to the RAGGED instances)
+    // no input buffer: the slots are scattered straight into the residual
+    if ((rc = ensure_workspace(ctx, P, false, row_lists, geom.size() * sizeof(int), ctx->rules.size() * sizeof(SignalRule)))) return rc;
+    EncodePlan plan = plan_encode<double>(ctx, kn, P, row_lists, min_T, ragged);
+    plan.rules = !ctx->rules.empty();
     if (ragged) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the previous batch's kernels may still read the old geometry)
         HIP_TRY(ctx, hipMemcpyAsync(ctx->ws.geom.p, geom.data(), geom.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        if (plan.rules)     // (behind the same wait; the context keeps the host table, so the upload may still read it)
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->ws.rules.p, ctx->rules.data(), ctx->rules.size() * sizeof(SignalRule), hipMemcpyHostToDevice, ctx->stream));
     }
     const bool lists = plan.row_lists;          // (the scatter writes them)
     const size_t bytes = (size_t)count * T * ctx->dict.F * sizeof(double);
@@ -1288,6 +1320,20 @@ extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, in
     // (only now: a failed launch leaves the buffer in an unknown state, and so does any other writer -- see the resets)
     if (plan.kept_lists) { ctx->listed_rows = (int64_t)count * T; ctx->listed_F = ctx->dict.F; }
     return HSCMP_OK;
+}
+
+extern "C" int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, int first, int count, double min_coefficients,
+                                             const hscmp_params* params)
+{
+    return from_level_common(ctx, prev, first, count, min_coefficients, nullptr, false, params, "hscmp_encode_batch_from_level");
+}
+
+extern "C" int hscmp_encode_batch_from_level_rules(hscmp_ctx* ctx, hscmp_ctx* prev, int first, int count, double min_coefficients,
+                                                   const hscmp_signal_rules* rules, const hscmp_params* params)
+{
+    const int rc = from_level_common(ctx, prev, first, count, min_coefficients, rules, true, params, "hscmp_encode_batch_from_level_rules");
+    if (rc && ctx && !ctx->have_batch) ctx->rules.clear();      // (a failure behind drop_batch: no batch, so no table either)
+    return rc;
 }
 
 // hscmp_load_level: the validation pass reads only the staged entries, so a rejected entry is known before anything of the

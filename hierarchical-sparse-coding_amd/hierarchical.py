@@ -164,6 +164,11 @@ class HierarchicalConvolutionalMatchingPursuit(SparseApproximator):
         (sum of squares, summed on the device); the residual samples -- T float64 per signal -- never cross PCIe.
         Returns (per-signal lists of per-level coefficient matrices, residuals [B,T(,F)] float64,
         per-level kernel timings); with returnEvents=True a fourth item: per-signal event record arrays.
+        toleranceSnr: None, one value, one value per level, or -- method='cmp' -- an array-like [B, nbLevels] with a target per
+        signal and level (row = signal, column = absolute level; finite and >= 0, else ValueError before any engine call).
+        Signal b then comes out byte for byte as this method returns sequences[b] alone with toleranceSnr=list(table[b]);
+        every level is a rules batch and its timing's variant ends in '_rules'.  The same holds for
+        computeCoefficientsRaggedBatch and the two from-level forms, which read the columns fromLevel .. only.
         The steps live in _LevelPipeline (below): level set-up, one level over one chunk with event-list regrowth, chunk sizing,
         the two epilogues, the per-signal fallback."""
         _reject_ragged(sequences, lengths, 'HierarchicalConvolutionalMatchingPursuit.computeCoefficientsBatch (levels >= 1, level chaining, epilogue)',
@@ -282,7 +287,7 @@ class HierarchicalConvolutionalMatchingPursuit(SparseApproximator):
         sequences = np.asarray(sequences)
         fromLevel = _check_given_levels(sequences, coefficients, multilevelDict)
         pipe = _LevelPipeline(self, sequences, multilevelDict, toleranceSnr, nbBlocks, singletonWeight, returnDistributed, epilogue,
-                              returnEvents, None, residuals, memoryBudget)
+                              returnEvents, None, residuals, memoryBudget, fromLevel=fromLevel)
         return pipe.run_from_level(coefficients, fromLevel)
 
     def computeCoefficientsRaggedBatch(self, sequences, multilevelDict, toleranceSnr=None, nbBlocks=1, singletonWeight=0.5,
@@ -318,8 +323,30 @@ class HierarchicalConvolutionalMatchingPursuit(SparseApproximator):
         fromLevel = _check_given_ragged_levels(ragged_signals(sequences, lengths, 1)[0], coefficients, multilevelDict)
         x, lens = _ragged_input(self, sequences, lengths, multilevelDict, fromLevel, 'computeCoefficientsFromLevelBatch')
         pipe = _LevelPipeline(self, x, multilevelDict, toleranceSnr, nbBlocks, singletonWeight, returnDistributed, epilogue,
-                              returnEvents, None, residuals, memoryBudget, lengths=lens)
+                              returnEvents, None, residuals, memoryBudget, lengths=lens, fromLevel=fromLevel)
         return pipe.run_from_level(coefficients, fromLevel)
+
+
+def _snr_table(toleranceSnr, B, nbLevels, fromLevel=0):
+    """toleranceSnr given per signal and level: the float64 table [B, nbLevels], row = signal, column =
+    absolute level, or None for the forms the reference has (None, a scalar, one value per level).  Columns fromLevel .. must
+    be finite and >= 0; the columns below are not read.  ValueError, naming the signal and the level, before any engine call."""
+    if toleranceSnr is None:
+        return None
+    try:
+        if np.ndim(toleranceSnr) != 2:
+            return None
+        table = np.array(toleranceSnr, dtype=np.float64)
+    except (ValueError, TypeError):
+        raise ValueError('toleranceSnr: a table per signal and level must be rectangular, (%d, %d)' % (B, nbLevels))
+    if table.shape != (B, nbLevels):
+        raise ValueError('toleranceSnr: a table per signal and level must have shape (%d, %d) -- signals x levels --, got %s' % (
+            B, nbLevels, table.shape))
+    for b in range(B):
+        for l in range(fromLevel, nbLevels):
+            if not np.isfinite(table[b, l]) or table[b, l] < 0:
+                raise ValueError('toleranceSnr: signal %d, level %d: the value %r must be finite and >= 0' % (b, l, float(table[b, l])))
+    return table
 
 
 def _reject_ragged(sequences, lengths, what, ragged_name):
@@ -417,7 +444,7 @@ class _LevelPipeline(object):
       host_signal      signal b on the host, from the device when the batch was handed over as a device pointer"""
 
     def __init__(self, hcmp, sequences, multilevelDict, toleranceSnr, nbBlocks, singletonWeight, returnDistributed, epilogue, returnEvents,
-                 deviceInput, residuals, memoryBudget, lengths=None):
+                 deviceInput, residuals, memoryBudget, lengths=None, fromLevel=0):
         self.hcmp, self.sequences, self.mld = hcmp, sequences, multilevelDict
         self.toleranceSnr, self.nbBlocks, self.singletonWeight = toleranceSnr, nbBlocks, singletonWeight
         self.returnDistributed, self.returnEvents, self.deviceInput, self.residuals = returnDistributed, returnEvents, deviceInput, residuals
@@ -428,6 +455,10 @@ class _LevelPipeline(object):
         self.locomp = hcmp.method == 'locomp'
         self.nbLevels = multilevelDict.getNbLevels()
         self.B, self.T = sequences.shape[0], sequences.shape[1]
+        # toleranceSnr per signal and level: every level is then a rules batch (hscmp_encode_batch_rules, ..._from_level_rules)
+        self.snr_table = _snr_table(toleranceSnr, self.B, self.nbLevels, fromLevel)
+        if self.snr_table is not None and self.locomp:
+            raise NotImplementedError('the LoCOMP loop has no per-signal stop rules')
         # a ragged batch (computeCoefficientsRaggedBatch): `sequences` is its padded form [B,T(,F)], T the longest length and the
         # stride of every device array; signal b owns rows [0, lengths[b]) -- of its input, its matrices (T_b, K_l) and its residual
         self.lengths = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
@@ -443,9 +474,12 @@ class _LevelPipeline(object):
 
     # ---- per level
     def level_setup(self, level):
-        """(D, weights, targetSnr, eps) of a level: :1439-1450"""
+        """(D, weights, targetSnr, eps) of a level: :1439-1450; targetSnr is the level's column [B] of a per-signal table"""
         snr = self.toleranceSnr
-        targetSnr = snr[level] if (snr is not None and isinstance(snr, collections.abc.Iterable)) else snr
+        if self.snr_table is not None:
+            targetSnr = np.ascontiguousarray(self.snr_table[:, level])
+        else:
+            targetSnr = snr[level] if (snr is not None and isinstance(snr, collections.abc.Iterable)) else snr
         D = self.mld.getRawDictionary(level)
         nbSingletons = D.shape[0] - self.mld.countsNoSingletons[level]
         weights = np.ones((D.shape[0],), dtype=D.dtype)
@@ -479,13 +513,18 @@ class _LevelPipeline(object):
             kernel_ms[2] += float(eng.last_kernel_ms()[2])
 
     def encode_level(self, eng, encode, count, targetSnr, eps, maxEvents=4096, lazy=False, offset=0):
-        """encode(params) on `eng`, with regrowth; returns (per-signal coefficients or None when they stay on the device,
-        timing dict, stats)"""
+        """encode(params, rules) on `eng`, with regrowth; returns (per-signal coefficients or None when they stay on the device,
+        timing dict, stats).  rules: None, or with a per-signal table the targets of signals [offset, offset + count) -- the
+        scalar of the params then only says that the rule exists."""
         from . import _native
         from .modeling import _slots_to_csc
         maxEvents = self.start_capacity(eng, maxEvents)
+        rules = None
+        if self.snr_table is not None:
+            rules = _native.make_rules(count, toleranceSnr=targetSnr[offset:offset + count])
+            targetSnr = float(targetSnr[offset])
         params = _native.make_params(None, None, targetSnr, self.nbBlocks, 1e-16, eps, maxEvents, 0)
-        encode(params)
+        encode(params, rules)
         kernel_ms = [float(v) for v in eng.last_kernel_ms()]
         stats, maxEvents = self.regrow_until_done(eng, maxEvents, kernel_ms)
         eng._capacity_hint = ((self.T, self.nbBlocks), maxEvents)
@@ -518,12 +557,13 @@ class _LevelPipeline(object):
 
     def fallback_signal(self, b):
         """(coefficients, residual) of signal b through the per-signal entry (host-loop methods have no group limit)."""
+        snr = self.toleranceSnr if self.snr_table is None else list(self.snr_table[b])
         if self.given is not None:
             seq = self.host_signal(b)
-            cb = self.hcmp.computeCoefficientsFromLevel(seq, self.given[b], self.mld, toleranceSnr=self.toleranceSnr, nbBlocks=self.nbBlocks,
+            cb = self.hcmp.computeCoefficientsFromLevel(seq, self.given[b], self.mld, toleranceSnr=snr, nbBlocks=self.nbBlocks,
                                                         singletonWeight=self.singletonWeight, returnDistributed=self.returnDistributed)
             return cb, (self.hcmp._calculateResidual(seq, cb, self.mld) if self.residuals is not None else None)
-        return self.hcmp.computeCoefficients(self.host_signal(b), self.mld, toleranceSnr=self.toleranceSnr, nbBlocks=self.nbBlocks,
+        return self.hcmp.computeCoefficients(self.host_signal(b), self.mld, toleranceSnr=snr, nbBlocks=self.nbBlocks,
                                              singletonWeight=self.singletonWeight, returnDistributed=self.returnDistributed)
 
     # ---- chained = False: dense level inputs built on the host (small cases)
@@ -574,7 +614,8 @@ class _LevelPipeline(object):
             # every input non-zero is explained at least once (by its singleton): size the lists for that
             nin = int(last_stats[pfirst:pfirst + count, _native.STAT_SLOTS].max())
             coefs, tm, last_stats = self.encode_level(
-                engines[l], lambda p, e=engines[l], pv=prev, pf=pfirst: e.encode_batch_from_level(pv, pf, count, 1e-16, p),
+                engines[l], lambda p, r, e=engines[l], pv=prev, pf=pfirst: (e.encode_batch_from_level(pv, pf, count, 1e-16, p) if r is None else
+                                                                           e.encode_batch_from_level_rules(pv, pf, count, 1e-16, r, p)),
                 count, targetSnr, eps, maxEvents=max(4096, nin + nin // 4 + 64), lazy=True, offset=first)
             if coefs is not None:
                 self.per_level[l][first:first + count] = coefs
@@ -619,13 +660,16 @@ class _LevelPipeline(object):
         engines[0].set_dictionary(D3, np.asarray(weights, dtype=dt))
         if self.deviceInput is not None:
             assert np.asarray(sequences).dtype == dt, 'deviceInput must hold the level-0 compute dtype'
-            enc0 = lambda p: engines[0].encode_batch_device(int(self.deviceInput), B, T, p)
+            enc0 = lambda p, r: (engines[0].encode_batch_device(int(self.deviceInput), B, T, p) if r is None else
+                                 engines[0].encode_batch_rules_device(int(self.deviceInput), B, T, None, r, p))
         else:
             x = np.ascontiguousarray(np.asarray(sequences).reshape((B, T, -1)), dtype=dt)
-            if self.lengths is not None:
-                enc0 = lambda p: engines[0].encode_batch_ragged(x, self.lengths, p)
+            if self.snr_table is not None:
+                enc0 = lambda p, r: engines[0].encode_batch_rules(x, self.lengths, r, p)      # (lengths None: every signal has T samples)
+            elif self.lengths is not None:
+                enc0 = lambda p, r: engines[0].encode_batch_ragged(x, self.lengths, p)
             else:
-                enc0 = lambda p: engines[0].encode_batch(x, p)
+                enc0 = lambda p, r: engines[0].encode_batch(x, p)
         self.per_level[0], tm, stats0 = self.encode_level(engines[0], enc0, B, targetSnr, eps, lazy=True)
         tm['level'] = 0
         self.timings.append(tm)
@@ -662,8 +706,11 @@ class _LevelPipeline(object):
         self.timings = [loaded(l) if l < fromLevel else dict(loaded(l), variant='') for l in range(nbLevels)]
         x = np.ascontiguousarray(self.sequences.reshape((B, T, -1)), dtype=dt)
         given = [coefficients[b][-1] for b in range(B)]
-        if self.lengths is not None:
-            load = lambda e, x_, ms: e.load_level_ragged(x_, T, self.lengths, ms)
+        if self.lengths is not None or self.snr_table is not None:
+            # (a per-signal table makes every level a ragged batch on the device -- of B lengths T when the input is uniform --, and
+            # the epilogue wants both of its levels of one kind)
+            lens = self.lengths if self.lengths is not None else np.full((B,), T, dtype=np.int32)
+            load = lambda e, x_, ms: e.load_level_ragged(x_, T, lens, ms)
         else:
             load = lambda e, x_, ms: e.load_level(x_, T, ms)
         if fromLevel == 1:

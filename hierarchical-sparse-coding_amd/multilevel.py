@@ -76,8 +76,9 @@ class MultilevelDictionaryLearner(object):
     def trainCorpus(self, sequences, nbRandomWindows, maxIterations=100, tolerance=0.0, initMethod='random_samples',
                     resetMethod='noise', nbAveragedPatches=8, toleranceSnr=None, nbBlocks=1, singletonWeight=0.5, lengths=None,
                     resume=True):
-        """`sequences` [B,T] or [B,T,F].  The k-means arguments go to every level's trainCorpus; toleranceSnr (one value, or
-        one per level), nbBlocks and singletonWeight to every encode.  Returns the MultilevelDictionary of all levels
+        """`sequences` [B,T] or [B,T,F].  The k-means arguments go to every level's trainCorpus; toleranceSnr (one value,
+        one per level, or -- method='cmp' -- a table [B, >= nbLevels - 1] with a target per signal and level, DESIGN.md section
+        26), nbBlocks and singletonWeight to every encode.  Returns the MultilevelDictionary of all levels
         (levels >= 1 with their singleton bases, as the reference builds it).
         resume=True: from level 1 on, the hand-off encode carries on from the previous pass's coefficients
         (computeCoefficientsFromLevelBatch, as the reference's script calls encodeFromLevel) and runs the new level only;
@@ -115,7 +116,14 @@ class MultilevelDictionaryLearner(object):
         """The level loop of trainCorpus (`sequences` [B,T(,F)]) and trainRaggedCorpus (a list of [T_b(,F)] arrays)."""
         from .hierarchical import HierarchicalConvolutionalMatchingPursuit
         toleranceSnr = encode['toleranceSnr']
-        if toleranceSnr is not None and isinstance(toleranceSnr, collections.abc.Iterable) and len(toleranceSnr) < len(self.counts) - 1:
+        snr_table = None
+        if toleranceSnr is not None and np.ndim(toleranceSnr) == 2:
+            # a target per signal and level (DESIGN.md section 26): rows are signals, so the level count is the second axis
+            snr_table = np.asarray(toleranceSnr, dtype=np.float64)
+            if snr_table.shape[0] != len(sequences) or snr_table.shape[1] < len(self.counts) - 1:
+                raise ValueError('multilevel learner: toleranceSnr has shape %s, the corpus %d signals and the encodes run up to level %d' % (
+                    snr_table.shape, len(sequences), len(self.counts) - 2))
+        elif toleranceSnr is not None and isinstance(toleranceSnr, collections.abc.Iterable) and len(toleranceSnr) < len(self.counts) - 1:
             raise ValueError('multilevel learner: toleranceSnr has %d values, the encodes run up to level %d' % (
                 len(toleranceSnr), len(self.counts) - 2))
         nbLevels = len(self.counts)
@@ -143,6 +151,8 @@ class MultilevelDictionaryLearner(object):
                           input_shape=[tuple(m.shape) for m in inputs] if ragged else (B,) + tuple(inputs[0].shape) if sparse else tuple(sequences.shape),
                           input_nnz=int(sum(m.nnz for m in inputs)) if sparse else None, encode_s=None, encode_nnz=None, encode_timings=None)
                 if level < nbLevels - 1:
+                    if snr_table is not None:
+                        encode = dict(encode, toleranceSnr=snr_table[:, :level + 1])      # (the columns of this pass's levels)
                     if resume and level > 0:
                         # (the levels below keep the last pass's dictionaries and parameters: their coefficients are in hand)
                         coefficients, _, st['encode_timings'] = encode_from(sequences, coefficients, mld, **encode)

@@ -250,6 +250,20 @@ int hscmp_encode_batch_multi(hscmp_ctx* ctx, const void* x, int B, int T, const 
 int hscmp_encode_batch_from_level(hscmp_ctx* ctx, hscmp_ctx* prev, int first, int count, double min_coefficients,
                                   const hscmp_params* params);
 
+/* hscmp_encode_batch_from_level with stop rules per signal: the arrays of `rules` are host pointers, each
+ * NULL or [count], and entry i belongs to signal first + i of `prev`.  All three kinds of rule are taken, with the meaning,
+ * the checks and the messages of hscmp_encode_batch_rules.  Signal i comes out exactly as hscmp_encode_batch_from_level returns
+ * it alone (first + i, count 1) with its values in the scalar fields of `params`.  ctx then holds a ragged batch and its table,
+ * as after hscmp_encode_batch_rules: a uniform `prev` gives count lengths all equal to T, a ragged one its own lengths; the
+ * table serves hscmp_continue, hscmp_grow_events, hscmp_stop_signal, the fetches and hscmp_hierarchy_epilogue until the next
+ * encode of any kind (a following hscmp_encode_batch_from_level runs without one).  hscmp_last_variant is the ragged variant's
+ * name plus "_rules".  Before anything is queued (ctx's previous batch and its table stay as they were): HSCMP_ERR_INVALID for
+ * rules == NULL or three NULL arrays (use hscmp_encode_batch_from_level), and for a NaN or negative tolerance or a negative
+ * nb_nonzero_coefs (hscmp_last_error names the signal and the rule); HSCMP_ERR_UNSUPPORTED under HSCMP_METHOD_LOCOMP;
+ * everything hscmp_encode_batch_from_level refuses. */
+int hscmp_encode_batch_from_level_rules(hscmp_ctx* ctx, hscmp_ctx* prev, int first, int count, double min_coefficients,
+                                        const hscmp_signal_rules* rules, const hscmp_params* params);
+
 /* The inverse of hscmp_fetch_slots, for a hierarchy that is encoded one level at a time (the reference's encodeFromLevel,
  * modeling.py:1494-1554, in batch form): coefficient matrices [T][K] the caller already holds -- K the atom count of ctx's
  * dictionary, which must be set -- become the context's batch of B signals of length T, as if an encode had produced them.

@@ -13,7 +13,12 @@ The optimal rates -- the generator's own events handed down level by level (calc
 -- are printed first.  The corpus comes from tools/generate_dataset.py's generator under a seed; --synth takes planted
 signals of hsc_amd.synth on a random dictionary instead (no ground-truth events: no optimal rates).
 
+--snr-grid takes several rows of SNR targets (R x levels values, row after row) in place of --snr: per weight all rows are
+encoded as ONE batch -- R copies of the corpus, copy r with row r as every signal's targets (a 2-D toleranceSnr, DESIGN.md
+section 26) -- and reported row by row.
+
   python tools/scale_weight_effect.py [--signals 8] [--samples 16384] [--weights 0.5 0.7 0.9 1.0] [--snr 40 30 30] [--blocks 10]
+  python tools/scale_weight_effect.py --snr-grid 40 30 30  30 25 25  20 15 15
 """
 import argparse
 import json
@@ -35,11 +40,13 @@ from hsc_amd.modeling import HierarchicalConvolutionalMatchingPursuit, Hierarchi
 
 
 def encode_by_level(x, mld, weight, snrs, nbBlocks, hcmp):
-    """coefficientsForScales of the script: [stage][signal] distributed coefficients of an encode up to level `stage`."""
+    """coefficientsForScales of the script: [stage][signal] distributed coefficients of an encode up to level `stage`.
+    snrs: one target per level, or a table [signals, levels] with a row per signal of x."""
     stages, coefficients = [], None
     for level in range(mld.getNbLevels()):
         coder = HierarchicalConvolutionalSparseCoder(mld.upToLevel(level), hcmp)
-        kw = dict(toleranceSnr=snrs[level], nbBlocks=nbBlocks, singletonWeight=weight, returnDistributed=False)
+        snr = snrs[level] if np.ndim(snrs) == 1 else np.asarray(snrs)[:, :level + 1]      # (the columns of the stage's levels)
+        kw = dict(toleranceSnr=snr, nbBlocks=nbBlocks, singletonWeight=weight, returnDistributed=False)
         if level == 0:
             coefficients = coder.encodeBatch(x, **kw)[0]
         else:
@@ -69,6 +76,8 @@ def main():
     ap.add_argument('--rate', type=float, default=2e-3)
     ap.add_argument('--weights', type=float, nargs='+', default=[0.5, 0.7, 0.9, 1.0])
     ap.add_argument('--snr', type=float, nargs='+', default=[40.0, 30.0, 30.0, 30.0], help='SNR target per level, dB')
+    ap.add_argument('--snr-grid', type=float, nargs='+', default=None,
+                    help='several rows of SNR targets, R x levels values row after row: all rows of a weight in one batch')
     ap.add_argument('--blocks', type=int, default=10)
     ap.add_argument('--seed', type=int, default=5)
     ap.add_argument('--synth', action='store_true', help='planted signals of hsc_amd.synth instead of the generator')
@@ -78,6 +87,13 @@ def main():
     if len(a.snr) < mld.getNbLevels():
         ap.error('--snr needs one value per level')
     out = dict(scales=a.scales, counts=a.counts, signals=a.signals, samples=a.samples, snr=a.snr[:mld.getNbLevels()], blocks=a.blocks, weights=[])
+    grid = None
+    if a.snr_grid is not None:
+        if len(a.snr_grid) % mld.getNbLevels():
+            ap.error('--snr-grid needs rows of %d values, one per level' % mld.getNbLevels())
+        grid = np.asarray(a.snr_grid, dtype=np.float64).reshape((-1, mld.getNbLevels()))
+        out['snr'] = None
+        out['snr_grid'] = grid.tolist()
     if a.synth:
         import hsc_amd.synth as synth
         x = synth.make_batch(np.asarray(mld.getBaseDictionary()), a.samples, 0, a.signals, kind='planted',
@@ -91,6 +107,22 @@ def main():
     hcmp = HierarchicalConvolutionalMatchingPursuit(method='cmp')
     try:
         for weight in a.weights:
+            if grid is not None:
+                # all rows in one batch: copy r of the corpus with row r for every signal
+                S = len(x)
+                t0 = time.perf_counter()
+                stages = encode_by_level(np.concatenate([x] * len(grid), axis=0), mld, weight, np.repeat(grid, S, axis=0), a.blocks, hcmp)
+                seconds = time.perf_counter() - t0
+                rows = []
+                for r, targets in enumerate(grid):
+                    rows.append(dict(snr=targets.tolist(), **report([stage[r * S:(r + 1) * S] for stage in stages], mld, x)))
+                    print('weight %.2f, targets %s dB: rate per maximum level %s bit/sample; distribution %s; coefficient energy %.6g of signal '
+                          'energy %.6g' % (weight, ' '.join('%g' % v for v in targets), ' '.join('%.4f' % v for v in rows[-1]['information_rates']),
+                                           ' '.join('%.3f' % v for v in rows[-1]['distribution_ratios']), rows[-1]['coefficient_energy'],
+                                           rows[-1]['signal_energy']), flush=True)
+                out['weights'].append(dict(weight=weight, encode_s=seconds, rows=rows))
+                print('weight %.2f: %d rows in one batch of %d signals (%.2f s)' % (weight, len(grid), len(grid) * S, seconds), flush=True)
+                continue
             t0 = time.perf_counter()
             stages = encode_by_level(x, mld, weight, a.snr, a.blocks, hcmp)
             row = dict(weight=weight, encode_s=time.perf_counter() - t0, **report(stages, mld, x))
